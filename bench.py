@@ -10,7 +10,8 @@ already resident in HBM: stem (u8->bf16, /255, BGR->RGB) -> backbone -> neck -> 
 two-stage top-k -> [32,300,6]; at N>1 followed by the single RCCL all-gather of the detections. Frames are
 sharded across ranks (weak scaling: 32 frames per GPU). Rank 0 prints the result as ONE JSON line - the LAST line of stdout; when
 the roofline / cpu_baseline legs are on, the bare measurement is printed first (marked "partial") so that a fault in a diagnostic
-leg cannot cost it.
+leg cannot cost it. `--dump-outputs DIR` writes what the last timed step returned as DIR/<name>.npy (same seeded weights and frames
+on every run), so that two builds can be compared output for output.
 """
 from __future__ import annotations
 
@@ -56,7 +57,33 @@ def parse():
     ap.add_argument("--no-steady", action="store_true", help="skip the >= 200-step repetition of the timed loop (spread of the step time)")
     ap.add_argument("--no-spread", action="store_true", help="skip the leg with equal class biases on the three levels (winners on P3 / P4 / P5)")
     ap.add_argument("--cpu-frames", type=int, default=8, help="frames in the bounded CPU-baseline sample")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned (det, idx, coeff with --seg; det_gathered with RCCL) "
+                         "as DIR/<name>.npy in float32 / float64, for output-by-output comparison of two builds")
+    a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return a
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(d: str, arrays: dict) -> None:
+    """Writes {name: CPU tensor [frames, ...]} as d/<name>.npy: floats as float32, integers as float64 (exact). Over DUMP_LIMIT_BYTES in
+    all, every array keeps the same fixed, seeded sample of frames, whose indices go to d/frame_index.npy."""
+    import numpy as np
+    arrays = {k: v.double() if not v.is_floating_point() else v.float() for k, v in arrays.items()}
+    total = sum(v.numel() * v.element_size() for v in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        n = min(v.shape[0] for v in arrays.values())
+        keep = max(1, n * (DUMP_LIMIT_BYTES - (1 << 20)) // total)     # (1 MB left for the .npy headers and frame_index)
+        sel = torch.randperm(n, generator=torch.Generator().manual_seed(0))[:keep].sort().values
+        arrays = {k: v[sel] for k, v in arrays.items()}
+        arrays["frame_index"] = sel.double()
+    os.makedirs(d, exist_ok=True)
+    for k, v in arrays.items():
+        np.save(os.path.join(d, f"{k}.npy"), v.contiguous().numpy())
 
 
 def op_traffic() -> dict:
@@ -248,6 +275,13 @@ def main():
         dt = float(t.item())
     ms_per_step = dt / a.steps * 1e3
     value = world * B * a.steps / dt
+    if a.dump_outputs and rank == 0:
+        # the last timed step's results, before any later leg reuses the buffers (the ring's engine j took step j, j+n, ...)
+        last = outs[(nstep[0] - 1) % n_fl]
+        dumped = {k: v.cpu() for k, v in last.items() if v is not None}
+        if use_dist:
+            dumped["det_gathered"] = gath[(nstep[0] - 1) & 1].cpu()
+        dump_outputs(a.dump_outputs, dumped)
     one_fl = None
     if n_fl > 1 and rank == 0 and world == 1 and not a.no_one_in_flight:
         # the same K steps with ONE batch in flight (engine 0 alone, one step after the other): what a caller without a next batch ready sees
