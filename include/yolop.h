@@ -165,6 +165,29 @@ int yp_u2net_tensor_count(const yp_u2net* e);
 int yp_u2net_tensor_info(const yp_u2net* e, int i, char* name, int name_cap, int dims[4] /*B,H,W,C*/);
 int yp_u2net_tensor_read(yp_u2net* e, int i, float* host_out);   /* sync copy NHWC -> fp32 host (debug taps) */
 
+/* -- EfficientNet-B3 needle classifier: the third network of the reference's video loop, `load_classify_net` +
+ *    `predict_and_find_start_inserted` (yolo_seg/app.py:116-123 -> yolo_seg/tasks/needle_clasify.py:41-199), efficientnet_pytorch's
+ *    `EfficientNet.from_name('efficientnet-b3', num_classes=2)`. variant = 3 (b3; every other value is refused). Weights are handed over
+ *    folded (conv + eval-mode BatchNorm, eps 1e-3 -> one weight/bias pair), named after the reference modules: "_conv_stem",
+ *    "_blocks.{i}._expand_conv" / "._depthwise_conv" / "._project_conv", the SE convs "._se_reduce" / "._se_expand" (their own bias),
+ *    "_conv_head" and "_fc" (weight [2,1536], rank 2).
+ *    yp_cls_forward: frames_dev uint8 [B,H,W,3] (bgr = 1: BGR as cv2 reads them; 0: RGB), boxes_dev int32 [B,4] xyxy; the 380x380 crop
+ *      window of crop_frame(frame, box, 380, need_padding=True) is read straight from the frame (never materialised),
+ *      logits_out float [B,2], prob_out float [B] = max softmax, cls_out int32 [B] = argmax. */
+typedef struct yp_cls yp_cls;
+int yp_cls_create(int variant, int dtype, int device, yp_cls** out);
+int yp_cls_destroy(yp_cls* e);
+int yp_cls_weight_count(const yp_cls* e);
+int yp_cls_weight_info(const yp_cls* e, int i, char* name, int name_cap, int64_t shape[4], int* ndim);
+int yp_cls_set_weight(yp_cls* e, const char* name, const float* host, const int64_t* shape, int ndim);
+int yp_cls_finalize(yp_cls* e);
+int yp_cls_forward(yp_cls* e, const uint8_t* frames_dev, int B, int H, int W, int bgr, const int32_t* boxes_dev, float* logits_out,
+                   float* prob_out, int32_t* cls_out, void* stream);
+int yp_cls_set_graph(yp_cls* e, int enable);   /* hipGraph replay (default off); specialised on shape and pointers, a change re-captures */
+int yp_cls_tensor_count(const yp_cls* e);
+int yp_cls_tensor_info(const yp_cls* e, int i, char* name, int name_cap, int dims[4] /*B,H,W,C*/);
+int yp_cls_tensor_read(yp_cls* e, int i, float* host_out);   /* sync copy NHWC -> fp32 host (debug taps) */
+
 /* -- multi-GPU: frames are sharded over one process per GPU; the only data-path collective is ONE all-gather of
  *    the [B/G,max_det,6] detections per batch over RCCL (xGMI). The reference has no multi-GPU path (frames are independent inside
  *    `.predict`, yolo_seg/app.py:85-91). bench.py / parallel.py use torch.distributed's "nccl" backend for it; these entry points

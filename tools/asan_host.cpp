@@ -78,6 +78,41 @@ int main() {
     yp_model_desc bad{'q', 80, 0, 0, 300, 0};
     yp_engine* e = nullptr;
     CHECK(yp_create(&bad, 0, &e) < 0);
+    // EfficientNet-B3 classifier (yp_cls_*): create, weight table, set_weight with its error paths, refusal without a device, destroy
+    for (int dtype = 0; dtype < 2; ++dtype) {
+        yp_cls* c = nullptr;
+        CHECK(yp_cls_create(3, dtype, 0, &c) == YP_OK);
+        const int nw = yp_cls_weight_count(c);
+        CHECK(nw > 0);
+        for (int i = 0; i < nw; ++i) {
+            char name[256];
+            int64_t shp[4];
+            int nd = 0;
+            CHECK(yp_cls_weight_info(c, i, name, sizeof(name), shp, &nd) == YP_OK);
+            size_t n = 1;
+            for (int k = 0; k < nd; ++k) n *= (size_t)shp[k];
+            std::vector<float> w(n, 0.25f);
+            if (i < 2) {
+                int64_t bad[4] = {shp[0] + 1, shp[1], shp[2], shp[3]};
+                CHECK(yp_cls_set_weight(c, name, w.data(), bad, nd) < 0);
+                CHECK(yp_cls_set_weight(c, "_blocks.99._fc.weight", w.data(), shp, nd) < 0);
+                CHECK(yp_cls_finalize(c) < 0);                           // missing weights
+            }
+            CHECK(yp_cls_set_weight(c, name, w.data(), shp, nd) == YP_OK);
+        }
+        CHECK(yp_cls_weight_info(c, nw, nullptr, 0, nullptr, nullptr) < 0);
+        char tn[8];
+        int dims[4];
+        for (int i = 0; i < yp_cls_tensor_count(c); ++i) CHECK(yp_cls_tensor_info(c, i, tn, sizeof(tn), dims) == YP_OK);
+        float tmp[4];
+        CHECK(yp_cls_tensor_read(c, 0, tmp) < 0);                         // no forward yet
+        CHECK(yp_cls_finalize(c) < 0);                                    // no device here: must refuse, not fall back
+        CHECK(yp_cls_destroy(c) == YP_OK);
+    }
+    for (int v : {0, 4, 5, 7}) {
+        yp_cls* c = nullptr;
+        CHECK(yp_cls_create(v, 1, 0, &c) < 0 && c == nullptr);
+    }
     printf("asan_host: ok (%ld scheduled launches walked)\n", launches);
     return 0;
 }

@@ -17,6 +17,9 @@ def __getattr__(name):
     if name in ("load_unet", "unet_predict", "U2NetEngine"):
         from . import u2net
         return getattr(u2net, name)
+    if name in ("load_classify_net", "predict_images", "predict_and_find_start_inserted", "fix_class_prob", "ClassifierEngine"):
+        from . import classify
+        return getattr(classify, name)
     if name == "auto_segment":
         from .deva_adapter import auto_segment
         return auto_segment
