@@ -160,6 +160,16 @@ int yp_u2net_set_weight(yp_u2net* e, const char* name, const float* host, const 
 int yp_u2net_finalize(yp_u2net* e);
 int yp_u2net_forward(yp_u2net* e, const uint8_t* bgr_dev, int B, int H, int W, float* prob_out, float* norm_out,
                      uint8_t* mask_out, void* stream);
+/*    yp_u2net_forward_crops: the clip form of crop_frame + unet_predict + the app's paste (yolo_seg/app.py:127,183-186). frames_dev
+ *      uint8 [N,H,W,3] BGR; windows int32 [B,4] host array, each row the clipped (x1,y1,x2,y2) crop_frame returns; frame_idx int32 [B]
+ *      host array, the frame of each crop; (ch, cw) the crop shape every window of the call shares (each window no larger). Crop pixel
+ *      (y,x) is the frame pixel (y1+y, x1+x) inside the window and 0 elsewhere (the window sits at the top-left of the zero pad).
+ *      prob_out float [B,ch,cw] = sigmoid(d0) (may be NULL); crop_mask_out uint8 [B,ch,cw] = normPRED(prob) > 0.5 ? 255 : 0 with min /
+ *      max taken per crop, pad included, as the per-frame reference call does (may be NULL); frame_mask_out uint8 [N,H,W] (may be NULL):
+ *      for every frame a crop names (at most once), the crop mask's top-left (y2-y1) x (x2-x1) block at (y1,x1) and 0 everywhere else.
+ *      Windows, indices and sizes are checked before any launch (YP_ERR_ARG). Eager launches on `stream`, never graph replay. */
+int yp_u2net_forward_crops(yp_u2net* e, const uint8_t* frames_dev, int N, int H, int W, const int32_t* windows, const int32_t* frame_idx,
+                           int B, int ch, int cw, float* prob_out, uint8_t* crop_mask_out, uint8_t* frame_mask_out, void* stream);
 int yp_u2net_set_graph(yp_u2net* e, int enable);   /* hipGraph replay of the forward (default off: measured slower than eager launches; the first pass of a shape is always eager) */
 int yp_u2net_tensor_count(const yp_u2net* e);
 int yp_u2net_tensor_info(const yp_u2net* e, int i, char* name, int name_cap, int dims[4] /*B,H,W,C*/);

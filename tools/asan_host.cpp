@@ -113,6 +113,28 @@ int main() {
         yp_cls* c = nullptr;
         CHECK(yp_cls_create(v, 1, 0, &c) < 0 && c == nullptr);
     }
+    // U^2-Net-P clip path (yp_u2net_forward_crops): every argument check runs before the device is touched
+    for (int dtype = 0; dtype < 2; ++dtype) {
+        yp_u2net* u = nullptr;
+        CHECK(yp_u2net_create('p', dtype, 0, &u) == YP_OK);
+        static uint8_t frame_stub[16];                                   // never read: every call below is refused first
+        const int32_t ok_win[8] = {0, 0, 380, 380, 900, 340, 1280, 720};
+        const int32_t ok_idx[2] = {0, 1};
+        uint8_t mask_stub[1];
+        CHECK(yp_u2net_forward_crops(u, nullptr, 2, 720, 1280, ok_win, ok_idx, 2, 380, 380, nullptr, nullptr, nullptr, nullptr) == YP_ERR_ARG);
+        CHECK(yp_u2net_forward_crops(u, frame_stub, 2, 720, 1280, ok_win, ok_idx, 2, 31, 380, nullptr, nullptr, nullptr, nullptr) == YP_ERR_ARG);
+        CHECK(yp_u2net_forward_crops(u, frame_stub, 2, 720, 1280, ok_win, ok_idx, 30, 380, 380, nullptr, nullptr, nullptr, nullptr) == YP_ERR_ARG);
+        const int32_t bad_idx[2] = {0, 2};
+        CHECK(yp_u2net_forward_crops(u, frame_stub, 2, 720, 1280, ok_win, bad_idx, 2, 380, 380, nullptr, nullptr, nullptr, nullptr) == YP_ERR_ARG);
+        const int32_t dup_idx[2] = {1, 1};
+        CHECK(yp_u2net_forward_crops(u, frame_stub, 2, 720, 1280, ok_win, dup_idx, 2, 380, 380, nullptr, nullptr, mask_stub, nullptr) == YP_ERR_ARG);
+        const int32_t outside[4] = {1000, 0, 1380, 380}, wide[4] = {0, 0, 381, 380}, empty[4] = {5, 5, 5, 100};
+        for (const int32_t* w : {outside, wide, empty})
+            CHECK(yp_u2net_forward_crops(u, frame_stub, 2, 720, 1280, w, ok_idx, 1, 380, 380, nullptr, nullptr, nullptr, nullptr) == YP_ERR_ARG);
+        // valid arguments: refused only because no weights were finalized (no device here)
+        CHECK(yp_u2net_forward_crops(u, frame_stub, 2, 720, 1280, ok_win, dup_idx, 2, 380, 380, nullptr, nullptr, nullptr, nullptr) == YP_ERR_STATE);
+        CHECK(yp_u2net_destroy(u) == YP_OK);
+    }
     printf("asan_host: ok (%ld scheduled launches walked)\n", launches);
     return 0;
 }

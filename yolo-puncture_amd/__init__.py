@@ -14,7 +14,7 @@ def __getattr__(name):
     if name in ("Engine", "load_library"):
         from . import engine
         return getattr(engine, name)
-    if name in ("load_unet", "unet_predict", "U2NetEngine"):
+    if name in ("load_unet", "unet_predict", "unet_predict_clip", "crop_window", "U2NetEngine"):
         from . import u2net
         return getattr(u2net, name)
     if name in ("load_classify_net", "predict_images", "predict_and_find_start_inserted", "fix_class_prob", "ClassifierEngine"):

@@ -8,6 +8,9 @@
 // Kernels: dilated 3x3 conv + folded BatchNorm + ReLU = conv_igemm (matrix cores; fp32 mode = exact fp32 FMA chains), plus the
 // small ones below - u8 BGR -> RGB/255 (channel-padded to 8), ceil-mode 2x2 max-pool, PyTorch-exact bilinear resize-to-size, and
 // the tail: six side maps -> bilinear to full size -> 1x1 fusion -> sigmoid -> min/max -> normPRED -> mask.
+// Clip path (yp_u2net_forward_crops): the input op crops B windows straight from the uint8 frames on the device, the tail keeps one
+// min/max per image (the reference's normPRED runs per `unet_predict` call, i.e. per frame) and the last kernel writes the crop mask and
+// pastes it into the full-frame mask in the same pass.
 #include "../../include/yolop.h"
 #include "common.h"
 #include <algorithm>
@@ -18,6 +21,7 @@
 #include <map>
 #include <memory>
 #include <string>
+#include <tuple>
 #include <vector>
 
 using namespace yp;
@@ -70,6 +74,8 @@ struct U2Op {
     int up_op = -1;        // convs: index of the bilinear up-sample op that produces the first channels of this conv's input (graph pass)
     int consumer = -1;     // pools / up-samples: index of that conv; the op does not launch while the conv runs with impl 2
 };
+// one crop of yp_u2net_forward_crops: the clipped window (x1,y1,x2,y2) of frame f
+struct U2Win { int x1, y1, x2, y2, f; };
 
 }  // namespace
 
@@ -97,6 +103,13 @@ struct yp_u2net {
     hipGraphExec_t gexec = nullptr;
     int gB = 0, gH = 0, gW = 0;
     uint8_t* in_buf = nullptr; float* o_prob = nullptr; float* o_norm = nullptr; uint8_t* o_mask = nullptr; size_t io_cap = 0;
+    // conv choices of every (B, H, W) this engine has timed, restored when a plan returns to that shape (a clip alternates between
+    // 380x380 chunks and edge groups; re-timing ~119 convolutions per switch would cost more than the forward)
+    std::map<std::tuple<int, int, int>, std::vector<int>> tuned;
+    // yp_u2net_forward_crops: windows (pinned staging -> device), per-image [min bits, max bits], prob scratch when the caller wants none
+    U2Win* h_win = nullptr; U2Win* d_win = nullptr; unsigned* d_mm = nullptr; int win_cap = 0;
+    hipEvent_t ev_win = nullptr; bool win_pending = false;
+    float* d_prob = nullptr; size_t prob_cap = 0;
     int es() const { return dtype == DT_BF16 ? 2 : 4; }
 };
 
@@ -293,6 +306,30 @@ __global__ __launch_bounds__(256) void u2_input_kernel(const uint8_t* __restrict
     for (int c = 3; c < 8; ++c) o[c] = (T)0.f;
 }
 
+// crop_frame + numpy2tensor on the device: crop pixel (y, x) of image b is frame[f][y1 + y][x1 + x] inside the window and 0 (the
+// zero pad) elsewhere, the window at the top-left as in yolo_seg/utils/transform.py:45-49. Same float operations as u2_input_kernel,
+// so an unpadded crop gives the same bits. The crop never exists as uint8. Thread 0 of each image also resets that image's normPRED
+// range for the tail (stream order: the previous call's last kernel has read it).
+template <typename T>
+__global__ __launch_bounds__(256) void u2_crop_input_kernel(const uint8_t* __restrict__ frames, int H, int W, const U2Win* __restrict__ win,
+                                                           T* __restrict__ out, int ch, int cw, unsigned* __restrict__ minmax) {
+    const int b = blockIdx.y;
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i == 0) { minmax[2 * b] = 0x7f800000u; minmax[2 * b + 1] = 0u; }
+    if (i >= ch * cw) return;
+    const int y = i / cw, x = i - y * cw;
+    const U2Win w = win[b];
+    float r = 0.f, g = 0.f, bl = 0.f;
+    if (y < w.y2 - w.y1 && x < w.x2 - w.x1) {
+        const uint8_t* s = frames + (((size_t)w.f * H + (w.y1 + y)) * W + (w.x1 + x)) * 3;
+        r = (float)s[2] / 255.0f; g = (float)s[1] / 255.0f; bl = (float)s[0] / 255.0f;
+    }
+    T* o = out + ((size_t)b * ch * cw + i) * 8;
+    o[0] = (T)r; o[1] = (T)g; o[2] = (T)bl;
+#pragma unroll
+    for (int c = 3; c < 8; ++c) o[c] = (T)0.f;
+}
+
 // nn.MaxPool2d(2, stride=2, ceil_mode=True): windows clipped at the border
 template <typename T>
 __global__ __launch_bounds__(256) void u2_pool_kernel(const T* __restrict__ x, int xs, int xc, T* __restrict__ y, int ys, int yc, int B, int H, int W,
@@ -368,20 +405,21 @@ struct U2Tail {
     int h[6], w[6];
     int B, H, W;
     const float* fuse;         // [6 weights | bias]
-    unsigned* minmax;          // [min bits | max bits] of the positive floats
+    unsigned* minmax;          // [min bits | max bits] of the positive floats: one pair for the call, or [B][2] with per_image
+    int per_image;
     float* prob;
 };
 // d0 = outconv(cat(d1, up(d2), ..., up(d6))) ; sigmoid (U2Net.py:498-520) ; running min / max for normPRED
+// grid (H*W / 256, B): a block never spans two images, so the wave reduction below is per image
 __global__ __launch_bounds__(256) void u2_tail_kernel(const U2Tail t) {
-    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const size_t n = (size_t)t.B * t.H * t.W;
+    const int b = blockIdx.y;
+    const size_t j = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const size_t hw = (size_t)t.H * t.W;
     float pr = 0.5f;
-    const bool live = i < n;
+    const bool live = j < hw;
     if (live) {
-        size_t r = i;
-        const int wo = (int)(r % t.W); r /= t.W;
-        const int ho = (int)(r % t.H);
-        const int b = (int)(r / t.H);
+        const int wo = (int)(j % t.W);
+        const int ho = (int)(j / t.W);
         float acc = 0.f;
 #pragma unroll
         for (int k = 0; k < 6; ++k) {
@@ -399,7 +437,7 @@ __global__ __launch_bounds__(256) void u2_tail_kernel(const U2Tail t) {
         }
         acc += t.fuse[6];
         pr = 1.f / (1.f + expf(-acc));
-        t.prob[i] = pr;
+        t.prob[(size_t)b * hw + j] = pr;
     }
     // sigmoid outputs are >= 0: their bit patterns order like unsigned integers
     unsigned lo = live ? __float_as_uint(pr) : 0x7f800000u, hi = live ? __float_as_uint(pr) : 0u;
@@ -408,9 +446,15 @@ __global__ __launch_bounds__(256) void u2_tail_kernel(const U2Tail t) {
         lo = min(lo, (unsigned)__shfl_xor((int)lo, o));
         hi = max(hi, (unsigned)__shfl_xor((int)hi, o));
     }
-    if ((threadIdx.x & 63) == 0) {
-        atomicMin(&t.minmax[0], lo);
-        atomicMax(&t.minmax[1], hi);
+    // one atomic pair per block: every block of an image updates the same two words, and at B = 16 per-wave atomics on them cost more
+    // than the fusion itself
+    __shared__ unsigned red[2][4];
+    if ((threadIdx.x & 63) == 0) { red[0][threadIdx.x >> 6] = lo; red[1][threadIdx.x >> 6] = hi; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        unsigned* mm = t.minmax + (t.per_image ? 2 * b : 0);
+        atomicMin(&mm[0], min(min(red[0][0], red[0][1]), min(red[0][2], red[0][3])));
+        atomicMax(&mm[1], max(max(red[1][0], red[1][1]), max(red[1][2], red[1][3])));
     }
 }
 // normPRED (unet_segment.py:24-30) + `> 0.5 -> 255` (:66-71)
@@ -423,6 +467,40 @@ __global__ __launch_bounds__(256) void u2_norm_kernel(const float* __restrict__ 
     if (norm) norm[i] = dn;
     if (mask) mask[i] = dn > 0.5f ? 255 : 0;
 }
+
+struct U2Paste {
+    const float* prob;         // [B][ch][cw]
+    const unsigned* minmax;    // [B][2]
+    const U2Win* win;
+    int ch, cw, H, W;
+    uint8_t* crop_mask;        // [B][ch][cw] or null
+    uint8_t* frame_mask;       // [N][H][W] or null
+};
+// per-image normPRED + `> 0.5 -> 255`, then the app's paste (yolo_seg/app.py:183-186): every pixel of frame f's mask is written, the
+// crop mask's top-left (y2-y1) x (x2-x1) block at (y1, x1) and 0 elsewhere. grid (max(ch*cw, H*W) / 256, B).
+__global__ __launch_bounds__(256) void u2_crop_norm_kernel(const U2Paste p) {
+    const int b = blockIdx.y;
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    const float mi = __uint_as_float(p.minmax[2 * b]), ma = __uint_as_float(p.minmax[2 * b + 1]);
+    const float* pr = p.prob + (size_t)b * p.ch * p.cw;
+    if (p.crop_mask && i < p.ch * p.cw) {
+        const float dn = (pr[i] - mi) / (ma - mi);
+        p.crop_mask[(size_t)b * p.ch * p.cw + i] = dn > 0.5f ? 255 : 0;
+    }
+    if (p.frame_mask && i < p.H * p.W) {
+        const U2Win w = p.win[b];
+        const int fy = i / p.W, fx = i - fy * p.W;
+        uint8_t v = 0;
+        if (fy >= w.y1 && fy < w.y2 && fx >= w.x1 && fx < w.x2) {
+            const float dn = (pr[(fy - w.y1) * p.cw + (fx - w.x1)] - mi) / (ma - mi);
+            v = dn > 0.5f ? 255 : 0;
+        }
+        p.frame_mask[(size_t)w.f * p.H * p.W + i] = v;
+    }
+}
+
+// every activation offset of a plan fits in 32 bits (the widest level-0 tensor has 128 channels, at most 4 bytes each)
+static bool u2_offsets_fit(int B, int H, int W) { return (size_t)B * H * W * 128 * 4 < (1ull << 31); }
 
 static int plan_u2(yp_u2net& e, int B, int H, int W) {
     if (B <= 0 || H < 32 || W < 32) return u2fail(YP_ERR_ARG, "input must be [B,H,W,3] with H,W >= 32 (got %d,%d,%d)", B, H, W);
@@ -437,7 +515,7 @@ static int plan_u2(yp_u2net& e, int B, int H, int W) {
         t.bytes = (size_t)B * t.H * t.W * t.C * (t.f32 ? 4 : e.es());
         total += (t.bytes + 255) & ~(size_t)255;
     }
-    if ((size_t)B * H * W * 128 * 4 >= (1ull << 31)) return u2fail(YP_ERR_ARG, "input too large for 32-bit tensor offsets");
+    if (!u2_offsets_fit(B, H, W)) return u2fail(YP_ERR_ARG, "input too large for 32-bit tensor offsets");
     U2HIP(hipSetDevice(e.device));
     if (total > e.arena_bytes) {
         U2HIP(hipDeviceSynchronize());
@@ -449,7 +527,8 @@ static int plan_u2(yp_u2net& e, int B, int H, int W) {
     size_t off = 0;
     for (auto& t : e.tensors) { t.ptr = (char*)e.arena + off; off += (t.bytes + 255) & ~(size_t)255; }
     e.pB = B; e.pH = H; e.pW = W;
-    for (auto& o : e.ops) o.impl = -1;
+    const auto memo = e.tuned.find(std::make_tuple(B, H, W));
+    for (size_t i = 0; i < e.ops.size(); ++i) e.ops[i].impl = memo != e.tuned.end() ? memo->second[i] : -1;
     if (e.gexec) { (void)hipDeviceSynchronize(); (void)hipGraphExecDestroy(e.gexec); e.gexec = nullptr; }
     return YP_OK;
 }
@@ -603,6 +682,11 @@ int yp_u2net_destroy(yp_u2net* e) {
     if (e->in_buf) { (void)hipFree(e->in_buf); (void)hipFree(e->o_prob); (void)hipFree(e->o_norm); (void)hipFree(e->o_mask); }
     if (e->ev_in) (void)hipEventDestroy(e->ev_in);
     if (e->ev_out) (void)hipEventDestroy(e->ev_out);
+    if (e->ev_win) (void)hipEventDestroy(e->ev_win);
+    if (e->h_win) (void)hipHostFree(e->h_win);
+    if (e->d_win) (void)hipFree(e->d_win);
+    if (e->d_mm) (void)hipFree(e->d_mm);
+    if (e->d_prob) (void)hipFree(e->d_prob);
     if (e->own_stream) (void)hipStreamDestroy(e->own_stream);
     delete e;
     return YP_OK;
@@ -673,23 +757,62 @@ int yp_u2net_finalize(yp_u2net* e) {
     return YP_OK;
 }
 
-static int u2_run(yp_u2net* e, const uint8_t* bgr, float* prob, float* norm, uint8_t* mask, hipStream_t st) {
+// the crop path's extra state for u2_run (null: whole-frame input, normPRED over the whole call)
+struct U2CropRun {
+    const uint8_t* frames;
+    int H, W;
+    uint8_t* crop_mask;
+    uint8_t* frame_mask;
+};
+
+static int u2_run(yp_u2net* e, const uint8_t* bgr, float* prob, float* norm, uint8_t* mask, hipStream_t st, const U2CropRun* cr = nullptr) {
+    bool timed = false;
     for (U2Op& o : e->ops) {
         if (o.kind == U2_CONV && o.impl < 0) {             // (never under a capture: a plan's first pass is eager)
             const int rc = u2_tune_op(*e, o, st);
             if (rc != YP_OK) return rc;
+            timed = true;
         }
-        hipError_t err = run_u2_op(*e, o, bgr, st);
+        hipError_t err;
+        if (cr && o.kind == U2_INPUT) {
+            const U2Tensor& to = e->tensors[o.out.t];
+            const dim3 grid((unsigned)((to.H * to.W + 255) / 256), (unsigned)e->pB);
+            if (e->dtype == DT_BF16)
+                hipLaunchKernelGGL(u2_crop_input_kernel<__bf16>, grid, dim3(256), 0, st, cr->frames, cr->H, cr->W, e->d_win, (__bf16*)to.ptr, to.H, to.W, e->d_mm);
+            else
+                hipLaunchKernelGGL(u2_crop_input_kernel<float>, grid, dim3(256), 0, st, cr->frames, cr->H, cr->W, e->d_win, (float*)to.ptr, to.H, to.W, e->d_mm);
+            err = hipGetLastError();
+        } else {
+            err = run_u2_op(*e, o, bgr, st);
+        }
         if (err != hipSuccess) return u2fail(YP_ERR_HIP, "launch of op '%s' failed: %s", o.name.c_str(), hipGetErrorString(err));
+    }
+    if (timed) {
+        std::vector<int>& memo = e->tuned[std::make_tuple(e->pB, e->pH, e->pW)];
+        memo.clear();
+        for (const U2Op& o : e->ops) memo.push_back(o.impl);
     }
     U2Tail t{};
     for (int k = 0; k < 6; ++k) { const U2Tensor& s = e->tensors[e->side_t[k]]; t.side[k] = (const float*)s.ptr; t.h[k] = s.H; t.w[k] = s.W; }
-    t.B = e->pB; t.H = e->pH; t.W = e->pW; t.fuse = e->d_fuse; t.minmax = (unsigned*)(e->d_fuse + 7); t.prob = prob;
-    U2HIP(hipMemsetD32Async((hipDeviceptr_t)t.minmax, (int)0x7f800000u, 1, st));
-    U2HIP(hipMemsetD32Async((hipDeviceptr_t)(t.minmax + 1), 0, 1, st));
-    const size_t n = (size_t)e->pB * e->pH * e->pW;
-    hipLaunchKernelGGL(u2_tail_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, t);
-    if (norm || mask) hipLaunchKernelGGL(u2_norm_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, prob, t.minmax, norm, mask, n);
+    t.B = e->pB; t.H = e->pH; t.W = e->pW; t.fuse = e->d_fuse; t.prob = prob;
+    const size_t hw = (size_t)e->pH * e->pW;
+    const dim3 tgrid((unsigned)((hw + 255) / 256), (unsigned)e->pB);
+    if (cr) {                                              // per-image range, reset by u2_crop_input_kernel
+        t.minmax = e->d_mm; t.per_image = 1;
+        hipLaunchKernelGGL(u2_tail_kernel, tgrid, dim3(256), 0, st, t);
+        if (cr->crop_mask || cr->frame_mask) {
+            const U2Paste p{prob, e->d_mm, e->d_win, e->pH, e->pW, cr->H, cr->W, cr->crop_mask, cr->frame_mask};
+            const size_t n = std::max(cr->crop_mask ? hw : 0, cr->frame_mask ? (size_t)cr->H * cr->W : 0);
+            hipLaunchKernelGGL(u2_crop_norm_kernel, dim3((unsigned)((n + 255) / 256), (unsigned)e->pB), dim3(256), 0, st, p);
+        }
+    } else {
+        t.minmax = (unsigned*)(e->d_fuse + 7); t.per_image = 0;
+        U2HIP(hipMemsetD32Async((hipDeviceptr_t)t.minmax, (int)0x7f800000u, 1, st));
+        U2HIP(hipMemsetD32Async((hipDeviceptr_t)(t.minmax + 1), 0, 1, st));
+        const size_t n = (size_t)e->pB * hw;
+        hipLaunchKernelGGL(u2_tail_kernel, tgrid, dim3(256), 0, st, t);
+        if (norm || mask) hipLaunchKernelGGL(u2_norm_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, prob, t.minmax, norm, mask, n);
+    }
     U2HIP(hipGetLastError());
     return YP_OK;
 }
@@ -745,6 +868,64 @@ int yp_u2net_forward(yp_u2net* e, const uint8_t* bgr_dev, int B, int H, int W, f
     U2HIP(hipEventRecord(e->ev_out, e->own_stream));
     U2HIP(hipStreamWaitEvent(st, e->ev_out, 0));
     return YP_OK;
+}
+
+int yp_u2net_forward_crops(yp_u2net* e, const uint8_t* frames_dev, int N, int H, int W, const int32_t* windows, const int32_t* frame_idx,
+                           int B, int ch, int cw, float* prob_out, uint8_t* crop_mask_out, uint8_t* frame_mask_out, void* stream) {
+    // every argument is checked before anything is launched or allocated
+    if (!e || !frames_dev || !windows || !frame_idx) return u2fail(YP_ERR_ARG, "null argument");
+    if (N <= 0 || H <= 0 || W <= 0) return u2fail(YP_ERR_ARG, "frames must be [N,H,W,3] with N,H,W >= 1 (got %d,%d,%d)", N, H, W);
+    if (B <= 0 || ch < 32 || cw < 32) return u2fail(YP_ERR_ARG, "crops must be [B,ch,cw] with B >= 1 and ch,cw >= 32 (got %d,%d,%d)", B, ch, cw);
+    if (!u2_offsets_fit(B, ch, cw)) return u2fail(YP_ERR_ARG, "%d crops of %dx%d are too many for 32-bit tensor offsets: split the call", B, ch, cw);
+    std::vector<char> seen(frame_mask_out ? N : 0, 0);
+    for (int b = 0; b < B; ++b) {
+        const int32_t* w = windows + 4 * b;
+        const int f = frame_idx[b];
+        if (f < 0 || f >= N) return u2fail(YP_ERR_ARG, "crop %d: frame index %d outside [0,%d)", b, f, N);
+        if (w[0] < 0 || w[1] < 0 || w[2] > W || w[3] > H || w[0] >= w[2] || w[1] >= w[3])
+            return u2fail(YP_ERR_ARG, "crop %d: window (%d,%d,%d,%d) is empty or leaves the %dx%d frame", b, w[0], w[1], w[2], w[3], W, H);
+        if (w[2] - w[0] > cw || w[3] - w[1] > ch)
+            return u2fail(YP_ERR_ARG, "crop %d: window (%d,%d,%d,%d) is larger than the %dx%d crop", b, w[0], w[1], w[2], w[3], cw, ch);
+        if (frame_mask_out) {                         // each frame mask is written whole by the one crop that names it
+            if (seen[f]) return u2fail(YP_ERR_ARG, "crop %d: frame %d is named twice while a frame mask is requested", b, f);
+            seen[f] = 1;
+        }
+    }
+    if (!e->finalized) return u2fail(YP_ERR_STATE, "yp_u2net_finalize has not been called");
+    U2HIP(hipSetDevice(e->device));
+    hipStream_t st = (hipStream_t)stream;
+    if (B > e->win_cap) {
+        U2HIP(hipDeviceSynchronize());
+        if (e->h_win) { (void)hipHostFree(e->h_win); (void)hipFree(e->d_win); (void)hipFree(e->d_mm); }
+        e->h_win = nullptr; e->d_win = nullptr; e->d_mm = nullptr; e->win_cap = 0; e->win_pending = false;
+        U2HIP(hipHostMalloc((void**)&e->h_win, (size_t)B * sizeof(U2Win)));
+        U2HIP(hipMalloc((void**)&e->d_win, (size_t)B * sizeof(U2Win)));
+        U2HIP(hipMalloc((void**)&e->d_mm, (size_t)B * 2 * sizeof(unsigned)));
+        e->win_cap = B;
+    }
+    if (!e->ev_win) U2HIP(hipEventCreateWithFlags(&e->ev_win, hipEventDisableTiming));
+    float* prob = prob_out;
+    if (!prob) {
+        const size_t n = (size_t)B * ch * cw;
+        if (n > e->prob_cap) {
+            U2HIP(hipDeviceSynchronize());
+            if (e->d_prob) (void)hipFree(e->d_prob);
+            e->d_prob = nullptr; e->prob_cap = 0;
+            U2HIP(hipMalloc((void**)&e->d_prob, n * sizeof(float)));
+            e->prob_cap = n;
+        }
+        prob = e->d_prob;
+    }
+    int rc = plan_u2(*e, B, ch, cw);
+    if (rc != YP_OK) return rc;
+    // the staging buffer is rewritten only once the previous call's copy out of it has run
+    if (e->win_pending) U2HIP(hipEventSynchronize(e->ev_win));
+    for (int b = 0; b < B; ++b) e->h_win[b] = U2Win{windows[4 * b], windows[4 * b + 1], windows[4 * b + 2], windows[4 * b + 3], frame_idx[b]};
+    U2HIP(hipMemcpyAsync(e->d_win, e->h_win, (size_t)B * sizeof(U2Win), hipMemcpyHostToDevice, st));
+    U2HIP(hipEventRecord(e->ev_win, st));
+    e->win_pending = true;
+    const U2CropRun cr{frames_dev, H, W, crop_mask_out, frame_mask_out};
+    return u2_run(e, nullptr, prob, nullptr, nullptr, st, &cr);
 }
 
 int yp_u2net_set_graph(yp_u2net* e, int enable) {

@@ -5,12 +5,15 @@ The network itself (yolo_seg/tasks/models/U2Net.py:424-526: six RSU encoder stag
 fusion, sigmoid) runs only through the HIP library: dilated 3x3 convolutions with the folded BatchNorm + ReLU (+ the block
 residual) in the epilogue on the matrix cores, ceil-mode 2x2 max-pool, bilinear resize-to-size written straight into the concat
 buffer, and one tail kernel for side maps -> fusion -> sigmoid -> min-max normalisation -> mask. There is no CPU fallback.
+
+`unet_predict_clip` is the clip form of the app's per-frame `crop_frame` + `unet_predict` + paste (yolo_seg/app.py:127,183-186): the
+crops are cut from the uint8 frames on the device and run in batches, with normPRED per frame as the per-frame call has it.
 """
 from __future__ import annotations
 
 import ctypes as C
 import os
-from typing import Dict, List, Optional, Tuple
+from typing import Dict, List, Optional, Sequence, Tuple, Union
 
 import numpy as np
 import torch
@@ -103,13 +106,14 @@ def _declare(lib: C.CDLL) -> None:
     lib.yp_u2net_set_weight.argtypes = [vp, C.c_char_p, vp, C.POINTER(C.c_int64), C.c_int]
     lib.yp_u2net_finalize.argtypes = [vp]
     lib.yp_u2net_forward.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp]
+    lib.yp_u2net_forward_crops.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp]
     lib.yp_u2net_set_graph.argtypes = [vp, C.c_int]
     lib.yp_u2net_set_graph.restype = C.c_int
     lib.yp_u2net_tensor_count.argtypes = [vp]
     lib.yp_u2net_tensor_info.argtypes = [vp, C.c_int, C.c_char_p, C.c_int, C.POINTER(C.c_int)]
     lib.yp_u2net_tensor_read.argtypes = [vp, C.c_int, vp]
     for fn in ("yp_u2net_create", "yp_u2net_destroy", "yp_u2net_weight_count", "yp_u2net_weight_info", "yp_u2net_set_weight",
-               "yp_u2net_finalize", "yp_u2net_forward", "yp_u2net_tensor_count", "yp_u2net_tensor_info", "yp_u2net_tensor_read"):
+               "yp_u2net_finalize", "yp_u2net_forward", "yp_u2net_forward_crops", "yp_u2net_tensor_count", "yp_u2net_tensor_info", "yp_u2net_tensor_read"):
         getattr(lib, fn).restype = C.c_int
     lib._u2_declared = True
 
@@ -186,6 +190,41 @@ class U2NetEngine:
         self._last = im_bgr
         return prob, norm, mask
 
+    def forward_crops(self, frames: torch.Tensor, windows, frame_idx, crop_hw: Tuple[int, int], *, want_prob: bool = True,
+                      want_crop_mask: bool = True, frame_mask: Union[None, bool, torch.Tensor] = None):
+        """Crops of uint8 cuda frames [N,H,W,3] (BGR) -> (prob float32 [B,ch,cw], crop mask uint8 [B,ch,cw], frame mask uint8 [N,H,W]),
+        each None unless asked for. `windows` int [B,4] are clipped (x1,y1,x2,y2) windows (crop_window), `frame_idx` int [B] the frame of
+        each; every window fits in crop_hw = (ch, cw) and sits at its top-left, the rest of the crop is zero. normPRED runs per crop. The
+        frame mask (True = allocate, or a uint8 cuda [N,H,W] tensor to write into) gets every pixel of each named frame written: the crop
+        mask inside the window, 0 outside; frames no crop names are left as they are. Launches on the caller's current stream."""
+        if not (frames.is_cuda and frames.dtype == torch.uint8 and frames.dim() == 4 and frames.shape[-1] == 3):
+            raise TypeError("forward_crops expects uint8 CUDA frames [N,H,W,3]")
+        frames = frames.contiguous()
+        N, H, W, _ = frames.shape
+        win = np.ascontiguousarray(np.asarray(windows, dtype=np.int32).reshape(-1, 4))
+        fidx = np.ascontiguousarray(np.asarray(frame_idx, dtype=np.int32).reshape(-1))
+        if win.shape[0] != fidx.shape[0]:
+            raise ValueError(f"{win.shape[0]} windows but {fidx.shape[0]} frame indices")
+        B = win.shape[0]
+        ch, cw = (int(v) for v in crop_hw)
+        dev = frames.device
+        prob = torch.empty((B, ch, cw), dtype=torch.float32, device=dev) if want_prob else None
+        cmask = torch.empty((B, ch, cw), dtype=torch.uint8, device=dev) if want_crop_mask else None
+        if frame_mask is True:
+            frame_mask = torch.empty((N, H, W), dtype=torch.uint8, device=dev)
+        elif frame_mask is False:
+            frame_mask = None
+        if frame_mask is not None and not (frame_mask.device == dev and frame_mask.dtype == torch.uint8 and tuple(frame_mask.shape) == (N, H, W)
+                                           and frame_mask.is_contiguous()):
+            raise TypeError(f"frame_mask must be a contiguous uint8 tensor [{N},{H},{W}] on {dev}")
+
+        def ptr(t):
+            return C.c_void_p(t.data_ptr() if t is not None else None)
+        self._chk(self.lib.yp_u2net_forward_crops(self._h, ptr(frames), N, H, W, win.ctypes.data_as(C.c_void_p), fidx.ctypes.data_as(C.c_void_p),
+                                                  B, ch, cw, ptr(prob), ptr(cmask), ptr(frame_mask),
+                                                  C.c_void_p(int(torch.cuda.current_stream(dev).cuda_stream))))
+        return prob, cmask, frame_mask
+
     def tensors(self) -> List[dict]:
         n = self._chk(self.lib.yp_u2net_tensor_count(self._h))
         name = C.create_string_buffer(256)
@@ -225,3 +264,123 @@ def unet_predict(model: U2NetEngine, image: np.ndarray, device="cuda") -> np.nda
     x = torch.from_numpy(np.ascontiguousarray(image)).to(torch.device("cuda", model.device_index))[None]
     _, _, mask = model.forward(x)
     return mask[0].cpu().numpy()
+
+
+# ---- the app's crop + predict + paste over a whole clip (yolo_seg/app.py:127,183-186) ---------------------------------------------------
+U2_OFFSET_LIMIT = 1 << 31          # plan_u2 (u2net.hip): B x H x W x 128 channels x 4 bytes must stay below 2^31
+
+
+def crop_window(box: Sequence[int], height: int, width: int, crop_size: int = 380) -> Tuple[Tuple[int, int, int, int], Tuple[int, int]]:
+    """crop_frame(frame, box, crop_size, need_padding=False) (yolo_seg/utils/transform.py:22-50) as geometry: ((x1, y1, x2, y2), (ch, cw)).
+
+    The centre is int((x1+x2)/2), int((y1+y2)/2); the window [c - crop_size//2, c + crop_size//2) is clipped to the frame and returned as
+    crop_frame returns it. Its padding test reads `if need_padding and h < crop_size or w < crop_size`, which Python groups as
+    `(need_padding and h < crop_size) or (w < crop_size)`: with need_padding=False only a window narrower than crop_size is padded, to
+    crop_size x crop_size with the window at the top-left. A full-width window stays unpadded, (y2-y1) x crop_size, also when it is short.
+    classify.crop_geometry is the need_padding=True sibling (the classifier's crops are always crop_size^2)."""
+    x1, y1, x2, y2 = (int(v) for v in box)
+    cx, cy = int((x1 + x2) / 2), int((y1 + y2) / 2)
+    half = crop_size // 2
+    wx1, wy1 = max(0, cx - half), max(0, cy - half)
+    wx2, wy2 = min(int(width), cx + half), min(int(height), cy + half)
+    if max(0, wx2 - wx1) < crop_size:
+        shape = (crop_size, crop_size)
+    else:
+        shape = (wy2 - wy1, wx2 - wx1)
+    return (wx1, wy1, wx2, wy2), shape
+
+
+def max_crops_per_call(ch: int, cw: int) -> int:
+    """The most ch x cw crops one yp_u2net_forward_crops call takes (the engine's 32-bit offset guard)."""
+    return (U2_OFFSET_LIMIT - 1) // (int(ch) * int(cw) * 128 * 4)
+
+
+def clip_chunks(shapes: Sequence[Tuple[int, int]], batch_size: int = 16) -> List[Tuple[Tuple[int, int], List[int]]]:
+    """Group frame indices by crop shape (first appearance order) and split each group into chunks whose sizes are powers of two, the
+    largest first, capped by batch_size and by max_crops_per_call: each shape meets at most log2(batch_size)+1 batch sizes, so at most
+    that many engine plans (and tuning passes)."""
+    if int(batch_size) < 1:
+        raise ValueError(f"batch_size must be >= 1 (got {batch_size})")
+    groups: Dict[Tuple[int, int], List[int]] = {}
+    for i, s in enumerate(shapes):
+        groups.setdefault((int(s[0]), int(s[1])), []).append(i)
+    out: List[Tuple[Tuple[int, int], List[int]]] = []
+    for shape, idx in groups.items():
+        cap = min(int(batch_size), max_crops_per_call(*shape))
+        if cap < 1:
+            raise ValueError(f"a {shape[0]}x{shape[1]} crop is too large for the engine")
+        top = 1 << (cap.bit_length() - 1)
+        k = 0
+        while k < len(idx):
+            n = top
+            while n > len(idx) - k:
+                n >>= 1
+            out.append((shape, idx[k:k + n]))
+            k += n
+    return out
+
+
+def unet_predict_clip(model: U2NetEngine, frames, boxes, device="cuda", *, batch_size: int = 16, full_frame: bool = False):
+    """The app's loop body `crop_frame(frame, box)` -> `unet_predict(model, crop)` -> paste into a full-frame mask, for a whole clip.
+
+    frames: a list of same-shape BGR uint8 HWC ndarrays, or a uint8 CUDA tensor [N,H,W,3]; boxes: one integer xyxy per frame (the app's
+    yolo_pred_xyxy). Returns [(mask, (x1, y1, x2, y2)), ...] in input order, mask being the uint8 {0,255} ndarray
+    unet_predict(model, crop_frame(frame, box)[0]) returns (normPRED per frame, the zero pad included); with full_frame=True a uint8 CUDA
+    tensor [N,H,W] instead: each frame's crop mask pasted at its window, 0 elsewhere (the app's paste, which raises in the reference when
+    the crop is padded). Frames are grouped by crop shape and run batch_size at a time (clip_chunks); host frames go
+    up one chunk at a time. `device` is accepted for the reference's signature; the engine's device is used."""
+    on_dev = isinstance(frames, torch.Tensor)
+    if on_dev:
+        if not (frames.is_cuda and frames.dtype == torch.uint8 and frames.dim() == 4 and frames.shape[-1] == 3):
+            raise TypeError("unet_predict_clip expects BGR uint8 HWC ndarrays or a uint8 CUDA tensor [N,H,W,3]")
+        N, H, W = (int(v) for v in frames.shape[:3])
+    else:
+        frames = list(frames)
+        N = len(frames)
+        for f in frames:
+            if not (isinstance(f, np.ndarray) and f.dtype == np.uint8 and f.ndim == 3 and f.shape[2] == 3):
+                raise TypeError("unet_predict_clip expects BGR uint8 HWC ndarrays or a uint8 CUDA tensor [N,H,W,3]")
+            if f.shape != frames[0].shape:
+                raise ValueError(f"frames differ in shape: {f.shape} vs {frames[0].shape}")
+        H, W = (int(v) for v in frames[0].shape[:2]) if N else (0, 0)
+    boxes = list(boxes)
+    if len(boxes) != N:
+        raise ValueError(f"{N} frames but {len(boxes)} boxes")
+    if int(batch_size) < 1:
+        raise ValueError(f"batch_size must be >= 1 (got {batch_size})")
+    if N == 0:
+        return []
+    geo = [crop_window(b, H, W) for b in boxes]
+    for i, ((x1, y1, x2, y2), _) in enumerate(geo):
+        if x2 <= x1 or y2 <= y1:
+            raise ValueError(f"frame {i}: box {tuple(boxes[i])} has its centre outside the {W}x{H} frame")
+    chunks = clip_chunks([g[1] for g in geo], batch_size)
+
+    dev = torch.device("cuda", model.device_index)
+    if on_dev:
+        if frames.device != dev:
+            raise ValueError(f"frames are on {frames.device}, the engine on {dev}")
+        frames = frames.contiguous()
+    full = torch.empty((N, H, W), dtype=torch.uint8, device=dev) if full_frame else None
+    pending = []
+    for shape, idx in chunks:
+        win = np.array([geo[i][0] for i in idx], dtype=np.int32)
+        if on_dev:
+            _, cm, _ = model.forward_crops(frames, win, np.array(idx, dtype=np.int32), shape, want_prob=False, want_crop_mask=not full_frame,
+                                           frame_mask=full)
+        else:
+            up = torch.from_numpy(np.stack([frames[i] for i in idx])).to(dev)
+            _, cm, fm = model.forward_crops(up, win, np.arange(len(idx), dtype=np.int32), shape, want_prob=False,
+                                            want_crop_mask=not full_frame, frame_mask=full_frame)
+            if full_frame:
+                full.index_copy_(0, torch.tensor(idx, dtype=torch.long, device=dev), fm)
+        if not full_frame:
+            pending.append((idx, cm))
+    if full_frame:
+        return full
+    out: List = [None] * N
+    for idx, cm in pending:
+        host = cm.cpu().numpy()
+        for j, i in enumerate(idx):
+            out[i] = (host[j], geo[i][0])
+    return out
