@@ -540,3 +540,23 @@ def test_tuning_export_import_reproduces_bits():
     with pytest.raises(YolopError):
         b.tuning_import(*shape, bad)
     b.close()
+
+
+def test_forward_reads_only_its_own_frames():
+    """Two forwards on different frames: the second equals a fresh engine's forward on its frames, bit for bit. A fused pair whose
+    stored intermediate has a reader between the pair's two ops (v10-S at small shapes: model.19.cv2 -> one2one_cv3.1.0.0 past the
+    SCDown model.20) would hand that reader the previous forward's values."""
+    from helpers import rand_image
+    from yolo_puncture_amd.engine import Engine
+    st, im_a = make_case("s", 80, False, 0, (2, 96, 128))
+    im_b = rand_image(tuple(im_a.shape), seed=7)
+    outs = []
+    for frames in ((im_a, im_b), (im_b,)):
+        eng = Engine("s", 80, False, "bf16", 0, state=st)
+        eng.set_autotune(False)
+        for im in frames:
+            out = eng.forward(im.cuda())
+        torch.cuda.synchronize()
+        outs.append({k: out[k].cpu().clone() for k in ("det", "idx")})
+        eng.close()
+    assert torch.equal(outs[0]["idx"], outs[1]["idx"]) and torch.equal(outs[0]["det"], outs[1]["det"])

@@ -58,6 +58,19 @@ struct WeightDesc {
     size_t mat_bytes = 0;      // bytes of one packed GEMM matrix
 };
 
+// How a launching op runs (a plan decision). The ops whose work a fused form takes over are skipped.
+enum Form {
+    FORM_PLAIN = 0,       // the op's own kernel
+    FORM_DWPW,            // OP_CONV 1x1: the depthwise 3x3 in front (fuse_dw) and this conv as conv_dwpw_kernel
+    FORM_DWPW_TAIL,       // OP_CONV 1x1 logits: dw -> pw (fuse_tail) -> this conv (+ the class-max keys of tail_amax) as conv_dwpw_kernel's TAIL form
+    FORM_S2PW,            // OP_CONV 1x1: the 3x3 s2 conv in front (fuse_pre) and this conv as conv_halo_s2's PW2 form
+    FORM_FRONTEND,        // OP_CONV 1x1: stem (stem_op) -> 3x3 s2 (fuse_pre) -> this conv as frontend_kernel
+    FORM_C2F,             // OP_CONV 1x1: the bottleneck's two 3x3 convs (c2f_m1, c2f_m2) and this conv as c2f_fused_kernel
+    FORM_SCDOWN,          // OP_DWCONV 3x3 s2: the 1x1 in front (scd_pre) and this op as scdown_fused_kernel
+    FORM_PWSP,            // OP_DWCONV / OP_POOL3: the 1x1 in front (pw_pre) and this op as pwsp_kernel
+    FORM_CLS_OUT,         // OP_CONV logits: logits and the class-max keys of amax_post in one cls_out_kernel launch
+};
+
 struct Op {
     int kind = OP_CONV;
     std::string name;
@@ -73,26 +86,19 @@ struct Op {
     std::string kernel;           // device kernel symbol this op launches (filled by the plan)
     int cfg = -1;                 // autotuned conv_dma configuration (-1: heuristic)
     int fuse_dw = -1;             // OP_CONV 1x1: index of the depthwise 3x3 op feeding it that can be fused in (graph pass)
-    bool fused = false;           // plan decision: this conv runs as the fused dw->pw kernel
+    Form form = FORM_PLAIN;       // plan decision: launch form
     bool skip = false;            // plan decision: this op's work is done by a fused consumer
     int fuse_pre = -1;            // OP_CONV 1x1: index of the 3x3 stride-2 conv feeding it that can run as the first stage of one kernel
-    bool fused2 = false;          // plan decision: this 1x1 runs as the second stage of conv_halo_s2's PW2 form
-    int stem_op = -1;             // fused2 whose first stage reads the stem's output: index of the stem op
-    bool fused3 = false;          // plan decision: stem -> 3x3 s2 -> this 1x1 run as frontend_kernel
+    int stem_op = -1;             // FORM_FRONTEND: index of the stem op
     int fold_up = -1;             // OP_CONV 1x1 on a [upsampled | skip] concat: index of the nearest-x2 upsample op it can absorb
     bool folded = false;          // plan decision: the upsample is folded into this conv's input gather
     int c2f_m1 = -1, c2f_m2 = -1; // OP_CONV 1x1 closing a C2f with one plain bottleneck: indices of the bottleneck's two 3x3 convs
-    bool fused4 = false;          // plan decision: both 3x3 convs and this 1x1 run as c2f_fused_kernel
     int scd_pre = -1;             // OP_DWCONV 3x3 s2 closing an SCDown: index of the 1x1 conv in front of it
-    bool fused5 = false;          // plan decision: that 1x1 and this depthwise conv run as scdown_fused_kernel
     int fuse_tail = -1, tail_amax = -1;   // OP_CONV 1x1 without activation (fp32 logits): index of the dw->pw pointwise conv feeding it that can take it
                                   // on as a third stage, and of the OP_AMAX op behind it (or -1)
-    bool fused6 = false;          // plan decision: dw -> pw -> this 1x1 (+ the class-max keys) run as conv_dwpw_kernel's TAIL form
     int amax_post = -1;           // OP_CONV 1x1 that writes a level's fp32 class logits: index of the OP_AMAX op that reads them (graph pass)
-    bool fused8 = false;          // plan decision: logits and class-max keys come out of one cls_out_kernel launch; the OP_AMAX op is skipped
     int pw_pre = -1;              // OP_DWCONV (3x3 / 7x7, stride 1) / OP_POOL3: index of the 1x1 conv that produces its input and can run as the first stage of pwsp_kernel (graph pass)
-    bool fused7 = false;          // plan decision: that 1x1 and this spatial op run as pwsp_kernel (one workgroup per image and channel slice); the 1x1 is skipped
-    bool pw_store = false;        // fused7: the 1x1's own output has other readers and is written as well
+    bool pw_store = false;        // FORM_PWSP: the 1x1's own output has other readers and is written as well
     int lane = 0;                 // capture lane: independent head branches run on their own streams inside the hipGraph
     bool nms = false;             // OP_HEAD: conf filter + class-aware NMS (YOLOv8 / YOLO11) instead of the two-stage top-k (v10)
     int hb_box[3][3] = {{-1, -1, -1}, {-1, -1, -1}, {-1, -1, -1}}, hb_cf[3][3] = {{-1, -1, -1}, {-1, -1, -1}, {-1, -1, -1}};   // OP_HEAD (v10): op indices of the box / coefficient branch convs per level ({0,1,2} = 3x3, 3x3, 1x1), -1 = none
@@ -285,74 +291,36 @@ __device__ __forceinline__ void silu4_packed(float* v) {
 // launches (implemented in the .hip files); dtype selects the template instance
 hipError_t launch_conv(const ConvParams& p, int dtype, hipStream_t st);
 hipError_t launch_conv_igemm(const ConvParams& p, int dtype, hipStream_t st);   // always the register-staged kernel (dilation, ReLU, any Cin % 8 == 0)
-const char* conv_kernel_name(const ConvParams& p, int dtype);
+std::string conv_kernel_name(const ConvParams& p, int dtype);
 bool conv_cfg_usable(const ConvParams& p, int dtype, int cfg);   // a configuration id from a cache file / yp_tuning_import is launchable for p
-hipError_t launch_conv_dma(const ConvParams& p, hipStream_t st);
 bool conv_dma_supported(const ConvParams& p);
-const char* conv_dma_kernel_name(const ConvParams& p);
-int conv_dma_num_cfgs();
 void conv_dma_force_cfg(int cfg);
 int conv_dma_forced_cfg();
 void conv_set_debug_ablation(int v);
 int conv_debug_ablation();
 bool tile_balance_enabled(int family);  // tiles sized to whole rounds of workgroups? family 1 = conv_pxd, 2 = conv_wres, 4 = cls_out; YOLOP_BALANCE=<mask> (A/B switch)
-// halo-tiled 3x3 s1 kernel (conv_halo.hip); configuration ids are offset by 100 in ConvParams::cfg
-int conv_halo_num_cfgs();
-bool conv_halo_cfg_valid(const ConvParams& p, int c);
-const char* conv_halo_kernel_name(int c);
-hipError_t launch_conv_halo(const ConvParams& p, int c, hipStream_t st);
-// persistent im2col kernel (conv_dma_p.hip); ids offset by 300
-int conv_dma_p_num_cfgs();
-bool conv_dma_p_cfg_valid(const ConvParams& p, int c);
-const char* conv_dma_p_kernel_name(int c);
-hipError_t launch_conv_dma_p(const ConvParams& p, int c, hipStream_t st);
-int conv_tile1_num_cfgs();
-bool conv_tile1_cfg_valid(const ConvParams& p, int c);
-const char* conv_tile1_kernel_name(int c);
-hipError_t launch_conv_tile1(const ConvParams& p, int c, hipStream_t st);
-// K-split kernel for small pixel counts (conv_ks.hip); ids offset by 900
-int conv_ks_num_cfgs();
-bool conv_ks_cfg_valid(const ConvParams& p, int c);
-const char* conv_ks_kernel_name(int c);
-hipError_t launch_conv_ks(const ConvParams& p, int c, hipStream_t st);
-// weights-resident streaming 1x1 kernel (conv_wres.hip); ids offset by 1100
-int conv_wres_num_cfgs();
-bool conv_wres_cfg_valid(const ConvParams& p, int c);
-const char* conv_wres_kernel_name(int c);
-hipError_t launch_conv_wres(const ConvParams& p, int c, hipStream_t st);
 
-// weights-in-registers streaming 1x1 kernel (conv_wrs.hip); ids offset by 1200
-int conv_wrs_num_cfgs();
-bool conv_wrs_cfg_valid(const ConvParams& p, int c);
-const char* conv_wrs_kernel_name(int c);
-hipError_t launch_conv_wrs(const ConvParams& p, int c, hipStream_t st);
-
-// pixels-direct 1x1 kernel (conv_pxd.hip); ids offset by 800
-int conv_pxd_num_cfgs();
-bool conv_pxd_cfg_valid(const ConvParams& p, int c);
-const char* conv_pxd_kernel_name(int c);
-hipError_t launch_conv_pxd(const ConvParams& p, int c, hipStream_t st);
-// weights-in-registers 3x3 s1 kernel (conv_wreg.hip); ids offset by 700
-int conv_wreg_num_cfgs();
-bool conv_wreg_cfg_valid(const ConvParams& p, int c);
-const char* conv_wreg_kernel_name(int c);
-hipError_t launch_conv_wreg(const ConvParams& p, int c, hipStream_t st);
-int conv_halo_s2_num_cfgs();
-bool conv_halo_s2_cfg_valid(const ConvParams& p, int c);
-const char* conv_halo_s2_kernel_name(int c);
-hipError_t launch_conv_halo_s2(const ConvParams& p, int c, hipStream_t st);
+// One tile-kernel family of the dense conv. A configuration id (Op::cfg, ConvParams::cfg, the tune tables) in [base, base + num_cfgs) is
+// configuration id - base of that family; -1 is the heuristic (conv_dma or conv_igemm) and PWSP_CFG is launched by the engine itself.
+// conv_igemm.hip's kConvFamilies lists every family, in the order the autotuner times them.
+struct ConvFamily {
+    int base, num_cfgs;
+    bool (*valid)(const ConvParams& p, int c);
+    std::string (*symbol)(const ConvParams& p, int c);                    // the full kernel symbol launch() runs for p
+    hipError_t (*launch)(const ConvParams& p, int c, hipStream_t st);
+    bool two_source;                                                      // implements the folded-upsample gather (x2_C > 0)
+    const char* tune_env;                                                 // the tuner's A/B switch, null = always a candidate
+    bool opt_in;                                                          // tune_env = 1 adds the family instead of removing it
+};
+// ",HAS_RES,OUT_F32" of the persistent conv kernels, as their launchers pick the instance (out_f32 first)
+inline const char* res_f32_args(const ConvParams& p) { return p.out_f32 ? ",false,true" : p.res ? ",true,false" : ",false,false"; }
+// conv_dma (ids 0..) picks its configuration from p.cfg / the forced id itself and ignores c; conv_halo_s2 launches its fused trailing 1x1
+// form when p.C2 > 0 (configuration from conv_halo_s2_pw_cfg)
+extern const ConvFamily conv_dma_family, conv_halo_family, conv_halo_p_family, conv_dma_p_family, conv_dma_lc_family, conv_halo_s2_family,
+    conv_tile1_family, conv_wreg_family, conv_pxd_family, conv_ks_family, conv_wres_family, conv_wrs_family;
+constexpr int kNumConvFamilies = 12;
+extern const ConvFamily* const kConvFamilies[kNumConvFamilies];
 int conv_halo_s2_pw_cfg(const ConvParams& p);          // configuration for the fused trailing-1x1 form, or -1
-const char* conv_halo_s2_pw_kernel_name(int c);
-int conv_dma_lc_num_cfgs();
-bool conv_dma_lc_cfg_valid(const ConvParams& p, int c);
-const char* conv_dma_lc_kernel_name(int c);
-hipError_t launch_conv_dma_lc(const ConvParams& p, int c, hipStream_t st);
-// persistent weight-resident halo kernel (conv_halo_p.hip); ids offset by 200
-int conv_halo_p_num_cfgs();
-bool conv_halo_p_cfg_valid(const ConvParams& p, int c);
-const char* conv_halo_p_kernel_name(int c);
-hipError_t launch_conv_halo_p(const ConvParams& p, int c, hipStream_t st);
-bool conv_dma_cfg_valid(const ConvParams& p, int cfg);
 hipError_t launch_dwconv(const DwParams& p, int dtype, hipStream_t st);
 hipError_t launch_stem(const StemParams& p, int dtype, hipStream_t st);
 hipError_t launch_pool5(const PoolParams& p, int dtype, hipStream_t st);

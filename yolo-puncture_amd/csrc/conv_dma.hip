@@ -264,13 +264,12 @@ static const DmaCfg kCfgs[] = {
 };
 constexpr int kNumCfgs = (int)(sizeof(kCfgs) / sizeof(kCfgs[0]));
 
-int conv_dma_num_cfgs() { return kNumCfgs; }
 
 bool conv_dma_supported(const ConvParams& p) {
     return (p.Cin % 32) == 0 && (p.Kpad % 32) == 0 && p.x_bytes < (1ull << 31) && p.w_bytes < (1ull << 31) && p.ks <= 3;
 }
 
-bool conv_dma_cfg_valid(const ConvParams& p, int c) {
+static bool conv_dma_cfg_valid(const ConvParams& p, int c) {
     if (c < 0 || c >= kNumCfgs || !conv_dma_supported(p)) return false;
     const DmaCfg& k = kCfgs[c];
     if (k.BK == 64 && ((p.Cin % 64) != 0 || (p.Kpad % 64) != 0)) return false;
@@ -300,7 +299,7 @@ static int dma_choice(const ConvParams& p) {
     return conv_dma_cfg_valid(p, p.cfg) ? p.cfg : dma_heuristic(p);
 }
 
-const char* conv_dma_kernel_name(const ConvParams& p) { return kCfgs[dma_choice(p)].name; }
+static std::string conv_dma_symbol(const ConvParams& p, int) { return kCfgs[dma_choice(p)].name; }
 
 template <int BM, int BN, int WGM, int WGN, int BK, int NS>
 static hipError_t launch_one(const ConvParams& p, hipStream_t st) {
@@ -317,7 +316,7 @@ static hipError_t launch_one(const ConvParams& p, hipStream_t st) {
     return hipGetLastError();
 }
 
-hipError_t launch_conv_dma(const ConvParams& p, hipStream_t st) {
+static hipError_t launch_conv_dma(const ConvParams& p, int, hipStream_t st) {
     switch (dma_choice(p)) {
         case 0: return launch_one<128, 32, 4, 1, 32, 4>(p, st);
         case 1: return launch_one<128, 64, 2, 2, 32, 4>(p, st);
@@ -335,5 +334,9 @@ hipError_t launch_conv_dma(const ConvParams& p, hipStream_t st) {
         default: return launch_one<64, 128, 2, 2, 64, 3>(p, st);
     }
 }
+
+#if !defined(__HIP_DEVICE_COMPILE__)      // (host data: the device pass must not reference the host functions)
+const ConvFamily conv_dma_family = {0, kNumCfgs, conv_dma_cfg_valid, conv_dma_symbol, launch_conv_dma, false, nullptr, false};
+#endif
 
 }  // namespace yp

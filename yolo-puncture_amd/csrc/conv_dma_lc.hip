@@ -264,21 +264,20 @@ __global__ __launch_bounds__((WGM * WGN + NL) * 64) void conv_dma_lc_kernel(cons
 // ---------------------------------------------------------------------------------------------------------------
 struct LcCfg { int BM, BN, NC, NL, BK, NS; const char* name; };
 static const LcCfg kL[] = {
-    {128, 128, 8, 8, 64, 4, "conv_dma_lc_kernel<128,128,4,2,8,64,4>"},   // 0: 16 waves
-    {128, 128, 4, 8, 32, 4, "conv_dma_lc_kernel<128,128,2,2,8,32,4>"},   // 1: 12 waves, 32-deep k-steps (Cin % 64 != 0)
-    {128, 64, 4, 8, 64, 4, "conv_dma_lc_kernel<128,64,2,2,8,64,4>"},     // 2: 12 waves
-    {128, 64, 8, 8, 64, 4, "conv_dma_lc_kernel<128,64,4,2,8,64,4>"},     // 3
-    {128, 128, 4, 8, 64, 4, "conv_dma_lc_kernel<128,128,2,2,8,64,4>"},   // 4: 12 waves, one consumer per SIMD
-    {256, 64, 8, 8, 64, 3, "conv_dma_lc_kernel<256,64,4,2,8,64,3>"},     // 5
-    {64, 64, 4, 4, 64, 4, "conv_dma_lc_kernel<64,64,2,2,4,64,4>"},       // 6: 8 waves, two workgroups per CU
-    {128, 64, 4, 12, 64, 4, "conv_dma_lc_kernel<128,64,2,2,12,64,4>"},   // 7: 16 waves, 24 pieces over 12 loaders
-    {64, 128, 4, 12, 64, 4, "conv_dma_lc_kernel<64,128,2,2,12,64,4>"},   // 8
+    {128, 128, 8, 8, 64, 4, "conv_dma_lc_kernel<128,128,4,2,8,64,4"},   // 0: 16 waves
+    {128, 128, 4, 8, 32, 4, "conv_dma_lc_kernel<128,128,2,2,8,32,4"},   // 1: 12 waves, 32-deep k-steps (Cin % 64 != 0)
+    {128, 64, 4, 8, 64, 4, "conv_dma_lc_kernel<128,64,2,2,8,64,4"},     // 2: 12 waves
+    {128, 64, 8, 8, 64, 4, "conv_dma_lc_kernel<128,64,4,2,8,64,4"},     // 3
+    {128, 128, 4, 8, 64, 4, "conv_dma_lc_kernel<128,128,2,2,8,64,4"},   // 4: 12 waves, one consumer per SIMD
+    {256, 64, 8, 8, 64, 3, "conv_dma_lc_kernel<256,64,4,2,8,64,3"},     // 5
+    {64, 64, 4, 4, 64, 4, "conv_dma_lc_kernel<64,64,2,2,4,64,4"},       // 6: 8 waves, two workgroups per CU
+    {128, 64, 4, 12, 64, 4, "conv_dma_lc_kernel<128,64,2,2,12,64,4"},   // 7: 16 waves, 24 pieces over 12 loaders
+    {64, 128, 4, 12, 64, 4, "conv_dma_lc_kernel<64,128,2,2,12,64,4"},   // 8
 };
 constexpr int kNumL = (int)(sizeof(kL) / sizeof(kL[0]));
-int conv_dma_lc_num_cfgs() { return kNumL; }
-const char* conv_dma_lc_kernel_name(int c) { return kL[c].name; }
+static std::string conv_dma_lc_symbol(const ConvParams& p, int c) { return std::string(kL[c].name) + res_f32_args(p) + ">"; }
 
-bool conv_dma_lc_cfg_valid(const ConvParams& p, int c) {
+static bool conv_dma_lc_cfg_valid(const ConvParams& p, int c) {
     if (c < 0 || c >= kNumL) return false;
     if ((p.Cin % 32) != 0 || (p.Kpad % 32) != 0 || p.ks > 3 || p.up != 1) return false;
     if (p.x_bytes >= (1ull << 31) || p.w_bytes >= (1ull << 31) || p.y_bytes >= (1ull << 31)) return false;
@@ -337,7 +336,7 @@ static hipError_t launch_lc_one(const ConvParams& p, hipStream_t st) {
     return launch_lc_var<BM, BN, WGM, WGN, NL, BK, NS, false, false>(p, st);
 }
 
-hipError_t launch_conv_dma_lc(const ConvParams& p, int c, hipStream_t st) {
+static hipError_t launch_conv_dma_lc(const ConvParams& p, int c, hipStream_t st) {
     switch (c) {
         case 0: return launch_lc_one<128, 128, 4, 2, 8, 64, 4>(p, st);
         case 1: return launch_lc_one<128, 128, 2, 2, 8, 32, 4>(p, st);
@@ -350,5 +349,9 @@ hipError_t launch_conv_dma_lc(const ConvParams& p, int c, hipStream_t st) {
         default: return launch_lc_one<64, 128, 2, 2, 12, 64, 4>(p, st);
     }
 }
+
+#if !defined(__HIP_DEVICE_COMPILE__)      // (host data: the device pass must not reference the host functions)
+const ConvFamily conv_dma_lc_family = {400, kNumL, conv_dma_lc_cfg_valid, conv_dma_lc_symbol, launch_conv_dma_lc, true, "YOLOP_NO_LC", false};
+#endif
 
 }  // namespace yp

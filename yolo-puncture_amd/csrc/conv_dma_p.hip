@@ -416,55 +416,54 @@ __global__ __launch_bounds__(WGM * WGN * 64) void conv_dma_p_kernel(const ConvPa
 // ---------------------------------------------------------------------------------------------------------------
 struct DmaPCfg { int BM, BN, NW, BK, NS; const char* name; int wres; int pipe; int pp; };
 static const DmaPCfg kP[] = {
-    {128, 32, 4, 32, 4, "conv_dma_p_kernel<128,32,4,1,32,4>"},     // 0
-    {128, 64, 4, 32, 4, "conv_dma_p_kernel<128,64,2,2,32,4>"},     // 1
-    {128, 128, 4, 32, 4, "conv_dma_p_kernel<128,128,2,2,32,4>"},   // 2
-    {64, 64, 4, 32, 4, "conv_dma_p_kernel<64,64,2,2,32,4>"},       // 3
-    {256, 64, 8, 32, 4, "conv_dma_p_kernel<256,64,4,2,32,4>"},     // 4
-    {256, 128, 8, 32, 4, "conv_dma_p_kernel<256,128,4,2,32,4>"},   // 5
-    {128, 128, 4, 64, 3, "conv_dma_p_kernel<128,128,2,2,64,3>"},   // 6
-    {128, 64, 4, 64, 3, "conv_dma_p_kernel<128,64,2,2,64,3>"},     // 7
-    {128, 256, 8, 32, 4, "conv_dma_p_kernel<128,256,2,4,32,4>"},   // 8
-    {64, 128, 4, 64, 3, "conv_dma_p_kernel<64,128,2,2,64,3>"},     // 9
-    {64, 64, 4, 64, 4, "conv_dma_p_kernel<64,64,2,2,64,4>"},       // 10
-    {128, 64, 8, 64, 4, "conv_dma_p_kernel<128,64,4,2,64,4>"},     // 11
+    {128, 32, 4, 32, 4, "conv_dma_p_kernel<128,32,4,1,32,4"},     // 0
+    {128, 64, 4, 32, 4, "conv_dma_p_kernel<128,64,2,2,32,4"},     // 1
+    {128, 128, 4, 32, 4, "conv_dma_p_kernel<128,128,2,2,32,4"},   // 2
+    {64, 64, 4, 32, 4, "conv_dma_p_kernel<64,64,2,2,32,4"},       // 3
+    {256, 64, 8, 32, 4, "conv_dma_p_kernel<256,64,4,2,32,4"},     // 4
+    {256, 128, 8, 32, 4, "conv_dma_p_kernel<256,128,4,2,32,4"},   // 5
+    {128, 128, 4, 64, 3, "conv_dma_p_kernel<128,128,2,2,64,3"},   // 6
+    {128, 64, 4, 64, 3, "conv_dma_p_kernel<128,64,2,2,64,3"},     // 7
+    {128, 256, 8, 32, 4, "conv_dma_p_kernel<128,256,2,4,32,4"},   // 8
+    {64, 128, 4, 64, 3, "conv_dma_p_kernel<64,128,2,2,64,3"},     // 9
+    {64, 64, 4, 64, 4, "conv_dma_p_kernel<64,64,2,2,64,4"},       // 10
+    {128, 64, 8, 64, 4, "conv_dma_p_kernel<128,64,4,2,64,4"},     // 11
     // weight-resident forms (ids 12..): the [BN][K] weight block stays in LDS, only the pixel tile streams
-    {128, 64, 4, 32, 4, "conv_dma_p_kernel<128,64,2,2,32,4,W>", 1},   // 12
-    {128, 64, 4, 64, 4, "conv_dma_p_kernel<128,64,2,2,64,4,W>", 1},   // 13
-    {64, 64, 4, 32, 4, "conv_dma_p_kernel<64,64,2,2,32,4,W>", 1},     // 14
-    {64, 64, 4, 64, 4, "conv_dma_p_kernel<64,64,2,2,64,4,W>", 1},     // 15
-    {128, 128, 4, 64, 3, "conv_dma_p_kernel<128,128,2,2,64,3,W>", 1}, // 16
-    {128, 128, 8, 64, 4, "conv_dma_p_kernel<128,128,4,2,64,4,W>", 1}, // 17
-    {128, 32, 4, 32, 4, "conv_dma_p_kernel<128,32,4,1,32,4,W>", 1},   // 18
-    {256, 64, 8, 64, 3, "conv_dma_p_kernel<256,64,4,2,64,3,W>", 1},   // 19
-    {128, 256, 8, 64, 3, "conv_dma_p_kernel<128,256,2,4,64,3,W>", 1}, // 20
+    {128, 64, 4, 32, 4, "conv_dma_p_kernel<128,64,2,2,32,4", 1},   // 12
+    {128, 64, 4, 64, 4, "conv_dma_p_kernel<128,64,2,2,64,4", 1},   // 13
+    {64, 64, 4, 32, 4, "conv_dma_p_kernel<64,64,2,2,32,4", 1},     // 14
+    {64, 64, 4, 64, 4, "conv_dma_p_kernel<64,64,2,2,64,4", 1},     // 15
+    {128, 128, 4, 64, 3, "conv_dma_p_kernel<128,128,2,2,64,3", 1}, // 16
+    {128, 128, 8, 64, 4, "conv_dma_p_kernel<128,128,4,2,64,4", 1}, // 17
+    {128, 32, 4, 32, 4, "conv_dma_p_kernel<128,32,4,1,32,4", 1},   // 18
+    {256, 64, 8, 64, 3, "conv_dma_p_kernel<256,64,4,2,64,3", 1},   // 19
+    {128, 256, 8, 64, 3, "conv_dma_p_kernel<128,256,2,4,64,3", 1}, // 20
     // software-pipelined fragment forms (ids 21..)
-    {256, 128, 8, 32, 4, "conv_dma_p_kernel<256,128,4,2,32,4,P>", 0, 1},     // 21
-    {256, 64, 8, 32, 4, "conv_dma_p_kernel<256,64,4,2,32,4,P>", 0, 1},       // 22
-    {128, 256, 8, 32, 4, "conv_dma_p_kernel<128,256,2,4,32,4,P>", 0, 1},     // 23
-    {128, 128, 4, 32, 4, "conv_dma_p_kernel<128,128,2,2,32,4,P>", 0, 1},     // 24
-    {128, 64, 4, 32, 4, "conv_dma_p_kernel<128,64,2,2,32,4,P>", 0, 1},       // 25
-    {64, 64, 4, 32, 4, "conv_dma_p_kernel<64,64,2,2,32,4,P>", 0, 1},         // 26
-    {64, 64, 4, 64, 4, "conv_dma_p_kernel<64,64,2,2,64,4,P>", 0, 1},         // 27
-    {128, 64, 8, 64, 4, "conv_dma_p_kernel<128,64,4,2,64,4,P>", 0, 1},       // 28
-    {128, 128, 8, 64, 4, "conv_dma_p_kernel<128,128,4,2,64,4,W,P>", 1, 1},   // 29
-    {64, 64, 4, 64, 4, "conv_dma_p_kernel<64,64,2,2,64,4,W,P>", 1, 1},       // 30
-    {128, 64, 4, 64, 4, "conv_dma_p_kernel<128,64,2,2,64,4,W,P>", 1, 1},     // 31
-    {128, 128, 8, 64, 4, "conv_dma_p_kernel<128,128,4,2,64,4,P>", 0, 1},     // 32
+    {256, 128, 8, 32, 4, "conv_dma_p_kernel<256,128,4,2,32,4", 0, 1},     // 21
+    {256, 64, 8, 32, 4, "conv_dma_p_kernel<256,64,4,2,32,4", 0, 1},       // 22
+    {128, 256, 8, 32, 4, "conv_dma_p_kernel<128,256,2,4,32,4", 0, 1},     // 23
+    {128, 128, 4, 32, 4, "conv_dma_p_kernel<128,128,2,2,32,4", 0, 1},     // 24
+    {128, 64, 4, 32, 4, "conv_dma_p_kernel<128,64,2,2,32,4", 0, 1},       // 25
+    {64, 64, 4, 32, 4, "conv_dma_p_kernel<64,64,2,2,32,4", 0, 1},         // 26
+    {64, 64, 4, 64, 4, "conv_dma_p_kernel<64,64,2,2,64,4", 0, 1},         // 27
+    {128, 64, 8, 64, 4, "conv_dma_p_kernel<128,64,4,2,64,4", 0, 1},       // 28
+    {128, 128, 8, 64, 4, "conv_dma_p_kernel<128,128,4,2,64,4", 1, 1},   // 29
+    {64, 64, 4, 64, 4, "conv_dma_p_kernel<64,64,2,2,64,4", 1, 1},       // 30
+    {128, 64, 4, 64, 4, "conv_dma_p_kernel<128,64,2,2,64,4", 1, 1},     // 31
+    {128, 128, 8, 64, 4, "conv_dma_p_kernel<128,128,4,2,64,4", 0, 1},     // 32
     // ping-pong forms (ids 33..): the two waves of each SIMD alternate between a load segment and a matrix burst
-    {256, 128, 8, 32, 4, "conv_dma_p_kernel<256,128,4,2,32,4,Q>", 0, 0, 1},     // 33
-    {256, 64, 8, 32, 4, "conv_dma_p_kernel<256,64,4,2,32,4,Q>", 0, 0, 1},       // 34
-    {128, 256, 8, 32, 4, "conv_dma_p_kernel<128,256,2,4,32,4,Q>", 0, 0, 1},     // 35
-    {128, 128, 8, 64, 4, "conv_dma_p_kernel<128,128,4,2,64,4,Q>", 0, 0, 1},     // 36
-    {128, 64, 8, 64, 4, "conv_dma_p_kernel<128,64,4,2,64,4,Q>", 0, 0, 1},       // 37
-    {128, 128, 8, 64, 4, "conv_dma_p_kernel<128,128,4,2,64,4,W,Q>", 1, 0, 1},   // 38
-    {256, 64, 8, 64, 3, "conv_dma_p_kernel<256,64,4,2,64,3,W,Q>", 1, 0, 1},     // 39
-    {256, 128, 8, 64, 3, "conv_dma_p_kernel<256,128,4,2,64,3,Q>", 0, 0, 1},     // 40 (3 x 48 KiB stages)
+    {256, 128, 8, 32, 4, "conv_dma_p_kernel<256,128,4,2,32,4", 0, 0, 1},     // 33
+    {256, 64, 8, 32, 4, "conv_dma_p_kernel<256,64,4,2,32,4", 0, 0, 1},       // 34
+    {128, 256, 8, 32, 4, "conv_dma_p_kernel<128,256,2,4,32,4", 0, 0, 1},     // 35
+    {128, 128, 8, 64, 4, "conv_dma_p_kernel<128,128,4,2,64,4", 0, 0, 1},     // 36
+    {128, 64, 8, 64, 4, "conv_dma_p_kernel<128,64,4,2,64,4", 0, 0, 1},       // 37
+    {128, 128, 8, 64, 4, "conv_dma_p_kernel<128,128,4,2,64,4", 1, 0, 1},   // 38
+    {256, 64, 8, 64, 3, "conv_dma_p_kernel<256,64,4,2,64,3", 1, 0, 1},     // 39
+    {256, 128, 8, 64, 3, "conv_dma_p_kernel<256,128,4,2,64,3", 0, 0, 1},     // 40 (3 x 48 KiB stages)
 };
 constexpr int kNumP = (int)(sizeof(kP) / sizeof(kP[0]));
-int conv_dma_p_num_cfgs() { return kNumP; }
 
-bool conv_dma_p_cfg_valid(const ConvParams& p, int c) {
+static bool conv_dma_p_cfg_valid(const ConvParams& p, int c) {
     if (c < 0 || c >= kNumP) return false;
     if ((p.Cin % 32) != 0 || (p.Kpad % 32) != 0 || p.ks > 3 || p.up != 1) return false;
     if (p.x_bytes >= (1ull << 31) || p.w_bytes >= (1ull << 31) || p.y_bytes >= (1ull << 31)) return false;
@@ -482,7 +481,10 @@ bool conv_dma_p_cfg_valid(const ConvParams& p, int c) {
     }
     return true;
 }
-const char* conv_dma_p_kernel_name(int c) { return kP[c].name; }
+static std::string conv_dma_p_symbol(const ConvParams& p, int c) {
+    const DmaPCfg& k = kP[c];
+    return std::string(k.name) + res_f32_args(p) + (k.wres ? ",true" : ",false") + (k.pipe ? ",true" : ",false") + (k.pp ? ",true>" : ",false>");
+}
 
 template <int BM, int BN, int WGM, int WGN, int BK, int NS, bool HAS_RES, bool OUT_F32, bool WRES, bool PIPE, bool PP>
 static hipError_t launch_p_var(const ConvParams& p, hipStream_t st) {
@@ -509,7 +511,7 @@ static hipError_t launch_p_one(const ConvParams& p, hipStream_t st) {
     return launch_p_var<BM, BN, WGM, WGN, BK, NS, false, false, WRES, PIPE, PP>(p, st);
 }
 
-hipError_t launch_conv_dma_p(const ConvParams& p, int c, hipStream_t st) {
+static hipError_t launch_conv_dma_p(const ConvParams& p, int c, hipStream_t st) {
     switch (c) {
         case 0: return launch_p_one<128, 32, 4, 1, 32, 4>(p, st);
         case 1: return launch_p_one<128, 64, 2, 2, 32, 4>(p, st);
@@ -554,5 +556,9 @@ hipError_t launch_conv_dma_p(const ConvParams& p, int c, hipStream_t st) {
         default: return launch_p_one<256, 128, 4, 2, 64, 3, false, false, true>(p, st);
     }
 }
+
+#if !defined(__HIP_DEVICE_COMPILE__)      // (host data: the device pass must not reference the host functions)
+const ConvFamily conv_dma_p_family = {300, kNumP, conv_dma_p_cfg_valid, conv_dma_p_symbol, launch_conv_dma_p, true, nullptr, false};
+#endif
 
 }  // namespace yp

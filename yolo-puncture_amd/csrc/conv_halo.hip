@@ -252,9 +252,8 @@ static const HaloCfg kHalo[] = {
 };
 constexpr int kNumHalo = 4;
 
-int conv_halo_num_cfgs() { return kNumHalo; }
 
-bool conv_halo_cfg_valid(const ConvParams& p, int c) {
+static bool conv_halo_cfg_valid(const ConvParams& p, int c) {
     if (c < 0 || c >= kNumHalo) return false;
     if (p.ks != 3 || p.stride != 1 || p.pad != 1 || p.up != 1 || (p.Cin % 32) != 0 || (p.Kpad != 9 * p.Cin)) return false;
     if (p.x_bytes >= (1ull << 31) || p.w_bytes >= (1ull << 31)) return false;
@@ -268,7 +267,7 @@ bool conv_halo_cfg_valid(const ConvParams& p, int c) {
     return true;
 }
 
-const char* conv_halo_kernel_name(int c) { return kHalo[c].name; }
+static std::string conv_halo_symbol(const ConvParams& p, int c) { return kHalo[c].name; }
 
 template <int FM, int FN, int WGM, int WGN>
 static hipError_t launch_halo_one(const ConvParams& p, hipStream_t st) {
@@ -289,7 +288,7 @@ static hipError_t launch_halo_one(const ConvParams& p, hipStream_t st) {
     return hipGetLastError();
 }
 
-hipError_t launch_conv_halo(const ConvParams& p, int c, hipStream_t st) {
+static hipError_t launch_conv_halo(const ConvParams& p, int c, hipStream_t st) {
     switch (c) {
         case 0: return launch_halo_one<8, 2, 2, 2>(p, st);
         case 1: return launch_halo_one<4, 2, 4, 1>(p, st);
@@ -297,5 +296,9 @@ hipError_t launch_conv_halo(const ConvParams& p, int c, hipStream_t st) {
         default: return launch_halo_one<4, 2, 4, 2>(p, st);
     }
 }
+
+#if !defined(__HIP_DEVICE_COMPILE__)      // (host data: the device pass must not reference the host functions)
+const ConvFamily conv_halo_family = {100, kNumHalo, conv_halo_cfg_valid, conv_halo_symbol, launch_conv_halo, false, nullptr, false};
+#endif
 
 }  // namespace yp

@@ -245,17 +245,16 @@ __global__ __launch_bounds__(WGM * WGN * 64) void conv_halo_p_kernel(const ConvP
 // ---------------------------------------------------------------------------------------------------------------
 struct HaloPCfg { int FM, FN, WGM, WGN; const char* name; };
 static const HaloPCfg kHaloP[] = {
-    {4, 2, 4, 1, "conv_halo_p_kernel<4,2,4,1,3>"},   // 0: 16x16 px x 32 ch, 4 waves
-    {8, 2, 2, 2, "conv_halo_p_kernel<8,2,2,2,3>"},   // 1: 16x16 px x 64 ch, 4 waves
-    {4, 2, 4, 2, "conv_halo_p_kernel<4,2,4,2,3>"},   // 2: 16x16 px x 64 ch, 8 waves
-    {4, 2, 2, 2, "conv_halo_p_kernel<4,2,2,2,3>"},   // 3:  8x16 px x 64 ch, 4 waves
-    {4, 2, 2, 1, "conv_halo_p_kernel<4,2,2,1,3>"},   // (2 waves: not instantiated)
-    {2, 2, 4, 1, "conv_halo_p_kernel<2,2,4,1,3>"},   // 4:  8x16 px x 32 ch, 4 waves
+    {4, 2, 4, 1, "conv_halo_p_kernel<4,2,4,1,3"},   // 0: 16x16 px x 32 ch, 4 waves
+    {8, 2, 2, 2, "conv_halo_p_kernel<8,2,2,2,3"},   // 1: 16x16 px x 64 ch, 4 waves
+    {4, 2, 4, 2, "conv_halo_p_kernel<4,2,4,2,3"},   // 2: 16x16 px x 64 ch, 8 waves
+    {4, 2, 2, 2, "conv_halo_p_kernel<4,2,2,2,3"},   // 3:  8x16 px x 64 ch, 4 waves
+    {4, 2, 2, 1, "conv_halo_p_kernel<4,2,2,1,3"},   // (2 waves: not instantiated)
+    {2, 2, 4, 1, "conv_halo_p_kernel<2,2,4,1,3"},   // 4:  8x16 px x 32 ch, 4 waves
 };
 constexpr int kNumHaloP = 5;
 static const int kHaloPIdx[kNumHaloP] = {0, 1, 2, 3, 5};
 
-int conv_halo_p_num_cfgs() { return kNumHaloP; }
 
 static size_t halo_p_lds(const HaloPCfg& k, int Cin) {
     const int NW = k.WGM * k.WGN, TH = k.WGM * k.FM, BN = k.WGN * k.FN * 16;
@@ -264,7 +263,7 @@ static size_t halo_p_lds(const HaloPCfg& k, int Cin) {
     return (size_t)3 * H_INSTR * 1024 + 1024 + (size_t)9 * (Cin / 32) * BN * 64;
 }
 
-bool conv_halo_p_cfg_valid(const ConvParams& p, int c) {
+static bool conv_halo_p_cfg_valid(const ConvParams& p, int c) {
     if (c < 0 || c >= kNumHaloP) return false;
     if (p.ks != 3 || p.stride != 1 || p.pad != 1 || p.up != 1 || (p.Cin % 32) != 0 || (p.Kpad != 9 * p.Cin)) return false;
     if (p.x_bytes >= (1ull << 31) || p.w_bytes >= (1ull << 31) || p.y_bytes >= (1ull << 31)) return false;
@@ -281,7 +280,7 @@ bool conv_halo_p_cfg_valid(const ConvParams& p, int c) {
     return true;
 }
 
-const char* conv_halo_p_kernel_name(int c) { return kHaloP[kHaloPIdx[c]].name; }
+static std::string conv_halo_p_symbol(const ConvParams& p, int c) { return std::string(kHaloP[kHaloPIdx[c]].name) + res_f32_args(p) + ">"; }
 
 template <int FM, int FN, int WGM, int WGN, bool HAS_RES, bool OUT_F32>
 static hipError_t launch_halo_p_var(const ConvParams& p, const HaloPCfg& k, hipStream_t st) {
@@ -312,7 +311,7 @@ static hipError_t launch_halo_p_one(const ConvParams& p, const HaloPCfg& k, hipS
     return launch_halo_p_var<FM, FN, WGM, WGN, false, false>(p, k, st);
 }
 
-hipError_t launch_conv_halo_p(const ConvParams& p, int c, hipStream_t st) {
+static hipError_t launch_conv_halo_p(const ConvParams& p, int c, hipStream_t st) {
     const HaloPCfg& k = kHaloP[kHaloPIdx[c]];
     switch (c) {
         case 0: return launch_halo_p_one<4, 2, 4, 1>(p, k, st);
@@ -322,5 +321,9 @@ hipError_t launch_conv_halo_p(const ConvParams& p, int c, hipStream_t st) {
         default: return launch_halo_p_one<2, 2, 4, 1>(p, k, st);
     }
 }
+
+#if !defined(__HIP_DEVICE_COMPILE__)      // (host data: the device pass must not reference the host functions)
+const ConvFamily conv_halo_p_family = {200, kNumHaloP, conv_halo_p_cfg_valid, conv_halo_p_symbol, launch_conv_halo_p, false, nullptr, false};
+#endif
 
 }  // namespace yp

@@ -321,15 +321,16 @@ __global__ __launch_bounds__(WGM * WGN * 64) void conv_halo_s2_kernel(const Conv
 // ---------------------------------------------------------------------------------------------------------------
 struct HaloS2Cfg { int FM, FN, WGM, WGN; const char* name; };
 static const HaloS2Cfg kS2[] = {
-    {2, 2, 4, 2, "conv_halo_s2_kernel<2,2,4,2,3>"},   // 0: 8x16 out px x 64 ch, 8 waves
-    {1, 2, 4, 2, "conv_halo_s2_kernel<1,2,4,2,3>"},   // 1: 4x16 out px x 64 ch, 8 waves
-    {2, 2, 4, 1, "conv_halo_s2_kernel<2,2,4,1,3>"},   // 2: 8x16 out px x 32 ch, 4 waves
-    {1, 2, 4, 1, "conv_halo_s2_kernel<1,2,4,1,3>"},   // 3: 4x16 out px x 32 ch, 4 waves
-    {2, 4, 4, 2, "conv_halo_s2_kernel<2,4,4,2,3>"},   // 4: 8x16 out px x 128 ch, 8 waves (Cin = 32)
+    {2, 2, 4, 2, "conv_halo_s2_kernel<2,2,4,2,3"},   // 0: 8x16 out px x 64 ch, 8 waves
+    {1, 2, 4, 2, "conv_halo_s2_kernel<1,2,4,2,3"},   // 1: 4x16 out px x 64 ch, 8 waves
+    {2, 2, 4, 1, "conv_halo_s2_kernel<2,2,4,1,3"},   // 2: 8x16 out px x 32 ch, 4 waves
+    {1, 2, 4, 1, "conv_halo_s2_kernel<1,2,4,1,3"},   // 3: 4x16 out px x 32 ch, 4 waves
+    {2, 4, 4, 2, "conv_halo_s2_kernel<2,4,4,2,3"},   // 4: 8x16 out px x 128 ch, 8 waves (Cin = 32)
 };
 constexpr int kNumS2 = (int)(sizeof(kS2) / sizeof(kS2[0]));
-int conv_halo_s2_num_cfgs() { return kNumS2; }
-const char* conv_halo_s2_kernel_name(int c) { return kS2[c].name; }
+static std::string conv_halo_s2_symbol(const ConvParams& p, int c) {
+    return std::string(kS2[c].name) + (p.C2 > 0 ? ",false,false,true>" : std::string(res_f32_args(p)) + ",false>");
+}
 
 static size_t halo_s2_lds(const HaloS2Cfg& k, int Cin, bool pw2 = false) {
     const int TH = k.WGM * k.FM, BN = k.WGN * k.FN * 16;
@@ -337,7 +338,7 @@ static size_t halo_s2_lds(const HaloS2Cfg& k, int Cin, bool pw2 = false) {
     return (size_t)3 * H_INSTR * 1024 + 1024 + (size_t)9 * (Cin / 32) * BN * 64 + (pw2 ? (size_t)BN * 128 : 0);
 }
 
-bool conv_halo_s2_cfg_valid(const ConvParams& p, int c) {
+static bool conv_halo_s2_cfg_valid(const ConvParams& p, int c) {
     if (c < 0 || c >= kNumS2) return false;
     if (p.ks != 3 || p.stride != 2 || p.pad != 1 || p.up != 1 || (p.Cin % 32) != 0 || (p.Kpad != 9 * p.Cin)) return false;
     if ((p.H & 1) || (p.W & 1) || p.Ho * 2 != p.H || p.Wo * 2 != p.W) return false;
@@ -398,9 +399,8 @@ int conv_halo_s2_pw_cfg(const ConvParams& p) {
     }
     return -1;
 }
-const char* conv_halo_s2_pw_kernel_name(int c) { return c == 0 ? "conv_halo_s2_kernel<2,2,4,2,3,false,false,true>" : "conv_halo_s2_kernel<1,2,4,2,3,false,false,true>"; }
 
-hipError_t launch_conv_halo_s2(const ConvParams& p, int c, hipStream_t st) {
+static hipError_t launch_conv_halo_s2(const ConvParams& p, int c, hipStream_t st) {
     const HaloS2Cfg& k = kS2[c];
     if (p.C2 > 0) {
         if (c == 0) return launch_halo_s2_var<2, 2, 4, 2, false, false, true>(p, k, st);
@@ -415,5 +415,9 @@ hipError_t launch_conv_halo_s2(const ConvParams& p, int c, hipStream_t st) {
         default: return launch_halo_s2_one<2, 4, 4, 2>(p, k, st);
     }
 }
+
+#if !defined(__HIP_DEVICE_COMPILE__)      // (host data: the device pass must not reference the host functions)
+const ConvFamily conv_halo_s2_family = {500, kNumS2, conv_halo_s2_cfg_valid, conv_halo_s2_symbol, launch_conv_halo_s2, false, "YOLOP_NO_S2", false};
+#endif
 
 }  // namespace yp

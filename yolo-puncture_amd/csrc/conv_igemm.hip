@@ -249,76 +249,54 @@ static int conv_tile_choice(const ConvParams& p) {
     if ((p.Cout % 128) != 0 || p.M < 128 * 256) return 1;
     return 2;
 }
-// halo configuration selected for p (explicit p.cfg in [100,200) / [200,300), or the test override), or -1.
-// returns 100+c (conv_halo) or 200+c (conv_halo_p)
-static int halo_choice(const ConvParams& p, int dtype) {
+#if !defined(__HIP_DEVICE_COMPILE__)
+// In the autotuner's order (engine.hip autotune). A new family is one more descriptor here.
+const ConvFamily* const kConvFamilies[kNumConvFamilies] = {
+    &conv_dma_family, &conv_halo_family, &conv_halo_p_family, &conv_dma_p_family, &conv_halo_s2_family, &conv_tile1_family,
+    &conv_dma_lc_family, &conv_wreg_family, &conv_pxd_family, &conv_ks_family, &conv_wres_family, &conv_wrs_family};
+#endif
+
+// the family that owns configuration id `cfg`, or null (-1, PWSP_CFG, an id no family has)
+static const ConvFamily* conv_family_of(int cfg) {
+    for (const ConvFamily* f : kConvFamilies)
+        if (cfg >= f->base && cfg < f->base + f->num_cfgs) return f;
+    return nullptr;
+}
+// can configuration id `cfg` launch p? (conv_dma's configurations include conv_dma_supported)
+static bool conv_cfg_fits(const ConvParams& p, int cfg) {
+    const ConvFamily* f = conv_family_of(cfg);
+    return f && (f->two_source || p.x2_C == 0) && f->valid(p, cfg - f->base);
+}
+
+// Configuration id >= 100 that launches p (the test override first, then p.cfg), or -1 (conv_dma / conv_igemm pick their own).
+// A folded upsample (x2_C > 0) needs a two-source family: the first valid conv_dma_p configuration when neither id is one, -2 if none.
+static int conv_choice(const ConvParams& p, int dtype) {
     if (dtype != DT_BF16) return -1;
-    if (p.x2_C > 0) {        // folded upsample: only the persistent LDS-DMA families implement the two-source gather
-        auto ok = [&](int c) { return c >= 1200 ? conv_wrs_cfg_valid(p, c - 1200) : c >= 1100 ? conv_wres_cfg_valid(p, c - 1100) : c >= 900 ? false : c >= 800 ? conv_pxd_cfg_valid(p, c - 800) : (c >= 400 && c < 500 ? conv_dma_lc_cfg_valid(p, c - 400) : (c >= 300 && c < 400 && conv_dma_p_cfg_valid(p, c - 300))); };
-        const int f = conv_dma_forced_cfg();
-        if (ok(f)) return f;
-        if (ok(p.cfg)) return p.cfg;
-        for (int c = 0; c < conv_dma_p_num_cfgs(); ++c)
-            if (conv_dma_p_cfg_valid(p, c)) return 300 + c;
+    const int f = conv_dma_forced_cfg();
+    if (p.x2_C > 0) {
+        if (conv_cfg_fits(p, f)) return f;
+        if (conv_cfg_fits(p, p.cfg)) return p.cfg;
+        for (int c = 0; c < conv_dma_p_family.num_cfgs; ++c)
+            if (conv_dma_p_family.valid(p, c)) return conv_dma_p_family.base + c;
         return -2;
     }
-    auto valid = [&](int c) {
-        if (c >= 1200) return conv_wrs_cfg_valid(p, c - 1200);
-        if (c >= 1100) return conv_wres_cfg_valid(p, c - 1100);
-        if (c >= 1000) return false;                                 // (1000 = pwsp_kernel: the engine launches it itself)
-        if (c >= 900) return conv_ks_cfg_valid(p, c - 900);
-        if (c >= 800) return conv_pxd_cfg_valid(p, c - 800);
-        if (c >= 700) return conv_wreg_cfg_valid(p, c - 700);
-        if (c >= 600) return conv_tile1_cfg_valid(p, c - 600);
-        if (c >= 500) return conv_halo_s2_cfg_valid(p, c - 500);
-        if (c >= 400) return conv_dma_lc_cfg_valid(p, c - 400);
-        if (c >= 300) return conv_dma_p_cfg_valid(p, c - 300);
-        if (c >= 200) return conv_halo_p_cfg_valid(p, c - 200);
-        if (c >= 100) return conv_halo_cfg_valid(p, c - 100);
-        return false;
-    };
-    const int f = conv_dma_forced_cfg();
-    if (f >= 100 && valid(f)) return f;
+    if (f >= 100 && conv_cfg_fits(p, f)) return f;
     if (f >= 0 && f < 100) return -1;
-    if (p.cfg >= 100 && valid(p.cfg)) return p.cfg;
+    if (p.cfg >= 100 && conv_cfg_fits(p, p.cfg)) return p.cfg;
     return -1;
 }
 
-// Is tile configuration id `cfg` (the autotuner's numbering: < 100 conv_dma, 100+ conv_halo, 200+ conv_halo_p, 300+ conv_dma_p, 400+ conv_dma_lc,
-// 500+ conv_halo_s2, 600+ conv_tile1, 700+ conv_wreg, 800+ conv_pxd, 900+ conv_ks, 1100+ conv_wres, 1200+ conv_wrs; -1 = heuristic) one this build can launch for p? Used for
-// configurations that come from outside the tuner (tune cache files, yp_tuning_import).
+// Is configuration id `cfg` (-1 = heuristic) one this build can launch for p? Used for configurations that come from outside the tuner
+// (tune cache files, yp_tuning_import).
 bool conv_cfg_usable(const ConvParams& p, int dtype, int cfg) {
     if (cfg == -1) return true;
-    if (dtype != DT_BF16 || cfg < -1) return false;
-    if (cfg >= 1200) return cfg - 1200 < conv_wrs_num_cfgs() && conv_wrs_cfg_valid(p, cfg - 1200);
-    if (cfg >= 1100) return cfg - 1100 < conv_wres_num_cfgs() && conv_wres_cfg_valid(p, cfg - 1100);
-    if (cfg >= 1000) return false;
-    if (cfg >= 900) return cfg - 900 < conv_ks_num_cfgs() && p.x2_C == 0 && conv_ks_cfg_valid(p, cfg - 900);
-    if (cfg >= 800) return cfg - 800 < conv_pxd_num_cfgs() && conv_pxd_cfg_valid(p, cfg - 800);
-    if (cfg >= 700) return cfg - 700 < conv_wreg_num_cfgs() && p.x2_C == 0 && conv_wreg_cfg_valid(p, cfg - 700);
-    if (cfg >= 600) return cfg - 600 < conv_tile1_num_cfgs() && p.x2_C == 0 && conv_tile1_cfg_valid(p, cfg - 600);
-    if (cfg >= 500) return cfg - 500 < conv_halo_s2_num_cfgs() && p.x2_C == 0 && conv_halo_s2_cfg_valid(p, cfg - 500);
-    if (cfg >= 400) return cfg - 400 < conv_dma_lc_num_cfgs() && conv_dma_lc_cfg_valid(p, cfg - 400);
-    if (cfg >= 300) return cfg - 300 < conv_dma_p_num_cfgs() && conv_dma_p_cfg_valid(p, cfg - 300);
-    if (cfg >= 200) return cfg - 200 < conv_halo_p_num_cfgs() && p.x2_C == 0 && conv_halo_p_cfg_valid(p, cfg - 200);
-    if (cfg >= 100) return cfg - 100 < conv_halo_num_cfgs() && p.x2_C == 0 && conv_halo_cfg_valid(p, cfg - 100);
-    return cfg < conv_dma_num_cfgs() && p.x2_C == 0 && conv_dma_supported(p) && conv_dma_cfg_valid(p, cfg);
+    return dtype == DT_BF16 && conv_cfg_fits(p, cfg);
 }
 
-const char* conv_kernel_name(const ConvParams& p, int dtype) {
-    const int h = halo_choice(p, dtype);
-    if (h >= 1200) return conv_wrs_kernel_name(h - 1200);
-    if (h >= 1100) return conv_wres_kernel_name(h - 1100);
-    if (h >= 900) return conv_ks_kernel_name(h - 900);
-    if (h >= 800) return conv_pxd_kernel_name(h - 800);
-    if (h >= 700) return conv_wreg_kernel_name(h - 700);
-    if (h >= 600) return conv_tile1_kernel_name(h - 600);
-    if (h >= 500) return conv_halo_s2_kernel_name(h - 500);
-    if (h >= 400) return conv_dma_lc_kernel_name(h - 400);
-    if (h >= 300) return conv_dma_p_kernel_name(h - 300);
-    if (h >= 200) return conv_halo_p_kernel_name(h - 200);
-    if (h >= 100) return conv_halo_kernel_name(h - 100);
-    if (dtype == DT_BF16 && conv_dma_supported(p)) return conv_dma_kernel_name(p);
+std::string conv_kernel_name(const ConvParams& p, int dtype) {
+    const int h = conv_choice(p, dtype);
+    if (h >= 100) { const ConvFamily& f = *conv_family_of(h); return f.symbol(p, h - f.base); }
+    if (dtype == DT_BF16 && conv_dma_supported(p)) return conv_dma_family.symbol(p, -1);
     static const char* names[2][4] = {
         {"conv_igemm_kernel<bf16,128,32,4,1>", "conv_igemm_kernel<bf16,128,64,2,2>", "conv_igemm_kernel<bf16,128,128,2,2>", "conv_igemm_kernel<bf16,128,16,4,1>"},
         {"conv_igemm_kernel<f32,128,32,4,1>", "conv_igemm_kernel<f32,128,64,2,2>", "conv_igemm_kernel<f32,128,128,2,2>", "conv_igemm_kernel<f32,128,16,4,1>"}};
@@ -353,20 +331,10 @@ hipError_t launch_conv_igemm(const ConvParams& p, int dtype, hipStream_t st) {
 }
 
 hipError_t launch_conv(const ConvParams& p, int dtype, hipStream_t st) {
-    const int h = halo_choice(p, dtype);
-    if (p.x2_C > 0 && h < 300) return hipErrorInvalidValue;      // (the plan folds an upsample only when such a configuration exists)
-    if (h >= 1200) return launch_conv_wrs(p, h - 1200, st);
-    if (h >= 1100) return launch_conv_wres(p, h - 1100, st);
-    if (h >= 900) return launch_conv_ks(p, h - 900, st);
-    if (h >= 800) return launch_conv_pxd(p, h - 800, st);
-    if (h >= 700) return launch_conv_wreg(p, h - 700, st);
-    if (h >= 600) return launch_conv_tile1(p, h - 600, st);
-    if (h >= 500) return launch_conv_halo_s2(p, h - 500, st);
-    if (h >= 400) return launch_conv_dma_lc(p, h - 400, st);
-    if (h >= 300) return launch_conv_dma_p(p, h - 300, st);
-    if (h >= 200) return launch_conv_halo_p(p, h - 200, st);
-    if (h >= 100) return launch_conv_halo(p, h - 100, st);
-    if (dtype == DT_BF16 && conv_dma_supported(p)) return launch_conv_dma(p, st);
+    const int h = conv_choice(p, dtype);
+    if (p.x2_C > 0 && h < 0) return hipErrorInvalidValue;      // (the plan folds an upsample only when such a configuration exists)
+    if (h >= 100) { const ConvFamily& f = *conv_family_of(h); return f.launch(p, h - f.base, st); }
+    if (dtype == DT_BF16 && conv_dma_supported(p)) return conv_dma_family.launch(p, -1, st);
     if (dtype == DT_BF16) return launch_conv_t<__bf16>(p, st);
     return launch_conv_t<float>(p, st);
 }

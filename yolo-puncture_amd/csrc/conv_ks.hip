@@ -124,16 +124,15 @@ __global__ __launch_bounds__(256) void conv_ks_kernel(const ConvParams p) {
 
 struct KsCfg { int FN, PXF; const char* name; };
 static const KsCfg kKs[] = {
-    {4, 1, "conv_ks_kernel<4,1,4>"},      // 16 px x 64 couts
-    {4, 2, "conv_ks_kernel<4,2,3>"},      // 32 px x 64 couts
-    {8, 1, "conv_ks_kernel<8,1,2>"},      // 16 px x 128 couts
-    {2, 2, "conv_ks_kernel<2,2,4>"},      // 32 px x 32 couts
+    {4, 1, "conv_ks_kernel<4,1,4"},      // 16 px x 64 couts
+    {4, 2, "conv_ks_kernel<4,2,3"},      // 32 px x 64 couts
+    {8, 1, "conv_ks_kernel<8,1,2"},      // 16 px x 128 couts
+    {2, 2, "conv_ks_kernel<2,2,4"},      // 32 px x 32 couts
 };
 constexpr int kNumKs = (int)(sizeof(kKs) / sizeof(kKs[0]));
 
-int conv_ks_num_cfgs() { return kNumKs; }
 
-bool conv_ks_cfg_valid(const ConvParams& p, int c) {
+static bool conv_ks_cfg_valid(const ConvParams& p, int c) {
     if (c < 0 || c >= kNumKs) return false;
     const KsCfg& k = kKs[c];
     if ((p.ks != 1 && p.ks != 3) || p.up != 1 || p.w2 || p.x2_C > 0 || p.pool_in) return false;
@@ -149,7 +148,7 @@ bool conv_ks_cfg_valid(const ConvParams& p, int c) {
     return true;
 }
 
-const char* conv_ks_kernel_name(int c) { return kKs[c].name; }
+static std::string conv_ks_symbol(const ConvParams& p, int c) { return std::string(kKs[c].name) + res_f32_args(p) + ">"; }
 
 template <int FN, int PXF, int UB>
 static hipError_t launch_ks_one(const ConvParams& p, hipStream_t st) {
@@ -160,7 +159,7 @@ static hipError_t launch_ks_one(const ConvParams& p, hipStream_t st) {
     return hipGetLastError();
 }
 
-hipError_t launch_conv_ks(const ConvParams& p, int c, hipStream_t st) {
+static hipError_t launch_conv_ks(const ConvParams& p, int c, hipStream_t st) {
     if (!conv_ks_cfg_valid(p, c)) return hipErrorInvalidValue;
     switch (c) {
         case 0: return launch_ks_one<4, 1, 4>(p, st);
@@ -169,5 +168,9 @@ hipError_t launch_conv_ks(const ConvParams& p, int c, hipStream_t st) {
         default: return launch_ks_one<2, 2, 4>(p, st);
     }
 }
+
+#if !defined(__HIP_DEVICE_COMPILE__)      // (host data: the device pass must not reference the host functions)
+const ConvFamily conv_ks_family = {900, kNumKs, conv_ks_cfg_valid, conv_ks_symbol, launch_conv_ks, false, "YOLOP_NO_KS", false};
+#endif
 
 }  // namespace yp

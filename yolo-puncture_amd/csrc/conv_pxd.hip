@@ -227,20 +227,19 @@ __global__ __launch_bounds__(WGM * WGN * 64) void conv_pxd_kernel(const ConvPara
 // ---------------------------------------------------------------------------------------------------------------
 struct PxdCfg { int PXW, FN, WGM, WGN; const char* name; };
 static const PxdCfg kPxd[] = {
-    {2, 16, 8, 1, "conv_pxd_kernel<2,16,8,1>"},   // 0: 256 px x 256 couts
-    {2, 8, 8, 1, "conv_pxd_kernel<2,8,8,1>"},     // 1: 256 px x 128 couts
-    {2, 8, 4, 2, "conv_pxd_kernel<2,8,4,2>"},     // 2: 128 px x 256 couts
-    {1, 8, 8, 1, "conv_pxd_kernel<1,8,8,1>"},     // 3: 128 px x 128 couts
-    {1, 8, 4, 2, "conv_pxd_kernel<1,8,4,2>"},     // 4:  64 px x 256 couts
-    {2, 4, 8, 1, "conv_pxd_kernel<2,4,8,1>"},     // 5: 256 px x  64 couts
-    {1, 16, 8, 1, "conv_pxd_kernel<1,16,8,1>"},   // 6: 128 px x 256 couts, one pixel fragment per wave
-    {1, 4, 8, 1, "conv_pxd_kernel<1,4,8,1>"},     // 7: 128 px x  64 couts
+    {2, 16, 8, 1, "conv_pxd_kernel<2,16,8,1"},   // 0: 256 px x 256 couts
+    {2, 8, 8, 1, "conv_pxd_kernel<2,8,8,1"},     // 1: 256 px x 128 couts
+    {2, 8, 4, 2, "conv_pxd_kernel<2,8,4,2"},     // 2: 128 px x 256 couts
+    {1, 8, 8, 1, "conv_pxd_kernel<1,8,8,1"},     // 3: 128 px x 128 couts
+    {1, 8, 4, 2, "conv_pxd_kernel<1,8,4,2"},     // 4:  64 px x 256 couts
+    {2, 4, 8, 1, "conv_pxd_kernel<2,4,8,1"},     // 5: 256 px x  64 couts
+    {1, 16, 8, 1, "conv_pxd_kernel<1,16,8,1"},   // 6: 128 px x 256 couts, one pixel fragment per wave
+    {1, 4, 8, 1, "conv_pxd_kernel<1,4,8,1"},     // 7: 128 px x  64 couts
 };
 constexpr int kNumPxd = (int)(sizeof(kPxd) / sizeof(kPxd[0]));
 
-int conv_pxd_num_cfgs() { return kNumPxd; }
 
-bool conv_pxd_cfg_valid(const ConvParams& p, int c) {
+static bool conv_pxd_cfg_valid(const ConvParams& p, int c) {
     if (c < 0 || c >= kNumPxd) return false;
     const PxdCfg& k = kPxd[c];
     if (p.ks != 1 || p.stride != 1 || p.up != 1 || p.w2 || (p.Cin % 32) != 0 || p.Kpad != p.Cin) return false;
@@ -257,7 +256,7 @@ bool conv_pxd_cfg_valid(const ConvParams& p, int c) {
     return true;
 }
 
-const char* conv_pxd_kernel_name(int c) { return kPxd[c].name; }
+static std::string conv_pxd_symbol(const ConvParams& p, int c) { return std::string(kPxd[c].name) + res_f32_args(p) + ">"; }
 
 template <int PXW, int FN, int WGM, int WGN, bool HAS_RES, bool OUT_F32>
 static hipError_t launch_pxd_var(const ConvParams& p, hipStream_t st) {
@@ -293,7 +292,7 @@ static hipError_t launch_pxd_one(const ConvParams& p, hipStream_t st) {
     return launch_pxd_var<PXW, FN, WGM, WGN, false, false>(p, st);
 }
 
-hipError_t launch_conv_pxd(const ConvParams& p, int c, hipStream_t st) {
+static hipError_t launch_conv_pxd(const ConvParams& p, int c, hipStream_t st) {
     switch (c) {
         case 0: return launch_pxd_one<2, 16, 8, 1>(p, st);
         case 1: return launch_pxd_one<2, 8, 8, 1>(p, st);
@@ -305,5 +304,9 @@ hipError_t launch_conv_pxd(const ConvParams& p, int c, hipStream_t st) {
         default: return launch_pxd_one<1, 4, 8, 1>(p, st);
     }
 }
+
+#if !defined(__HIP_DEVICE_COMPILE__)      // (host data: the device pass must not reference the host functions)
+const ConvFamily conv_pxd_family = {800, kNumPxd, conv_pxd_cfg_valid, conv_pxd_symbol, launch_conv_pxd, true, "YOLOP_NO_PXD", false};
+#endif
 
 }  // namespace yp

@@ -477,10 +477,12 @@ static bool tile1_geometry(const ConvParams& p, int BN, Tile1Geo& g, size_t& lds
     return found;
 }
 
-int conv_tile1_num_cfgs() { return 3; }
-const char* conv_tile1_kernel_name(int c) { return c == 0 ? "conv_tile1_kernel<4>" : c == 1 ? "conv_tile1_kernel<2>" : "conv_tile1w_kernel<7>"; }
+static std::string conv_tile1_symbol(const ConvParams& p, int c) {
+    if (c == 2) return "conv_tile1w_kernel<" + std::to_string(T1_FMX) + res_f32_args(p) + ">";
+    return std::string(c == 0 ? "conv_tile1_kernel<4" : "conv_tile1_kernel<2") + res_f32_args(p) + ",false>";
+}
 
-bool conv_tile1_cfg_valid(const ConvParams& p, int c) {
+static bool conv_tile1_cfg_valid(const ConvParams& p, int c) {
     if (c < 0 || c >= 3) return false;
     if (p.ks != 3 || p.stride != 1 || p.pad != 1 || p.up != 1 || (p.Cin % 32) != 0 || p.Kpad != 9 * p.Cin || p.x2_C > 0) return false;
     if (p.x_bytes >= (1ull << 31) || p.w_bytes >= (1ull << 31) || p.y_bytes >= (1ull << 31)) return false;
@@ -551,7 +553,7 @@ static hipError_t launch_tile1w_var(const ConvParams& p, hipStream_t st) {
     return hipGetLastError();
 }
 
-hipError_t launch_conv_tile1(const ConvParams& p, int c, hipStream_t st) {
+static hipError_t launch_conv_tile1(const ConvParams& p, int c, hipStream_t st) {
     if (c == 2) {
         if (p.out_f32) return launch_tile1w_var<false, true>(p, st);
         if (p.res) return launch_tile1w_var<true, false>(p, st);
@@ -566,5 +568,9 @@ hipError_t launch_conv_tile1(const ConvParams& p, int c, hipStream_t st) {
     if (p.res) return launch_tile1_var<2, true, false>(p, st);
     return launch_tile1_var<2, false, false>(p, st);
 }
+
+#if !defined(__HIP_DEVICE_COMPILE__)      // (host data: the device pass must not reference the host functions)
+const ConvFamily conv_tile1_family = {600, 3, conv_tile1_cfg_valid, conv_tile1_symbol, launch_conv_tile1, false, "YOLOP_NO_T1", false};
+#endif
 
 }  // namespace yp

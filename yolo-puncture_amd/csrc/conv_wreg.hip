@@ -302,24 +302,23 @@ __global__ __launch_bounds__(WGM * WGN * 64) void conv_wreg_kernel(const ConvPar
 // ---------------------------------------------------------------------------------------------------------------
 struct WregCfg { int NCH, FM, FN, WGM, WGN, TW; const char* name; };
 static const WregCfg kWreg[] = {
-    {2, 4, 4, 4, 1, 16, "conv_wreg_kernel<2,4,4,4,1,16>"},   // 0: 64 -> <=64, 16x16 px tile
-    {2, 2, 4, 4, 1, 16, "conv_wreg_kernel<2,2,4,4,1,16>"},   // 1: 64 -> <=64,  8x16 px tile
-    {4, 8, 2, 1, 4, 16, "conv_wreg_kernel<4,8,2,1,4,16>"},   // 2: 128 -> <=128, 8x16 px tile
-    {4, 4, 2, 1, 4, 16, "conv_wreg_kernel<4,4,2,1,4,16>"},   // 3: 128 -> <=128, 4x16 px tile
-    {4, 4, 2, 1, 4, 8, "conv_wreg_kernel<4,4,2,1,4,8>"},     // 4: 128 -> <=128, 8x8 px tile (40-wide maps)
-    {2, 2, 4, 4, 1, 8, "conv_wreg_kernel<2,2,4,4,1,8>"},     // 5: 64 -> <=64, 16x8 px tile
-    {4, 4, 2, 2, 2, 16, "conv_wreg_kernel<4,4,2,2,2,16>"},   // 6: 128 -> <=64, 8x16 px tile
+    {2, 4, 4, 4, 1, 16, "conv_wreg_kernel<2,4,4,4,1,16"},   // 0: 64 -> <=64, 16x16 px tile
+    {2, 2, 4, 4, 1, 16, "conv_wreg_kernel<2,2,4,4,1,16"},   // 1: 64 -> <=64,  8x16 px tile
+    {4, 8, 2, 1, 4, 16, "conv_wreg_kernel<4,8,2,1,4,16"},   // 2: 128 -> <=128, 8x16 px tile
+    {4, 4, 2, 1, 4, 16, "conv_wreg_kernel<4,4,2,1,4,16"},   // 3: 128 -> <=128, 4x16 px tile
+    {4, 4, 2, 1, 4, 8, "conv_wreg_kernel<4,4,2,1,4,8"},     // 4: 128 -> <=128, 8x8 px tile (40-wide maps)
+    {2, 2, 4, 4, 1, 8, "conv_wreg_kernel<2,2,4,4,1,8"},     // 5: 64 -> <=64, 16x8 px tile
+    {4, 4, 2, 2, 2, 16, "conv_wreg_kernel<4,4,2,2,2,16"},   // 6: 128 -> <=64, 8x16 px tile
     // two waves per SIMD (256 registers each, 144 of them weights): the partner's MFMAs cover a wave's LDS latency and epilogue
-    {2, 4, 2, 4, 2, 16, "conv_wreg_kernel<2,4,2,4,2,16>"},   // 7: 64 -> <=64, 16x16 px tile, 8 waves
-    {2, 2, 2, 4, 2, 16, "conv_wreg_kernel<2,2,2,4,2,16>"},   // 8: 64 -> <=64,  8x16 px tile, 8 waves
-    {4, 8, 1, 1, 8, 16, "conv_wreg_kernel<4,8,1,1,8,16>"},   // 9: 128 -> <=128, 8x16 px tile, 8 waves
-    {4, 4, 1, 1, 8, 8, "conv_wreg_kernel<4,4,1,1,8,8>"},     // 10: 128 -> <=128, 8x8 px tile, 8 waves
-    {4, 8, 1, 1, 8, 8, "conv_wreg_kernel<4,8,1,1,8,8>"},     // 11: 128 -> <=128, 16x8 px tile, 8 waves
-    {2, 2, 2, 4, 2, 8, "conv_wreg_kernel<2,2,2,4,2,8>"},     // 12: 64 -> <=64, 16x8 px tile, 8 waves
+    {2, 4, 2, 4, 2, 16, "conv_wreg_kernel<2,4,2,4,2,16"},   // 7: 64 -> <=64, 16x16 px tile, 8 waves
+    {2, 2, 2, 4, 2, 16, "conv_wreg_kernel<2,2,2,4,2,16"},   // 8: 64 -> <=64,  8x16 px tile, 8 waves
+    {4, 8, 1, 1, 8, 16, "conv_wreg_kernel<4,8,1,1,8,16"},   // 9: 128 -> <=128, 8x16 px tile, 8 waves
+    {4, 4, 1, 1, 8, 8, "conv_wreg_kernel<4,4,1,1,8,8"},     // 10: 128 -> <=128, 8x8 px tile, 8 waves
+    {4, 8, 1, 1, 8, 8, "conv_wreg_kernel<4,8,1,1,8,8"},     // 11: 128 -> <=128, 16x8 px tile, 8 waves
+    {2, 2, 2, 4, 2, 8, "conv_wreg_kernel<2,2,2,4,2,8"},     // 12: 64 -> <=64, 16x8 px tile, 8 waves
 };
 constexpr int kNumWreg = (int)(sizeof(kWreg) / sizeof(kWreg[0]));
 
-int conv_wreg_num_cfgs() { return kNumWreg; }
 
 static size_t wreg_lds(const WregCfg& k) {
     const int RPF = 16 / k.TW, TH = k.WGM * k.FM * RPF;
@@ -327,7 +326,7 @@ static size_t wreg_lds(const WregCfg& k) {
     return (size_t)3 * H_INSTR * 1024 + 1024 + (size_t)9 * (k.WGN * k.FN * 16) * 64;
 }
 
-bool conv_wreg_cfg_valid(const ConvParams& p, int c) {
+static bool conv_wreg_cfg_valid(const ConvParams& p, int c) {
     if (c < 0 || c >= kNumWreg) return false;
     const WregCfg& k = kWreg[c];
     if (p.ks != 3 || p.stride != 1 || p.pad != 1 || p.up != 1 || p.Cin != k.NCH * 32 || p.Kpad != 9 * p.Cin || p.x2_C > 0 || p.w2) return false;
@@ -343,7 +342,7 @@ bool conv_wreg_cfg_valid(const ConvParams& p, int c) {
     return true;
 }
 
-const char* conv_wreg_kernel_name(int c) { return kWreg[c].name; }
+static std::string conv_wreg_symbol(const ConvParams& p, int c) { return std::string(kWreg[c].name) + res_f32_args(p) + ">"; }
 
 template <int NCH, int FM, int FN, int WGM, int WGN, int TW, bool HAS_RES, bool OUT_F32>
 static hipError_t launch_wreg_var(const ConvParams& p, const WregCfg& k, hipStream_t st) {
@@ -392,7 +391,7 @@ static hipError_t launch_wreg_one(const ConvParams& p, const WregCfg& k, hipStre
     return launch_wreg_var<NCH, FM, FN, WGM, WGN, TW, false, false>(p, k, st);
 }
 
-hipError_t launch_conv_wreg(const ConvParams& p, int c, hipStream_t st) {
+static hipError_t launch_conv_wreg(const ConvParams& p, int c, hipStream_t st) {
     const WregCfg& k = kWreg[c];
     switch (c) {
         case 0: return launch_wreg_one<2, 4, 4, 4, 1, 16>(p, k, st);
@@ -410,5 +409,9 @@ hipError_t launch_conv_wreg(const ConvParams& p, int c, hipStream_t st) {
         default: return launch_wreg_one<2, 2, 2, 4, 2, 8>(p, k, st);
     }
 }
+
+#if !defined(__HIP_DEVICE_COMPILE__)      // (host data: the device pass must not reference the host functions)
+const ConvFamily conv_wreg_family = {700, kNumWreg, conv_wreg_cfg_valid, conv_wreg_symbol, launch_conv_wreg, false, "YOLOP_NO_WREG", false};
+#endif
 
 }  // namespace yp

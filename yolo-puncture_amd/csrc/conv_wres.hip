@@ -228,14 +228,13 @@ __global__ __launch_bounds__(WR_NW * 64) void conv_wres_kernel(const ConvParams 
 // ---------------------------------------------------------------------------------------------------------------------------------------
 struct WresCfg { int TP, WGN; const char* name; };
 static const WresCfg kWres[] = {
-    {64, 2, "conv_wres_kernel<64,2>"},
-    {128, 2, "conv_wres_kernel<128,2>"},
-    {32, 4, "conv_wres_kernel<32,4>"},
+    {64, 2, "conv_wres_kernel<64,2"},
+    {128, 2, "conv_wres_kernel<128,2"},
+    {32, 4, "conv_wres_kernel<32,4"},
 };
-static const int kNumWres = (int)(sizeof(kWres) / sizeof(kWres[0]));
+constexpr int kNumWres = (int)(sizeof(kWres) / sizeof(kWres[0]));
 
-int conv_wres_num_cfgs() { return kNumWres; }
-const char* conv_wres_kernel_name(int c) { return kWres[c].name; }
+static std::string conv_wres_symbol(const ConvParams& p, int c) { return std::string(kWres[c].name) + (p.res ? ",true>" : ",false>"); }
 
 // channel block of a workgroup: as few blocks as 128 channels each allow, equal sizes, whole fragments (pairs of them for two channel waves)
 static void wres_blocks(const ConvParams& p, const WresCfg& k, int& NB, int& nblk) {
@@ -249,7 +248,7 @@ static size_t wres_lds(const ConvParams& p, const WresCfg& k) {
     return (size_t)NB * p.Cin * 2 + (size_t)2 * k.TP * p.Cin * 2;
 }
 
-bool conv_wres_cfg_valid(const ConvParams& p, int c) {
+static bool conv_wres_cfg_valid(const ConvParams& p, int c) {
     if (c < 0 || c >= kNumWres) return false;
     const WresCfg& k = kWres[c];
     if (p.ks != 1 || p.stride != 1 || p.up != 1 || p.w2 || p.out_f32 || p.pool_in || p.up_bilinear) return false;
@@ -290,7 +289,7 @@ static hipError_t launch_wres_t(const ConvParams& p, const WresCfg& k, hipStream
     return hipGetLastError();
 }
 
-hipError_t launch_conv_wres(const ConvParams& p, int c, hipStream_t st) {
+static hipError_t launch_conv_wres(const ConvParams& p, int c, hipStream_t st) {
     if (!conv_wres_cfg_valid(p, c)) return hipErrorInvalidValue;
     const WresCfg& k = kWres[c];
     const bool r = p.res != nullptr;
@@ -300,5 +299,9 @@ hipError_t launch_conv_wres(const ConvParams& p, int c, hipStream_t st) {
         default: return r ? launch_wres_t<32, 4, true>(p, k, st) : launch_wres_t<32, 4, false>(p, k, st);
     }
 }
+
+#if !defined(__HIP_DEVICE_COMPILE__)      // (host data: the device pass must not reference the host functions)
+const ConvFamily conv_wres_family = {1100, kNumWres, conv_wres_cfg_valid, conv_wres_symbol, launch_conv_wres, true, "YOLOP_NO_WRES", false};
+#endif
 
 }  // namespace yp

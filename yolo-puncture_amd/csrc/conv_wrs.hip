@@ -197,15 +197,9 @@ __global__ __launch_bounds__(WS_NW * 64) void conv_wrs_kernel(const ConvParams p
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------------------
-struct WrsCfg { int TP; const char* name; };
-static const WrsCfg kWrs[] = {
-    {64, "conv_wrs_kernel<64>"},
-    {32, "conv_wrs_kernel<32>"},
-};
-static const int kNumWrs = (int)(sizeof(kWrs) / sizeof(kWrs[0]));
-
-int conv_wrs_num_cfgs() { return kNumWrs; }
-const char* conv_wrs_kernel_name(int c) { return kWrs[c].name; }
+struct WrsCfg { int TP; };
+static const WrsCfg kWrs[] = {{64}, {32}};
+constexpr int kNumWrs = (int)(sizeof(kWrs) / sizeof(kWrs[0]));
 
 // (K / 32, channel fragments per wave) pairs this build instantiates: NKS * NFW * 4 weight registers per lane, 128 at most
 static bool wrs_shape(const ConvParams& p, int& nks, int& nfw) {
@@ -219,7 +213,13 @@ static bool wrs_shape(const ConvParams& p, int& nks, int& nfw) {
     return false;
 }
 
-bool conv_wrs_cfg_valid(const ConvParams& p, int c) {
+static std::string conv_wrs_symbol(const ConvParams& p, int c) {
+    int nks = 0, nfw = 0;
+    wrs_shape(p, nks, nfw);
+    return "conv_wrs_kernel<" + std::to_string(nks) + "," + std::to_string(nfw) + "," + std::to_string(kWrs[c].TP) + ">";
+}
+
+static bool conv_wrs_cfg_valid(const ConvParams& p, int c) {
     if (c < 0 || c >= kNumWrs) return false;
     const WrsCfg& k = kWrs[c];
     int nks, nfw;
@@ -291,11 +291,15 @@ static hipError_t launch_wrs_tp(const ConvParams& p, int nks, int nfw, hipStream
     return hipErrorInvalidValue;
 }
 
-hipError_t launch_conv_wrs(const ConvParams& p, int c, hipStream_t st) {
+static hipError_t launch_conv_wrs(const ConvParams& p, int c, hipStream_t st) {
     if (!conv_wrs_cfg_valid(p, c)) return hipErrorInvalidValue;
     int nks, nfw;
     wrs_shape(p, nks, nfw);
     return kWrs[c].TP == 64 ? launch_wrs_tp<64>(p, nks, nfw, st) : launch_wrs_tp<32>(p, nks, nfw, st);
 }
+
+#if !defined(__HIP_DEVICE_COMPILE__)      // (host data: the device pass must not reference the host functions)
+const ConvFamily conv_wrs_family = {1200, kNumWrs, conv_wrs_cfg_valid, conv_wrs_symbol, launch_conv_wrs, true, "YOLOP_WRS", true};
+#endif
 
 }  // namespace yp

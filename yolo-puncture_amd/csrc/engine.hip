@@ -715,6 +715,9 @@ static ScdParams scd_params(const yp_engine& e, const Op& o);
 static PwSpParams pwsp_params(const yp_engine& e, const Op& o);
 static ClsOutParams cls_out_params(const yp_engine& e, const Op& o);
 static bool views_overlap(const View& a, const View& b);
+static void op_views(const yp_engine& e, const Op& o, std::vector<View>& rd, std::vector<View>& wr);
+// a conv that launches as itself through launch_conv (or pwsp_kernel under PWSP_CFG): its configuration id is the tuner's to choose
+static bool plain_conv(const Op& o) { return (o.kind == OP_CONV || o.kind == OP_CONVT) && !o.skip && o.form == FORM_PLAIN; }
 static size_t tensor_elem_bytes(const yp_engine& e, const TensorDesc& t) { return (t.f32 || e.dtype == DT_F32) ? 4 : 2; }
 
 // ---- winners-only head (head_branch.hip): workspace layout and parameter blocks -----------------------------------------------------------------
@@ -819,23 +822,24 @@ static int make_plan(yp_engine& e, int B, int H, int W) {
     e.pB = B; e.pH = H; e.pW = W; e.planned = true; e.allocated = false; e.warmed = false;
     for (auto& o : e.ops) o.cfg = -1;
     static const char* kn[] = {"stem_kernel", "", "dwconv_kernel", "pool5_kernel", "upsample2_kernel", "attention_kernel", "head_select_kernel", "", "sppf_pool3_kernel", "anchor_max_level_kernel"};
-    for (auto& o : e.ops) { o.fused = false; o.skip = false; o.folded = false; o.fused2 = false; o.fused3 = false; o.fused4 = false; o.fused5 = false; o.fused6 = false; o.fused7 = false; o.fused8 = false; o.pw_store = false; o.sparse_box = false; o.sparse_cf = false; }
+    for (auto& o : e.ops) { o.form = FORM_PLAIN; o.skip = false; o.folded = false; o.pw_store = false; o.sparse_box = false; o.sparse_cf = false; }
     static const bool no_fold = [] { const char* v = std::getenv("YOLOP_NO_FOLD"); return v && *v == '1'; }();   // A/B switch
     for (auto& o : e.ops) {
         if (o.kind != OP_CONV || o.fold_up < 0 || e.dtype != DT_BF16 || no_fold) continue;
         o.folded = true;                                   // tentatively, so that conv_params describes the folded form
         const ConvParams q = conv_params(e, o);
         bool any = false;
-        for (int c = 0; c < conv_dma_p_num_cfgs() && !any; ++c) any = conv_dma_p_cfg_valid(q, c);
+        for (int c = 0; c < conv_dma_p_family.num_cfgs && !any; ++c) any = conv_dma_p_family.valid(q, c);
         if (any) e.ops[o.fold_up].skip = true;
         else o.folded = false;
     }
     for (auto& o : e.ops) {
         if (o.kind == OP_CONV && o.fuse_pre >= 0 && e.dtype == DT_BF16 && e.fuse) {
-            o.fused2 = true;
-            const int c = conv_halo_s2_pw_cfg(conv_params(e, o));
+            o.form = FORM_S2PW;                            // tentatively, so that conv_params describes the fused form
+            const ConvParams q = conv_params(e, o);
+            const int c = conv_halo_s2_pw_cfg(q);
             if (c >= 0) {
-                e.ops[o.fuse_pre].skip = true; o.cfg = 500 + c; o.kernel = conv_halo_s2_pw_kernel_name(c);
+                e.ops[o.fuse_pre].skip = true; o.cfg = conv_halo_s2_family.base + c; o.kernel = conv_halo_s2_family.symbol(q, c);
                 // ... and with the stem in front of it, when the stem's output has no other reader
                 static const bool no_front = [] { const char* v = std::getenv("YOLOP_NO_FRONT"); return v && *v == '1'; }();   // A/B switch
                 const Op& c1 = e.ops[o.fuse_pre];
@@ -846,29 +850,29 @@ static int make_plan(yp_engine& e, int B, int H, int W) {
                 }
                 if (stem >= 0 && readers == 1 && !no_front && e.weights[e.ops[stem].widx].d_w2 != nullptr) {
                     o.stem_op = stem;
-                    if (frontend_valid(front_params(e, o, nullptr))) { o.fused3 = true; e.ops[stem].skip = true; o.kernel = "frontend_kernel"; }
+                    if (frontend_valid(front_params(e, o, nullptr))) { o.form = FORM_FRONTEND; e.ops[stem].skip = true; o.kernel = "frontend_kernel"; }
                 }
                 continue;
             }
-            o.fused2 = false;
+            o.form = FORM_PLAIN;
         }
         static const bool no_c2f = [] { const char* v = std::getenv("YOLOP_NO_C2F"); return v && *v == '1'; }();   // A/B switch
         if (o.kind == OP_CONV && o.c2f_m1 >= 0 && e.dtype == DT_BF16 && e.fuse && !no_c2f && c2f_fused_valid(c2f_params(e, o))) {
-            o.fused4 = true; e.ops[o.c2f_m1].skip = true; e.ops[o.c2f_m2].skip = true; o.kernel = "c2f_fused_kernel";
+            o.form = FORM_C2F; e.ops[o.c2f_m1].skip = true; e.ops[o.c2f_m2].skip = true; o.kernel = "c2f_fused_kernel";
             continue;
         }
         if (o.kind == OP_CONV && o.fuse_dw >= 0 && e.dtype == DT_BF16 && e.fuse) {
             const DwPwParams q = dwpw_params(e, o);
-            if (conv_dwpw_valid(q)) { o.fused = true; e.ops[o.fuse_dw].skip = true; o.kernel = conv_dwpw_kernel_name(q); continue; }
+            if (conv_dwpw_valid(q)) { o.form = FORM_DWPW; e.ops[o.fuse_dw].skip = true; o.kernel = conv_dwpw_kernel_name(q); continue; }
         }
         // TAIL form (logit conv + class-max keys as a third stage of the last dw -> pw pair): opt-in, YOLOP_TAIL=1. Alone it takes 33 us less
         // than the three launches it replaces (213 -> 180 us over the P3 / P4 class branches, -105 MB of HBM traffic), but in the replayed
         // graph the step is 0.7 % SLOWER with it (1.936 vs 1.922 ms, same box, three alternating runs): the 1x1 conv and the max pass it
         // removes were HBM-bound and ran beside the VALU-bound kernels of the other head lanes for free, while the longer fused kernel holds
         // its statically assigned CUs for longer.
-        if (o.kind == OP_CONV && o.fuse_tail >= 0 && e.dtype == DT_BF16 && e.fuse && e.tail && e.ops[o.fuse_tail].fused) {
+        if (o.kind == OP_CONV && o.fuse_tail >= 0 && e.dtype == DT_BF16 && e.fuse && e.tail && e.ops[o.fuse_tail].form == FORM_DWPW) {
             // (ops are visited in order: the pointwise conv in front has already been decided)
-            o.fused6 = true;
+            o.form = FORM_DWPW_TAIL;
             const DwPwParams q = dwpw_params(e, o);
             if (conv_dwpw_valid(q)) {
                 e.ops[o.fuse_tail].skip = true;
@@ -876,7 +880,7 @@ static int make_plan(yp_engine& e, int B, int H, int W) {
                 o.kernel = conv_dwpw_kernel_name(q);
                 continue;
             }
-            o.fused6 = false;
+            o.form = FORM_PLAIN;
         }
         if (o.kind == OP_CONV) o.kernel = conv_kernel_name(conv_params(e, o), e.dtype);
         else if (o.kind == OP_CONVT) {
@@ -887,7 +891,7 @@ static int make_plan(yp_engine& e, int B, int H, int W) {
         } else if (o.kind == OP_DWCONV) {
             static const bool no_scd = [] { const char* v = std::getenv("YOLOP_NO_SCD"); return v && *v == '1'; }();   // A/B switch
             if (o.scd_pre >= 0 && e.dtype == DT_BF16 && e.fuse && !no_scd && scdown_fused_valid(scd_params(e, o))) {
-                o.fused5 = true; e.ops[o.scd_pre].skip = true; o.kernel = scdown_fused_kernel_name(scd_params(e, o));
+                o.form = FORM_SCDOWN; e.ops[o.scd_pre].skip = true; o.kernel = scdown_fused_kernel_name(scd_params(e, o));
                 continue;
             }
             const char* t = e.dtype == DT_BF16 ? "bf16" : "f32";
@@ -950,32 +954,30 @@ static int make_plan(yp_engine& e, int B, int H, int W) {
         static const bool no_pwsp = [] { const char* v = std::getenv("YOLOP_NO_PWSP"); return v && *v == '1'; }();   // A/B switch
         for (size_t i = 0; i < e.ops.size(); ++i) {
             Op& d = e.ops[i];
-            if (d.pw_pre < 0 || e.dtype != DT_BF16 || !e.fuse || no_pwsp || d.skip || d.fused5) continue;
+            if (d.pw_pre < 0 || e.dtype != DT_BF16 || !e.fuse || no_pwsp || d.skip || d.form != FORM_PLAIN) continue;
             Op& c = e.ops[d.pw_pre];
-            if (c.skip || c.fused || c.fused2 || c.fused3 || c.fused4 || c.fused6 || c.folded) continue;
+            if (!plain_conv(c) || c.folded) continue;
+            // from the effective read / write sets of the ops that still launch: the conv's output read anywhere else = other readers;
+            // moved to the spatial op's place, the conv must not pass an op that reads or writes its output, writes its input or residual,
+            // or touches the spatial op's output / residual
             bool between = false, other = false;
+            std::vector<View> rd, wr;
+            auto any_overlap = [](const std::vector<View>& vs, const View& v) {
+                for (const View& x : vs) if (views_overlap(x, v)) return true;
+                return false;
+            };
             for (size_t j = 0; j < e.ops.size(); ++j) {
-                const Op& q = e.ops[j];
-                if (j == i || (int)j == d.pw_pre || q.skip) continue;
-                bool reads = false;
-                for (const View* v : {&q.in, &q.res}) reads |= views_overlap(*v, c.out);
-                if (q.kind == OP_HEAD)
-                    for (int l = 0; l < 3; ++l) {
-                        for (const View* v : {&q.box[l], &q.cls[l], &q.cf[l], &q.amax[l]}) reads |= views_overlap(*v, c.out);
-                        for (int which = 0; which < 2; ++which) {
-                            const int b0 = (which == 0 ? q.hb_box : q.hb_cf)[l][0];
-                            if (b0 >= 0 && (which == 0 ? q.sparse_box : q.sparse_cf)) reads |= views_overlap(e.ops[b0].in, c.out);
-                        }
-                    }
+                if (j == i || (int)j == d.pw_pre || e.ops[j].skip) continue;
+                op_views(e, e.ops[j], rd, wr);
+                const bool reads = any_overlap(rd, c.out);
                 other |= reads;
-                if ((int)j > d.pw_pre && j < i) {
-                    between |= reads || views_overlap(q.out, c.out) || views_overlap(q.out, d.out) || views_overlap(q.out, d.res) || views_overlap(q.in, d.out) ||
-                               views_overlap(q.res, d.out);
-                }
+                if ((int)j > d.pw_pre && j < i)
+                    between |= reads || any_overlap(wr, c.out) || any_overlap(wr, c.in) || any_overlap(wr, c.res) || any_overlap(wr, d.out) || any_overlap(wr, d.res) ||
+                               any_overlap(rd, d.out);
             }
             if (between) continue;
-            d.fused7 = true; d.pw_store = other;
-            if (!pwsp_valid(pwsp_params(e, d))) { d.fused7 = false; d.pw_store = false; continue; }
+            d.form = FORM_PWSP; d.pw_store = other;
+            if (!pwsp_valid(pwsp_params(e, d))) { d.form = FORM_PLAIN; d.pw_store = false; continue; }
             c.skip = true;
             d.kernel = pwsp_kernel_name(pwsp_params(e, d));
         }
@@ -985,9 +987,9 @@ static int make_plan(yp_engine& e, int B, int H, int W) {
         static const bool no_co = [] { const char* v = std::getenv("YOLOP_NO_CLSOUT"); return v && *v == '1'; }();   // A/B switch
         for (auto& o : e.ops) {
             if (o.kind != OP_CONV || o.amax_post < 0 || e.dtype != DT_BF16 || !e.fuse || no_co) continue;
-            if (o.skip || o.fused || o.fused2 || o.fused3 || o.fused4 || o.fused6 || o.folded || e.ops[o.amax_post].skip) continue;
+            if (!plain_conv(o) || o.folded || e.ops[o.amax_post].skip) continue;
             if (!cls_out_valid(cls_out_params(e, o))) continue;
-            o.fused8 = true; e.ops[o.amax_post].skip = true;
+            o.form = FORM_CLS_OUT; e.ops[o.amax_post].skip = true;
             o.kernel = cls_out_kernel_name(cls_out_params(e, o));
         }
     }
@@ -1003,31 +1005,38 @@ static int make_plan(yp_engine& e, int B, int H, int W) {
         };
         auto wb = [&](const Op& q) { const WeightDesc& w = e.weights[q.widx]; return (double)w.cout * w.cin_g * w.k * w.k * es; };
         for (auto& o : e.ops) {
-            if (o.kind == OP_DWCONV && o.fused5) { const Op& c1 = e.ops[o.scd_pre]; o.flops += c1.flops; o.bytes = vb(c1.in) + vb(o.out) + wb(c1) + wb(o); }
-            if (o.fused7) {
-                const Op& c1 = e.ops[o.pw_pre];
-                o.flops += c1.flops;
-                o.bytes = vb(c1.in) + (o.pw_store ? vb(c1.out) : 0.0) + vb(o.out) + vb(o.res) + wb(c1) + (o.kind == OP_DWCONV ? wb(o) : 0.0);
-            }
-            if (o.kind != OP_CONV) continue;
-            if (o.fused) { const Op& d = e.ops[o.fuse_dw]; o.flops += d.flops; o.bytes = vb(d.in) + vb(d.res) + vb(o.out) + wb(d) + wb(o); }
-            else if (o.fused6) {                    // (its pointwise conv, visited before, already carries the depthwise stage's FLOPs)
-                const Op& c1 = e.ops[o.fuse_tail];
-                const Op& d = e.ops[c1.fuse_dw];
-                o.flops += c1.flops;
-                o.bytes = vb(d.in) + vb(o.out) + wb(d) + wb(c1) + wb(o) + (o.tail_amax >= 0 ? vb(e.ops[o.tail_amax].out) : 0.0);
-            }
-            else if (o.fused3) {
-                const Op &c1 = e.ops[o.fuse_pre], &st = e.ops[o.stem_op];
-                o.flops += c1.flops + st.flops; o.bytes = (double)B * H * W * 3 + vb(o.out) + wb(st) + wb(c1) + wb(o);
-            } else if (o.fused2) { const Op& c1 = e.ops[o.fuse_pre]; o.flops += c1.flops; o.bytes = vb(c1.in) + vb(o.out) + wb(c1) + wb(o); }
-            else if (o.fused4) {
-                const Op &m1 = e.ops[o.c2f_m1], &m2 = e.ops[o.c2f_m2];
-                o.flops += m1.flops + m2.flops;
-                o.bytes = vb(View{o.in.t, o.in.coff, 2 * m1.in.C}) + vb(o.out) + wb(m1) + wb(m2) + wb(o);
+            switch (o.form) {
+                case FORM_PLAIN: break;
+                case FORM_SCDOWN: { const Op& c1 = e.ops[o.scd_pre]; o.flops += c1.flops; o.bytes = vb(c1.in) + vb(o.out) + wb(c1) + wb(o); break; }
+                case FORM_PWSP: {
+                    const Op& c1 = e.ops[o.pw_pre];
+                    o.flops += c1.flops;
+                    o.bytes = vb(c1.in) + (o.pw_store ? vb(c1.out) : 0.0) + vb(o.out) + vb(o.res) + wb(c1) + (o.kind == OP_DWCONV ? wb(o) : 0.0);
+                    break;
+                }
+                case FORM_DWPW: { const Op& d = e.ops[o.fuse_dw]; o.flops += d.flops; o.bytes = vb(d.in) + vb(d.res) + vb(o.out) + wb(d) + wb(o); break; }
+                case FORM_DWPW_TAIL: {                 // (its pointwise conv, visited before, already carries the depthwise stage's FLOPs)
+                    const Op& c1 = e.ops[o.fuse_tail];
+                    const Op& d = e.ops[c1.fuse_dw];
+                    o.flops += c1.flops;
+                    o.bytes = vb(d.in) + vb(o.out) + wb(d) + wb(c1) + wb(o) + (o.tail_amax >= 0 ? vb(e.ops[o.tail_amax].out) : 0.0);
+                    break;
+                }
+                case FORM_FRONTEND: {
+                    const Op &c1 = e.ops[o.fuse_pre], &st = e.ops[o.stem_op];
+                    o.flops += c1.flops + st.flops; o.bytes = (double)B * H * W * 3 + vb(o.out) + wb(st) + wb(c1) + wb(o);
+                    break;
+                }
+                case FORM_S2PW: { const Op& c1 = e.ops[o.fuse_pre]; o.flops += c1.flops; o.bytes = vb(c1.in) + vb(o.out) + wb(c1) + wb(o); break; }
+                case FORM_C2F: {
+                    const Op &m1 = e.ops[o.c2f_m1], &m2 = e.ops[o.c2f_m2];
+                    o.flops += m1.flops + m2.flops;
+                    o.bytes = vb(View{o.in.t, o.in.coff, 2 * m1.in.C}) + vb(o.out) + wb(m1) + wb(m2) + wb(o);
+                    break;
+                }
+                case FORM_CLS_OUT: o.bytes += vb(e.ops[o.amax_post].out); break;
             }
             if (o.folded) { const Op& u = e.ops[o.fold_up]; o.bytes += vb(u.in) - vb(u.out); }
-            if (o.fused8) o.bytes += vb(e.ops[o.amax_post].out);
         }
         for (auto& o : e.ops) {
             if (o.kind != OP_HEAD) continue;
@@ -1136,7 +1145,7 @@ static int allocate_plan(yp_engine& e) {
 struct RunArgs { const uint8_t* in; float* det; int32_t* idx; float* coeff; };
 
 static ConvParams conv_params(const yp_engine& e, const Op& o) {
-    if (o.fused2) {            // the 3x3 s2 producer's parameters with this 1x1 as the trailing stage
+    if (o.form == FORM_S2PW || o.form == FORM_FRONTEND) {      // the 3x3 s2 producer's parameters with this 1x1 as the trailing stage
         const Op& a = e.ops[o.fuse_pre];
         Op a1 = a;
         a1.cfg = o.cfg;
@@ -1154,7 +1163,7 @@ static ConvParams conv_params(const yp_engine& e, const Op& o) {
     if (w.cin_pad > o.in.C) p.Cin = w.cin_pad;      // (packed with padded taps: the kernels read cin_pad channels per pixel)
     p.w = w.d_w; p.Kpad = w.Kpad; p.bias = w.d_b;
     p.y = to.ptr; p.y_stride = to.C; p.y_coff = o.out.coff; p.Ho = to.H; p.Wo = to.W; p.Cout = o.out.C;
-    if (o.res.t >= 0) { p.res = e.tensors[o.res.t].ptr; p.res_stride = e.tensors[o.res.t].C; p.res_coff = o.res.coff; }
+    if (o.res.t >= 0) { const TensorDesc& tr = e.tensors[o.res.t]; p.res = tr.ptr ? tr.ptr : (const void*)1; p.res_stride = tr.C; p.res_coff = o.res.coff; }
     p.M = e.pB * to.H * to.W; p.ks = o.k; p.stride = o.s; p.pad = o.k / 2; p.act = o.act;
     p.out_f32 = (to.f32 && e.dtype == DT_BF16) ? 1 : 0;
     p.up = 1; p.oy = 0; p.ox = 0;
@@ -1227,7 +1236,7 @@ static ClsOutParams cls_out_params(const yp_engine& e, const Op& o) {
     return p;
 }
 
-// pwsp_kernel: `o` is the spatial op of a fused pair (o.fused7) or a plain 1x1 conv that runs in the same decomposition (cfg PWSP_CFG)
+// pwsp_kernel: `o` is the spatial op of a fused pair (FORM_PWSP) or a plain 1x1 conv that runs in the same decomposition (cfg PWSP_CFG)
 static PwSpParams pwsp_params(const yp_engine& e, const Op& o) {
     PwSpParams p{};
     const bool pair = o.kind != OP_CONV;
@@ -1270,11 +1279,14 @@ static hipError_t run_op(yp_engine& e, const Op& o, const RunArgs& a, hipStream_
             return launch_stem(p, e.dtype, st);
         }
         case OP_CONV:
-            if (o.fused || o.fused6) return launch_conv_dwpw(dwpw_params(e, o), st);
-            if (o.fused3) return launch_frontend(front_params(e, o, a.in), st);
-            if (o.fused4) return launch_c2f_fused(c2f_params(e, o), st);
-            if (o.fused2) { const ConvParams q = conv_params(e, o); return launch_conv_halo_s2(q, o.cfg - 500, st); }
-            if (o.fused8) return launch_cls_out(cls_out_params(e, o), st);
+            switch (o.form) {
+                case FORM_DWPW: case FORM_DWPW_TAIL: return launch_conv_dwpw(dwpw_params(e, o), st);
+                case FORM_FRONTEND: return launch_frontend(front_params(e, o, a.in), st);
+                case FORM_C2F: return launch_c2f_fused(c2f_params(e, o), st);
+                case FORM_S2PW: return conv_halo_s2_family.launch(conv_params(e, o), o.cfg - conv_halo_s2_family.base, st);
+                case FORM_CLS_OUT: return launch_cls_out(cls_out_params(e, o), st);
+                default: break;
+            }
             if (o.cfg == PWSP_CFG) return launch_pwsp(pwsp_params(e, o), st);
             if (conv_dma_forced_cfg() == PWSP_CFG && e.dtype == DT_BF16 && !o.folded) {          // test hook (yp_debug_force_conv_cfg): every 1x1 that admits it
                 const PwSpParams q = pwsp_params(e, o);
@@ -1300,8 +1312,8 @@ static hipError_t run_op(yp_engine& e, const Op& o, const RunArgs& a, hipStream_
             return hipSuccess;
         }
         case OP_DWCONV: {
-            if (o.fused5) return launch_scdown_fused(scd_params(e, o), st);
-            if (o.fused7) return launch_pwsp(pwsp_params(e, o), st);
+            if (o.form == FORM_SCDOWN) return launch_scdown_fused(scd_params(e, o), st);
+            if (o.form == FORM_PWSP) return launch_pwsp(pwsp_params(e, o), st);
             const WeightDesc& w = e.weights[o.widx];
             const TensorDesc &ti = T(o.in), &to = T(o.out);
             DwParams p{};
@@ -1322,7 +1334,7 @@ static hipError_t run_op(yp_engine& e, const Op& o, const RunArgs& a, hipStream_
         }
         case OP_POOL3: {
             const TensorDesc &ti = T(o.in), &to = T(o.out);
-            if (o.fused7) return launch_pwsp(pwsp_params(e, o), st);
+            if (o.form == FORM_PWSP) return launch_pwsp(pwsp_params(e, o), st);
             PoolParams p{};
             p.x = ti.ptr; p.x_stride = ti.C; p.x_coff = o.in.coff; p.y = to.ptr; p.y_stride = to.C; p.y_coff = o.out.coff;
             p.B = B; p.H = ti.H; p.W = ti.W; p.C = o.in.C;
@@ -1429,7 +1441,7 @@ static int autotune(yp_engine& e) {
     auto time_cfg = [&](Op& o, float& tmin) -> hipError_t {
         tmin = 1e30f;
         const Op* prod = (cold_mode == 2) ? producer_of(o) : nullptr;
-        if (prod && (prod->kind == OP_STEM || prod->fused3) && !tune_in) prod = nullptr;      // (needs the caller's frames)
+        if (prod && (prod->kind == OP_STEM || prod->form == FORM_FRONTEND) && !tune_in) prod = nullptr;      // (needs the caller's frames)
         for (int rep = 0; rep < 4; ++rep) {
             if (flush && rep > 0 && (cold_mode == 1 || !prod)) { hipError_t fe = hipMemsetAsync(flush, rep, flush_bytes, nullptr); if (fe != hipSuccess) return fe; }
             if (prod) {
@@ -1450,8 +1462,7 @@ static int autotune(yp_engine& e) {
         return hipSuccess;
     };
     for (Op& o : e.ops) {
-        if (o.kind != OP_CONV && o.kind != OP_CONVT) continue;
-        if (o.fused || o.fused2 || o.fused4 || o.fused6 || o.fused8 || o.skip) continue;
+        if (!plain_conv(o)) continue;
         ConvParams p{};
         if (o.kind == OP_CONV) p = conv_params(e, o);
         else { p.Cin = o.in.C; p.Cout = o.out.C; p.ks = 1; p.Kpad = e.weights[o.widx].Kpad; p.M = e.pB * e.tensors[o.in.t].H * e.tensors[o.in.t].W;
@@ -1460,48 +1471,34 @@ static int autotune(yp_engine& e) {
         float best = 1e30f;
         int bestc = -1;
         std::vector<std::pair<float, int>> timed;                           // (first-pass time, cfg) of every candidate
-        for (int c = 0; c < conv_dma_num_cfgs(); ++c) {
-            if (p.x2_C > 0 || !conv_dma_cfg_valid(p, c)) continue;          // (the one-tile-per-workgroup family has no folded-upsample gather)
-            o.cfg = c;
+        // every configuration of every family that can run p, in kConvFamilies' order (a ConvTranspose: conv_dma only), then pwsp_kernel.
+        // (opt-in YOLOP_WRS: stand-alone - the tuner's protocol - the weights-in-registers form wins several 40x40 layers by 1-3 us; with it
+        // among the candidates the step is 1.6977 against 1.7003 ms over three tunings each: two more configurations to time for nothing;
+        // DESIGN.md "Round 4")
+        static const std::vector<bool> family_on = [] {
+            std::vector<bool> v;
+            for (const ConvFamily* f : kConvFamilies) {
+                const char* s = f->tune_env ? std::getenv(f->tune_env) : nullptr;
+                v.push_back((s && *s == '1') == f->opt_in);          // A/B switch (YOLOP_NO_*) or opt-in
+            }
+            return v;
+        }();
+        std::vector<int> cands;
+        for (int i = 0; i < kNumConvFamilies; ++i) {
+            const ConvFamily& f = *kConvFamilies[i];
+            if (!family_on[i] || (o.kind != OP_CONV && &f != &conv_dma_family)) continue;
+            for (int c = 0; c < f.num_cfgs; ++c)
+                if ((f.two_source || p.x2_C == 0) && f.valid(p, c)) cands.push_back(f.base + c);
+        }
+        static const bool no_ps = [] { const char* v = std::getenv("YOLOP_NO_PWSP"); return v && *v == '1'; }();     // A/B switch
+        if (o.kind == OP_CONV && !no_ps && !o.folded && p.x2_C == 0 && pwsp_valid(pwsp_params(e, o))) cands.push_back(PWSP_CFG);
+        for (int cc : cands) {
+            o.cfg = cc;
             float tmin;
             hipError_t err = time_cfg(o, tmin);
-            if (err != hipSuccess) return fail(YP_ERR_HIP, "autotune op %s cfg %d: %s", o.name.c_str(), c, hipGetErrorString(err));
-            timed.emplace_back(tmin, c);
-            if (tmin < best) { best = tmin; bestc = c; }
-        }
-        if (o.kind == OP_CONV) {
-            std::vector<int> cands;
-            for (int c = 0; c < conv_halo_num_cfgs(); ++c) if (conv_halo_cfg_valid(p, c)) cands.push_back(100 + c);
-            for (int c = 0; c < conv_halo_p_num_cfgs(); ++c) if (conv_halo_p_cfg_valid(p, c)) cands.push_back(200 + c);
-            for (int c = 0; c < conv_dma_p_num_cfgs(); ++c) if (conv_dma_p_cfg_valid(p, c)) cands.push_back(300 + c);
-            static const bool no_s2 = [] { const char* v = std::getenv("YOLOP_NO_S2"); return v && *v == '1'; }();   // A/B switch
-            for (int c = 0; !no_s2 && c < conv_halo_s2_num_cfgs(); ++c) if (conv_halo_s2_cfg_valid(p, c)) cands.push_back(500 + c);
-            static const bool no_t1 = [] { const char* v = std::getenv("YOLOP_NO_T1"); return v && *v == '1'; }();   // A/B switch
-            for (int c = 0; !no_t1 && c < conv_tile1_num_cfgs(); ++c) if (conv_tile1_cfg_valid(p, c)) cands.push_back(600 + c);
-            static const bool no_lc = [] { const char* v = std::getenv("YOLOP_NO_LC"); return v && *v == '1'; }();   // A/B switch
-            for (int c = 0; !no_lc && c < conv_dma_lc_num_cfgs(); ++c) if (conv_dma_lc_cfg_valid(p, c)) cands.push_back(400 + c);
-            static const bool no_wr = [] { const char* v = std::getenv("YOLOP_NO_WREG"); return v && *v == '1'; }();   // A/B switch
-            for (int c = 0; !no_wr && c < conv_wreg_num_cfgs(); ++c) if (conv_wreg_cfg_valid(p, c)) cands.push_back(700 + c);
-            static const bool no_px = [] { const char* v = std::getenv("YOLOP_NO_PXD"); return v && *v == '1'; }();     // A/B switch
-            for (int c = 0; !no_px && c < conv_pxd_num_cfgs(); ++c) if (conv_pxd_cfg_valid(p, c)) cands.push_back(800 + c);
-            static const bool no_ks = [] { const char* v = std::getenv("YOLOP_NO_KS"); return v && *v == '1'; }();     // A/B switch
-            for (int c = 0; !no_ks && c < conv_ks_num_cfgs(); ++c) if (conv_ks_cfg_valid(p, c)) cands.push_back(900 + c);
-            static const bool no_wres = [] { const char* v = std::getenv("YOLOP_NO_WRES"); return v && *v == '1'; }();   // A/B switch
-            for (int c = 0; !no_wres && c < conv_wres_num_cfgs(); ++c) if (conv_wres_cfg_valid(p, c)) cands.push_back(1100 + c);
-            // (opt-in: stand-alone - the tuner's protocol - the weights-in-registers form wins several 40x40 layers by 1-3 us; with it among the
-            // candidates the step is 1.6977 against 1.7003 ms over three tunings each: two more configurations to time for nothing; DESIGN.md "Round 4")
-            static const bool use_wrs = [] { const char* v = std::getenv("YOLOP_WRS"); return v && *v == '1'; }();
-            for (int c = 0; use_wrs && c < conv_wrs_num_cfgs(); ++c) if (conv_wrs_cfg_valid(p, c)) cands.push_back(1200 + c);
-            static const bool no_ps = [] { const char* v = std::getenv("YOLOP_NO_PWSP"); return v && *v == '1'; }();     // A/B switch
-            if (!no_ps && !o.folded && p.x2_C == 0 && pwsp_valid(pwsp_params(e, o))) cands.push_back(PWSP_CFG);
-            for (int cc : cands) {
-                o.cfg = cc;
-                float tmin;
-                hipError_t err = time_cfg(o, tmin);
-                if (err != hipSuccess) return fail(YP_ERR_HIP, "autotune op %s cfg %d: %s", o.name.c_str(), cc, hipGetErrorString(err));
-                timed.emplace_back(tmin, cc);
-                if (tmin < best) { best = tmin; bestc = cc; }
-            }
+            if (err != hipSuccess) return fail(YP_ERR_HIP, "autotune op %s cfg %d: %s", o.name.c_str(), cc, hipGetErrorString(err));
+            timed.emplace_back(tmin, cc);
+            if (tmin < best) { best = tmin; bestc = cc; }
         }
         // second pass over the three fastest: a minimum of three samples is noisy enough that a 5 % slower configuration sometimes
         // wins the first pass, and one bad pick on a 50-us layer costs the whole step 1-2 %
@@ -1576,7 +1573,7 @@ static bool apply_tuning(yp_engine& e, const int* cfgs, int n) {
     if (n != (int)e.ops.size()) return false;
     for (size_t i = 0; i < e.ops.size(); ++i) {
         const Op& o = e.ops[i];
-        if ((o.kind != OP_CONV && o.kind != OP_CONVT) || o.fused || o.fused2 || o.fused4 || o.fused6 || o.fused8 || o.skip) continue;
+        if (!plain_conv(o)) continue;
         ConvParams p = tune_params(e, o);
         p.cfg = -1;
         if (cfgs[i] == PWSP_CFG) { if (o.kind != OP_CONV || o.folded || !pwsp_valid(pwsp_params(e, o))) return false; continue; }
@@ -1584,7 +1581,7 @@ static bool apply_tuning(yp_engine& e, const int* cfgs, int n) {
     }
     for (size_t i = 0; i < e.ops.size(); ++i) {
         Op& o = e.ops[i];
-        if ((o.kind != OP_CONV && o.kind != OP_CONVT) || o.fused || o.fused2 || o.fused4 || o.fused6 || o.fused8 || o.skip) continue;   // a fused op keeps its own symbol / id
+        if (!plain_conv(o)) continue;   // a fused op keeps its own symbol / id
         o.cfg = cfgs[i];
         if (o.cfg == PWSP_CFG) { o.kernel = pwsp_kernel_name(pwsp_params(e, o)); continue; }
         ConvParams p = tune_params(e, o);
@@ -1621,10 +1618,8 @@ static void save_tune_cache(const yp_engine& e) {
 }
 
 static DwPwParams dwpw_params(const yp_engine& e, const Op& c) {
-    if (c.fused6) {            // the dw -> pw pair in front with this 1x1 (and the class-max keys) as the third stage
-        Op c1 = e.ops[c.fuse_tail];
-        c1.fused6 = false;
-        DwPwParams p = dwpw_params(e, c1);
+    if (c.form == FORM_DWPW_TAIL) {      // the dw -> pw pair in front with this 1x1 (and the class-max keys) as the third stage
+        DwPwParams p = dwpw_params(e, e.ops[c.fuse_tail]);
         const WeightDesc& w3 = e.weights[c.widx];
         const TensorDesc& to = e.tensors[c.out.t];
         p.w3 = w3.d_w ? w3.d_w : (const void*)1; p.Kpad3 = w3.Kpad; p.w3_bytes = w3.mat_bytes; p.b3 = w3.d_b ? w3.d_b : (const float*)1; p.C3 = c.out.C;
@@ -1645,24 +1640,6 @@ static DwPwParams dwpw_params(const yp_engine& e, const Op& c) {
     return p;
 }
 
-// the persistent conv kernels are additionally templated on <HAS_RES, OUT_F32>: make the reported symbol exact
-static void finish_kernel_names(yp_engine& e) {
-    for (Op& o : e.ops) {
-        const bool lc = o.kernel.find("_lc_kernel<") != std::string::npos || o.kernel.find("_s2_kernel<") != std::string::npos || o.kernel.find("_tile1_kernel<") != std::string::npos || o.kernel.find("_tile1w_kernel<") != std::string::npos || o.kernel.find("_wreg_kernel<") != std::string::npos || o.kernel.find("_pxd_kernel<") != std::string::npos || o.kernel.find("_ks_kernel<") != std::string::npos;
-        if ((o.kernel.find("_p_kernel<") == std::string::npos && !lc) || o.kernel.find(",false>") != std::string::npos || o.kernel.find(",true>") != std::string::npos) continue;
-        const bool f32 = (o.kind == OP_CONV) && e.tensors[o.out.t].f32 && e.dtype == DT_BF16;
-        const bool res = o.res.t >= 0;
-        bool wres = false, pipe = false, pp = false;
-        if (o.kernel.size() > 3 && o.kernel.compare(o.kernel.size() - 3, 3, ",P>") == 0) { pipe = true; o.kernel.erase(o.kernel.size() - 3); o.kernel += ">"; }
-        if (o.kernel.size() > 3 && o.kernel.compare(o.kernel.size() - 3, 3, ",Q>") == 0) { pp = true; o.kernel.erase(o.kernel.size() - 3); o.kernel += ">"; }
-        if (o.kernel.size() > 3 && o.kernel.compare(o.kernel.size() - 3, 3, ",W>") == 0) { wres = true; o.kernel.erase(o.kernel.size() - 3); }
-        else o.kernel.pop_back();
-        o.kernel += f32 ? ",false,true" : (res ? ",true,false" : ",false,false");
-        if (o.kernel.find("conv_dma_p_kernel") != std::string::npos) { o.kernel += wres ? ",true" : ",false"; o.kernel += pipe ? ",true" : ",false"; o.kernel += pp ? ",true" : ",false"; }
-        o.kernel += ">";
-    }
-}
-
 // ---------------------------------------------------------------------------------------------------------
 // Multi-lane launch for graph capture: ops carry a lane; every lane is a stream. Dependencies are derived from the
 // tensor views (RAW / WAR / WAW on overlapping channel ranges); a dependency that crosses lanes becomes an event
@@ -1675,20 +1652,28 @@ static bool views_overlap(const View& a, const View& b) {
 static void op_views(const yp_engine& e, const Op& o, std::vector<View>& rd, std::vector<View>& wr) {
     rd.clear(); wr.clear();
     if (o.skip) return;
-    if (o.fused) rd.push_back(e.ops[o.fuse_dw].in);
-    else if (o.fused6) rd.push_back(e.ops[e.ops[o.fuse_tail].fuse_dw].in);
-    else if (o.fused5) rd.push_back(e.ops[o.scd_pre].in);
-    else if (o.fused7) rd.push_back(e.ops[o.pw_pre].in);
-    else if (o.fused4) rd.push_back(View{o.in.t, o.in.coff, 2 * e.ops[o.c2f_m1].in.C});
-    else if (o.fused3) { /* reads the caller's frames only */ }
-    else if (o.fused2) rd.push_back(e.ops[o.fuse_pre].in);
-    else if (o.in.t >= 0) rd.push_back(o.in);
+    View extra;                                            // a second tensor the fused form writes
+    switch (o.form) {
+        case FORM_DWPW: rd.push_back(e.ops[o.fuse_dw].in); break;
+        case FORM_DWPW_TAIL:
+            rd.push_back(e.ops[e.ops[o.fuse_tail].fuse_dw].in);
+            if (o.tail_amax >= 0) extra = e.ops[o.tail_amax].out;
+            break;
+        case FORM_SCDOWN: rd.push_back(e.ops[o.scd_pre].in); break;
+        case FORM_PWSP:
+            rd.push_back(e.ops[o.pw_pre].in);
+            if (o.pw_store) extra = e.ops[o.pw_pre].out;
+            break;
+        case FORM_C2F: rd.push_back(View{o.in.t, o.in.coff, 2 * e.ops[o.c2f_m1].in.C}); break;
+        case FORM_FRONTEND: break;                         // (reads the caller's frames only)
+        case FORM_S2PW: rd.push_back(e.ops[o.fuse_pre].in); break;
+        case FORM_CLS_OUT: extra = e.ops[o.amax_post].out; [[fallthrough]];
+        case FORM_PLAIN: if (o.in.t >= 0) rd.push_back(o.in); break;
+    }
     if (o.folded) rd.push_back(e.ops[o.fold_up].in);      // (besides the concat buffer, whose skip part it still reads)
     if (o.res.t >= 0) rd.push_back(o.res);
     if (o.out.t >= 0) wr.push_back(o.out);
-    if (o.fused7 && o.pw_store) wr.push_back(e.ops[o.pw_pre].out);
-    if (o.fused8) wr.push_back(e.ops[o.amax_post].out);
-    if (o.fused6 && o.tail_amax >= 0) wr.push_back(e.ops[o.tail_amax].out);
+    if (extra.t >= 0) wr.push_back(extra);
     if (o.kind == OP_HEAD)
         for (int l = 0; l < 3; ++l) {
             if (o.sparse_box) rd.push_back(e.ops[o.hb_box[l][0]].in);              // the level's feature map instead of the dense box map
@@ -2117,8 +2102,8 @@ int yp_op_kernel(const yp_engine* e, int i, char* name, int cap) {
 int yp_op_fusion(const yp_engine* e, int i, int* pre, int* pre_stored) {
     if (!e || i < 0 || i >= (int)e->ops.size()) return fail(YP_ERR_ARG, "bad op index");
     const Op& o = e->ops[i];
-    if (pre) *pre = o.fused7 ? o.pw_pre : -1;
-    if (pre_stored) *pre_stored = (o.fused7 && o.pw_store) ? 1 : 0;
+    if (pre) *pre = o.form == FORM_PWSP ? o.pw_pre : -1;
+    if (pre_stored) *pre_stored = (o.form == FORM_PWSP && o.pw_store) ? 1 : 0;
     return YP_OK;
 }
 
@@ -2243,7 +2228,6 @@ static int prepare(yp_engine* e, int B, int H, int W, const uint8_t* in, float* 
                 if (rc != YP_OK) return rc;
                 save_tune_cache(*e);
             }
-            finish_kernel_names(*e);
             remember_tuning(*e);
         }
         rc = build_lane_schedule(*e);
@@ -2508,7 +2492,7 @@ int yp_debug_ablation(int v) {
 
 int yp_debug_force_conv_cfg(int cfg) {
     conv_dma_force_cfg(cfg);
-    return conv_dma_num_cfgs();
+    return conv_dma_family.num_cfgs;
 }
 
 // Host-only walk over everything the executor computes for the current plan short of launching: parameter blocks of every op,
@@ -2527,15 +2511,15 @@ int yp_debug_host_selftest(yp_engine* e) {
         }
     for (const Op& o : e->ops) {
         if (o.skip) continue;
-        if (o.kind == OP_CONV) {
-            if (o.fused || o.fused6) acc += (size_t)dwpw_params(*e, o).Cout;
-            else if (o.fused3) acc += (size_t)front_params(*e, o, nullptr).C2;
-            else if (o.fused4) acc += (size_t)c2f_params(*e, o).Cout;
-            else acc += (size_t)conv_params(*e, o).Cout;
-        } else if (o.kind == OP_DWCONV && o.fused5) acc += (size_t)scd_params(*e, o).C;
-        else if (o.fused7) acc += (size_t)pwsp_params(*e, o).C1;
+        switch (o.form) {
+            case FORM_DWPW: case FORM_DWPW_TAIL: acc += (size_t)dwpw_params(*e, o).Cout; break;
+            case FORM_FRONTEND: acc += (size_t)front_params(*e, o, nullptr).C2; break;
+            case FORM_C2F: acc += (size_t)c2f_params(*e, o).Cout; break;
+            case FORM_SCDOWN: acc += (size_t)scd_params(*e, o).C; break;
+            case FORM_PWSP: acc += (size_t)pwsp_params(*e, o).C1; break;
+            default: if (o.kind == OP_CONV) acc += (size_t)conv_params(*e, o).Cout;
+        }
     }
-    finish_kernel_names(*e);
     save_tune_cache(*e);
     (void)load_tune_cache(*e);
     {   // a packaged table for this plan's key, if one is shipped, must be launchable by this build (every id passes the tuner's own
@@ -2549,7 +2533,6 @@ int yp_debug_host_selftest(yp_engine* e) {
             if (!ok) return fail(YP_ERR_STATE, "packaged tune table %s does not apply to this build's plan", tp.c_str());
         }
     }
-    finish_kernel_names(*e);
     remember_tuning(*e);
     if (!recall_tuning(*e)) return fail(YP_ERR_STATE, "internal: tuning memo lost");
     int rc = build_lane_schedule(*e);
@@ -2639,7 +2622,6 @@ int yp_tuning_import(yp_engine* e, int B, int H, int W, const int32_t* cfg, int 
     if (n != (int)e->ops.size()) return fail(YP_ERR_ARG, "yp_tuning_import: %d ids for a plan of %zu ops", n, e->ops.size());
     std::vector<int> v(cfg, cfg + n);
     if (!apply_tuning(*e, v.data(), n)) return fail(YP_ERR_ARG, "yp_tuning_import: a configuration id is not launchable for its layer in this build");
-    finish_kernel_names(*e);
     remember_tuning(*e);                            // prepare() recalls it instead of tuning
     return YP_OK;
 }
