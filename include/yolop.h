@@ -112,6 +112,17 @@ int yp_masks(yp_engine* e, int b, const float* coeff_dev, const float* boxes_dev
 int yp_id_mask_resized(yp_engine* e, int b, const float* coeff_dev, const float* boxes_dev, int n, int oh, int ow, int rh,
                        int rw, int64_t* id_out, int32_t* kept_out, int suppress_small, int min_area, void* stream);
 
+/* The clip form of `results[0].masks` for the app's best row (yolo_seg/app.py:91-101): one retina mask per selected image of the last
+ * forward. Mask j is process_mask_native of the coefficient row coeff_dev + frame_idx[j] * coeff_row_stride against image frame_idx[j]'s
+ * prototypes, byte-equal to yp_masks(e, frame_idx[j], that row, boxes_dev + 4j, 1, oh, ow, retina=1, ...).
+ *    frame_idx_host int32 [k] host array, each in [0,B) of the last forward (gaps and repeats allowed); copied to the device in the call
+ *    coeff_dev      float, row 0 of image 0 (e.g. yp_forward's coeff_out with coeff_row_stride = max_det * YP_NM)
+ *    boxes_dev      float [k,4] x1,y1,x2,y2 in original-image (oh,ow) pixels
+ *    masks_out      uint8 [k,oh,ow] {0,1}; every byte is written (0 outside the box); k*oh*ow < 2^31
+ * Every argument is checked before anything is launched. */
+int yp_masks_frames(yp_engine* e, const int32_t* frame_idx_host, int k, const float* coeff_dev, long coeff_row_stride,
+                    const float* boxes_dev, int oh, int ow, uint8_t* masks_out, void* stream);
+
 /* `results[0].masks.xy[i]` and `get_coord_min_rect_len(...)` on the device (yolo_seg/app.py:101-103, yolo_seg/utils/mask_tools.py:12-22;
  * [U] Masks.xy = masks2segments(strategy): cv2.findContours(RETR_EXTERNAL, CHAIN_APPROX_SIMPLE), then "all" (the 8.3.x line the app's
  * YOLO11 weights need: every contour, concatenated) or "largest" (8.0-8.2: the contour with the most points, the first of them on a tie);
@@ -141,6 +152,10 @@ int yp_mask_contours(const uint8_t* masks_dev, int n, int H, int W, int strategy
  *    The geometry is the caller's (LetterBox arithmetic is host integer math: predictor.py / hostops.letterbox_geometry). */
 int yp_letterbox(const uint8_t* src_dev, int h0, int w0, uint8_t* dst_dev, int out_h, int out_w, int new_h, int new_w,
                  int top, int left, int pad_value, void* stream);
+/* n frames of one geometry in one launch: src_dev uint8 [n,h0,w0,3] -> dst_dev uint8 [n,out_h,out_w,3], byte-equal to n calls of
+ * yp_letterbox. 0 <= n <= 65535; n*h0*w0*3 and n*out_h*out_w*3 < 2^31. */
+int yp_letterbox_batch(const uint8_t* src_dev, int n, int h0, int w0, uint8_t* dst_dev, int out_h, int out_w, int new_h,
+                       int new_w, int top, int left, int pad_value, void* stream);
 
 /* -- U^2-Net-P / U^2-Net: the second per-frame network of the reference's video loop, `unet_predict(unet_model,
  *    cropped_frame)` at yolo_seg/app.py:184. Model: yolo_seg/tasks/models/U2Net.py:424-526 (U2NETP) / :318-420 (U2NET); loader and

@@ -135,6 +135,41 @@ int main() {
         CHECK(yp_u2net_forward_crops(u, frame_stub, 2, 720, 1280, ok_win, dup_idx, 2, 380, 380, nullptr, nullptr, nullptr, nullptr) == YP_ERR_STATE);
         CHECK(yp_u2net_destroy(u) == YP_OK);
     }
+    // clip form of the YOLO segmentation pass (yp_masks_frames, yp_letterbox_batch): bad arguments fail before anything is launched
+    for (int task = 0; task < 2; ++task) {
+        yp_model_desc d{'n', 80, task, YP_F32, 300, YP_FAMILY_V10};
+        yp_engine* eng = nullptr;
+        CHECK(yp_create(&d, 0, &eng) == YP_OK);
+        static float stub_f[8];                                          // never read: every call below is refused first
+        static uint8_t stub_u8[16];
+        const int32_t idx[3] = {0, 2, 2};
+        CHECK(yp_masks_frames(nullptr, idx, 3, stub_f, 300 * 32, stub_f, 720, 1280, stub_u8, nullptr) == YP_ERR_ARG);
+        CHECK(yp_masks_frames(eng, idx, -1, stub_f, 300 * 32, stub_f, 720, 1280, stub_u8, nullptr) == YP_ERR_ARG);
+        CHECK(yp_masks_frames(eng, idx, 3, stub_f, 300 * 32, stub_f, 0, 1280, stub_u8, nullptr) == YP_ERR_ARG);
+        CHECK(yp_masks_frames(eng, idx, 3, stub_f, 300 * 32, stub_f, 720, -5, stub_u8, nullptr) == YP_ERR_ARG);
+        CHECK(yp_masks_frames(eng, idx, 3000, stub_f, 300 * 32, stub_f, 720, 1280, stub_u8, nullptr) == YP_ERR_ARG);   // k*oh*ow >= 2^31
+        CHECK(yp_masks_frames(eng, nullptr, 3, stub_f, 300 * 32, stub_f, 720, 1280, stub_u8, nullptr) == YP_ERR_ARG);
+        CHECK(yp_masks_frames(eng, idx, 3, nullptr, 300 * 32, stub_f, 720, 1280, stub_u8, nullptr) == YP_ERR_ARG);
+        CHECK(yp_masks_frames(eng, idx, 3, stub_f, 300 * 32, nullptr, 720, 1280, stub_u8, nullptr) == YP_ERR_ARG);
+        CHECK(yp_masks_frames(eng, idx, 3, stub_f, 300 * 32, stub_f, 720, 1280, nullptr, nullptr) == YP_ERR_ARG);
+        CHECK(yp_masks_frames(eng, idx, 3, stub_f, 31, stub_f, 720, 1280, stub_u8, nullptr) == YP_ERR_ARG);
+        // valid arguments: a detect engine has no prototypes, a segment engine has run no forward (no device here)
+        CHECK(yp_masks_frames(eng, idx, 3, stub_f, 300 * 32, stub_f, 720, 1280, stub_u8, nullptr) == YP_ERR_STATE);
+        CHECK(yp_masks_frames(eng, idx, 0, stub_f, 300 * 32, stub_f, 720, 1280, stub_u8, nullptr) == YP_ERR_STATE);
+        CHECK(yp_destroy(eng) == YP_OK);
+    }
+    {
+        static uint8_t src[16], dst[16];                                 // never read: every call below is refused first or launches nothing
+        CHECK(yp_letterbox_batch(nullptr, 2, 720, 1280, dst, 384, 640, 360, 640, 12, 0, 114, nullptr) == YP_ERR_ARG);
+        CHECK(yp_letterbox_batch(src, 2, 720, 1280, nullptr, 384, 640, 360, 640, 12, 0, 114, nullptr) == YP_ERR_ARG);
+        CHECK(yp_letterbox_batch(src, -1, 720, 1280, dst, 384, 640, 360, 640, 12, 0, 114, nullptr) == YP_ERR_ARG);
+        CHECK(yp_letterbox_batch(src, 70000, 4, 4, dst, 4, 4, 4, 4, 0, 0, 114, nullptr) == YP_ERR_ARG);
+        CHECK(yp_letterbox_batch(src, 2, 720, 1280, dst, 384, 640, 360, 640, 30, 0, 114, nullptr) == YP_ERR_ARG);     // past the bottom
+        CHECK(yp_letterbox_batch(src, 2, 720, 1280, dst, 384, 640, 360, 640, 12, 0, 256, nullptr) == YP_ERR_ARG);
+        CHECK(yp_letterbox_batch(src, 2, 0, 1280, dst, 384, 640, 360, 640, 12, 0, 114, nullptr) == YP_ERR_ARG);
+        CHECK(yp_letterbox_batch(src, 800, 720, 1280, dst, 384, 640, 360, 640, 12, 0, 114, nullptr) == YP_ERR_ARG);  // > 2^31 bytes
+        CHECK(yp_letterbox_batch(src, 0, 720, 1280, dst, 384, 640, 360, 640, 12, 0, 114, nullptr) == YP_OK);         // nothing to do
+    }
     printf("asan_host: ok (%ld scheduled launches walked)\n", launches);
     return 0;
 }

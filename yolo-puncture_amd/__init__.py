@@ -8,7 +8,7 @@ __version__ = "0.1.0"
 
 def __getattr__(name):
     # lazy: importing the package must not require the built .so (tests of pure host logic run without it)
-    if name in ("YOLO", "Results", "Boxes", "Masks"):
+    if name in ("YOLO", "Results", "Boxes", "Masks", "ClipResults"):
         from . import predictor
         return getattr(predictor, name)
     if name in ("Engine", "load_library"):

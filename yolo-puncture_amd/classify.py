@@ -435,18 +435,29 @@ def predict_images(model: ClassifierEngine, images):
 
 
 def predict_and_find_start_inserted(model: ClassifierEngine, frames=None, boxes_list=None, judge_wnd: int = 20, batch_size: int = 8):
-    """BGR frames + integer xyxy boxes -> (class_list, prob_list, insert_frame_index), repaired. The frames go up in chunks of
-    batch_size and are cropped on the device; every image's result is independent of the chunking."""
+    """BGR frames + integer xyxy boxes -> (class_list, prob_list, insert_frame_index), repaired. frames: BGR uint8 HWC ndarrays, which go
+    up in chunks of batch_size, or a uint8 CUDA tensor [N,H,W,3] on the model's device (a clip uploaded once), sliced per chunk. Frames
+    are cropped on the device; every image's result is independent of the chunking."""
     frames = [] if frames is None else frames
     boxes_list = [] if boxes_list is None else boxes_list
+    dev = torch.device("cuda", model.device_index)
+    on_dev = isinstance(frames, torch.Tensor)
+    if on_dev:
+        if not (frames.is_cuda and frames.dtype == torch.uint8 and frames.dim() == 4 and frames.shape[-1] == 3):
+            raise TypeError("predict_and_find_start_inserted expects BGR uint8 HWC ndarrays or a uint8 CUDA tensor [N,H,W,3]")
+        if frames.device != dev:
+            raise ValueError(f"frames are on {frames.device}, the model on {dev}")
+        frames = frames.contiguous()
     if len(frames) != len(boxes_list):
         raise ValueError("The length of frames and boxes_list must be the same.")
-    dev = torch.device("cuda", model.device_index)
     class_list: list = []
     prob_list: list = []
     for i in range(0, len(frames), batch_size):
         chunk = frames[i:i + batch_size]
-        x = torch.from_numpy(np.stack([np.ascontiguousarray(f, dtype=np.uint8) for f in chunk])).to(dev)
+        if on_dev:
+            x = chunk
+        else:
+            x = torch.from_numpy(np.stack([np.ascontiguousarray(f, dtype=np.uint8) for f in chunk])).to(dev)
         b = torch.tensor([[int(v) for v in bx] for bx in boxes_list[i:i + batch_size]], dtype=torch.int32, device=dev)
         _, prob, cls = model.forward(x, b, bgr=True)
         class_list.extend(cls.cpu().numpy().astype(np.int64))

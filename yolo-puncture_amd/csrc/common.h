@@ -339,6 +339,8 @@ hipError_t launch_conv_halo_f32(const ConvParams& p, int dtype, hipStream_t st);
 hipError_t launch_head(const HeadParams& p, hipStream_t st);
 hipError_t launch_letterbox(const uint8_t* src, int h0, int w0, uint8_t* dst, int out_h, int out_w, int new_h, int new_w, int top,
                             int left, int pad, hipStream_t st);
+hipError_t launch_letterbox_batch(const uint8_t* src, int n, int h0, int w0, uint8_t* dst, int out_h, int out_w, int new_h, int new_w,
+                                  int top, int left, int pad, hipStream_t st);
 size_t head_scratch_bytes(int B, int A);
 hipError_t head_read_clocks(unsigned long long* out8);
 hipError_t head_branch_read_clocks(unsigned long long* out8);
@@ -410,6 +412,15 @@ struct MaskParams {
 };
 hipError_t launch_masks(const MaskParams& p, int dtype, hipStream_t st);
 size_t masks_workspace_bytes(const MaskParams& p);
+// One retina mask per selected frame (yp_masks_frames): p describes image 0 with n = 1 (proto, coeff = row 0 of frame 0, crop, oh, ow);
+// mask j uses frame fidx[j] (device int32 [k]): proto + fidx[j] * proto_stride bytes, coeff + fidx[j] * coeff_stride floats, box
+// boxes[4j..4j+4). M: float workspace [k, ch*cw]. masks uint8 [k,oh,ow], every byte written.
+struct MaskFramesParams {
+    MaskParams p;
+    const int32_t* fidx; int k;
+    size_t proto_stride; long coeff_stride;
+};
+hipError_t launch_masks_frames(const MaskFramesParams& f, float* M, int dtype, hipStream_t st);
 hipError_t contour_read_clocks(unsigned long long* out12);
 hipError_t launch_contours(const uint8_t* masks, int n, int H, int W, int strategy, int max_pts, int32_t* pts, int32_t* count, int32_t* parts, int parts_cap,
                            double* rect, hipStream_t st);

@@ -2400,6 +2400,20 @@ int yp_letterbox(const uint8_t* src_dev, int h0, int w0, uint8_t* dst_dev, int o
     return YP_OK;
 }
 
+int yp_letterbox_batch(const uint8_t* src_dev, int n, int h0, int w0, uint8_t* dst_dev, int out_h, int out_w, int new_h, int new_w, int top,
+                       int left, int pad_value, void* stream) {
+    if (n < 0 || n > 65535) return fail(YP_ERR_ARG, "yp_letterbox_batch: n = %d outside [0,65535]", n);
+    if (n > 0 && (!src_dev || !dst_dev)) return fail(YP_ERR_ARG, "yp_letterbox_batch: null buffer");
+    if (h0 <= 0 || w0 <= 0 || new_h <= 0 || new_w <= 0 || out_h <= 0 || out_w <= 0 || top < 0 || left < 0 || top + new_h > out_h ||
+        left + new_w > out_w || pad_value < 0 || pad_value > 255)
+        return fail(YP_ERR_ARG, "yp_letterbox_batch: bad geometry %dx%d -> %dx%d at (%d,%d) in %dx%d", h0, w0, new_h, new_w, top, left, out_h, out_w);
+    if ((long long)n * h0 * w0 * 3 >= (1ll << 31) || (long long)n * out_h * out_w * 3 >= (1ll << 31))
+        return fail(YP_ERR_ARG, "yp_letterbox_batch: batch too large");
+    if (n == 0) return YP_OK;
+    HIPCHK(launch_letterbox_batch(src_dev, n, h0, w0, dst_dev, out_h, out_w, new_h, new_w, top, left, pad_value, (hipStream_t)stream));
+    return YP_OK;
+}
+
 int yp_debug_head_clocks(uint64_t* out8) {
     if (!out8) return fail(YP_ERR_ARG, "yp_debug_head_clocks: null output");
     HIPCHK(hipDeviceSynchronize());
@@ -2686,6 +2700,28 @@ int yp_proto(const yp_engine* e, const void** proto_dev, int* Hp, int* Wp) {
     return YP_OK;
 }
 
+// the crop rectangle of the prototypes that maps onto an (oh,ow) original image (process_mask_native / retina masks)
+static void retina_crop(const TensorDesc& t, int oh, int ow, MaskParams& p) {
+    // scale_masks (A.7): gain=min(mh/oh,mw/ow); pad=((mw-ow*gain)/2,(mh-oh*gain)/2); crop [int(pad):int(m-pad)]
+    const double gain = std::min((double)t.H / oh, (double)t.W / ow);
+    const double padw = (t.W - ow * gain) / 2, padh = (t.H - oh * gain) / 2;
+    p.t = (int)padh; p.l = (int)padw;
+    p.ch = (int)(t.H - padh) - p.t; p.cw = (int)(t.W - padw) - p.l;
+    p.bsx = 1.f; p.bsy = 1.f; p.crop_before = 0;
+}
+
+// grows the engine's mask workspace to `need` bytes (after the stream has finished with the old one)
+static int ensure_mask_ws(yp_engine* e, size_t need, void* stream) {
+    if (need > e->mask_ws_bytes) {
+        HIPCHK(hipStreamSynchronize((hipStream_t)stream));
+        if (e->mask_ws) HIPCHK(hipFree(e->mask_ws));
+        e->mask_ws = nullptr; e->mask_ws_bytes = 0;
+        HIPCHK(hipMalloc(&e->mask_ws, need));
+        e->mask_ws_bytes = need;
+    }
+    return YP_OK;
+}
+
 static int masks_common(yp_engine* e, int b, const float* coeff_dev, const float* boxes_dev, int n, int oh, int ow, int retina, int rh, int rw,
                         uint8_t* masks_out, int64_t* id_out, int32_t* kept_out, int suppress_small, int min_area, void* stream) {
     if (!e) return fail(YP_ERR_ARG, "null engine");
@@ -2702,12 +2738,7 @@ static int masks_common(yp_engine* e, int b, const float* coeff_dev, const float
     p.proto = (const char*)t.ptr + (size_t)b * t.H * t.W * t.C * tensor_elem_bytes(*e, t);
     p.Hp = t.H; p.Wp = t.W; p.coeff = coeff_dev; p.boxes = boxes_dev; p.n = n; p.oh = oh; p.ow = ow;
     if (retina) {
-        // scale_masks (A.7): gain=min(mh/oh,mw/ow); pad=((mw-ow*gain)/2,(mh-oh*gain)/2); crop [int(pad):int(m-pad)]
-        const double gain = std::min((double)t.H / oh, (double)t.W / ow);
-        const double padw = (t.W - ow * gain) / 2, padh = (t.H - oh * gain) / 2;
-        p.t = (int)padh; p.l = (int)padw;
-        p.ch = (int)(t.H - padh) - p.t; p.cw = (int)(t.W - padw) - p.l;
-        p.bsx = 1.f; p.bsy = 1.f; p.crop_before = 0;
+        retina_crop(t, oh, ow, p);
     } else {
         p.t = 0; p.l = 0; p.ch = t.H; p.cw = t.W;
         p.bsx = (float)t.W / (float)e->pW; p.bsy = (float)t.H / (float)e->pH; p.crop_before = 1;
@@ -2719,14 +2750,8 @@ static int masks_common(yp_engine* e, int b, const float* coeff_dev, const float
         p.rh = rh; p.rw = rw;
     }
     {
-        const size_t need = masks_workspace_bytes(p);
-        if (need > e->mask_ws_bytes) {
-            HIPCHK(hipStreamSynchronize((hipStream_t)stream));
-            if (e->mask_ws) HIPCHK(hipFree(e->mask_ws));
-            e->mask_ws = nullptr; e->mask_ws_bytes = 0;
-            HIPCHK(hipMalloc(&e->mask_ws, need));
-            e->mask_ws_bytes = need;
-        }
+        const int rc = ensure_mask_ws(e, masks_workspace_bytes(p), stream);
+        if (rc != YP_OK) return rc;
         p.area = (int32_t*)e->mask_ws;
     }
     hipError_t err = launch_masks(p, e->dtype, (hipStream_t)stream);
@@ -2737,6 +2762,42 @@ static int masks_common(yp_engine* e, int b, const float* coeff_dev, const float
 int yp_masks(yp_engine* e, int b, const float* coeff_dev, const float* boxes_dev, int n, int oh, int ow, int retina,
              uint8_t* masks_out, int64_t* id_out, int32_t* kept_out, int suppress_small, int min_area, void* stream) {
     return masks_common(e, b, coeff_dev, boxes_dev, n, oh, ow, retina, 0, 0, masks_out, id_out, kept_out, suppress_small, min_area, stream);
+}
+
+int yp_masks_frames(yp_engine* e, const int32_t* frame_idx_host, int k, const float* coeff_dev, long coeff_row_stride, const float* boxes_dev,
+                    int oh, int ow, uint8_t* masks_out, void* stream) {
+    if (!e) return fail(YP_ERR_ARG, "null engine");
+    if (k < 0 || oh <= 0 || ow <= 0) return fail(YP_ERR_ARG, "yp_masks_frames: bad sizes k=%d %dx%d", k, oh, ow);
+    if ((long long)k * oh * ow >= (1ll << 31)) return fail(YP_ERR_ARG, "yp_masks_frames: k*oh*ow >= 2^31");
+    if (k > 65535) return fail(YP_ERR_ARG, "yp_masks_frames: at most 65535 masks per call");
+    if (k > 0 && (!frame_idx_host || !coeff_dev || !boxes_dev || !masks_out)) return fail(YP_ERR_ARG, "yp_masks_frames: null buffer");
+    if (coeff_row_stride < YP_NM) return fail(YP_ERR_ARG, "yp_masks_frames: coeff_row_stride %ld < %d", coeff_row_stride, YP_NM);
+    if (e->proto_t < 0) return fail(YP_ERR_STATE, "engine was not created with YP_TASK_SEGMENT");
+    if (!e->allocated) return fail(YP_ERR_STATE, "no forward has run yet");
+    for (int j = 0; j < k; ++j)
+        if (frame_idx_host[j] < 0 || frame_idx_host[j] >= e->pB)
+            return fail(YP_ERR_ARG, "yp_masks_frames: frame_idx[%d] = %d outside [0,%d)", j, frame_idx_host[j], e->pB);
+    if (k == 0) return YP_OK;
+    HIPCHK(hipSetDevice(e->device));
+    const TensorDesc& t = e->tensors[e->proto_t];
+    MaskFramesParams f{};
+    MaskParams& p = f.p;
+    p.proto = t.ptr; p.Hp = t.H; p.Wp = t.W; p.coeff = coeff_dev; p.boxes = boxes_dev; p.n = 1; p.oh = oh; p.ow = ow;
+    retina_crop(t, oh, ow, p);
+    p.masks = masks_out;
+    f.k = k;
+    f.proto_stride = (size_t)t.H * t.W * t.C * tensor_elem_bytes(*e, t);
+    f.coeff_stride = coeff_row_stride;
+    // workspace: int32 frame_idx[k] (256-byte aligned block) | float M[k, ch*cw]
+    const size_t idx_bytes = ((size_t)k * sizeof(int32_t) + 255) & ~(size_t)255;
+    const int rc = ensure_mask_ws(e, idx_bytes + (size_t)k * p.ch * p.cw * sizeof(float), stream);
+    if (rc != YP_OK) return rc;
+    int32_t* fidx_dev = (int32_t*)e->mask_ws;
+    HIPCHK(hipMemcpyAsync(fidx_dev, frame_idx_host, (size_t)k * sizeof(int32_t), hipMemcpyHostToDevice, (hipStream_t)stream));
+    f.fidx = fidx_dev;
+    hipError_t err = launch_masks_frames(f, (float*)((char*)e->mask_ws + idx_bytes), e->dtype, (hipStream_t)stream);
+    if (err != hipSuccess) return fail(YP_ERR_HIP, "mask kernels: %s", hipGetErrorString(err));
+    return YP_OK;
 }
 
 int yp_id_mask_resized(yp_engine* e, int b, const float* coeff_dev, const float* boxes_dev, int n, int oh, int ow, int rh, int rw,

@@ -25,11 +25,14 @@ __device__ __forceinline__ AxisCoef axis_coef(int d, int n_src, double scale) {
     return c;
 }
 
+// One launch covers n frames of the same geometry: frame = blockIdx.z, [n,h0,w0,3] -> [n,out_h,out_w,3] (yp_letterbox is n = 1).
 __global__ __launch_bounds__(256) void letterbox_kernel(const uint8_t* __restrict__ src, int h0, int w0, uint8_t* __restrict__ dst,
                                                         int out_h, int out_w, int new_h, int new_w, int top, int left, int pad,
                                                         double sx, double sy, int identity) {
     const int x = blockIdx.x * 64 + (threadIdx.x & 63), y = blockIdx.y * 4 + (threadIdx.x >> 6);
     if (x >= out_w || y >= out_h) return;
+    src += (size_t)blockIdx.z * h0 * w0 * 3;
+    dst += (size_t)blockIdx.z * out_h * out_w * 3;
     uint8_t* o = dst + ((size_t)y * out_w + x) * 3;
     const int rx = x - left, ry = y - top;
     if ((unsigned)rx >= (unsigned)new_w || (unsigned)ry >= (unsigned)new_h) {
@@ -54,13 +57,18 @@ __global__ __launch_bounds__(256) void letterbox_kernel(const uint8_t* __restric
     }
 }
 
-hipError_t launch_letterbox(const uint8_t* src, int h0, int w0, uint8_t* dst, int out_h, int out_w, int new_h, int new_w, int top,
-                            int left, int pad, hipStream_t st) {
+hipError_t launch_letterbox_batch(const uint8_t* src, int n, int h0, int w0, uint8_t* dst, int out_h, int out_w, int new_h, int new_w,
+                                  int top, int left, int pad, hipStream_t st) {
     const double sx = (double)w0 / (double)new_w, sy = (double)h0 / (double)new_h;
     const int identity = (h0 == new_h && w0 == new_w) ? 1 : 0;
-    hipLaunchKernelGGL(letterbox_kernel, dim3((out_w + 63) / 64, (out_h + 3) / 4), dim3(256), 0, st, src, h0, w0, dst, out_h, out_w,
+    hipLaunchKernelGGL(letterbox_kernel, dim3((out_w + 63) / 64, (out_h + 3) / 4, n), dim3(256), 0, st, src, h0, w0, dst, out_h, out_w,
                        new_h, new_w, top, left, pad, sx, sy, identity);
     return hipGetLastError();
+}
+
+hipError_t launch_letterbox(const uint8_t* src, int h0, int w0, uint8_t* dst, int out_h, int out_w, int new_h, int new_w, int top,
+                            int left, int pad, hipStream_t st) {
+    return launch_letterbox_batch(src, 1, h0, w0, dst, out_h, out_w, new_h, new_w, top, left, pad, st);
 }
 
 }  // namespace yp

@@ -34,8 +34,8 @@ template <> __device__ __forceinline__ void load32<float>(const float* p, float*
 
 // M[i][y][x] = sum_c coeff[i][c] * proto[t+y][l+x][c]   over the crop rectangle (ch x cw)
 template <typename T>
-__global__ __launch_bounds__(256) void mask_gemm_kernel(const MaskParams p, float* M) {
-    extern __shared__ float cs[];   // [n][32]
+__device__ __forceinline__ void mask_gemm_body(const MaskParams& p, float* M, float* cs) {
+    // cs: dynamic LDS [n][32]
     for (int i = threadIdx.x; i < p.n * 32; i += blockDim.x) cs[i] = p.coeff[i];
     __syncthreads();
     const int pix = blockIdx.x * blockDim.x + threadIdx.x;
@@ -51,6 +51,11 @@ __global__ __launch_bounds__(256) void mask_gemm_kernel(const MaskParams p, floa
         M[(size_t)i * p.ch * p.cw + pix] = acc;
     }
 }
+template <typename T>
+__global__ __launch_bounds__(256) void mask_gemm_kernel(const MaskParams p, float* M) {
+    extern __shared__ float cs[];
+    mask_gemm_body<T>(p, M, cs);
+}
 
 // The same product on the matrix cores (the "batched MFMA GEMM" of the prototype tail): D[mask][pixel] = coeff[mask][k] *
 // proto[pixel][k] with v_mfma_f32_16x16x4_f32 - exact fp32 FMAs accumulated in k order, i.e. the very chain
@@ -58,8 +63,8 @@ __global__ __launch_bounds__(256) void mask_gemm_kernel(const MaskParams p, floa
 // either way). One wave = 16 pixels x all masks, 16 masks per accumulator; coefficients are read from LDS as the A operand.
 typedef __attribute__((ext_vector_type(4))) float mf32x4;
 template <typename T>
-__global__ __launch_bounds__(256) void mask_gemm_mfma_kernel(const MaskParams p, float* M) {
-    extern __shared__ float cs[];   // [ceil16(n)][32], rows >= n zero
+__device__ __forceinline__ void mask_gemm_mfma_body(const MaskParams& p, float* M, float* cs) {
+    // cs: dynamic LDS [ceil16(n)][32], rows >= n zero
     const int npad = (p.n + 15) & ~15;
     for (int i = threadIdx.x; i < npad * 32; i += blockDim.x) cs[i] = (i < p.n * 32) ? p.coeff[i] : 0.f;
     __syncthreads();
@@ -87,6 +92,34 @@ __global__ __launch_bounds__(256) void mask_gemm_mfma_kernel(const MaskParams p,
         }
     }
 }
+template <typename T>
+__global__ __launch_bounds__(256) void mask_gemm_mfma_kernel(const MaskParams p, float* M) {
+    extern __shared__ float cs[];
+    mask_gemm_mfma_body<T>(p, M, cs);
+}
+
+// The 4-tap value of mask Mi at output pixel (x,y) (PyTorch upsample_bilinear2d, align_corners=False), with process_mask's zeroing of
+// taps outside the box at prototype resolution when p.crop_before. Shared by mask_resize_kernel and mask_frames_resize_kernel.
+__device__ __forceinline__ float mask_value(const MaskParams& p, const float* Mi, int x, int y, float x1, float y1, float x2, float y2) {
+    const float sy = (float)p.ch / (float)p.oh, sx = (float)p.cw / (float)p.ow;
+    float fy = sy * ((float)y + 0.5f) - 0.5f, fx = sx * ((float)x + 0.5f) - 0.5f;
+    fy = fmaxf(fy, 0.f);
+    fx = fmaxf(fx, 0.f);
+    const int y0 = (int)fy, x0 = (int)fx;
+    const int y1i = y0 + ((y0 < p.ch - 1) ? 1 : 0), x1i = x0 + ((x0 < p.cw - 1) ? 1 : 0);
+    const float ly1 = fy - (float)y0, lx1 = fx - (float)x0, ly0 = 1.f - ly1, lx0 = 1.f - lx1;
+    float v00 = Mi[y0 * p.cw + x0], v01 = Mi[y0 * p.cw + x1i], v10 = Mi[y1i * p.cw + x0], v11 = Mi[y1i * p.cw + x1i];
+    if (p.crop_before) {
+        // process_mask: zero outside the box scaled to prototype resolution, BEFORE interpolation
+        const float bx1 = x1 * p.bsx, bx2 = x2 * p.bsx, by1 = y1 * p.bsy, by2 = y2 * p.bsy;
+        auto in = [&](int yy, int xx) { return ((float)xx >= bx1) && ((float)xx < bx2) && ((float)yy >= by1) && ((float)yy < by2); };
+        if (!in(y0, x0)) v00 = 0.f;
+        if (!in(y0, x1i)) v01 = 0.f;
+        if (!in(y1i, x0)) v10 = 0.f;
+        if (!in(y1i, x1i)) v11 = 0.f;
+    }
+    return ly0 * (lx0 * v00 + lx1 * v01) + ly1 * (lx0 * v10 + lx1 * v11);
+}
 
 __global__ __launch_bounds__(256) void mask_resize_kernel(const MaskParams p, const float* M, uint8_t* masks, int32_t* area) {
     const int i = blockIdx.y;
@@ -98,27 +131,7 @@ __global__ __launch_bounds__(256) void mask_resize_kernel(const MaskParams p, co
         const float* Mi = M + (size_t)i * p.ch * p.cw;
         bool inside = true;
         if (!p.crop_before) inside = ((float)x >= x1) && ((float)x < x2) && ((float)y >= y1) && ((float)y < y2);
-        if (inside) {
-            const float sy = (float)p.ch / (float)p.oh, sx = (float)p.cw / (float)p.ow;
-            float fy = sy * ((float)y + 0.5f) - 0.5f, fx = sx * ((float)x + 0.5f) - 0.5f;
-            fy = fmaxf(fy, 0.f);
-            fx = fmaxf(fx, 0.f);
-            const int y0 = (int)fy, x0 = (int)fx;
-            const int y1i = y0 + ((y0 < p.ch - 1) ? 1 : 0), x1i = x0 + ((x0 < p.cw - 1) ? 1 : 0);
-            const float ly1 = fy - (float)y0, lx1 = fx - (float)x0, ly0 = 1.f - ly1, lx0 = 1.f - lx1;
-            float v00 = Mi[y0 * p.cw + x0], v01 = Mi[y0 * p.cw + x1i], v10 = Mi[y1i * p.cw + x0], v11 = Mi[y1i * p.cw + x1i];
-            if (p.crop_before) {
-                // process_mask: zero outside the box scaled to prototype resolution, BEFORE interpolation
-                const float bx1 = x1 * p.bsx, bx2 = x2 * p.bsx, by1 = y1 * p.bsy, by2 = y2 * p.bsy;
-                auto in = [&](int yy, int xx) { return ((float)xx >= bx1) && ((float)xx < bx2) && ((float)yy >= by1) && ((float)yy < by2); };
-                if (!in(y0, x0)) v00 = 0.f;
-                if (!in(y0, x1i)) v01 = 0.f;
-                if (!in(y1i, x0)) v10 = 0.f;
-                if (!in(y1i, x1i)) v11 = 0.f;
-            }
-            const float v = ly0 * (lx0 * v00 + lx1 * v01) + ly1 * (lx0 * v10 + lx1 * v11);
-            on = v > 0.f ? 1 : 0;
-        }
+        if (inside) on = mask_value(p, Mi, x, y, x1, y1, x2, y2) > 0.f ? 1 : 0;
         masks[(size_t)i * p.oh * p.ow + pix] = (uint8_t)on;
     }
     // mask.sum() per row (yolo_with_deva.py:75)
@@ -292,6 +305,95 @@ hipError_t launch_masks(const MaskParams& p, int dtype, hipStream_t st) {
     MaskParams pp = p;
     pp.oh = p.rh; pp.ow = p.rw;
     hipLaunchKernelGGL(mask_paint_kernel, dim3((p.rh * p.rw + 255) / 256), dim3(256), 0, st, pp, masks2, kept, p.ids);
+    return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// One retina mask per selected frame (yp_masks_frames, the clip form of `masks.xy[best]`): mask j is yp_masks(b = fidx[j], n = 1,
+// retina) of frame fidx[j]'s first coefficient row. The same GEMM bodies with a frame axis on the grid, then a resize that writes the
+// whole [k,oh,ow] output 16 bytes per lane: pixels outside the box are 0 without arithmetic, pixels inside take mask_value.
+// ---------------------------------------------------------------------------------------------------------------
+__device__ __forceinline__ MaskParams frame_view(const MaskFramesParams& f, int j) {
+    MaskParams q = f.p;
+    const int fi = f.fidx[j];
+    q.proto = (const char*)f.p.proto + (size_t)fi * f.proto_stride;
+    q.coeff = f.p.coeff + (size_t)fi * f.coeff_stride;
+    return q;
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void mask_frames_gemm_kernel(const MaskFramesParams f, float* M) {
+    extern __shared__ float cs[];
+    const int j = blockIdx.y;
+    mask_gemm_body<T>(frame_view(f, j), M + (size_t)j * f.p.ch * f.p.cw, cs);
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void mask_frames_gemm_mfma_kernel(const MaskFramesParams f, float* M) {
+    extern __shared__ float cs[];
+    const int j = blockIdx.y;
+    mask_gemm_mfma_body<T>(frame_view(f, j), M + (size_t)j * f.p.ch * f.p.cw, cs);
+}
+
+// lane t owns the 16 output bytes of the aligned 16-byte line t (line 0 starts at or before `masks`): one uint4 store for a whole line,
+// byte stores for the partial lines at either end of the buffer.
+__global__ __launch_bounds__(256) void mask_frames_resize_kernel(const MaskFramesParams f, const float* M, uint8_t* masks) {
+    const MaskParams& p = f.p;
+    const long long plane = (long long)p.oh * p.ow, total = plane * f.k;
+    const long long s = ((long long)blockIdx.x * blockDim.x + threadIdx.x) * 16 - (long long)((uintptr_t)masks & 15);
+    if (s >= total) return;
+    const long long b0 = s < 0 ? 0 : s;
+    int j = (int)(b0 / plane);
+    long long r = b0 - (long long)j * plane;
+    int y = (int)(r / p.ow), x = (int)(r - (long long)y * p.ow);
+    const float* bx = f.p.boxes + j * 4;
+    float x1 = bx[0], y1 = bx[1], x2 = bx[2], y2 = bx[3];
+    const float* Mi = M + (size_t)j * p.ch * p.cw;
+    uint32_t w[4] = {0u, 0u, 0u, 0u};
+#pragma unroll
+    for (int q = 0; q < 16; ++q) {
+        const long long b = s + q;
+        if (b < b0 || b >= total) continue;
+        const bool inside = ((float)x >= x1) && ((float)x < x2) && ((float)y >= y1) && ((float)y < y2);
+        if (inside && mask_value(p, Mi, x, y, x1, y1, x2, y2) > 0.f) w[q >> 2] |= 1u << (8 * (q & 3));
+        if (++x == p.ow) {
+            x = 0;
+            if (++y == p.oh && b + 1 < total) {
+                y = 0;
+                ++j;
+                bx = f.p.boxes + j * 4;
+                x1 = bx[0]; y1 = bx[1]; x2 = bx[2]; y2 = bx[3];
+                Mi = M + (size_t)j * p.ch * p.cw;
+            }
+        }
+    }
+    if (s >= 0 && s + 16 <= total) {
+        *(uint4*)(masks + s) = make_uint4(w[0], w[1], w[2], w[3]);
+    } else {
+        for (int q = 0; q < 16; ++q) {
+            const long long b = s + q;
+            if (b >= 0 && b < total) masks[b] = (uint8_t)((w[q >> 2] >> (8 * (q & 3))) & 0xffu);
+        }
+    }
+}
+
+// M: float [k, ch*cw] device workspace; f.fidx already on the device
+hipError_t launch_masks_frames(const MaskFramesParams& f, float* M, int dtype, hipStream_t st) {
+    if (f.k == 0) return hipSuccess;
+    const MaskParams& p = f.p;
+    const int npix = p.ch * p.cw;
+    static const bool valu_gemm = [] { const char* v = std::getenv("YOLOP_MASK_VALU"); return v && *v == '1'; }();   // as launch_masks
+    if (valu_gemm) {
+        const size_t sh = (size_t)p.n * 32 * sizeof(float);
+        if (dtype == DT_BF16) hipLaunchKernelGGL(mask_frames_gemm_kernel<__bf16>, dim3((npix + 255) / 256, f.k), dim3(256), sh, st, f, M);
+        else hipLaunchKernelGGL(mask_frames_gemm_kernel<float>, dim3((npix + 255) / 256, f.k), dim3(256), sh, st, f, M);
+    } else {
+        const size_t sh = (size_t)((p.n + 15) & ~15) * 32 * sizeof(float);
+        if (dtype == DT_BF16) hipLaunchKernelGGL(mask_frames_gemm_mfma_kernel<__bf16>, dim3((npix + 63) / 64, f.k), dim3(256), sh, st, f, M);
+        else hipLaunchKernelGGL(mask_frames_gemm_mfma_kernel<float>, dim3((npix + 63) / 64, f.k), dim3(256), sh, st, f, M);
+    }
+    const long long lines = ((long long)p.oh * p.ow * f.k + ((uintptr_t)p.masks & 15) + 15) / 16;
+    hipLaunchKernelGGL(mask_frames_resize_kernel, dim3((unsigned)((lines + 255) / 256)), dim3(256), 0, st, f, M, p.masks);
     return hipGetLastError();
 }
 

@@ -90,6 +90,10 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     lib.yp_debug_pwsp_clocks.argtypes = [C.POINTER(C.c_uint64)]
     lib.yp_letterbox.argtypes = [vp, C.c_int, C.c_int, vp] + [C.c_int] * 7 + [vp]
     lib.yp_letterbox.restype = C.c_int
+    lib.yp_letterbox_batch.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp] + [C.c_int] * 7 + [vp]
+    lib.yp_letterbox_batch.restype = C.c_int
+    lib.yp_masks_frames.argtypes = [vp, vp, C.c_int, vp, C.c_long, vp, C.c_int, C.c_int, vp, vp]
+    lib.yp_masks_frames.restype = C.c_int
     lib.yp_comm_unique_id.argtypes = [vp]
     lib.yp_comm_create.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.POINTER(vp)]
     lib.yp_allgather.argtypes = [vp, vp, vp, C.c_size_t, vp]
@@ -109,7 +113,7 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
 EXPORTS = ["yp_last_error", "yp_create", "yp_destroy", "yp_weight_count", "yp_weight_info", "yp_set_weight",
            "yp_finalize", "yp_forward", "yp_proto", "yp_masks", "yp_id_mask_resized", "yp_plan", "yp_op_info", "yp_op_output", "yp_op_input", "yp_op_fusion",
            "yp_tensor_count", "yp_tensor_info", "yp_tensor_read", "yp_profile", "yp_set_graph", "yp_run_op",
-           "yp_tensor_write", "yp_op_kernel", "yp_set_autotune", "yp_tuning_export", "yp_tuning_import", "yp_set_nms", "yp_debug_force_conv_cfg", "yp_debug_ablation", "yp_debug_head_clocks", "yp_debug_head_branch_clocks", "yp_debug_head_winners", "yp_debug_contour_clocks", "yp_debug_pwsp_clocks", "yp_debug_host_selftest", "yp_debug_graph_info", "yp_tuning_source", "yp_debug_head_positions", "yp_debug_marker", "yp_letterbox", "yp_mask_contours",
+           "yp_tensor_write", "yp_op_kernel", "yp_set_autotune", "yp_tuning_export", "yp_tuning_import", "yp_set_nms", "yp_debug_force_conv_cfg", "yp_debug_ablation", "yp_debug_head_clocks", "yp_debug_head_branch_clocks", "yp_debug_head_winners", "yp_debug_contour_clocks", "yp_debug_pwsp_clocks", "yp_debug_host_selftest", "yp_debug_graph_info", "yp_tuning_source", "yp_debug_head_positions", "yp_debug_marker", "yp_letterbox", "yp_letterbox_batch", "yp_masks_frames", "yp_mask_contours",
            "yp_comm_unique_id", "yp_comm_create", "yp_allgather", "yp_comm_destroy",
            "yp_u2net_create", "yp_u2net_destroy", "yp_u2net_weight_count", "yp_u2net_weight_info", "yp_u2net_set_weight", "yp_u2net_finalize",
            "yp_u2net_forward", "yp_u2net_forward_crops", "yp_u2net_set_graph", "yp_u2net_tensor_count", "yp_u2net_tensor_info", "yp_u2net_tensor_read",
@@ -136,6 +140,27 @@ def letterbox_device(src: torch.Tensor, geo: dict, out: Optional[torch.Tensor] =
         rc = lib.yp_letterbox(C.c_void_p(src.data_ptr()), int(src.shape[0]), int(src.shape[1]), C.c_void_p(out.data_ptr()), oh, ow,
                               int(geo["new_h"]), int(geo["new_w"]), int(geo["top"]), int(geo["left"]), int(pad_value),
                               C.c_void_p(_stream_ptr(src.device)))
+    if rc != 0:
+        raise YolopError(lib.yp_last_error().decode())
+    return out
+
+
+def letterbox_batch_device(frames: torch.Tensor, geo: dict, out: torch.Tensor, pad_value: int = 114) -> torch.Tensor:
+    """yp_letterbox_batch: `frames` uint8 cuda [n,h0,w0,3] of one shape, `geo` from hostops.letterbox_geometry -> written into `out`
+    uint8 cuda [n,out_h,out_w,3] in one launch (byte-equal to letterbox_device per frame)."""
+    if not (frames.is_cuda and frames.dtype == torch.uint8 and frames.dim() == 4 and frames.shape[3] == 3 and frames.is_contiguous()):
+        raise ValueError("letterbox_batch_device needs a contiguous uint8 CUDA tensor [n,H,W,3]")
+    n = int(frames.shape[0])
+    oh, ow = int(geo["out_h"]), int(geo["out_w"])
+    if not (out.is_cuda and out.dtype == torch.uint8 and tuple(out.shape) == (n, oh, ow, 3) and out.is_contiguous()):
+        raise ValueError(f"letterbox_batch_device: output must be a contiguous uint8 CUDA tensor [{n},{oh},{ow},3]")
+    if out.device != frames.device:
+        raise ValueError(f"letterbox_batch_device: frames on {frames.device}, output on {out.device}")
+    lib = load_library()
+    with torch.cuda.device(frames.device):
+        rc = lib.yp_letterbox_batch(C.c_void_p(frames.data_ptr()), n, int(frames.shape[1]), int(frames.shape[2]), C.c_void_p(out.data_ptr()),
+                                    oh, ow, int(geo["new_h"]), int(geo["new_w"]), int(geo["top"]), int(geo["left"]), int(pad_value),
+                                    C.c_void_p(_stream_ptr(frames.device)))
     if rc != 0:
         raise YolopError(lib.yp_last_error().decode())
     return out
@@ -336,6 +361,31 @@ class Engine:
                                     1 if suppress_small else 0, int(min_area), C.c_void_p(_stream_ptr(dev))))
         self._keep = [coeff, boxes]
         return m, ids, kept
+
+    def masks_frames(self, frame_idx, coeff: torch.Tensor, boxes: torch.Tensor, out_hw: Tuple[int, int],
+                     out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """yp_masks_frames: one retina mask per entry of `frame_idx` (images of the last forward; gaps and repeats allowed). `coeff` is the
+        forward's float32 cuda [B,max_det,32] (row 0 of image frame_idx[j] is used), `boxes` float32 cuda [k,4] in original-image pixels.
+        -> uint8 cuda [k,oh,ow] {0,1}, mask j equal to masks(frame_idx[j], coeff[frame_idx[j], :1], boxes[j:j+1], out_hw, retina=True)[0]."""
+        fidx = np.ascontiguousarray(np.asarray(frame_idx, dtype=np.int64).reshape(-1)).astype(np.int32)
+        k = int(fidx.shape[0])
+        oh, ow = int(out_hw[0]), int(out_hw[1])
+        if not (coeff.is_cuda and coeff.dtype == torch.float32 and coeff.dim() == 3 and coeff.shape[2] == 32 and coeff.is_contiguous()):
+            raise ValueError("masks_frames: coeff must be a contiguous float32 CUDA tensor [B,max_det,32]")
+        if not (boxes.is_cuda and boxes.dtype == torch.float32 and tuple(boxes.shape) == (k, 4) and boxes.device == coeff.device):
+            raise ValueError(f"masks_frames: boxes must be a float32 CUDA tensor [{k},4] on {coeff.device}")
+        if k and (fidx.min() < 0 or fidx.max() >= coeff.shape[0]):
+            raise ValueError(f"masks_frames: frame indices must lie in [0,{int(coeff.shape[0])})")
+        dev = coeff.device
+        boxes = boxes.contiguous()
+        if out is None:
+            out = torch.empty((k, oh, ow), dtype=torch.uint8, device=dev)
+        if not (out.is_cuda and out.dtype == torch.uint8 and tuple(out.shape) == (k, oh, ow) and out.is_contiguous() and out.device == dev):
+            raise ValueError(f"masks_frames: output must be a contiguous uint8 CUDA tensor [{k},{oh},{ow}] on {dev}")
+        self._chk(self.lib.yp_masks_frames(self._h, fidx.ctypes.data_as(C.c_void_p), k, C.c_void_p(coeff.data_ptr()), int(coeff.stride(0)),
+                                           C.c_void_p(boxes.data_ptr()), oh, ow, C.c_void_p(out.data_ptr()), C.c_void_p(_stream_ptr(dev))))
+        self._keep = [coeff, boxes]
+        return out
 
     def id_mask_resized(self, b: int, coeff: torch.Tensor, boxes: torch.Tensor, mask_hw: Tuple[int, int], out_hw: Tuple[int, int],
                         suppress_small: bool = False, min_area: int = 100):

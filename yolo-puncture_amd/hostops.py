@@ -326,3 +326,38 @@ def get_coord_min_rect_len(coord_xy) -> Tuple[float, float]:
     if width == 0:
         width = 1
     return length, length / width
+
+
+# ---- the app's first video loop over a whole clip (YOLO.predict_clip) -------------------------------------------------------
+def clip_plan(n: int, batch_size: int) -> Tuple[int, List[Tuple[int, int]]]:
+    """Chunks of YOLO.predict_clip for an n-frame clip: -> (B, [(start, count), ...]) with B = min(batch_size, n), contiguous chunks of
+    B frames; the last one (count < B) is padded to B by repeating its last frame, so a clip meets one engine plan."""
+    if int(batch_size) < 1:
+        raise ValueError(f"batch_size must be >= 1 (got {batch_size})")
+    n = int(n)
+    if n <= 0:
+        return 0, []
+    B = min(int(batch_size), n)
+    return B, [(s, min(B, n - s)) for s in range(0, n, B)]
+
+
+def clip_track(detected: Sequence[bool], xyxy: Sequence, polygons: Sequence, rect_lens: Sequence, width: int, height: int):
+    """The carry-forward of the reference's first video loop (yolo_seg/app.py:93-113) over per-frame results of the best detection:
+    detected[i], its float xyxy box, polygon (masks.xy[best]) and rectangle length (get_coord_min_rect_len(polygon)[0]).
+    -> (yolo_pred_xyxy, coord_xys, lens): a detection gives list(map(int, xyxy)), its polygon and its length; a frame without one repeats
+    the last box ((0, 0, width, height) before the first detection), gets None and repeats the last length (0 before the first)."""
+    boxes, coords, lens = [], [], []
+    last_box, last_rect_len = None, 0
+    for det, box, poly, rect_len in zip(detected, xyxy, polygons, rect_lens):
+        if det:
+            xyxy_box = list(map(int, box))
+            last_box = xyxy_box
+            coords.append(poly)
+            last_rect_len = rect_len
+            lens.append(rect_len)
+        else:
+            xyxy_box = (0, 0, width, height) if last_box is None else last_box
+            coords.append(None)
+            lens.append(last_rect_len)
+        boxes.append(xyxy_box)
+    return boxes, coords, lens

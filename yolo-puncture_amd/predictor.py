@@ -20,7 +20,7 @@ import numpy as np
 import torch
 
 from . import hostops
-from .engine import Engine, letterbox_device, mask_contours_device
+from .engine import Engine, letterbox_batch_device, letterbox_device, mask_contours_device
 from .weights import read_ultralytics_pt, synthetic_state
 
 _ENGINE_CACHE: Dict[tuple, Engine] = {}
@@ -171,7 +171,7 @@ class Masks:
         if i in self._polys:
             return self._polys[i]
         mh, mw = self.shape[1:]
-        poly, rect = None, None
+        poly, rect, parts = None, None, None
         u8 = self._u8
         one = None
         if u8 is None and isinstance(self._data, torch.Tensor) and self._data.is_cuda:
@@ -180,25 +180,22 @@ class Masks:
             one = u8[i:i + 1]
         if one is not None:
             if self.strategy == "all_merged":             # the device lists every external contour ("all") with its length; bridged on the host
-                polys, rects, parts = mask_contours_device(one, strategy="all", want_parts=True)
-                poly, rect = polys[0], rects[0]
-                if poly is not None and len(parts[0]) > 1:
-                    cuts = np.cumsum(parts[0])[:-1]
-                    poly = hostops.merge_contours(np.split(poly, cuts)).astype(np.int32)
+                polys, rects, all_parts = mask_contours_device(one, strategy="all", want_parts=True)
+                parts = all_parts[0]
             else:
                 polys, rects = mask_contours_device(one, strategy=self.strategy)
-                poly, rect = polys[0], rects[0]
-        if poly is None:                                  # (no GPU copy, or the device pass declined this mask: host trace)
+            poly, rect = polys[0], rects[0]
+
+        def host_mask():
             d = self.data[i]
             host = d.detach().cpu().numpy() if isinstance(d, torch.Tensor) else np.asarray(d)
-            poly = hostops.mask_polygon(host > 0.5, self.strategy)
-            rect = None
-        if rect is not None and (mh, mw) == self.orig_shape:
-            self._rects[i] = (float(rect[0]), float(rect[1]))   # (the device rectangle is of the polygon in mask pixels)
-        if poly.shape[0] and (mh, mw) != self.orig_shape:
-            poly = hostops.scale_coords((mh, mw), poly, self.orig_shape)
-        self._polys[i] = poly.astype(np.float32)
-        return self._polys[i]
+            return host > 0.5
+
+        poly, rect = _finish_contour(poly, rect, parts, self.strategy, host_mask, (mh, mw), self.orig_shape)
+        if rect is not None:
+            self._rects[i] = rect
+        self._polys[i] = poly
+        return poly
 
     @property
     def xy(self) -> "_LazyPolygons":
@@ -210,12 +207,34 @@ class Masks:
         poly = self._contour(i)
         if i < 0:
             i += len(self)
-        if i not in self._rects or len(poly) < 3:
-            return hostops.get_coord_min_rect_len(poly)
-        length, width = self._rects[i]
-        if width == 0:
-            width = 1
-        return length, length / width
+        return _rect_len(poly, self._rects.get(i))
+
+
+def _finish_contour(poly, rect, parts, strategy: str, host_mask, mask_hw: Tuple[int, int], orig_shape: Tuple[int, int]):
+    """What follows the device trace of one mask (Masks.xy and YOLO.predict_clip): poly / rect / parts as mask_contours_device gives them
+    for that mask (poly None: no device pass, or the device declined), the "all_merged" bridge, the host trace of `host_mask()` (bool
+    [mh,mw]) where there is no device polygon, and the scale to original-image pixels. -> (float32 [m,2] polygon, (long, short) device
+    rectangle or None; the device rectangle is of the polygon in mask pixels, so it is kept only when those are the original's)."""
+    if poly is not None and strategy == "all_merged" and parts is not None and len(parts) > 1:
+        cuts = np.cumsum(parts)[:-1]
+        poly = hostops.merge_contours(np.split(poly, cuts)).astype(np.int32)
+    if poly is None:
+        poly = hostops.mask_polygon(host_mask(), strategy)
+        rect = None
+    rect = (float(rect[0]), float(rect[1])) if rect is not None and tuple(mask_hw) == tuple(orig_shape) else None
+    if poly.shape[0] and tuple(mask_hw) != tuple(orig_shape):
+        poly = hostops.scale_coords(tuple(mask_hw), poly, orig_shape)
+    return poly.astype(np.float32), rect
+
+
+def _rect_len(poly: np.ndarray, rect) -> Tuple[float, float]:
+    """get_coord_min_rect_len(poly), from the device rectangle `rect` = (long, short) when there is one and the polygon has >= 3 points."""
+    if rect is None or len(poly) < 3:
+        return hostops.get_coord_min_rect_len(poly)
+    length, width = rect
+    if width == 0:
+        width = 1
+    return length, length / width
 
 
 class _LazyPolygons:
@@ -254,6 +273,29 @@ class Results:
 
     def numpy(self):
         return Results(self.orig_img, self.boxes.numpy(), self.masks.numpy() if self.masks is not None else None, self.names, self.path)
+
+
+class ClipResults(tuple):
+    """What YOLO.predict_clip returns: unpacks as `boxes, coords, lens` - the app's yolo_pred_xyxy, coord_xys and lens (yolo_seg/app.py:93-113)
+    - and also carries, per frame, `detected` (a row above conf), `conf` (its score, or None) and `xyxy` (its float32 [4] box in original-image
+    pixels, or None)."""
+
+    def __new__(cls, boxes, coords, lens, detected, conf, xyxy):
+        self = super().__new__(cls, (boxes, coords, lens))
+        self.detected, self.conf, self.xyxy = detected, conf, xyxy
+        return self
+
+    @property
+    def boxes(self):
+        return self[0]
+
+    @property
+    def coords(self):
+        return self[1]
+
+    @property
+    def lens(self):
+        return self[2]
 
 
 class _ModelHandle:
@@ -425,6 +467,107 @@ class YOLO:
         for i in range(len(imgs)):
             results.append(out_by_index[i])
         return results
+
+    def predict_clip(self, frames, conf: float = 0.25, iou: float = 0.7, imgsz: int = 640, batch_size: int = 32, device=None) -> ClipResults:
+        """The app's first video loop (yolo_seg/app.py:85-113: predict(frame, conf, retina_masks=True) -> best row -> masks.xy[best] ->
+        get_coord_min_rect_len, with the carry-forward of the last box and length) for a whole clip of same-shape frames.
+
+        frames: a list of BGR uint8 HWC ndarrays of one shape, or a uint8 CUDA tensor [N,H,W,3] on the engine's device. Frames run in
+        contiguous chunks of B = min(batch_size, N), the last one padded to B by repeating its last frame (hostops.clip_plan), so each chunk
+        is the computation predict() does on that padded chunk. Per chunk: one upload (host frames), one letterbox launch, the forward, ONE
+        copy of each frame's row 0 (rows are best first: np.argmax of the scores), the strict `> conf` test and scale_boxes on the host, one
+        mask per detected frame (yp_masks_frames) and one contour pass over them (MASK_POLYGON_STRATEGY, host trace where the device
+        declines). -> ClipResults: `boxes, coords, lens = model.predict_clip(frames)`."""
+        if not self.seg:
+            raise ValueError("predict_clip needs a segmentation checkpoint (-seg): the app reads masks.xy of the best row")
+        if int(batch_size) < 1:
+            raise ValueError(f"batch_size must be >= 1 (got {batch_size})")
+        strategy = MASK_POLYGON_STRATEGY
+        if strategy not in hostops.POLYGON_STRATEGIES:
+            raise ValueError(f"MASK_POLYGON_STRATEGY must be one of {hostops.POLYGON_STRATEGIES}, got {strategy!r}")
+        if device is not None:
+            self._set_device(device)
+        dev = torch.device("cuda", self._dev_index)
+        on_dev = isinstance(frames, torch.Tensor)
+        if on_dev:
+            if not (frames.is_cuda and frames.dtype == torch.uint8 and frames.dim() == 4 and frames.shape[-1] == 3):
+                raise TypeError("predict_clip expects BGR uint8 HWC ndarrays or a uint8 CUDA tensor [N,H,W,3]")
+            if frames.device != dev:
+                raise ValueError(f"frames are on {frames.device}, the engine on {dev}")
+            N, H, W = (int(v) for v in frames.shape[:3])
+        else:
+            frames = list(frames)
+            N = len(frames)
+            for f in frames:
+                if not (isinstance(f, np.ndarray) and f.dtype == np.uint8 and f.ndim == 3 and f.shape[2] == 3):
+                    raise TypeError("predict_clip expects BGR uint8 HWC ndarrays or a uint8 CUDA tensor [N,H,W,3]")
+                if f.shape != frames[0].shape:
+                    raise ValueError(f"frames differ in shape: {f.shape} vs {frames[0].shape}")
+            H, W = (int(v) for v in frames[0].shape[:2]) if N else (0, 0)
+        if N == 0:
+            return ClipResults([], [], [], [], [], [])
+        if H <= 0 or W <= 0:
+            raise ValueError(f"empty frames ({H}x{W})")
+        B, chunks = hostops.clip_plan(N, batch_size)
+        geo = hostops.letterbox_geometry(H, W, imgsz)
+        Hl, Wl = geo["out_h"], geo["out_w"]
+
+        eng = self._engine()
+        if self.family != "v10":
+            eng.set_nms(conf, iou)
+        mode = os.environ.get("YOLOP_PREDICT_GRAPH", "auto")
+        bcache = self.__dict__.setdefault("_batch_cache", {})          # the buffer predict() uses for this shape: one hipGraph per shape
+        batch = bcache.get((self._dev_index, B, Hl, Wl))
+        if batch is None:
+            batch = bcache[(self._dev_index, B, Hl, Wl)] = torch.empty((B, Hl, Wl, 3), dtype=torch.uint8, device=dev)
+        stage = None
+        if on_dev:
+            frames = frames.contiguous()
+        else:
+            scache = self.__dict__.setdefault("_clip_stage", {})
+            stage = scache.get((self._dev_index, B, H, W))
+            if stage is None:
+                stage = scache[(self._dev_index, B, H, W)] = torch.empty((B, H, W, 3), dtype=torch.uint8, device=dev)
+        cache = self.__dict__.setdefault("_out_cache", {})
+        okey = (self._dev_index, B)
+        dev_strategy = "all" if strategy == "all_merged" else strategy
+
+        detected: List[bool] = [False] * N
+        confs: List[Optional[float]] = [None] * N
+        xyxy: List[Optional[np.ndarray]] = [None] * N
+        polys: List[Optional[np.ndarray]] = [None] * N
+        rect_lens: List[float] = [0] * N
+        for s0, c in chunks:
+            if on_dev:
+                src = frames[s0:s0 + c]
+            else:
+                for q in range(c):                                      # straight into the device staging rows: no host-side stack
+                    stage[q].copy_(torch.from_numpy(np.ascontiguousarray(frames[s0 + q])), non_blocking=True)
+                src = stage[:c]
+            letterbox_batch_device(src, geo, out=batch[:c])
+            if c < B:                                                   # pad rows: the chunk's last frame again (their results are dropped)
+                batch[c:].copy_(batch[c - 1:c].expand(B - c, Hl, Wl, 3))
+            eng.set_graph("auto" if mode == "auto" else int(mode))
+            out = eng.forward(batch, cache.get(okey))
+            cache[okey] = out
+            rows = out["det"][:, 0].cpu()[:c]                           # ONE copy: row 0 of every frame (best first)
+            keep = rows[:, 4] > conf                                    # strict, as predict()
+            sel = [int(j) for j in torch.nonzero(keep).flatten()]
+            if not sel:
+                continue
+            boxes = hostops.scale_boxes_t((Hl, Wl), rows[sel, :4], (H, W))
+            m = eng.masks_frames(sel, out["coeff"], boxes.to(dev, non_blocking=True), (H, W))
+            dpolys, drects, *dparts = mask_contours_device(m, max_pts=131072, strategy=dev_strategy, want_parts=strategy == "all_merged")
+            bnp = boxes.numpy()
+            for t, j in enumerate(sel):
+                i = s0 + j
+                parts = dparts[0][t] if dparts else None
+                poly, rect = _finish_contour(dpolys[t], drects[t], parts, strategy, lambda t=t: m[t].cpu().numpy() > 0, (H, W), (H, W))
+                detected[i], confs[i], xyxy[i] = True, float(rows[j, 4]), bnp[t].copy()
+                polys[i] = poly
+                rect_lens[i] = _rect_len(poly, rect)[0]
+        boxes_l, coords, lens = hostops.clip_track(detected, xyxy, polys, rect_lens, W, H)
+        return ClipResults(boxes_l, coords, lens, detected, confs, xyxy)
 
     def predict_id_mask(self, image: np.ndarray, conf: float = 0.9, out_hw: Optional[Tuple[int, int]] = None,
                         suppress_small: bool = False, min_area: int = 100, imgsz: int = 640,
