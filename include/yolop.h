@@ -271,6 +271,14 @@ int yp_tuning_import(yp_engine* e, int B, int H, int W, const int32_t* cfg, int 
 
 /* Test hook: force conv tile configuration `cfg` wherever it is valid (-1 = off). Returns the number of configurations. */
 int yp_debug_force_conv_cfg(int cfg);
+/* Test hook, host only (no GPU needed): the tile configuration id that yp_run_op(e, i) launches op i of the current plan with, under the
+   forced id and the plan's own ids as they stand - a conv family's id (conv_dma's only when it was forced or tuned), 1000 for a 1x1 conv that
+   runs as pwsp_kernel, -1 where a heuristic picks or the op has no configuration id (fused forms other than the 3x3 s2 -> 1x1 pair, non-conv
+   ops), -2 for a folded upsample no configuration can run. */
+int yp_debug_op_cfg(const yp_engine* e, int i, int* cfg);
+/* Test hook: the conv tile families' configuration id ranges [base, base + num_cfgs), in the autotuner's order. Fills at most cap entries of
+   each array (either may be null) and returns the number of families. */
+int yp_debug_conv_families(int* base, int* num_cfgs, int cap);
 /* Timing ablation for tools (results become wrong): 0 off, 1 conv kernels drop their stores, 2 drop their pixel loads. */
 int yp_debug_ablation(int v);
 /* Profiling hook: 100 MHz timestamps of the phases of the top-k kernel (image 0's workgroup, last launch):

@@ -7,6 +7,7 @@ import pytest
 import torch
 
 from helpers import make_case, nchw_to_nhwc, rel_err
+from perop_bf16 import V10_SWEEP, per_op_bf16
 
 pytestmark = pytest.mark.gpu
 
@@ -74,24 +75,15 @@ def test_layerwise_fp32(variant, seg, shape):
     assert not bad, bad[:10]
 
 
-def _ulps_bf16(got, want):
-    """difference in units of the bf16 spacing at |want| (2^-7 of the leading power of two). The magnitude is
-    floored at 2^-10 of the tensor's max: a result that cancels to ~0 still carries the fp32 summation noise of
-    its O(max) terms (~1e-6*max), which is many 'ulps' of a tiny value but is not a rounding disagreement."""
-    mag = want.abs().clamp_min(float(want.abs().max()) * 2.0 ** -10 + 2.0 ** -126)
-    ulp = torch.exp2(torch.floor(torch.log2(mag)) - 7)
-    return (got - want).abs() / ulp
+def _per_op_bf16(*a, **k):
+    _dump(f"perop_bf16_{a[0]}", per_op_bf16(*a, **k)["rows"])
 
 
 @pytest.mark.parametrize("variant,seg,shape,cfg,fuse",
                          [("n", True, (2, 96, 128), -1, True), ("s", False, (1, 160, 192), -1, True), ("x", False, (1, 64, 64), -1, True),
                           ("s", False, (2, 256, 384), -1, True), ("s", False, (2, 256, 384), -1, False),
                           ("s", False, (1, 480, 608), -1, True), ("m", False, (2, 128, 160), -1, True)] +   # (m: 288- / 576-channel rows, K % 64 == 32)      # 60x76 at P3: partial tiles of the fused SCDown (4x8) and C2f-tail (8x16) kernels
-
-                         [("s", True, (3, 96, 160), c, True) for c in list(range(14)) + [100, 101, 102, 103, 200, 201, 202, 203, 204] + list(range(300, 341)) + list(range(400, 409)) + list(range(500, 505)) + [600, 601, 602] + list(range(700, 713)) + list(range(800, 808)) + list(range(900, 904)) + [1000, 1100, 1101, 1102, 1200, 1201]] +
-                         [("s", False, (1, 256, 256), c, True) for c in range(500, 505)] +    # stride-2 halo family: model.1 / .3 / .17 all valid here
-                         [(v, False, (2, 128, 160), c, True) for v in ("x", "m") for c in (1100, 1101, 1102, 1200, 1201)] +   # weights-resident 1x1: 80 / 320-, 48 / 192-channel rows, 3-5 channel blocks
-                         [("x", False, (1, 64, 64), c, True) for c in (801, 803, 807)])       # pixels-direct 1x1 with Cin % 64 == 32 (80 / 160 / 480-channel layers of v10-X)
+                         [c[1:] for c in V10_SWEEP])      # every conv tile configuration id, each on a graph and shape where ops take it (perop_bf16.py)
 def test_per_op_bf16_teacher_forced(variant, seg, shape, cfg, fuse, monkeypatch):
     _per_op_bf16(variant, seg, shape, cfg, fuse, monkeypatch, 80)
 
@@ -112,153 +104,6 @@ def test_per_op_bf16_small_nc(variant, seg, shape, nc, monkeypatch):
     yolo_with_deva.py:226): a 1- / 3-channel fp32 class map through the conv epilogues' 4-channel lane stores, the class-max pass'
     scalar branch and the class branch's narrow (max(ch0, min(nc,100)) wide) depthwise -> pointwise pairs. Same per-op contract as nc = 80."""
     _per_op_bf16(variant, seg, shape, -1, True, monkeypatch, nc)
-
-
-def _per_op_bf16(variant, seg, shape, cfg, fuse, monkeypatch, nc, want_tail=False):
-    """bf16 kernels one at a time: every op consumes the ORACLE's (bf16emu) tensors - after each op its output
-    slice is overwritten with the oracle's tap - so the only admissible difference is the bf16 rounding of an
-    fp32 sum taken in a different order: <= 1 bf16 ulp per element, on a small fraction of the elements.
-    (The chained bf16 forward cannot be compared this tightly: once two bf16 trajectories differ they decorrelate
-    to the bf16 noise floor, see test_end_to_end_bf16_accuracy.)"""
-    from oracle.yolov10_oracle import Oracle
-    st, im = make_case(variant, nc, seg, 0, shape)
-    taps = {}
-    Oracle(st, variant, nc, seg, "bf16emu", tap=lambda n, x: taps.__setitem__(n, x.float())).forward(im)
-    from yolo_puncture_amd.engine import load_library
-    assert load_library().yp_debug_force_conv_cfg(cfg) >= 14    # cfg >= 0: every conv that admits this tile config uses it
-    if not fuse:
-        monkeypatch.setenv("YOLOP_NO_FUSE", "1")     # read at yp_create: the dw / pw kernels of the fused pairs run unfused
-    eng = _engine(variant, nc, seg, "bf16", st)
-    if cfg >= 0:
-        eng.set_autotune(False)
-    imc = im.cuda()
-    out = eng.forward(imc)               # allocates the plan; results are recomputed op by op below
-    torch.cuda.synchronize()
-    ops = eng.plan(*shape)
-    if shape == (2, 256, 384):           # 8x12 P5 map: the 7x7 depthwise runs on the matrix-core kernel, or inside pwsp_kernel behind its 1x1 conv
-        k7 = [str(o.get("kernel", "")) for o in ops if o["name"].endswith("cv1.2")]
-        assert k7 and all(k.startswith(("dwconv_mfma", "pwsp_kernel") if fuse else "dwconv_mfma") for k in k7), k7
-    if cfg >= 1100:
-        assert variant != "s" or any(str(o.get("kernel", "")).startswith("conv_wres_kernel" if cfg < 1200 else "conv_wrs_kernel") for o in ops), "no op took the forced weights-resident configuration"
-    rows = []
-    from yolo_puncture_amd.weights import fold_state
-    folded = fold_state(st)
-    nfused = ntail = npwsp = nclsout = 0
-    for i, o in enumerate(ops):
-        if o["kind"] == "head":
-            continue
-        eng.run_op(i, imc, out)
-        is_pwsp = str(o.get("kernel", "")).startswith("pwsp_kernel") and o.get("pre", -1) >= 0
-        if is_pwsp:
-            npwsp += 1
-        if is_pwsp and o["kind"] == "pool3":
-            # pwsp_kernel, SPPF form: 1x1 conv -> three chained 5x5 max-pools in one launch. The pools are exact operators applied to the
-            # kernel's own 1x1 result, which is within 1 bf16 ulp of the oracle's on a small fraction of elements - so are the pooled maps
-            pre = ops[o["pre"]]
-            y = [taps[pre["name"]]]
-            for _ in range(3):
-                y.append(torch.nn.functional.max_pool2d(y[-1], 5, 1, 2))
-            t, c0, cc = o["out"]
-            want = nchw_to_nhwc(torch.cat(y[1:], 1))
-            got = eng.read_tensor(t)[..., c0:c0 + cc]
-            u = _ulps_bf16(got, want)
-            assert float(u.max()) <= 1.0 + 1e-6 and float((u > 0).float().mean()) < 0.02, (o["name"], float(u.max()), float((u > 0).float().mean()))
-            rows.append((o["name"], o["kind"], float(u.max()), float((u > 0).float().mean())))
-            eng.write_tensor(t, c0, want)
-            tp, cp0, cpc = pre["out"]
-            if o["pre_stored"]:                                    # the 1x1's own output, written by the same launch: the strict contract again
-                gp = eng.read_tensor(tp)[..., cp0:cp0 + cpc]
-                up = _ulps_bf16(gp, nchw_to_nhwc(taps[pre["name"]]))
-                assert float(up.max()) <= 1.0 + 1e-6 and float((up > 0).float().mean()) < 0.02, (pre["name"], float(up.max()))
-            eng.write_tensor(tp, cp0, nchw_to_nhwc(taps[pre["name"]]))
-            continue
-        if o["name"] not in taps:
-            continue
-        t, c0, cc = o["out"]
-        got = eng.read_tensor(t)[..., c0:c0 + cc]
-        want = nchw_to_nhwc(taps[o["name"]])
-        is_f32 = eng.tensors()[t]["f32"]
-        if is_f32 and str(o.get("kernel", "")).startswith("conv_dwpw"):
-            # TAIL form: depthwise -> pointwise -> this logit conv in one kernel; neither intermediate leaves the chip. A 1-ulp flip of an
-            # element of the pointwise result t moves a logit by |w3| * ulp(t); the fp32 sum itself carries summation-order noise 2e-5 * max
-            pw_name = ops[i - 1]["name"]
-            tmax = float(taps[pw_name].abs().max())
-            wmax = float(folded[o["name"]][0].abs().max())
-            ulp_t = 2.0 ** (torch.floor(torch.log2(torch.tensor(tmax))).item() - 7)
-            d = (got - want).abs()
-            bound = 2e-5 * float(want.abs().max()) + 6.0 * wmax * ulp_t
-            assert float(d.max()) <= bound, (o["name"], float(d.max()), bound)
-            assert float((d > 2e-5 * float(want.abs().max())).float().mean()) < 0.05, o["name"]     # ... and such flips are rare
-            rows.append((o["name"], o["kind"], float(d.max() / want.abs().max()), 0.0))
-            nfused += 1
-            ntail += 1
-            # the class-max keys the kernel wrote beside the logits: bits of sigmoid(max_c logit) of ITS logits
-            am = [q for q in ops if q["name"] == o["name"].replace("one2one_cv3", "amax").rsplit(".", 1)[0]]
-            if am and am[0]["kernel"] == "-":
-                keys = eng.read_tensor(am[0]["out"][0])[..., 0]
-                mx = got.max(-1).values
-                assert float((keys - torch.sigmoid(mx)).abs().max()) < 2e-7, o["name"]
-        elif is_f32:      # head logits are stored as fp32: compare like an fp32 op
-            err = rel_err(got, want)
-            rows.append((o["name"], o["kind"], err, 0.0))
-            assert err < 2e-5, (o["name"], err)
-            if str(o.get("kernel", "")).startswith("cls_out_kernel"):
-                # the same launch wrote the class-max keys (the OP_AMAX op is skipped): bits of sigmoid(max_c logit) of ITS logits
-                am = [q for q in ops if q["name"] == o["name"].replace("one2one_cv3", "amax").rsplit(".", 1)[0]]
-                assert am and am[0]["kernel"] == "-", (o["name"], am)
-                keys = eng.read_tensor(am[0]["out"][0])[..., 0]
-                assert float((keys - torch.sigmoid(got.max(-1).values)).abs().max()) < 2e-7, o["name"]
-                nclsout += 1
-        elif str(o.get("kernel", "")).startswith(("conv_dwpw", "frontend_kernel", "c2f_fused_kernel", "scdown_fused_kernel")) or is_pwsp or \
-                (str(o.get("kernel", "")).endswith(",false,false,true>") and "halo_s2" in str(o.get("kernel", ""))) or \
-                (o["kernel"] == "-" and o["kind"] == "conv" and i + 1 < len(ops) and ",tail," in str(ops[i + 1].get("kernel", ""))):
-            # (last case: the pointwise conv of a dw -> pw -> logits TAIL kernel; stepped on its own, yp_run_op runs it as the two-stage fused pair)
-            # fused depthwise -> pointwise (and 3x3 s2 -> 1x1): the first stage's result never leaves the chip, so it cannot be teacher-forced.
-            # It is itself within 1 bf16 ulp of the oracle's intermediate on a small fraction of elements (the contract
-            # of every unfused op), and such a flip of element j moves output co by |w[co,j]| * ulp(t_j). Tolerance:
-            # 1 output ulp + 4 simultaneous flips at the largest weight and the largest intermediate ulp; the differing
-            # fraction stays small because almost all such moves are far below an output ulp.
-            dw_name = ops[o["pre"] if is_pwsp else i - 1]["name"]   # the producer that was fused in (graph passes pair neighbours; pwsp names its own)
-            tmax = float(taps[dw_name].abs().max())
-            wmax = float(folded[o["name"]][0].abs().max())
-            ulp_t = 2.0 ** (torch.floor(torch.log2(torch.tensor(tmax))).item() - 7)
-            mag = torch.clamp(want.abs(), min=float(want.abs().max()) * 2.0 ** -10)
-            ulp_o = torch.exp2(torch.floor(torch.log2(mag)) - 7)
-            d = (got - want).abs()
-            assert bool((d <= ulp_o * (1.0 + 1e-6) + 4.0 * wmax * ulp_t).all()), (o["name"], float((d / ulp_o).max()))
-            u = d / ulp_o
-            frac = float((u > 0).float().mean())
-            rows.append((o["name"], o["kind"], min(float(u.max()), 1.0), frac))
-            assert float((u > 1.0 + 1e-6).float().mean()) < 0.005, (o["name"], float((u > 1.0).float().mean()))
-            assert frac < 0.05, (o["name"], frac)
-            nfused += 1
-            if is_pwsp:
-                # the launch also wrote the 1x1's own output when that has other readers: strict per-op contract, then the oracle's values
-                # again (this op overwrote what was teacher-forced after the stand-alone conv)
-                pre = ops[o["pre"]]
-                tp, cp0, cpc = pre["out"]
-                if o["pre_stored"]:
-                    gp = eng.read_tensor(tp)[..., cp0:cp0 + cpc]
-                    up = _ulps_bf16(gp, nchw_to_nhwc(taps[pre["name"]]))
-                    assert float(up.max()) <= 1.0 + 1e-6 and float((up > 0).float().mean()) < 0.02, (pre["name"], float(up.max()))
-                    eng.write_tensor(tp, cp0, nchw_to_nhwc(taps[pre["name"]]))
-        else:
-            u = _ulps_bf16(got, want)
-            frac = float((u > 0).float().mean())
-            rows.append((o["name"], o["kind"], float(u.max()), frac))
-            assert float(u.max()) <= 1.0 + 1e-6, (o["name"], float(u.max()))
-            assert frac < 0.02, (o["name"], frac)
-        eng.write_tensor(t, c0, want)    # teacher forcing
-    _dump(f"perop_bf16_{variant}", [(n, k, e) for n, k, e, _ in rows])
-    print(variant, "cfg", cfg, "ops checked", len(rows), "pwsp launches", npwsp, "cls_out launches", nclsout, "fused dw->pw ops", nfused, "of them with the logit conv as third stage", ntail, "max ulp", max(r[2] for r in rows if r[1] != "f32"),
-          "max differing fraction", max(r[3] for r in rows))
-    eng.close()
-    load_library().yp_debug_force_conv_cfg(-1)
-    assert len(rows) > 50
-    assert nfused == 0 if not fuse else (nfused > 0 or shape != (2, 256, 384) or nc != 80)
-    assert ntail > 0 if want_tail else ntail == 0
-    if fuse and cfg < 0 and variant == "s" and nc == 80 and not want_tail:
-        assert nclsout == 3, nclsout                 # one per level: the logit conv and the class-max keys in one launch
 
 
 def _final_report(res, ref, k):

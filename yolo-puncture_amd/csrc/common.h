@@ -294,6 +294,8 @@ hipError_t launch_conv_igemm(const ConvParams& p, int dtype, hipStream_t st);   
 std::string conv_kernel_name(const ConvParams& p, int dtype);
 bool conv_cfg_usable(const ConvParams& p, int dtype, int cfg);   // a configuration id from a cache file / yp_tuning_import is launchable for p
 bool conv_dma_supported(const ConvParams& p);
+int conv_dma_requested_cfg(const ConvParams& p);                 // conv_dma's configuration for p when forced or tuned (valid for p), else -1
+int conv_launch_cfg(const ConvParams& p, int dtype);             // the configuration id launch_conv runs p with, -1 = a heuristic's pick
 void conv_dma_force_cfg(int cfg);
 int conv_dma_forced_cfg();
 void conv_set_debug_ablation(int v);

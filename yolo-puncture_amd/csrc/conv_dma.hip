@@ -294,9 +294,13 @@ static int g_dbg_ablate = 0;
 void conv_set_debug_ablation(int v) { g_dbg_ablate = v; }
 int conv_debug_ablation() { return g_dbg_ablate; }
 bool tile_balance_enabled(int family) { static const int mask = [] { const char* v = std::getenv("YOLOP_BALANCE"); return v ? atoi(v) : 6; }(); return (mask & family) != 0; }
-static int dma_choice(const ConvParams& p) {
+int conv_dma_requested_cfg(const ConvParams& p) {
     if (conv_dma_cfg_valid(p, g_force_cfg)) return g_force_cfg;
-    return conv_dma_cfg_valid(p, p.cfg) ? p.cfg : dma_heuristic(p);
+    return conv_dma_cfg_valid(p, p.cfg) ? p.cfg : -1;
+}
+static int dma_choice(const ConvParams& p) {
+    const int c = conv_dma_requested_cfg(p);
+    return c >= 0 ? c : dma_heuristic(p);
 }
 
 static std::string conv_dma_symbol(const ConvParams& p, int) { return kCfgs[dma_choice(p)].name; }

@@ -293,6 +293,14 @@ bool conv_cfg_usable(const ConvParams& p, int dtype, int cfg) {
     return dtype == DT_BF16 && conv_cfg_fits(p, cfg);
 }
 
+// The id launch_conv resolves p to (yp_debug_op_cfg): conv_choice's, conv_dma's forced or tuned one, -1 where a heuristic picks, -2 none.
+int conv_launch_cfg(const ConvParams& p, int dtype) {
+    const int h = conv_choice(p, dtype);
+    if (h != -1) return h;
+    if (dtype == DT_BF16 && conv_dma_supported(p)) return conv_dma_requested_cfg(p);
+    return -1;
+}
+
 std::string conv_kernel_name(const ConvParams& p, int dtype) {
     const int h = conv_choice(p, dtype);
     if (h >= 100) { const ConvFamily& f = *conv_family_of(h); return f.symbol(p, h - f.base); }

@@ -1266,6 +1266,38 @@ static PwSpParams pwsp_params(const yp_engine& e, const Op& o) {
     return p;
 }
 
+// ConvTranspose 2x2 s2: output sub-position (dy, dx) is a 1x1 conv with its own weight slice, scattered with up = 2
+static ConvParams convt_params(const yp_engine& e, const Op& o, int dy, int dx) {
+    const WeightDesc& w = e.weights[o.widx];
+    const TensorDesc &ti = e.tensors[o.in.t], &to = e.tensors[o.out.t];
+    ConvParams p{};
+    p.x = ti.ptr; p.x_stride = ti.C; p.x_coff = o.in.coff; p.H = ti.H; p.W = ti.W; p.Cin = o.in.C;
+    const size_t sub = (size_t)((w.cout + 127) / 128 * 128) * w.Kpad * e.es();
+    p.w = (const char*)w.d_w + sub * (dy * 2 + dx); p.Kpad = w.Kpad; p.bias = w.d_b;
+    p.y = to.ptr; p.y_stride = to.C; p.y_coff = o.out.coff; p.Ho = ti.H; p.Wo = ti.W; p.Cout = o.out.C;
+    p.M = e.pB * ti.H * ti.W; p.ks = 1; p.stride = 1; p.pad = 0; p.act = o.act; p.out_f32 = 0;
+    p.up = 2; p.oy = dy; p.ox = dx;
+    p.x_bytes = ti.bytes; p.w_bytes = w.mat_bytes; p.y_bytes = to.bytes; p.cfg = o.cfg;
+    return p;
+}
+
+// The configuration id run_op launches o with (yp_debug_op_cfg): every branch here mirrors one of run_op's.
+static int op_launch_cfg(const yp_engine& e, const Op& o) {
+    if (o.kind == OP_CONVT) return conv_launch_cfg(convt_params(e, o, 0, 0), e.dtype);      // (the four sub-positions share a shape)
+    if (o.kind != OP_CONV) return -1;
+    switch (o.form) {
+        case FORM_DWPW: case FORM_DWPW_TAIL: case FORM_FRONTEND: case FORM_C2F: case FORM_CLS_OUT: return -1;
+        case FORM_S2PW: return o.cfg;
+        default: break;
+    }
+    if (o.cfg == PWSP_CFG) return PWSP_CFG;
+    if (conv_dma_forced_cfg() == PWSP_CFG && e.dtype == DT_BF16 && !o.folded) {
+        const PwSpParams q = pwsp_params(e, o);
+        if (q.sp == 0 && pwsp_valid(q)) return PWSP_CFG;
+    }
+    return conv_launch_cfg(conv_params(e, o), e.dtype);
+}
+
 static hipError_t run_op(yp_engine& e, const Op& o, const RunArgs& a, hipStream_t st) {
     auto T = [&](const View& v) -> const TensorDesc& { return e.tensors[v.t]; };
     const int B = e.pB;
@@ -1294,19 +1326,9 @@ static hipError_t run_op(yp_engine& e, const Op& o, const RunArgs& a, hipStream_
             }
             return launch_conv(conv_params(e, o), e.dtype, st);
         case OP_CONVT: {
-            const WeightDesc& w = e.weights[o.widx];
-            const TensorDesc &ti = T(o.in), &to = T(o.out);
             for (int dy = 0; dy < 2; ++dy)
                 for (int dx = 0; dx < 2; ++dx) {
-                    ConvParams p{};
-                    p.x = ti.ptr; p.x_stride = ti.C; p.x_coff = o.in.coff; p.H = ti.H; p.W = ti.W; p.Cin = o.in.C;
-                    const size_t sub = (size_t)((w.cout + 127) / 128 * 128) * w.Kpad * e.es();
-                    p.w = (const char*)w.d_w + sub * (dy * 2 + dx); p.Kpad = w.Kpad; p.bias = w.d_b;
-                    p.y = to.ptr; p.y_stride = to.C; p.y_coff = o.out.coff; p.Ho = ti.H; p.Wo = ti.W; p.Cout = o.out.C;
-                    p.M = B * ti.H * ti.W; p.ks = 1; p.stride = 1; p.pad = 0; p.act = o.act; p.out_f32 = 0;
-                    p.up = 2; p.oy = dy; p.ox = dx;
-                    p.x_bytes = ti.bytes; p.w_bytes = w.mat_bytes; p.y_bytes = to.bytes; p.cfg = o.cfg;
-                    hipError_t err = launch_conv(p, e.dtype, st);
+                    hipError_t err = launch_conv(convt_params(e, o, dy, dx), e.dtype, st);
                     if (err != hipSuccess) return err;
                 }
             return hipSuccess;
@@ -2507,6 +2529,20 @@ int yp_debug_ablation(int v) {
 int yp_debug_force_conv_cfg(int cfg) {
     conv_dma_force_cfg(cfg);
     return conv_dma_family.num_cfgs;
+}
+
+int yp_debug_op_cfg(const yp_engine* e, int i, int* cfg) {
+    if (!e || i < 0 || i >= (int)e->ops.size() || !cfg) return fail(YP_ERR_ARG, "bad argument");
+    *cfg = op_launch_cfg(*e, e->ops[i]);
+    return YP_OK;
+}
+
+int yp_debug_conv_families(int* base, int* num_cfgs, int cap) {
+    for (int f = 0; f < kNumConvFamilies && f < cap; ++f) {
+        if (base) base[f] = kConvFamilies[f]->base;
+        if (num_cfgs) num_cfgs[f] = kConvFamilies[f]->num_cfgs;
+    }
+    return kNumConvFamilies;
 }
 
 // Host-only walk over everything the executor computes for the current plan short of launching: parameter blocks of every op,

@@ -83,6 +83,10 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     lib.yp_debug_marker.argtypes = [vp]
     lib.yp_debug_marker.restype = C.c_int
     lib.yp_debug_force_conv_cfg.argtypes = [C.c_int]
+    lib.yp_debug_op_cfg.argtypes = [vp, C.c_int, ip]
+    lib.yp_debug_op_cfg.restype = C.c_int
+    lib.yp_debug_conv_families.argtypes = [ip, ip, C.c_int]
+    lib.yp_debug_conv_families.restype = C.c_int
     lib.yp_debug_ablation.argtypes = [C.c_int]
     lib.yp_debug_head_clocks.argtypes = [C.POINTER(C.c_uint64)]
     lib.yp_debug_head_branch_clocks.argtypes = [C.POINTER(C.c_uint64)]
@@ -113,12 +117,21 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
 EXPORTS = ["yp_last_error", "yp_create", "yp_destroy", "yp_weight_count", "yp_weight_info", "yp_set_weight",
            "yp_finalize", "yp_forward", "yp_proto", "yp_masks", "yp_id_mask_resized", "yp_plan", "yp_op_info", "yp_op_output", "yp_op_input", "yp_op_fusion",
            "yp_tensor_count", "yp_tensor_info", "yp_tensor_read", "yp_profile", "yp_set_graph", "yp_run_op",
-           "yp_tensor_write", "yp_op_kernel", "yp_set_autotune", "yp_tuning_export", "yp_tuning_import", "yp_set_nms", "yp_debug_force_conv_cfg", "yp_debug_ablation", "yp_debug_head_clocks", "yp_debug_head_branch_clocks", "yp_debug_head_winners", "yp_debug_contour_clocks", "yp_debug_pwsp_clocks", "yp_debug_host_selftest", "yp_debug_graph_info", "yp_tuning_source", "yp_debug_head_positions", "yp_debug_marker", "yp_letterbox", "yp_letterbox_batch", "yp_masks_frames", "yp_mask_contours",
+           "yp_tensor_write", "yp_op_kernel", "yp_set_autotune", "yp_tuning_export", "yp_tuning_import", "yp_set_nms", "yp_debug_force_conv_cfg", "yp_debug_op_cfg", "yp_debug_conv_families", "yp_debug_ablation", "yp_debug_head_clocks", "yp_debug_head_branch_clocks", "yp_debug_head_winners", "yp_debug_contour_clocks", "yp_debug_pwsp_clocks", "yp_debug_host_selftest", "yp_debug_graph_info", "yp_tuning_source", "yp_debug_head_positions", "yp_debug_marker", "yp_letterbox", "yp_letterbox_batch", "yp_masks_frames", "yp_mask_contours",
            "yp_comm_unique_id", "yp_comm_create", "yp_allgather", "yp_comm_destroy",
            "yp_u2net_create", "yp_u2net_destroy", "yp_u2net_weight_count", "yp_u2net_weight_info", "yp_u2net_set_weight", "yp_u2net_finalize",
            "yp_u2net_forward", "yp_u2net_forward_crops", "yp_u2net_set_graph", "yp_u2net_tensor_count", "yp_u2net_tensor_info", "yp_u2net_tensor_read",
            "yp_cls_create", "yp_cls_destroy", "yp_cls_weight_count", "yp_cls_weight_info", "yp_cls_set_weight", "yp_cls_finalize",
            "yp_cls_forward", "yp_cls_set_graph", "yp_cls_tensor_count", "yp_cls_tensor_info", "yp_cls_tensor_read"]
+
+
+def conv_families() -> List[Tuple[int, int]]:
+    """(base, number of configurations) of every conv tile family: configuration ids [base, base + n), in the autotuner's order."""
+    lib = load_library()
+    n = lib.yp_debug_conv_families(None, None, 0)
+    base, num = (C.c_int * n)(), (C.c_int * n)()
+    lib.yp_debug_conv_families(base, num, n)
+    return list(zip(base, num))
 
 
 def _stream_ptr(device: torch.device) -> int:
@@ -425,6 +438,8 @@ class Engine:
             pre, stored = C.c_int(), C.c_int()
             self._chk(self.lib.yp_op_fusion(self._h, i, C.byref(pre), C.byref(stored)))
             rec["pre"], rec["pre_stored"] = pre.value, bool(stored.value)     # pwsp_kernel: the 1x1 conv fused in front (or -1), and whether its output is written too
+            self._chk(self.lib.yp_debug_op_cfg(self._h, i, C.byref(pre)))
+            rec["cfg"] = pre.value          # the tile configuration id run_op launches it with under the forced id (-1: a heuristic picks)
             ops.append(rec)
         return ops
 
