@@ -122,6 +122,13 @@ int yp_id_mask_resized(yp_engine* e, int b, const float* coeff_dev, const float*
  * Every argument is checked before anything is launched. */
 int yp_masks_frames(yp_engine* e, const int32_t* frame_idx_host, int k, const float* coeff_dev, long coeff_row_stride,
                     const float* boxes_dev, int oh, int ow, uint8_t* masks_out, void* stream);
+/* The same for `predict(frame, conf)` without retina_masks (dev_tools/auto_speed_calc.py:62): ultralytics' process_mask at the letterboxed
+ * input size. Mask j is byte-equal to yp_masks(e, frame_idx[j], that row, boxes_dev + 4j, 1, oh, ow, retina=0, ...).
+ *    boxes_dev  float [k,4] x1,y1,x2,y2 in letterboxed-input pixels (the forward's rows, before scale_boxes)
+ *    (oh,ow)    the (H,W) of the last forward; masks_out uint8 [k,oh,ow] {0,1}, every byte written
+ * Other arguments and checks as yp_masks_frames. */
+int yp_masks_frames_input(yp_engine* e, const int32_t* frame_idx_host, int k, const float* coeff_dev, long coeff_row_stride,
+                          const float* boxes_dev, int oh, int ow, uint8_t* masks_out, void* stream);
 
 /* `results[0].masks.xy[i]` and `get_coord_min_rect_len(...)` on the device (yolo_seg/app.py:101-103, yolo_seg/utils/mask_tools.py:12-22;
  * [U] Masks.xy = masks2segments(strategy): cv2.findContours(RETR_EXTERNAL, CHAIN_APPROX_SIMPLE), then "all" (the 8.3.x line the app's
@@ -143,6 +150,14 @@ int yp_masks_frames(yp_engine* e, const int32_t* frame_idx_host, int k, const fl
 #define YP_CONTOURS_ALL 1
 int yp_mask_contours(const uint8_t* masks_dev, int n, int H, int W, int strategy, int max_pts, int32_t* pts_out, int32_t* count_out,
                      int32_t* parts_out, int parts_cap, double* rect_out, void* stream);
+/* yp_mask_contours of masks at the letterboxed input size (H,W) of a (H0,W0) frame, for `masks.xy[i]` without retina_masks: pts_out,
+ * count_out and parts_out are byte-equal to yp_mask_contours' (mask pixels). rect_out is the minimum-area rectangle of the polygon after
+ * hostops.scale_coords((H,W) -> (H0,W0)) and the int32 truncation of get_coord_min_rect_len - what get_coord_min_rect_len(masks.xy[i])
+ * measures: per point x' = (int)min(max(((float)x - padx) / gain, 0), W0) in fp32 (same for y with pady, H0), with gain = min(H/H0, W/W0),
+ * padx = (W - W0 * gain) / 2, pady = (H - H0 * gain) / 2 computed in double and rounded to float. When W0 >= 2048 (the hull's column
+ * tables cover 0..W0) the device declines the rectangle only: rect_out row = (-1, -1), points as usual. */
+int yp_mask_contours_scaled(const uint8_t* masks_dev, int n, int H, int W, int strategy, int max_pts, int32_t* pts_out, int32_t* count_out,
+                            int32_t* parts_out, int parts_cap, double* rect_out, int H0, int W0, void* stream);
 
 /* LetterBox on the device (the step before the network inside `.predict`; reference call sites yolo_seg/app.py:86-91,
  * [U] ultralytics LetterBox = cv2.resize INTER_LINEAR + cv2.copyMakeBorder(114)). Engine-free, pure function of its

@@ -135,7 +135,8 @@ int main() {
         CHECK(yp_u2net_forward_crops(u, frame_stub, 2, 720, 1280, ok_win, dup_idx, 2, 380, 380, nullptr, nullptr, nullptr, nullptr) == YP_ERR_STATE);
         CHECK(yp_u2net_destroy(u) == YP_OK);
     }
-    // clip form of the YOLO segmentation pass (yp_masks_frames, yp_letterbox_batch): bad arguments fail before anything is launched
+    // clip form of the YOLO segmentation pass (yp_masks_frames, yp_masks_frames_input, yp_letterbox_batch): bad arguments fail before
+    // anything is launched
     for (int task = 0; task < 2; ++task) {
         yp_model_desc d{'n', 80, task, YP_F32, 300, YP_FAMILY_V10};
         yp_engine* eng = nullptr;
@@ -156,7 +157,40 @@ int main() {
         // valid arguments: a detect engine has no prototypes, a segment engine has run no forward (no device here)
         CHECK(yp_masks_frames(eng, idx, 3, stub_f, 300 * 32, stub_f, 720, 1280, stub_u8, nullptr) == YP_ERR_STATE);
         CHECK(yp_masks_frames(eng, idx, 0, stub_f, 300 * 32, stub_f, 720, 1280, stub_u8, nullptr) == YP_ERR_STATE);
+        // the process_mask form (yp_masks_frames_input): the same checks, in the same order
+        CHECK(yp_masks_frames_input(nullptr, idx, 3, stub_f, 300 * 32, stub_f, 384, 640, stub_u8, nullptr) == YP_ERR_ARG);
+        CHECK(yp_masks_frames_input(eng, idx, -1, stub_f, 300 * 32, stub_f, 384, 640, stub_u8, nullptr) == YP_ERR_ARG);
+        CHECK(yp_masks_frames_input(eng, idx, 3, stub_f, 300 * 32, stub_f, 0, 640, stub_u8, nullptr) == YP_ERR_ARG);
+        CHECK(yp_masks_frames_input(eng, idx, 3, stub_f, 300 * 32, stub_f, 384, -5, stub_u8, nullptr) == YP_ERR_ARG);
+        CHECK(yp_masks_frames_input(eng, idx, 9000, stub_f, 300 * 32, stub_f, 384, 640, stub_u8, nullptr) == YP_ERR_ARG);   // k*oh*ow >= 2^31
+        CHECK(yp_masks_frames_input(eng, idx, 70000, stub_f, 300 * 32, stub_f, 4, 4, stub_u8, nullptr) == YP_ERR_ARG);      // k > 65535
+        CHECK(yp_masks_frames_input(eng, nullptr, 3, stub_f, 300 * 32, stub_f, 384, 640, stub_u8, nullptr) == YP_ERR_ARG);
+        CHECK(yp_masks_frames_input(eng, idx, 3, nullptr, 300 * 32, stub_f, 384, 640, stub_u8, nullptr) == YP_ERR_ARG);
+        CHECK(yp_masks_frames_input(eng, idx, 3, stub_f, 300 * 32, nullptr, 384, 640, stub_u8, nullptr) == YP_ERR_ARG);
+        CHECK(yp_masks_frames_input(eng, idx, 3, stub_f, 300 * 32, stub_f, 384, 640, nullptr, nullptr) == YP_ERR_ARG);
+        CHECK(yp_masks_frames_input(eng, idx, 3, stub_f, 31, stub_f, 384, 640, stub_u8, nullptr) == YP_ERR_ARG);
+        CHECK(yp_masks_frames_input(eng, idx, 3, stub_f, 300 * 32, stub_f, 384, 640, stub_u8, nullptr) == YP_ERR_STATE);
+        CHECK(yp_masks_frames_input(eng, idx, 0, stub_f, 300 * 32, stub_f, 384, 640, stub_u8, nullptr) == YP_ERR_STATE);
         CHECK(yp_destroy(eng) == YP_OK);
+    }
+    {
+        // yp_mask_contours_scaled: bad arguments fail before anything is launched; n = 0 launches nothing
+        static uint8_t m[16];
+        static int32_t pts[64], cnt[4], parts[8];
+        static double rect[8];
+        CHECK(yp_mask_contours_scaled(m, -1, 384, 640, YP_CONTOURS_ALL, 16, pts, cnt, parts, 4, rect, 720, 1280, nullptr) == YP_ERR_ARG);
+        CHECK(yp_mask_contours_scaled(m, 1, 0, 640, YP_CONTOURS_ALL, 16, pts, cnt, parts, 4, rect, 720, 1280, nullptr) == YP_ERR_ARG);
+        CHECK(yp_mask_contours_scaled(m, 1, 384, -1, YP_CONTOURS_ALL, 16, pts, cnt, parts, 4, rect, 720, 1280, nullptr) == YP_ERR_ARG);
+        CHECK(yp_mask_contours_scaled(m, 1, 384, 640, YP_CONTOURS_ALL, 1, pts, cnt, parts, 4, rect, 720, 1280, nullptr) == YP_ERR_ARG);
+        CHECK(yp_mask_contours_scaled(m, 1, 384, 640, YP_CONTOURS_ALL, 16, pts, cnt, parts, 4, rect, 0, 1280, nullptr) == YP_ERR_ARG);
+        CHECK(yp_mask_contours_scaled(m, 1, 384, 640, YP_CONTOURS_ALL, 16, pts, cnt, parts, 4, rect, 720, -3, nullptr) == YP_ERR_ARG);
+        CHECK(yp_mask_contours_scaled(m, 1, 384, 640, 7, 16, pts, cnt, parts, 4, rect, 720, 1280, nullptr) == YP_ERR_ARG);
+        CHECK(yp_mask_contours_scaled(nullptr, 1, 384, 640, YP_CONTOURS_ALL, 16, pts, cnt, parts, 4, rect, 720, 1280, nullptr) == YP_ERR_ARG);
+        CHECK(yp_mask_contours_scaled(m, 1, 384, 640, YP_CONTOURS_ALL, 16, nullptr, cnt, parts, 4, rect, 720, 1280, nullptr) == YP_ERR_ARG);
+        CHECK(yp_mask_contours_scaled(m, 1, 384, 640, YP_CONTOURS_ALL, 16, pts, nullptr, parts, 4, rect, 720, 1280, nullptr) == YP_ERR_ARG);
+        CHECK(yp_mask_contours_scaled(m, 1, 384, 640, YP_CONTOURS_ALL, 16, pts, cnt, parts, 1, rect, 720, 1280, nullptr) == YP_ERR_ARG);
+        CHECK(yp_mask_contours_scaled(m, 1, 50000, 50000, YP_CONTOURS_ALL, 16, pts, cnt, parts, 4, rect, 720, 1280, nullptr) == YP_ERR_ARG);
+        CHECK(yp_mask_contours_scaled(m, 0, 384, 640, YP_CONTOURS_ALL, 16, pts, cnt, parts, 4, rect, 720, 1280, nullptr) == YP_OK);
     }
     {
         static uint8_t src[16], dst[16];                                 // never read: every call below is refused first or launches nothing

@@ -414,7 +414,8 @@ struct MaskParams {
 };
 hipError_t launch_masks(const MaskParams& p, int dtype, hipStream_t st);
 size_t masks_workspace_bytes(const MaskParams& p);
-// One retina mask per selected frame (yp_masks_frames): p describes image 0 with n = 1 (proto, coeff = row 0 of frame 0, crop, oh, ow);
+// One mask per selected frame (yp_masks_frames: retina; yp_masks_frames_input: process_mask, p.crop_before = 1): p describes image 0 with
+// n = 1 (proto, coeff = row 0 of frame 0, crop, oh, ow);
 // mask j uses frame fidx[j] (device int32 [k]): proto + fidx[j] * proto_stride bytes, coeff + fidx[j] * coeff_stride floats, box
 // boxes[4j..4j+4). M: float workspace [k, ch*cw]. masks uint8 [k,oh,ow], every byte written.
 struct MaskFramesParams {
@@ -426,6 +427,9 @@ hipError_t launch_masks_frames(const MaskFramesParams& f, float* M, int dtype, h
 hipError_t contour_read_clocks(unsigned long long* out12);
 hipError_t launch_contours(const uint8_t* masks, int n, int H, int W, int strategy, int max_pts, int32_t* pts, int32_t* count, int32_t* parts, int parts_cap,
                            double* rect, hipStream_t st);
+// the same contours; rect of the points after hostops.scale_coords((H,W) -> (H0,W0)) and int32 truncation ((-1, -1) when W0 >= 2048)
+hipError_t launch_contours_scaled(const uint8_t* masks, int n, int H, int W, int H0, int W0, int strategy, int max_pts, int32_t* pts, int32_t* count,
+                                  int32_t* parts, int parts_cap, double* rect, hipStream_t st);
 
 // host-side float -> bf16 (round to nearest even), as the device's v_cvt_pk_bf16_f32
 static inline uint16_t f2bf(float f) {

@@ -27,6 +27,7 @@
 // The same definitions, stated on the host: hostops.external_contours / mask_polygon (connected components + hole filling); a third,
 // independent statement (Suzuki & Abe's raster labelling as cv2 runs it) checks both in tests/.
 #include "common.h"
+#include <algorithm>
 #include <cstdio>
 
 namespace yp {
@@ -49,7 +50,20 @@ struct ContourParams {
     int parts_cap;
     double* rect;              // [n][2] (long side, short side) of the minimum-area rectangle of those points, or null
     int boxg;                  // workgroups per mask of the bounding-box pre-pass (their partial boxes sit at the head of the mask's `pts`)
+    // contour_kernel<true> (yp_mask_contours_scaled): the rectangle is of the points scaled to the original (H0,W0) frame, see scale_coord
+    int H0, W0;
+    float gain, padx, pady;
 };
+
+// hostops.scale_coords((H,W) -> (H0,W0)) of one polygon coordinate as numpy evaluates it on an int32 polygon, then the int32 truncation of
+// get_coord_min_rect_len: float32 (v - pad) / gain (gain and pad computed in double and rounded to float32 on the host), clipped to
+// [0, hi]. Correctly rounded fp32 division; nothing is contracted.
+__device__ __forceinline__ int scale_coord(int v, float pad, float gain, int hi) {
+#pragma clang fp contract(off)
+    const float d = (float)v - pad;
+    const float s = d / gain;
+    return (int)fminf(fmaxf(s, 0.f), (float)hi);
+}
 
 // clockwise from east, as hostops._DIRS: (dy,dx)
 // (dy, dx) = {0,1,1,1,0,-1,-1,-1}, {1,1,0,-1,-1,-1,0,1}, each + 1 in two bits per direction: decoded in registers - a `__constant__` table indexed
@@ -282,6 +296,9 @@ __global__ __launch_bounds__(256) void contour_bbox_kernel(const ContourParams p
     if (tid < 4) p.pts[(size_t)mi * p.max_pts * 2 + 4 * g + tid] = s_box[tid];
 }
 
+// SCALED: yp_mask_contours_scaled - points, counts and parts as the unscaled instance; the hull and the calipers run over the points scaled
+// to the original frame (scale_coord), with the column tables covering 0..W0 (the rectangle is declined, (-1, -1), when W0 + 1 > CT_MAXCOL)
+template <bool SCALED>
 __global__ __launch_bounds__(CT_THREADS) void contour_kernel(const ContourParams p) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     __shared__ int s_box[4];                 // x0, y0, x1, y1 (inclusive)
@@ -797,14 +814,26 @@ __global__ __launch_bounds__(CT_THREADS) void contour_kernel(const ContourParams
     CT_STAMP(5);
     if (!p.rect) return;
     const int np = s_np;
+    // hull columns: the bounding box's, or (SCALED) those its points scale to - scale_coord is monotone, so [f(bx0), f(bx1)] within 0..W0
+    int cx0 = bx0, ncol = bw;
+    if constexpr (SCALED) {
+        if (p.W0 + 1 > CT_MAXCOL) {
+            if (tid == 0) { p.rect[2 * mi] = -1.0; p.rect[2 * mi + 1] = -1.0; }
+            return;
+        }
+        cx0 = scale_coord(bx0, p.padx, p.gain, p.W0);
+        ncol = scale_coord(bx1, p.padx, p.gain, p.W0) - cx0 + 1;
+    }
     int* colmin = (int*)smem;
     int* colmax = colmin + CT_MAXCOL;
     int* hull = colmax + CT_MAXCOL;           // up to 2 * CT_MAXCOL + 2 vertices, (x, y) interleaved; behind it the two chains under construction
     static_assert((size_t)(2 * CT_MAXCOL + 2 * (2 * CT_MAXCOL + 2) + 4 * (CT_MAXCOL + 2)) * sizeof(int) <= (size_t)CT_BITMAP_BYTES, "hull tables fit the bit image's LDS");
-    for (int i = tid; i < bw; i += CT_THREADS) { colmin[i] = 0x7fffffff; colmax[i] = -1; }
+    for (int i = tid; i < ncol; i += CT_THREADS) { colmin[i] = 0x7fffffff; colmax[i] = -1; }
     __syncthreads();
     for (int i = tid; i < np; i += CT_THREADS) {
-        const int x = out[2 * i] - bx0, y = out[2 * i + 1];
+        int x = out[2 * i], y = out[2 * i + 1];
+        if constexpr (SCALED) { x = scale_coord(x, p.padx, p.gain, p.W0); y = scale_coord(y, p.pady, p.gain, p.H0); }
+        x -= cx0;
         atomicMin(&colmin[x], y);
         atomicMax(&colmax[x], y);
     }
@@ -819,7 +848,7 @@ __global__ __launch_bounds__(CT_THREADS) void contour_kernel(const ContourParams
     int* const chain_up = chain_lo + 2 * (CT_MAXCOL + 2);
     if (tid == 0) {
         int nuniq = 0, fx = 0, fy = 0, gx = 0, gy = 0;
-        for (int x = 0; x < bw; ++x) {
+        for (int x = 0; x < ncol; ++x) {
             const int lo = colmin[x], hi = colmax[x];
             if (hi >= 0) {
                 if (nuniq == 0) { fx = x; fy = lo; }
@@ -844,7 +873,7 @@ __global__ __launch_bounds__(CT_THREADS) void contour_kernel(const ContourParams
             ax = bx; ay = by; bx = qx; by = qy;
         };
         if (!upper) {
-            for (int x = 0; x < bw; ++x) {
+            for (int x = 0; x < ncol; ++x) {
                 const int lo = colmin[x], hi = colmax[x];
                 if (hi >= 0) {
                     push(x, lo);
@@ -852,7 +881,7 @@ __global__ __launch_bounds__(CT_THREADS) void contour_kernel(const ContourParams
                 }
             }
         } else {
-            for (int x = bw - 1; x >= 0; --x) {
+            for (int x = ncol - 1; x >= 0; --x) {
                 const int lo = colmin[x], hi = colmax[x];
                 if (hi >= 0) {
                     if (hi != lo) push(x, hi);
@@ -902,7 +931,7 @@ __global__ __launch_bounds__(CT_THREADS) void contour_kernel(const ContourParams
         const double vx = -uy, vy = ux;
         double amin = 1e300, amax = -1e300, bmin = 1e300, bmax = -1e300;
         for (int k = 0; k < nh; ++k) {
-            const double hx = (double)(hull[2 * k] + bx0), hy = (double)hull[2 * k + 1];
+            const double hx = (double)(hull[2 * k] + cx0), hy = (double)hull[2 * k + 1];
             const double a = hx * ux + hy * uy, b = hx * vx + hy * vy;
             amin = fmin(amin, a); amax = fmax(amax, a); bmin = fmin(bmin, b); bmax = fmax(bmax, b);
         }
@@ -927,22 +956,41 @@ __global__ __launch_bounds__(CT_THREADS) void contour_kernel(const ContourParams
 
 hipError_t contour_read_clocks(unsigned long long* out12) { return hipMemcpyFromSymbol(out12, HIP_SYMBOL(g_ct_clk), 12 * sizeof(unsigned long long)); }
 
-hipError_t launch_contours(const uint8_t* masks, int n, int H, int W, int strategy, int max_pts, int32_t* pts, int32_t* count, int32_t* parts, int parts_cap,
-                           double* rect, hipStream_t st) {
-    if (n == 0) return hipSuccess;
-    ContourParams p{masks, n, H, W, max_pts, pts, count, strategy, parts, parts ? parts_cap : 0, rect, 0};
-    p.boxg = max_pts / 2 < CT_BOXG ? max_pts / 2 : CT_BOXG;      // a partial box takes two points' worth of the list
+template <bool SCALED>
+static hipError_t launch_contour_kernels(ContourParams& p, hipStream_t st) {
+    p.boxg = p.max_pts / 2 < CT_BOXG ? p.max_pts / 2 : CT_BOXG;  // a partial box takes two points' worth of the list
     if (p.boxg < 1) return hipErrorInvalidValue;
     const size_t sh = (size_t)CT_BITMAP_BYTES + (size_t)CT_MAXCAND * sizeof(int);
     static bool attr = false;
     if (!attr) {
-        hipError_t e = hipFuncSetAttribute((const void*)contour_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh);
+        hipError_t e = hipFuncSetAttribute((const void*)contour_kernel<SCALED>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh);
         if (e != hipSuccess) return e;
         attr = true;
     }
-    hipLaunchKernelGGL(contour_bbox_kernel, dim3(p.boxg, n), dim3(256), 0, st, p);
-    hipLaunchKernelGGL(contour_kernel, dim3(n), dim3(CT_THREADS), sh, st, p);
+    hipLaunchKernelGGL(contour_bbox_kernel, dim3(p.boxg, p.n), dim3(256), 0, st, p);
+    hipLaunchKernelGGL(contour_kernel<SCALED>, dim3(p.n), dim3(CT_THREADS), sh, st, p);
     return hipGetLastError();
+}
+
+hipError_t launch_contours(const uint8_t* masks, int n, int H, int W, int strategy, int max_pts, int32_t* pts, int32_t* count, int32_t* parts, int parts_cap,
+                           double* rect, hipStream_t st) {
+    if (n == 0) return hipSuccess;
+    ContourParams p{masks, n, H, W, max_pts, pts, count, strategy, parts, parts ? parts_cap : 0, rect, 0};
+    return launch_contour_kernels<false>(p, st);
+}
+
+hipError_t launch_contours_scaled(const uint8_t* masks, int n, int H, int W, int H0, int W0, int strategy, int max_pts, int32_t* pts, int32_t* count,
+                                  int32_t* parts, int parts_cap, double* rect, hipStream_t st) {
+#pragma clang fp contract(off)
+    if (n == 0) return hipSuccess;
+    ContourParams p{masks, n, H, W, max_pts, pts, count, strategy, parts, parts ? parts_cap : 0, rect, 0};
+    // hostops.scale_coords: gain and pads in double (Python floats), rounded to float32 where numpy meets the float32 polygon
+    const double gain = std::min((double)H / H0, (double)W / W0);
+    const double wg = W0 * gain, hg = H0 * gain;
+    const double padx = (W - wg) / 2, pady = (H - hg) / 2;
+    p.H0 = H0; p.W0 = W0;
+    p.gain = (float)gain; p.padx = (float)padx; p.pady = (float)pady;
+    return launch_contour_kernels<true>(p, st);
 }
 
 }  // namespace yp

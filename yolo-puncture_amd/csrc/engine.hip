@@ -1106,9 +1106,11 @@ static int allocate_plan(yp_engine& e) {
             if (e.sp_ws) HIPCHK(hipFree(e.sp_ws));
             e.sp_ws = nullptr; e.sp_ws_bytes = 0;
             HIPCHK(hipMalloc(&e.sp_ws, need));
-            HIPCHK(hipMemset(e.sp_ws, 0, need));
             e.sp_ws_bytes = need;
         }
+        // zeroed for every plan, not only when it grows: the layout moves with B, so the head's live position counters (which every
+        // forward empties behind itself) can land on rows the previous plan left behind - garbage counts index the lists out of bounds
+        if (need) HIPCHK(hipMemset(e.sp_ws, 0, need));
     }
     if (e.desc.family != YP_FAMILY_V10) {
         size_t A = 0;
@@ -2411,6 +2413,20 @@ int yp_mask_contours(const uint8_t* masks_dev, int n, int H, int W, int strategy
     return YP_OK;
 }
 
+int yp_mask_contours_scaled(const uint8_t* masks_dev, int n, int H, int W, int strategy, int max_pts, int32_t* pts_out, int32_t* count_out,
+                            int32_t* parts_out, int parts_cap, double* rect_out, int H0, int W0, void* stream) {
+    if (n < 0 || H <= 0 || W <= 0 || max_pts < 2) return fail(YP_ERR_ARG, "yp_mask_contours_scaled: bad sizes (max_pts >= 2)");
+    if (H0 <= 0 || W0 <= 0) return fail(YP_ERR_ARG, "yp_mask_contours_scaled: bad original size %dx%d", H0, W0);
+    if (strategy != YP_CONTOURS_LARGEST && strategy != YP_CONTOURS_ALL)
+        return fail(YP_ERR_ARG, "yp_mask_contours_scaled: strategy must be YP_CONTOURS_LARGEST or YP_CONTOURS_ALL");
+    if (n > 0 && (!masks_dev || !pts_out || !count_out)) return fail(YP_ERR_ARG, "yp_mask_contours_scaled: null buffer");
+    if (parts_out && parts_cap < 2) return fail(YP_ERR_ARG, "yp_mask_contours_scaled: parts_cap >= 2 with a parts buffer");
+    if ((long)H * W >= (1l << 31)) return fail(YP_ERR_ARG, "yp_mask_contours_scaled: image too large");
+    HIPCHK(launch_contours_scaled(masks_dev, n, H, W, H0, W0, strategy, max_pts, pts_out, count_out, parts_out, parts_cap, rect_out,
+                                  (hipStream_t)stream));
+    return YP_OK;
+}
+
 int yp_letterbox(const uint8_t* src_dev, int h0, int w0, uint8_t* dst_dev, int out_h, int out_w, int new_h, int new_w, int top, int left,
                  int pad_value, void* stream) {
     if (!src_dev || !dst_dev) return fail(YP_ERR_ARG, "yp_letterbox: null buffer");
@@ -2746,6 +2762,12 @@ static void retina_crop(const TensorDesc& t, int oh, int ow, MaskParams& p) {
     p.bsx = 1.f; p.bsy = 1.f; p.crop_before = 0;
 }
 
+// the whole prototype map for masks at the letterboxed input size (process_mask): boxes scaled to prototype pixels, crop before upsampling
+static void input_crop(const yp_engine* e, const TensorDesc& t, MaskParams& p) {
+    p.t = 0; p.l = 0; p.ch = t.H; p.cw = t.W;
+    p.bsx = (float)t.W / (float)e->pW; p.bsy = (float)t.H / (float)e->pH; p.crop_before = 1;
+}
+
 // grows the engine's mask workspace to `need` bytes (after the stream has finished with the old one)
 static int ensure_mask_ws(yp_engine* e, size_t need, void* stream) {
     if (need > e->mask_ws_bytes) {
@@ -2773,12 +2795,8 @@ static int masks_common(yp_engine* e, int b, const float* coeff_dev, const float
     MaskParams p{};
     p.proto = (const char*)t.ptr + (size_t)b * t.H * t.W * t.C * tensor_elem_bytes(*e, t);
     p.Hp = t.H; p.Wp = t.W; p.coeff = coeff_dev; p.boxes = boxes_dev; p.n = n; p.oh = oh; p.ow = ow;
-    if (retina) {
-        retina_crop(t, oh, ow, p);
-    } else {
-        p.t = 0; p.l = 0; p.ch = t.H; p.cw = t.W;
-        p.bsx = (float)t.W / (float)e->pW; p.bsy = (float)t.H / (float)e->pH; p.crop_before = 1;
-    }
+    if (retina) retina_crop(t, oh, ow, p);
+    else input_crop(e, t, p);
     p.masks = masks_out; p.ids = id_out; p.kept = kept_out; p.suppress_small = suppress_small; p.min_area = min_area;
     if (rh > 0 && (rh != oh || rw != ow)) {
         if (rw <= 0 || !id_out) return fail(YP_ERR_ARG, "the second resize needs a target size and id_out");
@@ -2800,26 +2818,30 @@ int yp_masks(yp_engine* e, int b, const float* coeff_dev, const float* boxes_dev
     return masks_common(e, b, coeff_dev, boxes_dev, n, oh, ow, retina, 0, 0, masks_out, id_out, kept_out, suppress_small, min_area, stream);
 }
 
-int yp_masks_frames(yp_engine* e, const int32_t* frame_idx_host, int k, const float* coeff_dev, long coeff_row_stride, const float* boxes_dev,
-                    int oh, int ow, uint8_t* masks_out, void* stream) {
+// yp_masks_frames (retina) and yp_masks_frames_input (process_mask at the letterboxed input size): the mask geometry is masks_common's
+static int masks_frames_common(const char* fn, yp_engine* e, const int32_t* frame_idx_host, int k, const float* coeff_dev, long coeff_row_stride,
+                               const float* boxes_dev, int oh, int ow, int retina, uint8_t* masks_out, void* stream) {
     if (!e) return fail(YP_ERR_ARG, "null engine");
-    if (k < 0 || oh <= 0 || ow <= 0) return fail(YP_ERR_ARG, "yp_masks_frames: bad sizes k=%d %dx%d", k, oh, ow);
-    if ((long long)k * oh * ow >= (1ll << 31)) return fail(YP_ERR_ARG, "yp_masks_frames: k*oh*ow >= 2^31");
-    if (k > 65535) return fail(YP_ERR_ARG, "yp_masks_frames: at most 65535 masks per call");
-    if (k > 0 && (!frame_idx_host || !coeff_dev || !boxes_dev || !masks_out)) return fail(YP_ERR_ARG, "yp_masks_frames: null buffer");
-    if (coeff_row_stride < YP_NM) return fail(YP_ERR_ARG, "yp_masks_frames: coeff_row_stride %ld < %d", coeff_row_stride, YP_NM);
+    if (k < 0 || oh <= 0 || ow <= 0) return fail(YP_ERR_ARG, "%s: bad sizes k=%d %dx%d", fn, k, oh, ow);
+    if ((long long)k * oh * ow >= (1ll << 31)) return fail(YP_ERR_ARG, "%s: k*oh*ow >= 2^31", fn);
+    if (k > 65535) return fail(YP_ERR_ARG, "%s: at most 65535 masks per call", fn);
+    if (k > 0 && (!frame_idx_host || !coeff_dev || !boxes_dev || !masks_out)) return fail(YP_ERR_ARG, "%s: null buffer", fn);
+    if (coeff_row_stride < YP_NM) return fail(YP_ERR_ARG, "%s: coeff_row_stride %ld < %d", fn, coeff_row_stride, YP_NM);
     if (e->proto_t < 0) return fail(YP_ERR_STATE, "engine was not created with YP_TASK_SEGMENT");
     if (!e->allocated) return fail(YP_ERR_STATE, "no forward has run yet");
+    if (!retina && (oh != e->pH || ow != e->pW))
+        return fail(YP_ERR_ARG, "%s: masks are produced at the letterboxed input size %dx%d, not %dx%d", fn, e->pH, e->pW, oh, ow);
     for (int j = 0; j < k; ++j)
         if (frame_idx_host[j] < 0 || frame_idx_host[j] >= e->pB)
-            return fail(YP_ERR_ARG, "yp_masks_frames: frame_idx[%d] = %d outside [0,%d)", j, frame_idx_host[j], e->pB);
+            return fail(YP_ERR_ARG, "%s: frame_idx[%d] = %d outside [0,%d)", fn, j, frame_idx_host[j], e->pB);
     if (k == 0) return YP_OK;
     HIPCHK(hipSetDevice(e->device));
     const TensorDesc& t = e->tensors[e->proto_t];
     MaskFramesParams f{};
     MaskParams& p = f.p;
     p.proto = t.ptr; p.Hp = t.H; p.Wp = t.W; p.coeff = coeff_dev; p.boxes = boxes_dev; p.n = 1; p.oh = oh; p.ow = ow;
-    retina_crop(t, oh, ow, p);
+    if (retina) retina_crop(t, oh, ow, p);
+    else input_crop(e, t, p);
     p.masks = masks_out;
     f.k = k;
     f.proto_stride = (size_t)t.H * t.W * t.C * tensor_elem_bytes(*e, t);
@@ -2834,6 +2856,16 @@ int yp_masks_frames(yp_engine* e, const int32_t* frame_idx_host, int k, const fl
     hipError_t err = launch_masks_frames(f, (float*)((char*)e->mask_ws + idx_bytes), e->dtype, (hipStream_t)stream);
     if (err != hipSuccess) return fail(YP_ERR_HIP, "mask kernels: %s", hipGetErrorString(err));
     return YP_OK;
+}
+
+int yp_masks_frames(yp_engine* e, const int32_t* frame_idx_host, int k, const float* coeff_dev, long coeff_row_stride, const float* boxes_dev,
+                    int oh, int ow, uint8_t* masks_out, void* stream) {
+    return masks_frames_common("yp_masks_frames", e, frame_idx_host, k, coeff_dev, coeff_row_stride, boxes_dev, oh, ow, 1, masks_out, stream);
+}
+
+int yp_masks_frames_input(yp_engine* e, const int32_t* frame_idx_host, int k, const float* coeff_dev, long coeff_row_stride,
+                          const float* boxes_dev, int oh, int ow, uint8_t* masks_out, void* stream) {
+    return masks_frames_common("yp_masks_frames_input", e, frame_idx_host, k, coeff_dev, coeff_row_stride, boxes_dev, oh, ow, 0, masks_out, stream);
 }
 
 int yp_id_mask_resized(yp_engine* e, int b, const float* coeff_dev, const float* boxes_dev, int n, int oh, int ow, int rh, int rw,

@@ -309,9 +309,9 @@ hipError_t launch_masks(const MaskParams& p, int dtype, hipStream_t st) {
 }
 
 // ---------------------------------------------------------------------------------------------------------------
-// One retina mask per selected frame (yp_masks_frames, the clip form of `masks.xy[best]`): mask j is yp_masks(b = fidx[j], n = 1,
-// retina) of frame fidx[j]'s first coefficient row. The same GEMM bodies with a frame axis on the grid, then a resize that writes the
-// whole [k,oh,ow] output 16 bytes per lane: pixels outside the box are 0 without arithmetic, pixels inside take mask_value.
+// One mask per selected frame (the clip form of `masks.xy[best]`): mask j is yp_masks(b = fidx[j], n = 1) of frame fidx[j]'s first
+// coefficient row, retina (yp_masks_frames) or process_mask at the letterboxed input size (yp_masks_frames_input). The same GEMM bodies
+// with a frame axis on the grid, then a resize that writes the whole [k,oh,ow] output 16 bytes per lane.
 // ---------------------------------------------------------------------------------------------------------------
 __device__ __forceinline__ MaskParams frame_view(const MaskFramesParams& f, int j) {
     MaskParams q = f.p;
@@ -335,9 +335,27 @@ __global__ __launch_bounds__(256) void mask_frames_gemm_mfma_kernel(const MaskFr
     mask_gemm_mfma_body<T>(frame_view(f, j), M + (size_t)j * f.p.ch * f.p.cw, cs);
 }
 
+// process_mask (crop_before) zeroes the taps outside the box at prototype resolution BEFORE the interpolation, so a pixel just outside
+// the box can still take an inside tap and be set. A pixel none of whose four taps lies in the box has four zero taps and is 0: this is
+// mask_value's own tap and box arithmetic, stopped before the loads.
+__device__ __forceinline__ bool taps_touch_box(const MaskParams& p, int x, int y, float x1, float y1, float x2, float y2) {
+    const float sy = (float)p.ch / (float)p.oh, sx = (float)p.cw / (float)p.ow;
+    float fy = sy * ((float)y + 0.5f) - 0.5f, fx = sx * ((float)x + 0.5f) - 0.5f;
+    fy = fmaxf(fy, 0.f);
+    fx = fmaxf(fx, 0.f);
+    const int y0 = (int)fy, x0 = (int)fx;
+    const int y1i = y0 + ((y0 < p.ch - 1) ? 1 : 0), x1i = x0 + ((x0 < p.cw - 1) ? 1 : 0);
+    const float bx1 = x1 * p.bsx, bx2 = x2 * p.bsx, by1 = y1 * p.bsy, by2 = y2 * p.bsy;
+    auto in_x = [&](int xx) { return ((float)xx >= bx1) && ((float)xx < bx2); };
+    auto in_y = [&](int yy) { return ((float)yy >= by1) && ((float)yy < by2); };
+    return (in_x(x0) || in_x(x1i)) && (in_y(y0) || in_y(y1i));
+}
+
 // lane t owns the 16 output bytes of the aligned 16-byte line t (line 0 starts at or before `masks`): one uint4 store for a whole line,
-// byte stores for the partial lines at either end of the buffer.
-__global__ __launch_bounds__(256) void mask_frames_resize_kernel(const MaskFramesParams f, const float* M, uint8_t* masks) {
+// byte stores for the partial lines at either end of the buffer. Pixels that cannot be set are 0 without arithmetic: retina
+// (CROP_BEFORE = false) those outside the box, process_mask (true) those with no tap in the box (taps_touch_box); the rest take mask_value.
+template <bool CROP_BEFORE>
+__device__ __forceinline__ void mask_frames_resize_body(const MaskFramesParams& f, const float* M, uint8_t* masks) {
     const MaskParams& p = f.p;
     const long long plane = (long long)p.oh * p.ow, total = plane * f.k;
     const long long s = ((long long)blockIdx.x * blockDim.x + threadIdx.x) * 16 - (long long)((uintptr_t)masks & 15);
@@ -354,8 +372,10 @@ __global__ __launch_bounds__(256) void mask_frames_resize_kernel(const MaskFrame
     for (int q = 0; q < 16; ++q) {
         const long long b = s + q;
         if (b < b0 || b >= total) continue;
-        const bool inside = ((float)x >= x1) && ((float)x < x2) && ((float)y >= y1) && ((float)y < y2);
-        if (inside && mask_value(p, Mi, x, y, x1, y1, x2, y2) > 0.f) w[q >> 2] |= 1u << (8 * (q & 3));
+        bool cand;
+        if constexpr (CROP_BEFORE) cand = taps_touch_box(p, x, y, x1, y1, x2, y2);
+        else cand = ((float)x >= x1) && ((float)x < x2) && ((float)y >= y1) && ((float)y < y2);
+        if (cand && mask_value(p, Mi, x, y, x1, y1, x2, y2) > 0.f) w[q >> 2] |= 1u << (8 * (q & 3));
         if (++x == p.ow) {
             x = 0;
             if (++y == p.oh && b + 1 < total) {
@@ -377,6 +397,14 @@ __global__ __launch_bounds__(256) void mask_frames_resize_kernel(const MaskFrame
     }
 }
 
+__global__ __launch_bounds__(256) void mask_frames_resize_kernel(const MaskFramesParams f, const float* M, uint8_t* masks) {
+    mask_frames_resize_body<false>(f, M, masks);
+}
+
+__global__ __launch_bounds__(256) void mask_frames_input_resize_kernel(const MaskFramesParams f, const float* M, uint8_t* masks) {
+    mask_frames_resize_body<true>(f, M, masks);
+}
+
 // M: float [k, ch*cw] device workspace; f.fidx already on the device
 hipError_t launch_masks_frames(const MaskFramesParams& f, float* M, int dtype, hipStream_t st) {
     if (f.k == 0) return hipSuccess;
@@ -393,7 +421,8 @@ hipError_t launch_masks_frames(const MaskFramesParams& f, float* M, int dtype, h
         else hipLaunchKernelGGL(mask_frames_gemm_mfma_kernel<float>, dim3((npix + 63) / 64, f.k), dim3(256), sh, st, f, M);
     }
     const long long lines = ((long long)p.oh * p.ow * f.k + ((uintptr_t)p.masks & 15) + 15) / 16;
-    hipLaunchKernelGGL(mask_frames_resize_kernel, dim3((unsigned)((lines + 255) / 256)), dim3(256), 0, st, f, M, p.masks);
+    if (p.crop_before) hipLaunchKernelGGL(mask_frames_input_resize_kernel, dim3((unsigned)((lines + 255) / 256)), dim3(256), 0, st, f, M, p.masks);
+    else hipLaunchKernelGGL(mask_frames_resize_kernel, dim3((unsigned)((lines + 255) / 256)), dim3(256), 0, st, f, M, p.masks);
     return hipGetLastError();
 }
 

@@ -56,6 +56,8 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     lib.yp_id_mask_resized.restype = C.c_int
     lib.yp_mask_contours.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp]
     lib.yp_mask_contours.restype = C.c_int
+    lib.yp_mask_contours_scaled.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, C.c_int, vp, C.c_int, C.c_int, vp]
+    lib.yp_mask_contours_scaled.restype = C.c_int
     lib.yp_plan.argtypes = [vp, C.c_int, C.c_int, C.c_int]
     lib.yp_op_info.argtypes = [vp, C.c_int, C.c_char_p, C.c_int, ip, C.POINTER(C.c_double), C.POINTER(C.c_double)]
     lib.yp_op_output.argtypes = [vp, C.c_int, ip, ip, ip]
@@ -98,6 +100,8 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     lib.yp_letterbox_batch.restype = C.c_int
     lib.yp_masks_frames.argtypes = [vp, vp, C.c_int, vp, C.c_long, vp, C.c_int, C.c_int, vp, vp]
     lib.yp_masks_frames.restype = C.c_int
+    lib.yp_masks_frames_input.argtypes = [vp, vp, C.c_int, vp, C.c_long, vp, C.c_int, C.c_int, vp, vp]
+    lib.yp_masks_frames_input.restype = C.c_int
     lib.yp_comm_unique_id.argtypes = [vp]
     lib.yp_comm_create.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.POINTER(vp)]
     lib.yp_allgather.argtypes = [vp, vp, vp, C.c_size_t, vp]
@@ -117,8 +121,8 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
 EXPORTS = ["yp_last_error", "yp_create", "yp_destroy", "yp_weight_count", "yp_weight_info", "yp_set_weight",
            "yp_finalize", "yp_forward", "yp_proto", "yp_masks", "yp_id_mask_resized", "yp_plan", "yp_op_info", "yp_op_output", "yp_op_input", "yp_op_fusion",
            "yp_tensor_count", "yp_tensor_info", "yp_tensor_read", "yp_profile", "yp_set_graph", "yp_run_op",
-           "yp_tensor_write", "yp_op_kernel", "yp_set_autotune", "yp_tuning_export", "yp_tuning_import", "yp_set_nms", "yp_debug_force_conv_cfg", "yp_debug_op_cfg", "yp_debug_conv_families", "yp_debug_ablation", "yp_debug_head_clocks", "yp_debug_head_branch_clocks", "yp_debug_head_winners", "yp_debug_contour_clocks", "yp_debug_pwsp_clocks", "yp_debug_host_selftest", "yp_debug_graph_info", "yp_tuning_source", "yp_debug_head_positions", "yp_debug_marker", "yp_letterbox", "yp_letterbox_batch", "yp_masks_frames", "yp_mask_contours",
-           "yp_comm_unique_id", "yp_comm_create", "yp_allgather", "yp_comm_destroy",
+           "yp_tensor_write", "yp_op_kernel", "yp_set_autotune", "yp_tuning_export", "yp_tuning_import", "yp_set_nms", "yp_debug_force_conv_cfg", "yp_debug_op_cfg", "yp_debug_conv_families", "yp_debug_ablation", "yp_debug_head_clocks", "yp_debug_head_branch_clocks", "yp_debug_head_winners", "yp_debug_contour_clocks", "yp_debug_pwsp_clocks", "yp_debug_host_selftest", "yp_debug_graph_info", "yp_tuning_source", "yp_debug_head_positions", "yp_debug_marker", "yp_letterbox", "yp_letterbox_batch", "yp_masks_frames", "yp_masks_frames_input", "yp_mask_contours",
+           "yp_mask_contours_scaled", "yp_comm_unique_id", "yp_comm_create", "yp_allgather", "yp_comm_destroy",
            "yp_u2net_create", "yp_u2net_destroy", "yp_u2net_weight_count", "yp_u2net_weight_info", "yp_u2net_set_weight", "yp_u2net_finalize",
            "yp_u2net_forward", "yp_u2net_forward_crops", "yp_u2net_set_graph", "yp_u2net_tensor_count", "yp_u2net_tensor_info", "yp_u2net_tensor_read",
            "yp_cls_create", "yp_cls_destroy", "yp_cls_weight_count", "yp_cls_weight_info", "yp_cls_set_weight", "yp_cls_finalize",
@@ -183,17 +187,23 @@ CONTOUR_STRATEGIES = {"largest": 0, "all": 1}      # include/yolop.h YP_CONTOURS
 _PARTS_CAP = 65                                     # [count | up to 64 contour lengths] (csrc/contour.hip CT_NLMAX)
 
 
-def mask_contours_device(masks: torch.Tensor, max_pts: Optional[int] = None, want_rect: bool = True, strategy: str = "all", want_parts: bool = False):
+def mask_contours_device(masks: torch.Tensor, max_pts: Optional[int] = None, want_rect: bool = True, strategy: str = "all", want_parts: bool = False,
+                         orig_hw: Optional[Tuple[int, int]] = None):
     """yp_mask_contours: uint8 cuda [n,H,W] -> (list of int32 [m,2] numpy polygons (None where the device path declined), rect float64 [n,2]
     numpy (long side, short side) or None[, list of per-mask contour lengths when `want_parts`]). `strategy` as ultralytics' masks2segments:
     "all" (every external contour, concatenated bottom-up) or "largest". The masks stay on the device; counts, contour lengths, rectangles
     and the heads of the point lists share one allocation so that a single mask (what the reference's loop asks for per frame) costs ONE
     device-to-host copy. `max_pts` also sizes the kernel's per-candidate lists (1024 points each behind the result): the default is
-    generous for one mask, 16384 per mask otherwise."""
+    generous for one mask, 16384 per mask otherwise.
+    orig_hw = (H0, W0): masks at the letterboxed input size of an (H0, W0) frame (yp_mask_contours_scaled). The polygons are the same; each
+    rectangle is of the polygon after hostops.scale_coords((H, W) -> orig_hw) and int32 truncation, (-1, -1) where the device declined it
+    (W0 >= 2048)."""
     if not (masks.is_cuda and masks.dtype == torch.uint8 and masks.dim() == 3):
         raise ValueError("mask_contours_device needs a uint8 CUDA tensor [n,H,W]")
     if strategy not in CONTOUR_STRATEGIES:
         raise ValueError(f"strategy must be 'all' or 'largest', got {strategy!r}")
+    if orig_hw is not None and not (int(orig_hw[0]) > 0 and int(orig_hw[1]) > 0):
+        raise ValueError(f"orig_hw must be a positive (H0, W0), got {orig_hw!r}")
     masks = masks.contiguous()
     n, H, W = (int(v) for v in masks.shape)
     if max_pts is None:
@@ -207,9 +217,12 @@ def mask_contours_device(masks: torch.Tensor, max_pts: Optional[int] = None, wan
     lib = load_library()
     with torch.cuda.device(dev):
         base = buf.data_ptr()
-        rc = lib.yp_mask_contours(C.c_void_p(masks.data_ptr()), n, H, W, CONTOUR_STRATEGIES[strategy], int(max_pts), C.c_void_p(base + 4 * o_pts),
-                                  C.c_void_p(base), C.c_void_p(base + 4 * o_parts), _PARTS_CAP, C.c_void_p(base + 4 * o_rect if want_rect else None),
-                                  C.c_void_p(_stream_ptr(dev)))
+        args = (C.c_void_p(masks.data_ptr()), n, H, W, CONTOUR_STRATEGIES[strategy], int(max_pts), C.c_void_p(base + 4 * o_pts), C.c_void_p(base),
+                C.c_void_p(base + 4 * o_parts), _PARTS_CAP, C.c_void_p(base + 4 * o_rect if want_rect else None))
+        if orig_hw is None:
+            rc = lib.yp_mask_contours(*args, C.c_void_p(_stream_ptr(dev)))
+        else:
+            rc = lib.yp_mask_contours_scaled(*args, int(orig_hw[0]), int(orig_hw[1]), C.c_void_p(_stream_ptr(dev)))
     if rc != 0:
         raise YolopError(lib.yp_last_error().decode())
     if n == 0:
@@ -376,10 +389,12 @@ class Engine:
         return m, ids, kept
 
     def masks_frames(self, frame_idx, coeff: torch.Tensor, boxes: torch.Tensor, out_hw: Tuple[int, int],
-                     out: Optional[torch.Tensor] = None) -> torch.Tensor:
+                     out: Optional[torch.Tensor] = None, retina: bool = True) -> torch.Tensor:
         """yp_masks_frames: one retina mask per entry of `frame_idx` (images of the last forward; gaps and repeats allowed). `coeff` is the
         forward's float32 cuda [B,max_det,32] (row 0 of image frame_idx[j] is used), `boxes` float32 cuda [k,4] in original-image pixels.
-        -> uint8 cuda [k,oh,ow] {0,1}, mask j equal to masks(frame_idx[j], coeff[frame_idx[j], :1], boxes[j:j+1], out_hw, retina=True)[0]."""
+        -> uint8 cuda [k,oh,ow] {0,1}, mask j equal to masks(frame_idx[j], coeff[frame_idx[j], :1], boxes[j:j+1], out_hw, retina=True)[0].
+        retina=False: yp_masks_frames_input - boxes in letterboxed-input pixels, out_hw the forward's input size (H, W), mask j equal to
+        masks(..., out_hw, retina=False)[0]."""
         fidx = np.ascontiguousarray(np.asarray(frame_idx, dtype=np.int64).reshape(-1)).astype(np.int32)
         k = int(fidx.shape[0])
         oh, ow = int(out_hw[0]), int(out_hw[1])
@@ -395,8 +410,9 @@ class Engine:
             out = torch.empty((k, oh, ow), dtype=torch.uint8, device=dev)
         if not (out.is_cuda and out.dtype == torch.uint8 and tuple(out.shape) == (k, oh, ow) and out.is_contiguous() and out.device == dev):
             raise ValueError(f"masks_frames: output must be a contiguous uint8 CUDA tensor [{k},{oh},{ow}] on {dev}")
-        self._chk(self.lib.yp_masks_frames(self._h, fidx.ctypes.data_as(C.c_void_p), k, C.c_void_p(coeff.data_ptr()), int(coeff.stride(0)),
-                                           C.c_void_p(boxes.data_ptr()), oh, ow, C.c_void_p(out.data_ptr()), C.c_void_p(_stream_ptr(dev))))
+        fn = self.lib.yp_masks_frames if retina else self.lib.yp_masks_frames_input
+        self._chk(fn(self._h, fidx.ctypes.data_as(C.c_void_p), k, C.c_void_p(coeff.data_ptr()), int(coeff.stride(0)), C.c_void_p(boxes.data_ptr()),
+                     oh, ow, C.c_void_p(out.data_ptr()), C.c_void_p(_stream_ptr(dev))))
         self._keep = [coeff, boxes]
         return out
 

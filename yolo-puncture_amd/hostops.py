@@ -123,6 +123,26 @@ def scale_coords(img1_hw: Sequence[int], coords: np.ndarray, img0_hw: Sequence[i
     return c
 
 
+def scale_coords_f32_geometry(img1_hw: Sequence[int], img0_hw: Sequence[int]) -> Tuple[np.float32, np.float32, np.float32]:
+    """(gain, padx, pady) of scale_coords as numpy meets them on a float32 polygon: computed in double (Python floats), rounded to float32.
+    yp_mask_contours_scaled derives the same three constants on the host (csrc/contour.hip launch_contours_scaled)."""
+    gain = min(img1_hw[0] / img0_hw[0], img1_hw[1] / img0_hw[1])
+    padx = (img1_hw[1] - img0_hw[1] * gain) / 2
+    pady = (img1_hw[0] - img0_hw[0] * gain) / 2
+    return np.float32(gain), np.float32(padx), np.float32(pady)
+
+
+def scale_coords_int(img1_hw: Sequence[int], points: np.ndarray, img0_hw: Sequence[int]) -> np.ndarray:
+    """np.array(scale_coords(img1_hw, points, img0_hw), np.int32) - the integer points get_coord_min_rect_len measures on the polygon of a
+    non-retina mask - stated as the device evaluates it per point (csrc/contour.hip scale_coord): float32 (v - pad) / gain, clipped to
+    [0, W0] / [0, H0], truncated to int32."""
+    gain, padx, pady = scale_coords_f32_geometry(img1_hw, img0_hw)
+    p = np.asarray(points).reshape(-1, 2).astype(np.float32)
+    x = np.minimum(np.maximum((p[:, 0] - padx) / gain, np.float32(0)), np.float32(img0_hw[1]))
+    y = np.minimum(np.maximum((p[:, 1] - pady) / gain, np.float32(0)), np.float32(img0_hw[0]))
+    return np.stack([x, y], 1).astype(np.int32)
+
+
 # ---- Masks.xy (A.7): cv2.findContours(RETR_EXTERNAL, CHAIN_APPROX_SIMPLE) + masks2segments, restated ----------------------------
 # Definitions this module and the device kernel (csrc/contour.hip) both implement - cv2 is absent here, so they are stated, not pinned:
 #   * foreground 8-connected, background 4-connected (the pairing of Suzuki & Abe's border following, which cv2.findContours implements);

@@ -210,18 +210,23 @@ class Masks:
         return _rect_len(poly, self._rects.get(i))
 
 
-def _finish_contour(poly, rect, parts, strategy: str, host_mask, mask_hw: Tuple[int, int], orig_shape: Tuple[int, int]):
+def _finish_contour(poly, rect, parts, strategy: str, host_mask, mask_hw: Tuple[int, int], orig_shape: Tuple[int, int], rect_in_orig: bool = False):
     """What follows the device trace of one mask (Masks.xy and YOLO.predict_clip): poly / rect / parts as mask_contours_device gives them
     for that mask (poly None: no device pass, or the device declined), the "all_merged" bridge, the host trace of `host_mask()` (bool
     [mh,mw]) where there is no device polygon, and the scale to original-image pixels. -> (float32 [m,2] polygon, (long, short) device
-    rectangle or None; the device rectangle is of the polygon in mask pixels, so it is kept only when those are the original's)."""
+    rectangle or None; the device rectangle is of the polygon in mask pixels, so it is kept only when those are the original's - or when
+    `rect_in_orig`: it was measured on the polygon already scaled to original-image pixels (mask_contours_device(orig_hw=...)); a declined
+    one, (-1, -1), is dropped)."""
     if poly is not None and strategy == "all_merged" and parts is not None and len(parts) > 1:
         cuts = np.cumsum(parts)[:-1]
         poly = hostops.merge_contours(np.split(poly, cuts)).astype(np.int32)
     if poly is None:
         poly = hostops.mask_polygon(host_mask(), strategy)
         rect = None
-    rect = (float(rect[0]), float(rect[1])) if rect is not None and tuple(mask_hw) == tuple(orig_shape) else None
+    if rect_in_orig:
+        rect = (float(rect[0]), float(rect[1])) if rect is not None and rect[0] >= 0 else None
+    else:
+        rect = (float(rect[0]), float(rect[1])) if rect is not None and tuple(mask_hw) == tuple(orig_shape) else None
     if poly.shape[0] and tuple(mask_hw) != tuple(orig_shape):
         poly = hostops.scale_coords(tuple(mask_hw), poly, orig_shape)
     return poly.astype(np.float32), rect
@@ -468,9 +473,13 @@ class YOLO:
             results.append(out_by_index[i])
         return results
 
-    def predict_clip(self, frames, conf: float = 0.25, iou: float = 0.7, imgsz: int = 640, batch_size: int = 32, device=None) -> ClipResults:
+    def predict_clip(self, frames, conf: float = 0.25, iou: float = 0.7, imgsz: int = 640, batch_size: int = 32, device=None,
+                     retina_masks: bool = True) -> ClipResults:
         """The app's first video loop (yolo_seg/app.py:85-113: predict(frame, conf, retina_masks=True) -> best row -> masks.xy[best] ->
         get_coord_min_rect_len, with the carry-forward of the last box and length) for a whole clip of same-shape frames.
+        retina_masks=False: the same loop as the speed-evaluation script runs it (dev_tools/auto_speed_calc.py:56-84: predict(frame, conf)
+        without retina masks): masks at the letterboxed input size from the boxes in its pixels (yp_masks_frames_input), polygons scaled to
+        the frame by hostops.scale_coords, rectangles of the scaled polygons (yp_mask_contours_scaled).
 
         frames: a list of BGR uint8 HWC ndarrays of one shape, or a uint8 CUDA tensor [N,H,W,3] on the engine's device. Frames run in
         contiguous chunks of B = min(batch_size, N), the last one padded to B by repeating its last frame (hostops.clip_plan), so each chunk
@@ -482,6 +491,7 @@ class YOLO:
             raise ValueError("predict_clip needs a segmentation checkpoint (-seg): the app reads masks.xy of the best row")
         if int(batch_size) < 1:
             raise ValueError(f"batch_size must be >= 1 (got {batch_size})")
+        retina = bool(retina_masks)
         strategy = MASK_POLYGON_STRATEGY
         if strategy not in hostops.POLYGON_STRATEGIES:
             raise ValueError(f"MASK_POLYGON_STRATEGY must be one of {hostops.POLYGON_STRATEGIES}, got {strategy!r}")
@@ -556,13 +566,20 @@ class YOLO:
             if not sel:
                 continue
             boxes = hostops.scale_boxes_t((Hl, Wl), rows[sel, :4], (H, W))
-            m = eng.masks_frames(sel, out["coeff"], boxes.to(dev, non_blocking=True), (H, W))
-            dpolys, drects, *dparts = mask_contours_device(m, max_pts=131072, strategy=dev_strategy, want_parts=strategy == "all_merged")
+            if retina:
+                m = eng.masks_frames(sel, out["coeff"], boxes.to(dev, non_blocking=True), (H, W))
+                mask_hw, orig_hw = (H, W), None
+            else:                                                       # process_mask from the boxes in letterboxed-input pixels
+                m = eng.masks_frames(sel, out["coeff"], rows[sel, :4].to(dev, non_blocking=True), (Hl, Wl), retina=False)
+                mask_hw, orig_hw = (Hl, Wl), (H, W)
+            dpolys, drects, *dparts = mask_contours_device(m, max_pts=131072, strategy=dev_strategy, want_parts=strategy == "all_merged",
+                                                           orig_hw=orig_hw)
             bnp = boxes.numpy()
             for t, j in enumerate(sel):
                 i = s0 + j
                 parts = dparts[0][t] if dparts else None
-                poly, rect = _finish_contour(dpolys[t], drects[t], parts, strategy, lambda t=t: m[t].cpu().numpy() > 0, (H, W), (H, W))
+                poly, rect = _finish_contour(dpolys[t], drects[t], parts, strategy, lambda t=t: m[t].cpu().numpy() > 0, mask_hw, (H, W),
+                                             rect_in_orig=not retina)
                 detected[i], confs[i], xyxy[i] = True, float(rows[j, 4]), bnp[t].copy()
                 polys[i] = poly
                 rect_lens[i] = _rect_len(poly, rect)[0]
