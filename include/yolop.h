@@ -143,7 +143,7 @@ int yp_masks_frames_input(yp_engine* e, const int32_t* frame_idx_host, int k, co
  *    strategy  YP_CONTOURS_LARGEST or YP_CONTOURS_ALL
  *    pts_out   int32 [n,max_pts,2] (x,y) polygon in mask pixels       count_out int32 [n]: number of points; 0 = empty mask;
  *              -1 = bounding box larger than the LDS image (1280x720 fits), -2 = more than max_pts points / 4096 border starts / 64 outer
- *              borders: use the host path (hostops.mask_polygon)
+ *              borders: use yp_mask_contours_large (below), or the host path (hostops.mask_polygon)
  *    parts_out int32 [n,parts_cap] or NULL: [0] = contours in the list, [1 .. ] = their point counts in list order (as many as fit)
  *    rect_out  double [n,2] = (long side, short side) of the minimum-area rectangle of the polygon (may be NULL) */
 #define YP_CONTOURS_LARGEST 0
@@ -155,9 +155,32 @@ int yp_mask_contours(const uint8_t* masks_dev, int n, int H, int W, int strategy
  * hostops.scale_coords((H,W) -> (H0,W0)) and the int32 truncation of get_coord_min_rect_len - what get_coord_min_rect_len(masks.xy[i])
  * measures: per point x' = (int)min(max(((float)x - padx) / gain, 0), W0) in fp32 (same for y with pady, H0), with gain = min(H/H0, W/W0),
  * padx = (W - W0 * gain) / 2, pady = (H - H0 * gain) / 2 computed in double and rounded to float. When W0 >= 2048 (the hull's column
- * tables cover 0..W0) the device declines the rectangle only: rect_out row = (-1, -1), points as usual. */
+ * tables cover 0..W0) the device declines the rectangle only: rect_out row = (-1, -1), points as usual (yp_mask_contours_large measures
+ * it for any W0). */
 int yp_mask_contours_scaled(const uint8_t* masks_dev, int n, int H, int W, int strategy, int max_pts, int32_t* pts_out, int32_t* count_out,
                             int32_t* parts_out, int parts_cap, double* rect_out, int H0, int W0, void* stream);
+
+/* The large path of the two calls above, for the masks they decline: 4K frames, bounding boxes beyond the LDS image, more than 64 outer
+ * borders. Same definitions, same outputs in the same layout (so the calls can share one set of buffers); every table lives in the
+ * caller's workspace (the bit image of the whole frame, the border starts in raster order, one record per border segment), and a mask's
+ * border starts are walked by as many workgroups as there are waves of them. Limits: H, W <= YP_CONTOURS_LARGE_MAX_DIM; up to
+ * YP_CONTOURS_LARGE_MAX_STARTS border starts per mask, and as many outer borders. Beyond them: H or W too large is an argument error
+ * (YP_ERR_ARG, nothing launched); more border starts, or more than max_pts points, give count_out = -2 as above (host path).
+ *    H0, W0     0, 0: rect_out in mask pixels (the large form of the plain call); both > 0: rect_out of the polygon scaled to the (H0,W0)
+ *               frame exactly as the scaled call defines it, for any W0 (the column tables are indexed by mask column)
+ *    flags      0, or YP_CONTOURS_ONLY_DECLINED: mask i is skipped - none of its rows is touched - when, on entry, count_out[i] >= 0 and
+ *               (rect_out is NULL or rect_out[2 * i] >= 0); a mask with count_out[i] >= 0 and a rectangle row at (-1, -1) keeps its points
+ *               and gets the rectangle only. So a second call on the buffers of a first fills in what that one declined.
+ *    parts_out  as above; its rows hold as many contour lengths as parts_cap allows (not capped at 64)
+ *    workspace_dev  device memory of at least the workspace query's size for (n, H, W), 16-byte aligned, owned by the caller;
+ *               its contents need not survive the call. The query returns 0 for sizes the call would reject. n <= 65535. */
+#define YP_CONTOURS_ONLY_DECLINED 1
+#define YP_CONTOURS_LARGE_MAX_DIM 4096
+#define YP_CONTOURS_LARGE_MAX_STARTS 65536
+size_t yp_mask_contours_large_workspace(int n, int H, int W);
+int yp_mask_contours_large(const uint8_t* masks_dev, int n, int H, int W, int strategy, int max_pts, int32_t* pts_out, int32_t* count_out,
+                           int32_t* parts_out, int parts_cap, double* rect_out, int H0, int W0, int flags, void* workspace_dev,
+                           size_t workspace_bytes, void* stream);
 
 /* LetterBox on the device (the step before the network inside `.predict`; reference call sites yolo_seg/app.py:86-91,
  * [U] ultralytics LetterBox = cv2.resize INTER_LINEAR + cv2.copyMakeBorder(114)). Engine-free, pure function of its

@@ -431,6 +431,14 @@ hipError_t launch_contours(const uint8_t* masks, int n, int H, int W, int strate
 hipError_t launch_contours_scaled(const uint8_t* masks, int n, int H, int W, int H0, int W0, int strategy, int max_pts, int32_t* pts, int32_t* count,
                                   int32_t* parts, int parts_cap, double* rect, hipStream_t st);
 
+// the large path (contour_large.hip): every table in a caller-provided workspace; H, W <= CL_MAXDIM, up to CL_MAXCAND border starts (and
+// as many outer borders) per mask. H0 = W0 = 0: rectangle in mask pixels, else as launch_contours_scaled (any W0)
+constexpr int CL_MAXDIM = 4096;              // = YP_CONTOURS_LARGE_MAX_DIM (engine.hip asserts both)
+constexpr int CL_MAXCAND = 65536;            // = YP_CONTOURS_LARGE_MAX_STARTS
+size_t contours_large_workspace_bytes(int n, int H, int W);            // 0 on bad sizes
+hipError_t launch_contours_large(const uint8_t* masks, int n, int H, int W, int strategy, int max_pts, int32_t* pts, int32_t* count, int32_t* parts,
+                                 int parts_cap, double* rect, int H0, int W0, int flags, void* workspace, hipStream_t st);
+
 // host-side float -> bf16 (round to nearest even), as the device's v_cvt_pk_bf16_f32
 static inline uint16_t f2bf(float f) {
     uint32_t u;

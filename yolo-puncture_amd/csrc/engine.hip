@@ -2427,6 +2427,31 @@ int yp_mask_contours_scaled(const uint8_t* masks_dev, int n, int H, int W, int s
     return YP_OK;
 }
 
+static_assert(CL_MAXDIM == YP_CONTOURS_LARGE_MAX_DIM && CL_MAXCAND == YP_CONTOURS_LARGE_MAX_STARTS, "include/yolop.h states the large path's limits");
+size_t yp_mask_contours_large_workspace(int n, int H, int W) { return contours_large_workspace_bytes(n, H, W); }
+
+int yp_mask_contours_large(const uint8_t* masks_dev, int n, int H, int W, int strategy, int max_pts, int32_t* pts_out, int32_t* count_out,
+                           int32_t* parts_out, int parts_cap, double* rect_out, int H0, int W0, int flags, void* workspace_dev,
+                           size_t workspace_bytes, void* stream) {
+    if (n < 0 || n > 65535 || H <= 0 || W <= 0 || max_pts < 2) return fail(YP_ERR_ARG, "yp_mask_contours_large: bad sizes (n <= 65535, max_pts >= 2)");
+    if (H > YP_CONTOURS_LARGE_MAX_DIM || W > YP_CONTOURS_LARGE_MAX_DIM)
+        return fail(YP_ERR_ARG, "yp_mask_contours_large: %dx%d masks, H and W must be <= %d", H, W, YP_CONTOURS_LARGE_MAX_DIM);
+    if ((H0 > 0) != (W0 > 0) || H0 < 0 || W0 < 0)
+        return fail(YP_ERR_ARG, "yp_mask_contours_large: bad original size %dx%d (0, 0 or both positive)", H0, W0);
+    if (strategy != YP_CONTOURS_LARGEST && strategy != YP_CONTOURS_ALL)
+        return fail(YP_ERR_ARG, "yp_mask_contours_large: strategy must be YP_CONTOURS_LARGEST or YP_CONTOURS_ALL");
+    if (flags & ~YP_CONTOURS_ONLY_DECLINED) return fail(YP_ERR_ARG, "yp_mask_contours_large: unknown flags 0x%x", flags);
+    if (n > 0 && (!masks_dev || !pts_out || !count_out)) return fail(YP_ERR_ARG, "yp_mask_contours_large: null buffer");
+    if (parts_out && parts_cap < 2) return fail(YP_ERR_ARG, "yp_mask_contours_large: parts_cap >= 2 with a parts buffer");
+    const size_t need = contours_large_workspace_bytes(n, H, W);
+    if (n > 0 && (!workspace_dev || ((uintptr_t)workspace_dev & 15))) return fail(YP_ERR_ARG, "yp_mask_contours_large: workspace null or not 16-byte aligned");
+    if (workspace_bytes < need)
+        return fail(YP_ERR_ARG, "yp_mask_contours_large: workspace of %zu bytes, %zu needed (yp_mask_contours_large_workspace)", workspace_bytes, need);
+    HIPCHK(launch_contours_large(masks_dev, n, H, W, strategy, max_pts, pts_out, count_out, parts_out, parts_cap, rect_out, H0, W0, flags,
+                                 workspace_dev, (hipStream_t)stream));
+    return YP_OK;
+}
+
 int yp_letterbox(const uint8_t* src_dev, int h0, int w0, uint8_t* dst_dev, int out_h, int out_w, int new_h, int new_w, int top, int left,
                  int pad_value, void* stream) {
     if (!src_dev || !dst_dev) return fail(YP_ERR_ARG, "yp_letterbox: null buffer");

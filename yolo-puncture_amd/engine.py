@@ -58,6 +58,11 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     lib.yp_mask_contours.restype = C.c_int
     lib.yp_mask_contours_scaled.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, C.c_int, vp, C.c_int, C.c_int, vp]
     lib.yp_mask_contours_scaled.restype = C.c_int
+    lib.yp_mask_contours_large_workspace.argtypes = [C.c_int, C.c_int, C.c_int]
+    lib.yp_mask_contours_large_workspace.restype = C.c_size_t
+    lib.yp_mask_contours_large.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, C.c_int, vp, C.c_int, C.c_int, C.c_int, vp,
+                                           C.c_size_t, vp]
+    lib.yp_mask_contours_large.restype = C.c_int
     lib.yp_plan.argtypes = [vp, C.c_int, C.c_int, C.c_int]
     lib.yp_op_info.argtypes = [vp, C.c_int, C.c_char_p, C.c_int, ip, C.POINTER(C.c_double), C.POINTER(C.c_double)]
     lib.yp_op_output.argtypes = [vp, C.c_int, ip, ip, ip]
@@ -122,7 +127,7 @@ EXPORTS = ["yp_last_error", "yp_create", "yp_destroy", "yp_weight_count", "yp_we
            "yp_finalize", "yp_forward", "yp_proto", "yp_masks", "yp_id_mask_resized", "yp_plan", "yp_op_info", "yp_op_output", "yp_op_input", "yp_op_fusion",
            "yp_tensor_count", "yp_tensor_info", "yp_tensor_read", "yp_profile", "yp_set_graph", "yp_run_op",
            "yp_tensor_write", "yp_op_kernel", "yp_set_autotune", "yp_tuning_export", "yp_tuning_import", "yp_set_nms", "yp_debug_force_conv_cfg", "yp_debug_op_cfg", "yp_debug_conv_families", "yp_debug_ablation", "yp_debug_head_clocks", "yp_debug_head_branch_clocks", "yp_debug_head_winners", "yp_debug_contour_clocks", "yp_debug_pwsp_clocks", "yp_debug_host_selftest", "yp_debug_graph_info", "yp_tuning_source", "yp_debug_head_positions", "yp_debug_marker", "yp_letterbox", "yp_letterbox_batch", "yp_masks_frames", "yp_masks_frames_input", "yp_mask_contours",
-           "yp_mask_contours_scaled", "yp_comm_unique_id", "yp_comm_create", "yp_allgather", "yp_comm_destroy",
+           "yp_mask_contours_scaled", "yp_mask_contours_large_workspace", "yp_mask_contours_large", "yp_comm_unique_id", "yp_comm_create", "yp_allgather", "yp_comm_destroy",
            "yp_u2net_create", "yp_u2net_destroy", "yp_u2net_weight_count", "yp_u2net_weight_info", "yp_u2net_set_weight", "yp_u2net_finalize",
            "yp_u2net_forward", "yp_u2net_forward_crops", "yp_u2net_set_graph", "yp_u2net_tensor_count", "yp_u2net_tensor_info", "yp_u2net_tensor_read",
            "yp_cls_create", "yp_cls_destroy", "yp_cls_weight_count", "yp_cls_weight_info", "yp_cls_set_weight", "yp_cls_finalize",
@@ -225,8 +230,22 @@ def mask_contours_device(masks: torch.Tensor, max_pts: Optional[int] = None, wan
             rc = lib.yp_mask_contours_scaled(*args, int(orig_hw[0]), int(orig_hw[1]), C.c_void_p(_stream_ptr(dev)))
     if rc != 0:
         raise YolopError(lib.yp_last_error().decode())
+    return _read_contours(buf, n, int(max_pts), _PARTS_CAP, o_parts, o_rect, o_pts, want_rect, want_parts)
+
+
+class ContourList(list):
+    """The polygons of one device contour call (a plain list to its users) with what a follow-up call on the declined ones needs:
+    `max_pts`, the per-mask point capacity the call ran with."""
+    max_pts: Optional[int] = None
+
+
+def _read_contours(buf: torch.Tensor, n: int, max_pts: int, parts_cap: int, o_parts: int, o_rect: int, o_pts: int, want_rect: bool, want_parts: bool):
+    """The host side of a contour call's one allocation ([count | parts | rect | points], int32 words): counts, contour lengths, rectangles
+    and the heads of the point lists in ONE device-to-host copy for a single mask, two otherwise."""
     if n == 0:
-        return ([], (np.zeros((0, 2)) if want_rect else None), []) if want_parts else ([], (np.zeros((0, 2)) if want_rect else None))
+        polys = ContourList()
+        polys.max_pts = max_pts
+        return (polys, (np.zeros((0, 2)) if want_rect else None), []) if want_parts else (polys, (np.zeros((0, 2)) if want_rect else None))
     head_pts = min(max_pts, 1024)
     if n == 1:
         h = buf[:o_pts + 2 * head_pts].cpu().numpy()
@@ -241,12 +260,57 @@ def mask_contours_device(masks: torch.Tensor, max_pts: Optional[int] = None, wan
         top = int(max(1, c.max()))
         host = buf[o_pts:].view(n, max_pts, 2)[:, :top].cpu().numpy()
     rect = h[o_rect:o_rect + 4 * n].view(np.float64).reshape(n, 2).copy() if want_rect else None
-    polys = [host[i, :c[i]].copy() if c[i] >= 0 else None for i in range(n)]
+    polys = ContourList(host[i, :c[i]].copy() if c[i] >= 0 else None for i in range(n))
+    polys.max_pts = max_pts
     if not want_parts:
         return polys, rect
-    pr = h[o_parts:o_parts + n * _PARTS_CAP].reshape(n, _PARTS_CAP)
-    parts = [[int(v) for v in pr[i, 1:1 + min(int(pr[i, 0]), _PARTS_CAP - 1)]] if c[i] >= 0 else None for i in range(n)]
+    pr = h[o_parts:o_parts + n * parts_cap].reshape(n, parts_cap)
+    parts = [[int(v) for v in pr[i, 1:1 + min(int(pr[i, 0]), parts_cap - 1)]] if c[i] >= 0 else None for i in range(n)]
     return polys, rect, parts
+
+
+LARGE_MAX_DIM = 4096                                # include/yolop.h YP_CONTOURS_LARGE_MAX_DIM
+_LARGE_MAX_BORDERS = 65536                          # ... YP_CONTOURS_LARGE_MAX_STARTS: a mask has at most as many outer borders
+YP_CONTOURS_ONLY_DECLINED = 1
+
+
+def mask_contours_large_device(masks: torch.Tensor, max_pts: Optional[int] = None, want_rect: bool = True, strategy: str = "all",
+                               want_parts: bool = False, orig_hw: Optional[Tuple[int, int]] = None):
+    """yp_mask_contours_large: arguments and return values of mask_contours_device, every mask through the large path (tables in a device
+    workspace instead of LDS; csrc/contour_large.hip): masks up to 4096 x 4096, up to 65536 border starts and outer borders each, the
+    scaled rectangle (`orig_hw`) for a frame of any width. `parts` lists every contour of the mask. None where it declines (more starts, or
+    more than `max_pts` points); masks higher or wider than 4096 raise YolopError. The workspace lives for the call only."""
+    if not (masks.is_cuda and masks.dtype == torch.uint8 and masks.dim() == 3):
+        raise ValueError("mask_contours_large_device needs a uint8 CUDA tensor [n,H,W]")
+    if strategy not in CONTOUR_STRATEGIES:
+        raise ValueError(f"strategy must be 'all' or 'largest', got {strategy!r}")
+    if orig_hw is not None and not (int(orig_hw[0]) > 0 and int(orig_hw[1]) > 0):
+        raise ValueError(f"orig_hw must be a positive (H0, W0), got {orig_hw!r}")
+    masks = masks.contiguous()
+    n, H, W = (int(v) for v in masks.shape)
+    if max_pts is None:
+        max_pts = 131072 if n <= 2 else 16384
+    max_pts = int(max_pts)
+    dev = masks.device
+    # parts rows: every length the mask can have (a contour has at least one point, so at most max_pts of them are ever listed)
+    parts_cap = 1 + min(_LARGE_MAX_BORDERS, max_pts, max(1, H * ((W + 1) // 2))) if want_parts else 2
+    o_parts = (n + 1) // 2 * 2
+    o_rect = o_parts + (n * parts_cap + 1) // 2 * 2
+    o_pts = o_rect + 4 * n
+    lib = load_library()
+    ws_bytes = int(lib.yp_mask_contours_large_workspace(n, H, W))
+    buf = torch.empty((o_pts + n * max_pts * 2,), dtype=torch.int32, device=dev)
+    ws = torch.empty((max(ws_bytes, 16) // 4,), dtype=torch.int32, device=dev)
+    h0, w0 = (int(orig_hw[0]), int(orig_hw[1])) if orig_hw is not None else (0, 0)
+    with torch.cuda.device(dev):
+        base = buf.data_ptr()
+        rc = lib.yp_mask_contours_large(C.c_void_p(masks.data_ptr()), n, H, W, CONTOUR_STRATEGIES[strategy], max_pts, C.c_void_p(base + 4 * o_pts),
+                                        C.c_void_p(base), C.c_void_p(base + 4 * o_parts if want_parts else None), parts_cap,
+                                        C.c_void_p(base + 4 * o_rect if want_rect else None), h0, w0, 0, C.c_void_p(ws.data_ptr()), ws_bytes,
+                                        C.c_void_p(_stream_ptr(dev)))
+    if rc != 0:
+        raise YolopError(lib.yp_last_error().decode())
+    return _read_contours(buf, n, max_pts, parts_cap, o_parts, o_rect, o_pts, want_rect, want_parts)
 
 
 class Engine:

@@ -20,7 +20,7 @@ import numpy as np
 import torch
 
 from . import hostops
-from .engine import Engine, letterbox_batch_device, letterbox_device, mask_contours_device
+from .engine import LARGE_MAX_DIM, Engine, letterbox_batch_device, letterbox_device, mask_contours_device, mask_contours_large_device
 from .weights import read_ultralytics_pt, synthetic_state
 
 _ENGINE_CACHE: Dict[tuple, Engine] = {}
@@ -178,13 +178,10 @@ class Masks:
             one = (self._data[i:i + 1] > 0.5).to(torch.uint8)
         elif u8 is not None and u8.is_cuda:
             one = u8[i:i + 1]
-        if one is not None:
-            if self.strategy == "all_merged":             # the device lists every external contour ("all") with its length; bridged on the host
-                polys, rects, all_parts = mask_contours_device(one, strategy="all", want_parts=True)
-                parts = all_parts[0]
-            else:
-                polys, rects = mask_contours_device(one, strategy=self.strategy)
-            poly, rect = polys[0], rects[0]
+        if one is not None:                               # "all_merged": the device lists every external contour ("all") with its length;
+            merged = self.strategy == "all_merged"        # bridged on the host
+            polys, rects, all_parts = _device_contours(one, None, "all" if merged else self.strategy, merged)
+            poly, rect, parts = polys[0], rects[0], (all_parts[0] if merged else None)
 
         def host_mask():
             d = self.data[i]
@@ -208,6 +205,29 @@ class Masks:
         if i < 0:
             i += len(self)
         return _rect_len(poly, self._rects.get(i))
+
+
+def _device_contours(masks: torch.Tensor, max_pts: Optional[int], strategy: str, want_parts: bool, orig_hw: Optional[Tuple[int, int]] = None):
+    """The device trace of Masks.xy and predict_clip: the LDS pass (mask_contours_device) over all masks, then whatever it declined - a
+    polygon, or with `orig_hw` a rectangle left at (-1, -1) - through the large path (mask_contours_large_device) in ONE further call,
+    with the point capacity the first call ran with. Nothing more is launched when nothing was declined. -> (polys, rects, parts or
+    None); what is still None goes to the host trace."""
+    got = mask_contours_device(masks, max_pts=max_pts, strategy=strategy, want_parts=want_parts, orig_hw=orig_hw)
+    polys, rects = got[0], got[1]
+    parts = got[2] if want_parts else None
+    need = [t for t in range(len(polys)) if polys[t] is None or (orig_hw is not None and rects is not None and rects[t][0] < 0)]
+    if not need or int(masks.shape[1]) > LARGE_MAX_DIM or int(masks.shape[2]) > LARGE_MAX_DIM:
+        return polys, rects, parts
+    sub = masks if len(need) == len(polys) else masks[torch.as_tensor(need, device=masks.device)]
+    big = mask_contours_large_device(sub, max_pts=getattr(polys, "max_pts", None) or max_pts, strategy=strategy, want_parts=want_parts, orig_hw=orig_hw)
+    for q, t in enumerate(need):
+        if big[0][q] is None:
+            continue
+        polys[t] = big[0][q]
+        rects[t] = big[1][q]
+        if want_parts:
+            parts[t] = big[2][q]
+    return polys, rects, parts
 
 
 def _finish_contour(poly, rect, parts, strategy: str, host_mask, mask_hw: Tuple[int, int], orig_shape: Tuple[int, int], rect_in_orig: bool = False):
@@ -485,8 +505,8 @@ class YOLO:
         contiguous chunks of B = min(batch_size, N), the last one padded to B by repeating its last frame (hostops.clip_plan), so each chunk
         is the computation predict() does on that padded chunk. Per chunk: one upload (host frames), one letterbox launch, the forward, ONE
         copy of each frame's row 0 (rows are best first: np.argmax of the scores), the strict `> conf` test and scale_boxes on the host, one
-        mask per detected frame (yp_masks_frames) and one contour pass over them (MASK_POLYGON_STRATEGY, host trace where the device
-        declines). -> ClipResults: `boxes, coords, lens = model.predict_clip(frames)`."""
+        mask per detected frame (yp_masks_frames) and one contour pass over them (MASK_POLYGON_STRATEGY; what the LDS kernel declines -
+        4K masks, many blobs - goes through the large path in one further call, host trace where that declines too). -> ClipResults: `boxes, coords, lens = model.predict_clip(frames)`."""
         if not self.seg:
             raise ValueError("predict_clip needs a segmentation checkpoint (-seg): the app reads masks.xy of the best row")
         if int(batch_size) < 1:
@@ -572,12 +592,11 @@ class YOLO:
             else:                                                       # process_mask from the boxes in letterboxed-input pixels
                 m = eng.masks_frames(sel, out["coeff"], rows[sel, :4].to(dev, non_blocking=True), (Hl, Wl), retina=False)
                 mask_hw, orig_hw = (Hl, Wl), (H, W)
-            dpolys, drects, *dparts = mask_contours_device(m, max_pts=131072, strategy=dev_strategy, want_parts=strategy == "all_merged",
-                                                           orig_hw=orig_hw)
+            dpolys, drects, dparts = _device_contours(m, 131072, dev_strategy, strategy == "all_merged", orig_hw)
             bnp = boxes.numpy()
             for t, j in enumerate(sel):
                 i = s0 + j
-                parts = dparts[0][t] if dparts else None
+                parts = dparts[t] if dparts is not None else None
                 poly, rect = _finish_contour(dpolys[t], drects[t], parts, strategy, lambda t=t: m[t].cpu().numpy() > 0, mask_hw, (H, W),
                                              rect_in_orig=not retina)
                 detected[i], confs[i], xyxy[i] = True, float(rows[j, 4]), bnp[t].copy()
