@@ -11,10 +11,6 @@ namespace yp {
 
 constexpr int QT = 16;
 
-template <typename T> __device__ __forceinline__ float rnd(float x);
-template <> __device__ __forceinline__ float rnd<__bf16>(float x) { return (float)(__bf16)x; }
-template <> __device__ __forceinline__ float rnd<float>(float x) { return x; }
-
 template <typename T> __device__ __forceinline__ void load4(const T* p, float* f);
 template <> __device__ __forceinline__ void load4<__bf16>(const __bf16* p, float* f) {
     const uint2 r = *(const uint2*)p;
@@ -94,7 +90,7 @@ __global__ __launch_bounds__(256) void attention_kernel(const AttnParams p) {
 #pragma unroll
         for (int o = 8; o >= 1; o >>= 1) sum += __shfl_xor(sum, o, 16);
         const float inv = 1.0f / sum;
-        for (int n = l; n < p.N; n += 16) row[n] = rnd<T>(row[n] * inv);
+        for (int n = l; n < p.N; n += 16) row[n] = round_to<T>(row[n] * inv);
     }
     __syncthreads();
 
@@ -136,18 +132,14 @@ __global__ __launch_bounds__(256) void attention_kernel(const AttnParams p) {
 // per 80 queries (5 workgroups per head: 3.7x the algorithmic bytes from L2 misses across XCDs, 83 scalar LDS writes per
 // thread); the run length is picked by the launcher so that the grid still covers the chip.
 // ---------------------------------------------------------------------------------------------------------------
-typedef __attribute__((ext_vector_type(8))) __bf16 abf16x8;
 typedef __attribute__((ext_vector_type(4))) __bf16 abf16x4;
 typedef __attribute__((ext_vector_type(4))) short as16x4;
-typedef __attribute__((ext_vector_type(4))) float af32x4;
-typedef __attribute__((address_space(3))) void a_lds_void;
 typedef __attribute__((address_space(3))) as16x4 a_lds_s4;
 
 constexpr int A_NT = 25;            // key tiles of 16 (N <= 400)
 constexpr int A_NPAD = 416;         // 26 tiles = 13 steps of 32 keys
 constexpr int A_MAXW = 8;           // waves per workgroup
 
-__device__ __forceinline__ int aswz(int row) { return ((row >> 2) & 1) << 1; }      // K image: 64-B rows
 __device__ __forceinline__ int vswz(int row) { return ((row >> 1) & 3) << 1; }      // V image: 128-B rows, 32-B pairs swizzled
 
 __global__ __launch_bounds__(A_MAXW * 64) void attention_mfma_kernel(const AttnParams p, const int tiles_per_wg, const unsigned qkv_bytes) {
@@ -166,16 +158,16 @@ __global__ __launch_bounds__(A_MAXW * 64) void attention_mfma_kernel(const AttnP
     // ---- stage K and V rows of this head (keys >= N: out-of-range offset = zero fill) ---------------------------------
     const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void*)p.qkv, 0, (int)qkv_bytes, 0x00020000);
     for (int ii = wave; ii < A_NPAD / 16; ii += nw) {          // 16 keys x 64 B per instruction
-        const int key = ii * 16 + (lane >> 2), c = (lane & 3) ^ aswz(key);
+        const int key = ii * 16 + (lane >> 2), c = (lane & 3) ^ cswz64(key);
         const unsigned voff = (key < p.N) ? (unsigned)((base_el + (size_t)key * p.q_stride + p.kd + c * 8) * 2) : OOB;
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (a_lds_void*)(Ks + ii * 1024), 16, voff, 0, 0, 0);
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (lds_void*)(Ks + ii * 1024), 16, voff, 0, 0, 0);
     }
     // the first tile's query fragment, issued between the K and V rows so that the counted wait below covers it (an asm load: the
     // compiler would wait for it with vmcnt(0), i.e. for the V rows behind it as well)
     const int fr = lane & 15, g = lane >> 4;
     const int ntiles = (p.N + 15) >> 4;
     const int t0 = blockIdx.x * tiles_per_wg, t1 = min(t0 + tiles_per_wg, ntiles);
-    abf16x8 qf0;
+    bf16x8 qf0;
     {
         const __bf16* qp = base + (size_t)min((t0 + wave) * 16 + fr, p.N - 1) * p.q_stride + g * 8;
         asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(qf0) : "v"(qp) : "memory");
@@ -186,7 +178,7 @@ __global__ __launch_bounds__(A_MAXW * 64) void attention_mfma_kernel(const AttnP
         const int ii = min(wave + k * A_MAXW, A_NPAD / 8 - 1);
         const int key = ii * 8 + (lane >> 3), c = (lane & 7) ^ vswz(key);
         const unsigned voff = (key < p.N) ? (unsigned)((base_el + (size_t)key * p.q_stride + 2 * p.kd + c * 8) * 2) : OOB;
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (a_lds_void*)(Vs + ii * 1024), 16, voff, 0, 0, 0);
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (lds_void*)(Vs + ii * 1024), 16, voff, 0, 0, 0);
     }
     // K (and the query fragment) first: the V rows may still be in flight while the first tile's scores and softmax run (they are
     // waited for, once per wave, in front of its first P.V)
@@ -209,21 +201,21 @@ __global__ __launch_bounds__(A_MAXW * 64) void attention_mfma_kernel(const AttnP
     for (int t = t0 + wave; t < t1; t += nw) {                  // wave-uniform: the transposing reads below need EXEC all ones
         const int q0 = t * 16;
         const int qi = q0 + fr;
-        abf16x8 qf;
+        bf16x8 qf;
         if (!v_ready) qf = qf0;                                  // (uniform) the wave's first tile
-        else qf = *(const abf16x8*)(base + (size_t)min(qi, p.N - 1) * p.q_stride + g * 8);
+        else qf = *(const bf16x8*)(base + (size_t)min(qi, p.N - 1) * p.q_stride + g * 8);
         if (qi >= p.N) {
 #pragma unroll
             for (int j = 0; j < 8; ++j) qf[j] = (__bf16)0.f;
         }
         // ---- S^T tiles: rows = keys (A operand), cols = queries (B operand) --------------------------------------------
-        af32x4 st[A_NT];
+        f32x4 st[A_NT];
         float mx = -INFINITY;
 #pragma unroll
         for (int j = 0; j < A_NT; ++j) {
             const int row = j * 16 + fr;
-            const abf16x8 kf = *(const abf16x8*)(Ks + row * 64 + ((g ^ aswz(row)) * 16));
-            af32x4 z = {0.f, 0.f, 0.f, 0.f};
+            const bf16x8 kf = *(const bf16x8*)(Ks + row * 64 + ((g ^ cswz64(row)) * 16));
+            f32x4 z = {0.f, 0.f, 0.f, 0.f};
             st[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf, qf, z, 0, 0, 0);
             if (j * 16 + 16 > p.N) {                             // (uniform) only a ragged or absent key tile needs masking
 #pragma unroll
@@ -253,12 +245,12 @@ __global__ __launch_bounds__(A_MAXW * 64) void attention_mfma_kernel(const AttnP
             __builtin_amdgcn_s_barrier();
             v_ready = true;
         }
-        af32x4 o[4];
+        f32x4 o[4];
 #pragma unroll
-        for (int dt = 0; dt < 4; ++dt) o[dt] = af32x4{0.f, 0.f, 0.f, 0.f};
+        for (int dt = 0; dt < 4; ++dt) o[dt] = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int s = 0; s < A_NPAD / 32; ++s) {
-            abf16x8 pf;
+            bf16x8 pf;
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 pf[r] = (__bf16)(st[2 * s][r] * inv);
@@ -268,7 +260,7 @@ __global__ __launch_bounds__(A_MAXW * 64) void attention_mfma_kernel(const AttnP
             for (int dt = 0; dt < 4; ++dt) {
                 const as16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((a_lds_s4*)(vaddr[dt] + s * 4096));
                 const as16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((a_lds_s4*)(vaddr[dt] + s * 4096 + 2048));
-                union { as16x4 h[2]; abf16x8 v; } u;
+                union { as16x4 h[2]; bf16x8 v; } u;
                 u.h[0] = lo; u.h[1] = hi;
                 o[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(pf, u.v, o[dt], 0, 0, 0);
             }
@@ -293,7 +285,7 @@ hipError_t launch_attention(const AttnParams& p, int dtype, hipStream_t st) {
     const size_t qkv_bytes = (size_t)p.B * p.N * p.q_stride * 2;
     if (dtype == DT_BF16 && p.kd == 32 && p.hd == 64 && p.N <= 16 * A_NT && (p.q_stride & 7) == 0 && (p.q_coff & 7) == 0 && qkv_bytes < (1ull << 31)) {
         // query tiles per workgroup: as long as possible (K/V are staged once per workgroup) while the grid still covers the chip
-        static const int target = [] { const char* s = getenv("YOLOP_ATTN_WGS"); const int v = s ? atoi(s) : 0; return v > 0 ? v : 256; }();
+        static const int target = [] { const int v = env_int("YOLOP_ATTN_WGS", 0); return v > 0 ? v : 256; }();
         const int ntiles = (p.N + 15) / 16, BH = p.B * p.nh;
         int nsplit = std::min(ntiles, std::max(1, (target + BH - 1) / BH));
         const int tpw = (ntiles + nsplit - 1) / nsplit;
@@ -304,13 +296,12 @@ hipError_t launch_attention(const AttnParams& p, int dtype, hipStream_t st) {
     const size_t sh = (size_t)(QT * p.kd + QT * p.N) * sizeof(float);
     if (sh > 150 * 1024 || (p.kd & 3) || (p.hd & 3)) return hipErrorInvalidValue;
     dim3 grid((p.N + QT - 1) / QT, p.B * p.nh);
+    static size_t granted[2] = {0, 0};
     if (dtype == DT_BF16) {
-        if (sh > 64 * 1024)
-            (void)hipFuncSetAttribute((const void*)attention_kernel<__bf16>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh);
+        if (hipError_t e = allow_dynamic_lds((const void*)attention_kernel<__bf16>, sh, granted[0])) return e;
         hipLaunchKernelGGL(attention_kernel<__bf16>, grid, dim3(256), sh, st, p);
     } else {
-        if (sh > 64 * 1024)
-            (void)hipFuncSetAttribute((const void*)attention_kernel<float>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh);
+        if (hipError_t e = allow_dynamic_lds((const void*)attention_kernel<float>, sh, granted[1])) return e;
         hipLaunchKernelGGL(attention_kernel<float>, grid, dim3(256), sh, st, p);
     }
     return hipGetLastError();

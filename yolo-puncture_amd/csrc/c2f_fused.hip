@@ -18,24 +18,6 @@
 
 namespace yp {
 
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-typedef __attribute__((address_space(3))) void lds_void;
-
-// LDS stores behind the compiler's back: it cannot tell a ds_write from the in-flight LDS-DMA of the next patch apart and would
-// drain vmcnt to 0 in front of every one of them (the patch buffers and Ts / Cs never overlap)
-__device__ __forceinline__ void lds_write8(unsigned char* dst, unsigned long long v) {
-    asm volatile("ds_write_b64 %0, %1" ::"v"((unsigned)(size_t)(__attribute__((address_space(3))) unsigned char*)dst), "v"(v) : "memory");
-}
-// (same for the 8-byte residual read of the current patch; the caller waits on lgkmcnt before the first use)
-__device__ __forceinline__ unsigned long long lds_read8_async(const unsigned char* src) {
-    unsigned long long v;
-    asm volatile("ds_read_b64 %0, %1" : "=v"(v) : "v"((unsigned)(size_t)(const __attribute__((address_space(3))) unsigned char*)src) : "memory");
-    return v;
-}
-__device__ __forceinline__ int cswz(int row) { return ((row >> 2) & 1) << 1; }     // 64-B rows
-__device__ __forceinline__ int cswz128(int row) { return (row >> 1) & 7; }         // 128-B rows
-
 constexpr int CF_NW = 8;
 constexpr int CF_TH = 8;                          // output rows per tile (x 16 columns)
 constexpr int CF_PW = 20, CF_PP = 12 * 20;        // [a | b] patch: 12 x 20 pixels
@@ -61,11 +43,7 @@ __global__ __launch_bounds__(CF_NW * 64) void c2f_fused_kernel(const C2fParams p
     const int fr = lane & 15, fc = lane >> 4;
     const int num_tiles = p.B * tiles_h * tiles_w;
 
-    int bid = blockIdx.x;
-    {
-        const int nwg = gridDim.x, q = nwg >> 3, r = nwg & 7, xcd = bid & 7, j = bid >> 3;
-        bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + j;
-    }
+    const int bid = xcd_remap(blockIdx.x, gridDim.x);
 
     const __amdgpu_buffer_rsrc_t xrs = __builtin_amdgcn_make_buffer_rsrc((void*)p.x, 0, (int)p.x_bytes, 0x00020000);
     const __amdgpu_buffer_rsrc_t w1rs = __builtin_amdgcn_make_buffer_rsrc((void*)p.w1, 0, (int)p.w1_bytes, 0x00020000);
@@ -100,7 +78,7 @@ __global__ __launch_bounds__(CF_NW * 64) void c2f_fused_kernel(const C2fParams p
     for (int ii = wave; ii < CF_W33 / 1024; ii += CF_NW) {               // row rg = tap*32 + co
         const int s = ii * 64 + lane;
         const int rg = s >> 2, pc = s & 3;
-        const int c8 = pc ^ cswz(rg);
+        const int c8 = pc ^ cswz64(rg);
         const int n = rg & 31, tap = rg >> 5;
         __builtin_amdgcn_raw_ptr_buffer_load_lds(w1rs, (lds_void*)(W1s + ii * 1024), 16, (unsigned)((n * p.Kpad1 + tap * 32 + c8 * 8) * 2), 0, 0, 0);
         __builtin_amdgcn_raw_ptr_buffer_load_lds(w2rs, (lds_void*)(W2s + ii * 1024), 16, (unsigned)((n * p.Kpad2 + tap * 32 + c8 * 8) * 2), 0, 0, 0);
@@ -108,7 +86,7 @@ __global__ __launch_bounds__(CF_NW * 64) void c2f_fused_kernel(const C2fParams p
     for (int ii = wave; ii < CF_W3 / 1024; ii += CF_NW) {                // row rg = chunk*64 + co
         const int s = ii * 64 + lane;
         const int rg = s >> 2, pc = s & 3;
-        const int c8 = pc ^ cswz(rg);
+        const int c8 = pc ^ cswz64(rg);
         const int n = rg & 63, ch = rg >> 6;
         __builtin_amdgcn_raw_ptr_buffer_load_lds(w3rs, (lds_void*)(W3s + ii * 1024), 16, (unsigned)((n * p.Kpad3 + ch * 32 + c8 * 8) * 2), 0, 0, 0);
     }
@@ -193,7 +171,7 @@ __global__ __launch_bounds__(CF_NW * 64) void c2f_fused_kernel(const C2fParams p
                 __attribute__((aligned(8))) __bf16 o[4];
 #pragma unroll
                 for (int i = 0; i < 4; ++i) o[i] = (__bf16)(in ? v[i] : 0.f);
-                if (q < CF_TP) lds_write8(Ts + q * 64 + (((cf * 2 + (fc >> 1)) ^ cswz(q)) * 16) + (fc & 1) * 8, *(const unsigned long long*)o);
+                if (q < CF_TP) lds_write8(Ts + q * 64 + (((cf * 2 + (fc >> 1)) ^ cswz64(q)) * 16) + (fc & 1) * 8, *(const unsigned long long*)o);
             }
         }
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
@@ -242,7 +220,7 @@ __global__ __launch_bounds__(CF_NW * 64) void c2f_fused_kernel(const C2fParams p
                 }
                 const int q = (wq + 4 * j) * 16 + fr;
                 __attribute__((aligned(8))) __bf16 o[4] = {(__bf16)v[0], (__bf16)v[1], (__bf16)v[2], (__bf16)v[3]};
-                lds_write8(Cs + q * 64 + (((cf * 2 + (fc >> 1)) ^ cswz(q)) * 16) + (fc & 1) * 8, *(const unsigned long long*)o);
+                lds_write8(Cs + q * 64 + (((cf * 2 + (fc >> 1)) ^ cswz64(q)) * 16) + (fc & 1) * 8, *(const unsigned long long*)o);
             }
         }
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
@@ -316,13 +294,9 @@ hipError_t launch_c2f_fused(const C2fParams& p, hipStream_t st) {
     const int num_tiles = p.B * tiles_h * tiles_w;
     int G = 256;
     if (G > num_tiles) G = num_tiles;
-    static bool attr = false;
-    if (!attr) {
-        hipError_t e = hipFuncSetAttribute((const void*)c2f_fused_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(160 * 1024));
-        if (e != hipSuccess) return e;
-        attr = true;
-    }
-    static const bool clocks = [] { const char* v = std::getenv("YOLOP_C2F_CLOCKS"); return v && *v == '1'; }();   // debug: per-stage s_memtime sums
+    static size_t granted = 0;
+    if (hipError_t e = allow_dynamic_lds((const void*)c2f_fused_kernel, (size_t)CF_LDS, granted)) return e;
+    static const bool clocks = env_on("YOLOP_C2F_CLOCKS");   // debug: per-stage s_memtime sums
     if (clocks) {
         C2fParams q = p;
         const size_t n = (size_t)G * CF_NW * 7;

@@ -14,12 +14,6 @@
 
 namespace yp {
 
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-typedef __attribute__((address_space(3))) void lds_void;
-
-__device__ __forceinline__ float co_sigmoid(float x) { return 1.0f / (1.0f + expf(-x)); }     // the form of head.hip's sigmoidf_: the same bits
-
 constexpr int CO_NW = 4;
 constexpr int CO_MAXNF = 8;             // up to 128 classes
 
@@ -113,7 +107,7 @@ __global__ __launch_bounds__(CO_NW * 64) void cls_out_kernel(const ClsOutParams 
             }
             mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
             mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-            if (ok && fc == 0) p.keys[m] = __float_as_uint(co_sigmoid(mx));
+            if (ok && fc == 0) p.keys[m] = __float_as_uint(sigmoid_ieee(mx));
         }
     }
     __builtin_amdgcn_s_waitcnt(0 | (7 << 4) | (0xF << 8));
@@ -141,12 +135,8 @@ template <int TP, int NF>
 static hipError_t launch_cls_out_t(const ClsOutParams& p, hipStream_t st) {
     const size_t sh = cls_out_lds(p, TP);
     auto kern = cls_out_kernel<TP, NF>;
-    static bool attr = false;
-    if (!attr) {
-        hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e != hipSuccess) return e;
-        attr = true;
-    }
+    static size_t granted = 0;
+    if (hipError_t e = allow_dynamic_lds((const void*)kern, sh, granted)) return e;
     const int ntiles = (p.M + TP - 1) / TP;
     // (an HBM-bound kernel: as many workgroups as fit - two per CU when the tiles are small - each walking every G-th tile)
     int G = sh <= 78 * 1024 ? 512 : 256;

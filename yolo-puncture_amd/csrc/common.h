@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <cstdlib>
 #include <string>
 #include <vector>
 
@@ -261,32 +262,25 @@ hipError_t launch_head_branch(const HeadBranchParams& p, hipStream_t st);
 hipError_t launch_head_nms(const HeadParams& p, hipStream_t st);
 size_t head_nms_scratch_bytes(int B, int A);
 
-#if defined(__HIPCC__)
-// LDS byte offset of the 16-byte piece `c` of the 64-byte row `row` under the chunk swizzle c ^ (((row >> 2) & 1) << 1), computed from the
-// UNSWIZZLED offset L = row * 64 + c * 16: the swizzle flips bit 5 of L where bit 2 of row = bit 8 of L is set. Written on L, a fragment read
-// costs one add (row offset of the tap, usually a constant) + two bit operations; written on `row`, the compiler spent ~9 VALU instructions per
-// read (PMC on conv_tile1: VALU issue 48 % of the kernel's cycles, matrix pipe busy 30 %).
-__device__ __forceinline__ unsigned swz64(unsigned L) { return L ^ ((L >> 3) & 32u); }
-#endif
+// Experiment switches (YOLOP_* environment variables). env_on: set and its first character is '1'; env_int: atoi of the value, dflt when
+// unset. A launcher keeps the result in a function-local static, so a switch is read once, at the first use of that function.
+inline bool env_on(const char* name) { const char* v = std::getenv(name); return v && *v == '1'; }
+inline int env_int(const char* name, int dflt) { const char* v = std::getenv(name); return v ? atoi(v) : dflt; }
 
-// Four SiLUs with the two multiplies and the add as packed fp32 operations (v_pk_mul_f32 / v_pk_add_f32: two values per
-// instruction). Same operations and roundings as  x * rcp(1 + exp2(-x * log2e))  element by element, so the same bits; the
-// conv epilogues are VALU-bound on exactly this sequence (28 -> 22 cycles per element).
-#if defined(__HIPCC__)
-typedef float yp_f32x2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ void silu4_packed(float* v) {
-#pragma unroll
-    for (int i = 0; i < 4; i += 2) {
-        yp_f32x2 x = {v[i], v[i + 1]};
-        yp_f32x2 t = x * -1.4426950408889634f;
-        t[0] = __builtin_amdgcn_exp2f(t[0]); t[1] = __builtin_amdgcn_exp2f(t[1]);
-        t = t + 1.0f;
-        t[0] = __builtin_amdgcn_rcpf(t[0]); t[1] = __builtin_amdgcn_rcpf(t[1]);
-        x = x * t;
-        v[i] = x[0]; v[i + 1] = x[1];
-    }
+// Lets `kern` be launched with `bytes` of dynamic LDS. Nothing to do up to the 64 KiB every kernel may have, or when `granted` (the caller's
+// `static size_t granted = 0`, one per kernel instantiation) already covers it; else the kernel's limit goes to the most the device has for
+// it, once: 160 KiB less the kernel's static LDS, which comes out of the same 160 KiB (asking for more is an invalid value). The attribute
+// only permits an allocation: a launch still gets just the LDS it asks for. The engine runs one process per GPU (parallel.py), so a
+// per-process static is the right lifetime for `granted`.
+inline hipError_t allow_dynamic_lds(const void* kern, size_t bytes, size_t& granted) {
+    if (bytes <= 64 * 1024 || bytes <= granted) return hipSuccess;
+    hipFuncAttributes fa;
+    if (hipError_t e = hipFuncGetAttributes(&fa, kern)) return e;
+    const size_t most = 160 * 1024 - fa.sharedSizeBytes;
+    if (hipError_t e = hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)most)) return e;
+    granted = most;
+    return hipSuccess;
 }
-#endif
 
 // launches (implemented in the .hip files); dtype selects the template instance
 hipError_t launch_conv(const ConvParams& p, int dtype, hipStream_t st);
@@ -455,3 +449,5 @@ static inline float bf2f(uint16_t h) {
 }
 
 }  // namespace yp
+
+#include "kernel_util.h"   // the device primitives shared by the kernel files (they name the enums above)

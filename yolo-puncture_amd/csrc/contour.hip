@@ -929,12 +929,8 @@ static hipError_t launch_contour_kernels(ContourParams& p, hipStream_t st) {
     p.boxg = p.max_pts / 2 < CT_BOXG ? p.max_pts / 2 : CT_BOXG;  // a partial box takes two points' worth of the list
     if (p.boxg < 1) return hipErrorInvalidValue;
     const size_t sh = (size_t)CT_BITMAP_BYTES + (size_t)CT_MAXCAND * sizeof(int);
-    static bool attr = false;
-    if (!attr) {
-        hipError_t e = hipFuncSetAttribute((const void*)contour_kernel<SCALED>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh);
-        if (e != hipSuccess) return e;
-        attr = true;
-    }
+    static size_t granted = 0;
+    if (hipError_t e = allow_dynamic_lds((const void*)contour_kernel<SCALED>, sh, granted)) return e;
     hipLaunchKernelGGL(contour_bbox_kernel, dim3(p.boxg, p.n), dim3(256), 0, st, p);
     hipLaunchKernelGGL(contour_kernel<SCALED>, dim3(p.n), dim3(CT_THREADS), sh, st, p);
     return hipGetLastError();

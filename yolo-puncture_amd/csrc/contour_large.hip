@@ -679,12 +679,8 @@ hipError_t launch_contours_large(const uint8_t* masks, int n, int H, int W, int 
         p.scaled = 1; p.H0 = H0; p.W0 = W0;
         p.gain = (float)gain; p.padx = (float)((W - wg) / 2); p.pady = (float)((H - hg) / 2);
     }
-    static bool attr = false;
-    if (!attr) {
-        hipError_t e = hipFuncSetAttribute((const void*)cl_hull_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, CL_HULL_LDS);
-        if (e != hipSuccess) return e;
-        attr = true;
-    }
+    static size_t granted = 0;
+    if (hipError_t e = allow_dynamic_lds((const void*)cl_hull_kernel, (size_t)CL_HULL_LDS, granted)) return e;
     const unsigned cg = (unsigned)((p.L.candcap + 63) / 64);
     hipLaunchKernelGGL(cl_init_kernel, dim3((n + 255) / 256), dim3(256), 0, st, p);
     hipLaunchKernelGGL(cl_bits_kernel, dim3((unsigned)((p.L.nwords + 255) / 256), n), dim3(256), 0, st, p);

@@ -17,24 +17,6 @@
 
 namespace yp {
 
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-typedef __attribute__((address_space(3))) void lds_void;
-
-__device__ __forceinline__ float silu2(float x) { return x / (1.0f + __expf(-x)); }
-
-// s_waitcnt vmcnt(N) only (gfx9 encoding: vmcnt[3:0] | expcnt[6:4]=7 | lgkmcnt[11:8]=15 | vmcnt_hi[15:14])
-template <int N> __device__ __forceinline__ void wait_vmcnt() {
-    static_assert(N >= 0 && N < 64, "vmcnt range");
-    __builtin_amdgcn_s_waitcnt((N & 0xF) | (7 << 4) | (0xF << 8) | (((N >> 4) & 3) << 14));
-}
-
-// XOR mask applied to the 16-B chunk index within a row. 64-B rows (BK=32): conflict-free for ds_read_b128 of ANY
-// 16 consecutive rows; 128-B rows (BK=64): conflict-free for 16-row aligned fragments. Derivations: DESIGN.md.
-template <int BK> __device__ __forceinline__ int swz_mask(int row) {
-    return BK == 32 ? (((row >> 2) & 1) << 1) : ((row >> 1) & 7);
-}
-
 template <int BM, int BN, int WGM, int WGN, int BK, int NS>
 __global__ __launch_bounds__(WGM * WGN * 64) void conv_dma_kernel(const ConvParams p, const int mtiles, const int ntiles) {
     constexpr int NW = WGM * WGN;             // waves per workgroup (4 or 8)
@@ -59,11 +41,7 @@ __global__ __launch_bounds__(WGM * WGN * 64) void conv_dma_kernel(const ConvPara
 
     // XCD-aware bijective remap of the linear block id (blocks b, b+8, ... share an XCD / L2): each XCD walks a
     // contiguous run of tiles, n-tile fastest so the CTAs that share a pixel tile are neighbours.
-    int bid = blockIdx.x;
-    {
-        const int nwg = mtiles * ntiles, q = nwg >> 3, r = nwg & 7, xcd = bid & 7, j = bid >> 3;
-        bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + j;
-    }
+    const int bid = xcd_remap(blockIdx.x, mtiles * ntiles);
     const int mt = bid / ntiles, nt = bid - mt * ntiles;
     const int m0 = mt * BM, n0 = nt * BN;
     const int HoWo = p.Ho * p.Wo;
@@ -77,7 +55,7 @@ __global__ __launch_bounds__(WGM * WGN * 64) void conv_dma_kernel(const ConvPara
     for (int j = 0; j < A_IPW; ++j) {
         const int s = (wave * A_IPW + j) * 64 + lane;
         const int row = s / CPR, pc = s - row * CPR;
-        const int c = pc ^ swz_mask<BK>(row);
+        const int c = pc ^ cswz<BK>(row);
         const int m = m0 + row;
         unsigned mask = 0, base = 0;
         if (m < p.M) {
@@ -99,7 +77,7 @@ __global__ __launch_bounds__(WGM * WGN * 64) void conv_dma_kernel(const ConvPara
         const int ii = wave * W_IPW + j;
         const int s = ii * 64 + lane;
         const int row = s / CPR, pc = s - row * CPR;
-        const int c = pc ^ swz_mask<BK>(row);
+        const int c = pc ^ cswz<BK>(row);
         wconst[j] = (ii < W_INSTR) ? (unsigned)(((n0 + row) * p.Kpad + c * 8) * 2) : OOB;
     }
 
@@ -144,8 +122,8 @@ __global__ __launch_bounds__(WGM * WGN * 64) void conv_dma_kernel(const ConvPara
 #pragma unroll
     for (int ss = 0; ss < KSUB; ++ss) {
         const int ra = wm * WM + fr, rw = wn * WN + fr;
-        aoff[ss] = ra * RB + (((ss * 4 + fc) ^ swz_mask<BK>(ra)) * 16);
-        woff[ss] = BM * RB + rw * RB + (((ss * 4 + fc) ^ swz_mask<BK>(rw)) * 16);
+        aoff[ss] = ra * RB + (((ss * 4 + fc) ^ cswz<BK>(ra)) * 16);
+        woff[ss] = BM * RB + rw * RB + (((ss * 4 + fc) ^ cswz<BK>(rw)) * 16);
     }
 
     const int nk = p.Kpad / BK;
@@ -204,7 +182,7 @@ __global__ __launch_bounds__(WGM * WGN * 64) void conv_dma_kernel(const ConvPara
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 float t = acc[a][b][r] + bias[a][r];
-                if (p.act == ACT_SILU) t = silu2(t);
+                if (p.act == ACT_SILU) t = silu_fdiv(t);
                 v[r] = t;
             }
             if (p.res) {
@@ -293,7 +271,7 @@ int conv_dma_forced_cfg() { return g_force_cfg; }
 static int g_dbg_ablate = 0;
 void conv_set_debug_ablation(int v) { g_dbg_ablate = v; }
 int conv_debug_ablation() { return g_dbg_ablate; }
-bool tile_balance_enabled(int family) { static const int mask = [] { const char* v = std::getenv("YOLOP_BALANCE"); return v ? atoi(v) : 6; }(); return (mask & family) != 0; }
+bool tile_balance_enabled(int family) { static const int mask = env_int("YOLOP_BALANCE", 6); return (mask & family) != 0; }
 int conv_dma_requested_cfg(const ConvParams& p) {
     if (conv_dma_cfg_valid(p, g_force_cfg)) return g_force_cfg;
     return conv_dma_cfg_valid(p, p.cfg) ? p.cfg : -1;
@@ -310,12 +288,8 @@ static hipError_t launch_one(const ConvParams& p, hipStream_t st) {
     const int mtiles = (p.M + BM - 1) / BM, ntiles = (p.Cout + BN - 1) / BN;
     const size_t sh = (size_t)NS * (BM + BN) * BK * 2 + 1024;
     auto kern = conv_dma_kernel<BM, BN, WGM, WGN, BK, NS>;
-    static bool attr = false;
-    if (!attr && sh > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh);
-        if (e != hipSuccess) return e;
-        attr = true;
-    }
+    static size_t granted = 0;
+    if (hipError_t e = allow_dynamic_lds((const void*)kern, sh, granted)) return e;
     hipLaunchKernelGGL(kern, dim3(mtiles * ntiles), dim3(WGM * WGN * 64), sh, st, p, mtiles, ntiles);
     return hipGetLastError();
 }

@@ -20,19 +20,6 @@
 
 namespace yp {
 
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-typedef __attribute__((address_space(3))) void lds_void;
-
-__device__ __forceinline__ float silu_lc(float x) { return x * __builtin_amdgcn_rcpf(1.0f + __expf(-x)); }
-template <int N> __device__ __forceinline__ void wait_vml() {
-    static_assert(N >= 0 && N < 64, "vmcnt range");
-    __builtin_amdgcn_s_waitcnt((N & 0xF) | (7 << 4) | (0xF << 8) | (((N >> 4) & 3) << 14));
-}
-template <int BK> __device__ __forceinline__ int swz_l(int row) {
-    return BK == 32 ? (((row >> 2) & 1) << 1) : ((row >> 1) & 7);
-}
-
 template <int BM, int BN, int WGM, int WGN, int NL, int BK, int NS, bool HAS_RES, bool OUT_F32>
 __global__ __launch_bounds__((WGM * WGN + NL) * 64) void conv_dma_lc_kernel(const ConvParams p, const int mtiles, const int ntiles, const int G) {
     constexpr int NC = WGM * WGN;
@@ -54,11 +41,7 @@ __global__ __launch_bounds__((WGM * WGN + NL) * 64) void conv_dma_lc_kernel(cons
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
 
-    int bid = blockIdx.x;
-    {
-        const int nwg = gridDim.x, q = nwg >> 3, r = nwg & 7, xcd = bid & 7, j = bid >> 3;
-        bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + j;
-    }
+    const int bid = xcd_remap(blockIdx.x, gridDim.x);
     const int nt = bid % ntiles, j0 = bid / ntiles;
     const int n0 = nt * BN;
     const int nk = p.Kpad / BK;
@@ -79,7 +62,7 @@ __global__ __launch_bounds__((WGM * WGN + NL) * 64) void conv_dma_lc_kernel(cons
                 if (q >= A_INSTR) continue;
                 const int s = q * 64 + lane;
                 const int row = s / CPR, pc = s - row * CPR;
-                const int c = pc ^ swz_l<BK>(row);
+                const int c = pc ^ cswz<BK>(row);
                 const int m = mt * BM + row;
                 unsigned mask = 0, base = 0;
                 if (mt < mtiles && m < p.M) {
@@ -112,7 +95,7 @@ __global__ __launch_bounds__((WGM * WGN + NL) * 64) void conv_dma_lc_kernel(cons
             if (q >= A_INSTR && q < PIECES) {
                 const int s = (q - A_INSTR) * 64 + lane;
                 const int row = s / CPR, pc = s - row * CPR;
-                const int c = pc ^ swz_l<BK>(row);
+                const int c = pc ^ cswz<BK>(row);
                 pconst[j] = (unsigned)(((n0 + row) * p.Kpad + c * 8) * 2);
                 pmask[j] = 0;
             }
@@ -155,8 +138,8 @@ __global__ __launch_bounds__((WGM * WGN + NL) * 64) void conv_dma_lc_kernel(cons
 #define LC_STAMP(i) if (p.clk) { const unsigned long long now = __builtin_amdgcn_s_memtime(); clk[i] += now - last; last = now; }
         for (int tile = j0; tile < mtiles; tile += G) {
             for (int kt = 0; kt < nk; ++kt) {
-                if (lw < FULL) wait_vml<(NS - 2) * MAXP>();   // this wave's pieces of stage g have landed
-                else wait_vml<(NS - 2) * (MAXP - 1)>();
+                if (lw < FULL) wait_vmcnt<(NS - 2) * MAXP>();   // this wave's pieces of stage g have landed
+                else wait_vmcnt<(NS - 2) * (MAXP - 1)>();
                 LC_STAMP(0)
                 __builtin_amdgcn_s_barrier();          // barrier(g): stage g is published, slot of stage g-1 is free
                 LC_STAMP(1)
@@ -164,7 +147,7 @@ __global__ __launch_bounds__((WGM * WGN + NL) * 64) void conv_dma_lc_kernel(cons
                 LC_STAMP(2)
             }
         }
-        wait_vml<0>();
+        wait_vmcnt<0>();
         if (p.clk && lane == 0)
             for (int i = 0; i < 3; ++i) p.clk[((size_t)blockIdx.x * (NC + NL) + wave) * 3 + i] = clk[i];
         return;
@@ -185,8 +168,8 @@ __global__ __launch_bounds__((WGM * WGN + NL) * 64) void conv_dma_lc_kernel(cons
 #pragma unroll
     for (int ss = 0; ss < KSUB; ++ss) {
         const int ra = wm * WM + fr, rw = wn * WN + fr;
-        aoff[ss] = ra * RB + (((ss * 4 + fc) ^ swz_l<BK>(ra)) * 16);
-        woff[ss] = BM * RB + rw * RB + (((ss * 4 + fc) ^ swz_l<BK>(rw)) * 16);
+        aoff[ss] = ra * RB + (((ss * 4 + fc) ^ cswz<BK>(ra)) * 16);
+        woff[ss] = BM * RB + rw * RB + (((ss * 4 + fc) ^ cswz<BK>(rw)) * 16);
     }
     f32x4 acc[FN][FM];
     int rslot = 0;
@@ -301,13 +284,9 @@ static hipError_t launch_lc_var(const ConvParams& p, hipStream_t st) {
     if (G < 1) G = 1;
     if (G > mtiles) G = mtiles;
     auto kern = conv_dma_lc_kernel<BM, BN, WGM, WGN, NL, BK, NS, HAS_RES, OUT_F32>;
-    static bool attr = false;
-    if (!attr && sh > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh);
-        if (e != hipSuccess) return e;
-        attr = true;
-    }
-    static const bool clocks = [] { const char* v = std::getenv("YOLOP_LC_CLOCKS"); return v && *v == '1'; }();   // debug: per-phase s_memtime sums
+    static size_t granted = 0;
+    if (hipError_t e = allow_dynamic_lds((const void*)kern, sh, granted)) return e;
+    static const bool clocks = env_on("YOLOP_LC_CLOCKS");   // debug: per-phase s_memtime sums
     if (clocks) {
         constexpr int NWV = WGM * WGN + NL;
         ConvParams q = p;

@@ -19,19 +19,6 @@
 
 namespace yp {
 
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-typedef __attribute__((address_space(3))) void lds_void;
-
-__device__ __forceinline__ float silu_f2(float x) { return x * __builtin_amdgcn_rcpf(1.0f + __expf(-x)); }
-template <int N> __device__ __forceinline__ void wait_vmp() {
-    static_assert(N >= 0 && N < 64, "vmcnt range");
-    __builtin_amdgcn_s_waitcnt((N & 0xF) | (7 << 4) | (0xF << 8) | (((N >> 4) & 3) << 14));
-}
-template <int BK> __device__ __forceinline__ int swz_p(int row) {
-    return BK == 32 ? (((row >> 2) & 1) << 1) : ((row >> 1) & 7);
-}
-
 template <int BM, int BN, int WGM, int WGN, int BK, int NS, bool HAS_RES, bool OUT_F32, bool WRES, bool PIPE, bool PP>
 __global__ __launch_bounds__(WGM * WGN * 64) void conv_dma_p_kernel(const ConvParams p, const int mtiles, const int ntiles, const int G) {
     constexpr int NW = WGM * WGN;
@@ -58,6 +45,8 @@ __global__ __launch_bounds__(WGM * WGN * 64) void conv_dma_p_kernel(const ConvPa
     const int wm = wave % WGM, wn = wave / WGM;
     const int fr = lane & 15, fc = lane >> 4;
 
+    // xcd_remap(blockIdx.x, gridDim.x), written out: through the helper `bid >> 3` ends up behind the select and this kernel's scalar
+    // register allocation changes (kernel_util.h)
     int bid = blockIdx.x;
     {
         const int nwg = gridDim.x, q = nwg >> 3, r = nwg & 7, xcd = bid & 7, j = bid >> 3;
@@ -89,7 +78,7 @@ __global__ __launch_bounds__(WGM * WGN * 64) void conv_dma_p_kernel(const ConvPa
             const int s = ii * 64 + lane;
             const int rowg = s / CPR, pc = s - rowg * CPR;
             const int kt = rowg / BN, n = rowg - kt * BN;
-            const int c = pc ^ swz_p<BK>(n);
+            const int c = pc ^ cswz<BK>(n);
             const unsigned voff = (unsigned)(((n0 + n) * p.Kpad + kt * BK + c * 8) * 2);
             __builtin_amdgcn_raw_ptr_buffer_load_lds(wrs, (lds_void*)(Wres + ii * 1024), 16, voff, 0, 0, 0);
         }
@@ -102,7 +91,7 @@ __global__ __launch_bounds__(WGM * WGN * 64) void conv_dma_p_kernel(const ConvPa
         for (int j = 0; j < A_IPW; ++j) {
             const int s = (wave * A_IPW + j) * 64 + lane;
             const int row = s / CPR, pc = s - row * CPR;
-            const int c = pc ^ swz_p<BK>(row);
+            const int c = pc ^ cswz<BK>(row);
             const int m = mt * BM + row;
             unsigned mask = 0, base = 0;
             if (mt < mtiles && m < p.M && p.dbg != 2) {
@@ -135,7 +124,7 @@ __global__ __launch_bounds__(WGM * WGN * 64) void conv_dma_p_kernel(const ConvPa
         const int ii = wave * W_IPW + j;
         const int s = ii * 64 + lane;
         const int row = s / CPR, pc = s - row * CPR;
-        const int c = pc ^ swz_p<BK>(row);
+        const int c = pc ^ cswz<BK>(row);
         wconst[j] = (ii < W_INSTR) ? (unsigned)(((n0 + row) * p.Kpad + c * 8) * 2) : OOB;
     }
     const int nk = p.Kpad / BK;
@@ -180,14 +169,14 @@ __global__ __launch_bounds__(WGM * WGN * 64) void conv_dma_p_kernel(const ConvPa
 #pragma unroll
     for (int ss = 0; ss < KSUB; ++ss) {
         const int ra = wm * WM + fr, rw = wn * WN + fr;
-        aoff[ss] = ra * RB + (((ss * 4 + fc) ^ swz_p<BK>(ra)) * 16);
-        woff[ss] = (WRES ? 0 : BM * RB) + rw * RB + (((ss * 4 + fc) ^ swz_p<BK>(rw)) * 16);
+        aoff[ss] = ra * RB + (((ss * 4 + fc) ^ cswz<BK>(ra)) * 16);
+        woff[ss] = (WRES ? 0 : BM * RB) + rw * RB + (((ss * 4 + fc) ^ cswz<BK>(rw)) * 16);
     }
 
 #pragma unroll
     for (int s = 0; s < NS - 1; ++s) issue_next();
     if (WRES) {                           // one-time drain: resident weights (and the first stages) have landed
-        wait_vmp<0>();
+        wait_vmcnt<0>();
         __builtin_amdgcn_s_barrier();
     }
 
@@ -266,7 +255,7 @@ __global__ __launch_bounds__(WGM * WGN * 64) void conv_dma_p_kernel(const ConvPa
         static_assert(NW == 8 && !PIPE, "ping-pong pairs the two waves of each SIMD");
         static_assert((NS - 2) * LPW + (NS - 1) * S < 64, "vmcnt immediate");
         if (!WRES) {
-            wait_vmp<(NS - 2) * LPW>();           // stage 0 landed
+            wait_vmcnt<(NS - 2) * LPW>();           // stage 0 landed
             __builtin_amdgcn_s_barrier();
         }
         auto mfma_all = [&]() {
@@ -279,10 +268,10 @@ __global__ __launch_bounds__(WGM * WGN * 64) void conv_dma_p_kernel(const ConvPa
                         acc[a][b] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(cw[ss][a], cx[ss][b], acc[a][b], 0, 0, 0);
         };
         auto wait_stage = [&](int k) {
-            if (k == 0) wait_vmp<(NS - 2) * LPW>();
-            else if (k == 1) wait_vmp<(NS - 2) * LPW + S>();
-            else if (k == 2) wait_vmp<(NS - 2) * LPW + 2 * S>();
-            else wait_vmp<(NS - 2) * LPW + (NS >= 4 ? 3 : 2) * S>();
+            if (k == 0) wait_vmcnt<(NS - 2) * LPW>();
+            else if (k == 1) wait_vmcnt<(NS - 2) * LPW + S>();
+            else if (k == 2) wait_vmcnt<(NS - 2) * LPW + 2 * S>();
+            else wait_vmcnt<(NS - 2) * LPW + (NS >= 4 ? 3 : 2) * S>();
         };
         reset_acc();
         if (wave < NW / 2) {
@@ -334,13 +323,13 @@ __global__ __launch_bounds__(WGM * WGN * 64) void conv_dma_p_kernel(const ConvPa
                 store_tile(prev_tile);
             }
         }
-        wait_vmp<0>();
+        wait_vmcnt<0>();
         return;
     }
 
     if (PIPE) {
         if (!WRES) {
-            wait_vmp<(NS - 2) * LPW>();           // stage 0 landed
+            wait_vmcnt<(NS - 2) * LPW>();           // stage 0 landed
             __builtin_amdgcn_s_barrier();
         }
         load_frags(0, 0, cw, cx);
@@ -352,9 +341,9 @@ __global__ __launch_bounds__(WGM * WGN * 64) void conv_dma_p_kernel(const ConvPa
             for (int kt = 0; kt < nk; ++kt) {
                 {
                     const int k = __builtin_popcount(epmask & ((1u << (NS - 2)) - 1u));
-                    if (k == 0) wait_vmp<(NS - 3) * LPW>();
-                    else if (k == 1) wait_vmp<(NS - 3) * LPW + S>();
-                    else wait_vmp<(NS - 3) * LPW + 2 * S>();
+                    if (k == 0) wait_vmcnt<(NS - 3) * LPW>();
+                    else if (k == 1) wait_vmcnt<(NS - 3) * LPW + S>();
+                    else wait_vmcnt<(NS - 3) * LPW + 2 * S>();
                 }
                 __builtin_amdgcn_s_barrier();
                 issue_next();
@@ -381,10 +370,10 @@ __global__ __launch_bounds__(WGM * WGN * 64) void conv_dma_p_kernel(const ConvPa
         for (int kt = 0; kt < nk; ++kt) {
             {
                 const int k = __builtin_popcount(epmask & ((1u << (NS - 1)) - 1u));
-                if (k == 0) wait_vmp<(NS - 2) * LPW>();
-                else if (k == 1) wait_vmp<(NS - 2) * LPW + S>();
-                else if (k == 2) wait_vmp<(NS - 2) * LPW + 2 * S>();
-                else wait_vmp<(NS - 2) * LPW + (NS >= 4 ? 3 : 2) * S>();
+                if (k == 0) wait_vmcnt<(NS - 2) * LPW>();
+                else if (k == 1) wait_vmcnt<(NS - 2) * LPW + S>();
+                else if (k == 2) wait_vmcnt<(NS - 2) * LPW + 2 * S>();
+                else wait_vmcnt<(NS - 2) * LPW + (NS >= 4 ? 3 : 2) * S>();
             }
             __builtin_amdgcn_s_barrier();
             issue_next();
@@ -410,7 +399,7 @@ __global__ __launch_bounds__(WGM * WGN * 64) void conv_dma_p_kernel(const ConvPa
         store_tile(tile);
         epmask |= 1u;
     }
-    wait_vmp<0>();
+    wait_vmcnt<0>();
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -495,12 +484,8 @@ static hipError_t launch_p_var(const ConvParams& p, hipStream_t st) {
     if (G < 1) G = 1;
     if (G > mtiles) G = mtiles;
     auto kern = conv_dma_p_kernel<BM, BN, WGM, WGN, BK, NS, HAS_RES, OUT_F32, WRES, PIPE, PP>;
-    static bool attr = false;
-    if (!attr && (WRES || sh > 64 * 1024)) {
-        hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(WRES ? 160 * 1024 : sh));
-        if (e != hipSuccess) return e;
-        attr = true;
-    }
+    static size_t granted = 0;
+    if (hipError_t e = allow_dynamic_lds((const void*)kern, sh, granted)) return e;
     hipLaunchKernelGGL(kern, dim3(G * ntiles), dim3(WGM * WGN * 64), sh, st, p, mtiles, ntiles, G);
     return hipGetLastError();
 }

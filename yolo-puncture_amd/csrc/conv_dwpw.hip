@@ -18,27 +18,6 @@
 
 namespace yp {
 
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-typedef __attribute__((address_space(3))) void lds_void;
-
-__device__ __forceinline__ float silu_q(float x) { return x * __builtin_amdgcn_rcpf(1.0f + __expf(-x)); }
-template <int N> __device__ __forceinline__ void wait_vmq() {
-    static_assert(N >= 0 && N < 64, "vmcnt range");
-    __builtin_amdgcn_s_waitcnt((N & 0xF) | (7 << 4) | (0xF << 8) | (((N >> 4) & 3) << 14));
-}
-// LDS accesses behind the compiler's back: it cannot tell them from the in-flight LDS-DMA of the next chunk apart and drains
-// vmcnt to 0 in front of them (= no prefetch at all). The caller orders them with explicit lgkmcnt waits.
-__device__ __forceinline__ f32x4 lds_read16_async(const unsigned char* src) {
-    f32x4 v;
-    asm volatile("ds_read_b128 %0, %1" : "=v"(v) : "v"((unsigned)(size_t)(const __attribute__((address_space(3))) unsigned char*)src) : "memory");
-    return v;
-}
-__device__ __forceinline__ void lds_write8(unsigned char* dst, uint2 v) {
-    asm volatile("ds_write_b64 %0, %1" ::"v"((unsigned)(size_t)(__attribute__((address_space(3))) unsigned char*)dst), "v"(*(const unsigned long long*)&v) : "memory");
-}
-__device__ __forceinline__ int qswz(int row) { return ((row >> 2) & 1) << 1; }
-
 // TH x 16 output pixels, BN output channels; NW waves as 2(m) x NW/2(n). NW = 8 puts two waves on every SIMD so that one
 // wave's VALU work (fragment build, SiLU) overlaps the other's MFMAs with a single set of resident weights per CU.
 template <int TH, int BN, bool OUT_F32, int NW, bool TAIL = false>
@@ -79,11 +58,7 @@ __global__ __launch_bounds__(NW * 64) void conv_dwpw_kernel(const DwPwParams p, 
     const int wm = wave % WGM, wn = wave / WGM;
     const int fr = lane & 15, fc = lane >> 4;
 
-    int bid = blockIdx.x;
-    {
-        const int nwg = gridDim.x, q = nwg >> 3, r = nwg & 7, xcd = bid & 7, j = bid >> 3;
-        bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + j;
-    }
+    const int bid = xcd_remap(blockIdx.x, gridDim.x);
     const int nt = bid % ntiles, j0 = bid / ntiles;
     const int n0 = nt * BN;
     const int num_tiles = p.B * tiles_h * tiles_w;
@@ -109,7 +84,7 @@ __global__ __launch_bounds__(NW * 64) void conv_dwpw_kernel(const DwPwParams p, 
             const int s = ii * 64 + lane;
             const int rg = s >> 2, pc = s & 3;
             const int ch = rg / BN, n = rg - ch * BN;
-            const int c8 = pc ^ qswz(rg);
+            const int c8 = pc ^ cswz64(rg);
             const unsigned voff = (unsigned)(((n0 + n) * p.Kpad + ch * 32 + c8 * 8) * 2);
             __builtin_amdgcn_raw_ptr_buffer_load_lds(wrs, (lds_void*)(Wpw + ii * 1024), 16, voff, 0, 0, 0);
         }
@@ -132,7 +107,7 @@ __global__ __launch_bounds__(NW * 64) void conv_dwpw_kernel(const DwPwParams p, 
                 const int s = ii * 64 + lane;
                 const int rg = s >> 2, pc = s & 3;
                 const int ch = rg / C3R, n = rg - ch * C3R;
-                const int c8 = pc ^ qswz(rg);
+                const int c8 = pc ^ cswz64(rg);
                 const unsigned voff = (unsigned)((n * p.Kpad3 + ch * 32 + c8 * 8) * 2);
                 __builtin_amdgcn_raw_ptr_buffer_load_lds(w3rs, (lds_void*)(W3s + ii * 1024), 16, voff, 0, 0, 0);
             }
@@ -156,7 +131,7 @@ __global__ __launch_bounds__(NW * 64) void conv_dwpw_kernel(const DwPwParams p, 
             const int ii = wave * LH + j;
             const int s = ii * 64 + lane;
             const int hp = s >> 2, pc = s & 3;
-            const int c8 = pc ^ qswz(hp);
+            const int c8 = pc ^ cswz64(hp);
             const int hy = hp / 18, hx = hp - hy * 18;
             const int hi = h0 - 1 + hy, wi = w0 - 1 + hx;
             const bool ok = (tile < num_tiles) && (ii < H_INSTR) && (hp < HP) && ((unsigned)hi < (unsigned)p.H) && ((unsigned)wi < (unsigned)p.W);
@@ -183,7 +158,7 @@ __global__ __launch_bounds__(NW * 64) void conv_dwpw_kernel(const DwPwParams p, 
     };
 #pragma unroll
     for (int s = 0; s < NSH - 1; ++s) issue_next();
-    wait_vmq<0>();
+    wait_vmcnt<0>();
     __builtin_amdgcn_s_barrier();
 
     // Depthwise stage of one chunk ON THE MATRIX CORES: out[ch][px] = sum_taps w[tap][ch] * x[ch][px + tap] as MFMAs whose A operand is
@@ -246,7 +221,7 @@ __global__ __launch_bounds__(NW * 64) void conv_dwpw_kernel(const DwPwParams p, 
 #pragma unroll
                 for (int i = 0; i < 4; ++i) o[i] = (__bf16)sv[i];
                 const int c8 = 2 * h + (fc >> 1);
-                lds_write8(asl + px * 64 + ((c8 ^ qswz(px)) * 16) + (fc & 1) * 8, *(const uint2*)o);
+                lds_write8(asl + px * 64 + ((c8 ^ cswz64(px)) * 16) + (fc & 1) * 8, *(const uint2*)o);
             }
         }
     };
@@ -300,7 +275,7 @@ __global__ __launch_bounds__(NW * 64) void conv_dwpw_kernel(const DwPwParams p, 
                     const int px = (wm * (WM / 16) + bb) * 16 + fr;
                     const int cch = wn * WN + a * 16 + fc * 4;               // channel inside the BN block
                     const int c8 = (cch >> 3) & 3;
-                    lds_write8(Ts + (size_t)(cch >> 5) * BM * 64 + px * 64 + ((c8 ^ qswz(px)) * 16) + (fc & 1) * 8, *(const uint2*)o);
+                    lds_write8(Ts + (size_t)(cch >> 5) * BM * 64 + px * 64 + ((c8 ^ cswz64(px)) * 16) + (fc & 1) * 8, *(const uint2*)o);
                 } else if (OUT_F32) {
                     const unsigned off = ok ? (m * (unsigned)p.y_stride + (unsigned)(p.y_coff + co)) * 4u : OOB;
                     __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(__attribute__((ext_vector_type(4))) unsigned, make_float4(v[0], v[1], v[2], v[3])), yrs, off, 0, 0);
@@ -376,9 +351,9 @@ __global__ __launch_bounds__(NW * 64) void conv_dwpw_kernel(const DwPwParams p, 
         for (int c = 0; c < nchunk; ++c, ++g) {
             if (!first) {
                 const int k = __builtin_popcount(epmask & 3u);
-                if (k == 0) wait_vmq<LH>();
-                else if (k == 1) wait_vmq<LH + SS>();
-                else wait_vmq<LH + 2 * SS>();
+                if (k == 0) wait_vmcnt<LH>();
+                else if (k == 1) wait_vmcnt<LH + SS>();
+                else wait_vmcnt<LH + 2 * SS>();
                 asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");        // this wave's A-tile (and TAIL: T-tile) writes of the previous phase are done
                 __builtin_amdgcn_s_barrier();
             }
@@ -421,7 +396,7 @@ __global__ __launch_bounds__(NW * 64) void conv_dwpw_kernel(const DwPwParams p, 
             gemm3(prev_tile);
         }
     }
-    wait_vmq<0>();
+    wait_vmcnt<0>();
     if (p.clk && lane == 0)
         for (int i = 0; i < 4; ++i) p.clk[((size_t)blockIdx.x * NW + wave) * 4 + i] = clk[i];
 }
@@ -484,13 +459,9 @@ static hipError_t launch_dwpw_t(const DwPwParams& p, hipStream_t st) {
     if (G < 1) G = 1;
     if (G > num_tiles) G = num_tiles;
     auto kern = conv_dwpw_kernel<TH, BN, OUT_F32, NW, TAIL>;
-    static bool attr = false;
-    if (!attr) {
-        hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(160 * 1024));
-        if (e != hipSuccess) return e;
-        attr = true;
-    }
-    static const bool clocks = [] { const char* v = std::getenv("YOLOP_DWPW_CLOCKS"); return v && *v == '1'; }();   // debug: per-phase s_memtime sums
+    static size_t granted = 0;
+    if (hipError_t e = allow_dynamic_lds((const void*)kern, sh, granted)) return e;
+    static const bool clocks = env_on("YOLOP_DWPW_CLOCKS");   // debug: per-phase s_memtime sums
     if (clocks) {
         DwPwParams q = p;
         const size_t n = (size_t)G * ntiles * NW * 4;

@@ -18,23 +18,12 @@
 
 namespace yp {
 
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-typedef __attribute__((ext_vector_type(2))) float f32x2;
-typedef __attribute__((address_space(3))) void lds_void;
-
 constexpr int DS_TH = 8, DS_TW = 16;                 // output tile (one row per wave, one MFMA pixel fragment per row)
 constexpr int DS_C = 128;                            // input channels = 64 pairs = one per lane
 constexpr int DS_HP = (DS_TH + 2) * (DS_TW + 2);     // 180 halo pixels
 constexpr int DS_PIECES = 48;                        // 1-KiB pieces of a halo slot, 6 per wave (45 in use: 4 pixels of 256 B each)
 constexpr int DS_HB = DS_PIECES * 1024;
 constexpr int DS_AB = DS_TH * DS_TW * 256;           // pixel-operand tile [128 px][128 ch] bf16
-
-template <int N> __device__ __forceinline__ void ds_wait_vm() {
-    static_assert(N >= 0 && N < 64, "vmcnt range");
-    __builtin_amdgcn_s_waitcnt((N & 0xF) | (7 << 4) | (0xF << 8) | (((N >> 4) & 3) << 14));
-}
-__device__ __forceinline__ unsigned ds_lds_addr(const void* p) { return (unsigned)(size_t)(const __attribute__((address_space(3))) unsigned char*)p; }
 
 // NW = 8: one workgroup per CU, two halo slots (the next tile's rows fly under this tile's stages). NW = 4: TWO co-resident workgroups of
 // four waves with ONE halo slot each (80 KB): a wave takes two output rows and 32 output channels; the rows of the next tile are issued
@@ -110,7 +99,7 @@ __global__ __launch_bounds__(NW * 64, 2) void conv_dwpw_stream_kernel(const DwPw
         for (int r = 0; r < 4; ++r) { const int co = (wave * NFW + i) * 16 + fc * 4 + r; bpw[i][r] = (co < p.Cout) ? p.b_pw[co] : 0.f; }
     }
     // (known complete before the loop, then passed through empty asm statements: see conv_wres.hip)
-    ds_wait_vm<0>();
+    wait_vmcnt<0>();
 #pragma unroll
     for (int t = 0; t < 9; ++t) asm volatile("" : "+v"(wd[t]));
     asm volatile("" : "+v"(bd));
@@ -122,11 +111,11 @@ __global__ __launch_bounds__(NW * 64, 2) void conv_dwpw_stream_kernel(const DwPw
         for (int r = 0; r < 4; ++r) asm volatile("" : "+v"(bpw[i][r]));
     }
 
-    const unsigned as_l = ds_lds_addr(As);
+    const unsigned as_l = lds_addr(As);
     for (int it = 0; tile < num_tiles; tile += G, ++it) {
         // (a) this tile's rows have landed (issued in front of the previous tile's stores, which may still fly)
-        if (it == 0) ds_wait_vm<0>();
-        else ds_wait_vm<NST>();
+        if (it == 0) wait_vmcnt<0>();
+        else wait_vmcnt<NST>();
         __builtin_amdgcn_s_barrier();
         const int slot = NSLOT == 2 ? (it & 1) : 0;
         if (NSLOT == 2) issue_tile(tile + G, slot ^ 1);
@@ -205,11 +194,11 @@ __global__ __launch_bounds__(NW * 64, 2) void conv_dwpw_stream_kernel(const DwPw
             }
         }
     }
-    ds_wait_vm<0>();
+    wait_vmcnt<0>();
 }
 
 bool dwpw_stream_valid(const DwPwParams& p) {
-    static const bool off = [] { const char* v = std::getenv("YOLOP_NO_DWPW_STREAM"); return v && *v == '1'; }();   // A/B switch
+    static const bool off = env_on("YOLOP_NO_DWPW_STREAM");   // A/B switch
     if (off || p.w3 || p.out_f32 || p.clk) return false;
     if (p.C != DS_C || p.Kpad != DS_C || p.Cout != 128) return false;      // (the class branch of the 128-wide heads: v10-S; other widths keep the chunked kernel)
     if ((p.x_stride & 7) || (p.x_coff & 7) || (p.y_stride & 3) || (p.y_coff & 3)) return false;
@@ -224,12 +213,8 @@ template <int NW>
 static hipError_t launch_dwpw_stream_t(const DwPwParams& p, hipStream_t st) {
     const size_t sh = (size_t)(NW == 8 ? 2 : 1) * DS_HB + DS_AB;
     auto kern = conv_dwpw_stream_kernel<NW>;
-    static bool attr = false;
-    if (!attr) {
-        hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e != hipSuccess) return e;
-        attr = true;
-    }
+    static size_t granted = 0;
+    if (hipError_t e = allow_dynamic_lds((const void*)kern, sh, granted)) return e;
     const int tiles_h = (p.H + DS_TH - 1) / DS_TH, tiles_w = (p.W + DS_TW - 1) / DS_TW;
     const int num_tiles = p.B * tiles_h * tiles_w;
     const int gmax = NW == 8 ? 256 : 512;
@@ -240,7 +225,7 @@ static hipError_t launch_dwpw_stream_t(const DwPwParams& p, hipStream_t st) {
 
 hipError_t launch_dwpw_stream(const DwPwParams& p, hipStream_t st) {
     if (!dwpw_stream_valid(p)) return hipErrorInvalidValue;
-    static const bool one = [] { const char* v = std::getenv("YOLOP_DWPW_STREAM_ONE"); return v && *v == '1'; }();   // A/B switch: one workgroup per CU
+    static const bool one = env_on("YOLOP_DWPW_STREAM_ONE");   // A/B switch: one workgroup per CU
     return one ? launch_dwpw_stream_t<8>(p, st) : launch_dwpw_stream_t<4>(p, st);
 }
 

@@ -23,17 +23,6 @@
 
 namespace yp {
 
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-typedef __attribute__((address_space(3))) void lds_void;
-
-__device__ __forceinline__ float silu3(float x) { return x / (1.0f + __expf(-x)); }
-template <int N> __device__ __forceinline__ void wait_vm() {
-    static_assert(N >= 0 && N < 64, "vmcnt range");
-    __builtin_amdgcn_s_waitcnt((N & 0xF) | (7 << 4) | (0xF << 8) | (((N >> 4) & 3) << 14));
-}
-__device__ __forceinline__ int hswz(int row) { return ((row >> 2) & 1) << 1; }   // 64-B rows, any 16 consecutive rows conflict-free
-
 template <int FM, int FN, int WGM, int WGN>
 __global__ __launch_bounds__(WGM * WGN * 64) void conv_halo_kernel(const ConvParams p, const int tiles_h, const int tiles_w,
                                                                   const int ntiles) {
@@ -60,11 +49,7 @@ __global__ __launch_bounds__(WGM * WGN * 64) void conv_halo_kernel(const ConvPar
     const int wm = wave % WGM, wn = wave / WGM;
     const int fr = lane & 15, fc = lane >> 4;
 
-    int bid = blockIdx.x;
-    {
-        const int nwg = gridDim.x, q = nwg >> 3, r = nwg & 7, xcd = bid & 7, j = bid >> 3;
-        bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + j;
-    }
+    const int bid = xcd_remap(blockIdx.x, gridDim.x);
     const int nt = bid % ntiles;
     int t = bid / ntiles;
     const int tw = t % tiles_w; t /= tiles_w;
@@ -82,7 +67,7 @@ __global__ __launch_bounds__(WGM * WGN * 64) void conv_halo_kernel(const ConvPar
         const int ii = wave * LH + j;
         const int s = ii * 64 + lane;
         const int hp = s >> 2, pc = s & 3;
-        const int c = pc ^ hswz(hp);
+        const int c = pc ^ cswz64(hp);
         const int hy = hp / 18, hx = hp - hy * 18;
         const int hi = h0 - 1 + hy, wi = w0 - 1 + hx;
         const bool ok = (ii < H_INSTR) && (hp < HP) && ((unsigned)hi < (unsigned)p.H) && ((unsigned)wi < (unsigned)p.W);
@@ -95,7 +80,7 @@ __global__ __launch_bounds__(WGM * WGN * 64) void conv_halo_kernel(const ConvPar
         const int ii = wave * LW + j;
         const int s = ii * 64 + lane;
         const int rw = s >> 2, pc = s & 3;
-        const int c = pc ^ hswz(rw);
+        const int c = pc ^ cswz64(rw);
         const int ky = rw / BN, n = rw - ky * BN;
         wconst[j] = (ii < W_INSTR) ? (unsigned)(((n0 + n) * p.Kpad + ky * 3 * p.Cin + c * 8) * 2) : OOB;
     }
@@ -162,23 +147,23 @@ __global__ __launch_bounds__(WGM * WGN * 64) void conv_halo_kernel(const ConvPar
     issue_w(0, 1);
     issue_w(0, 2);
     for (int c = 0; c < nchunk; ++c) {
-        wait_vm<2 * LW>();
+        wait_vmcnt<2 * LW>();
         __builtin_amdgcn_s_barrier();
         issue_w(c + 1, 0);
         issue_halo(c + 1);
         compute(c, 0);
 
-        wait_vm<2 * LW + LH>();
+        wait_vmcnt<2 * LW + LH>();
         __builtin_amdgcn_s_barrier();
         issue_w(c + 1, 1);
         compute(c, 1);
 
-        wait_vm<2 * LW + LH>();
+        wait_vmcnt<2 * LW + LH>();
         __builtin_amdgcn_s_barrier();
         issue_w(c + 1, 2);
         compute(c, 2);
     }
-    wait_vm<0>();
+    wait_vmcnt<0>();
 
     // ---- epilogue ------------------------------------------------------------------------------------------------
     const bool vec_ok = ((p.Cout & 3) == 0) && ((p.y_stride & 3) == 0) && ((p.y_coff & 3) == 0) &&
@@ -204,7 +189,7 @@ __global__ __launch_bounds__(WGM * WGN * 64) void conv_halo_kernel(const ConvPar
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
                 float tt = acc[a][r][i] + bias[a][i];
-                if (p.act == ACT_SILU) tt = silu3(tt);
+                if (p.act == ACT_SILU) tt = silu_fdiv(tt);
                 v[i] = tt;
             }
             if (p.res) {
@@ -278,12 +263,8 @@ static hipError_t launch_halo_one(const ConvParams& p, hipStream_t st) {
     const int B = p.M / (p.Ho * p.Wo);
     const int tiles_h = (p.Ho + TH - 1) / TH, tiles_w = (p.Wo + 15) / 16, ntiles = (p.Cout + BN - 1) / BN;
     auto kern = conv_halo_kernel<FM, FN, WGM, WGN>;
-    static bool attr = false;
-    if (!attr && sh > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh);
-        if (e != hipSuccess) return e;
-        attr = true;
-    }
+    static size_t granted = 0;
+    if (hipError_t e = allow_dynamic_lds((const void*)kern, sh, granted)) return e;
     hipLaunchKernelGGL(kern, dim3(B * tiles_h * tiles_w * ntiles), dim3(WGM * WGN * 64), sh, st, p, tiles_h, tiles_w, ntiles);
     return hipGetLastError();
 }

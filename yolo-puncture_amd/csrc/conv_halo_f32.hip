@@ -16,24 +16,7 @@
 
 namespace yp {
 
-typedef __attribute__((ext_vector_type(4))) float hf_f32x4;
-typedef __attribute__((address_space(3))) void hf_lds_void;
-
 constexpr int HF_TH = 8, HF_TW = 32;
-
-// LDS reads behind the compiler's back: it cannot tell them from the in-flight LDS-DMA of the next chunk apart and would drain vmcnt to 0
-// in front of the first one (= no prefetch at all). Ordered by explicit lgkmcnt waits below.
-__device__ __forceinline__ float4 hf_read16(const unsigned char* src) {
-    float4 v;
-    asm volatile("ds_read_b128 %0, %1" : "=v"(v) : "v"((unsigned)(size_t)(const __attribute__((address_space(3))) unsigned char*)src) : "memory");
-    return v;
-}
-
-__device__ __forceinline__ float hf_act(float v, int act) {
-    if (act == ACT_RELU) return fmaxf(v, 0.f);
-    if (act == ACT_SILU) return v / (1.0f + __expf(-v));
-    return v;
-}
 
 // LDS per buffer: X patch (PP pixels rounded up to 16, 64 B each) then W (9 * FN * 16 rows of 64 B)
 // Two LDS buffers (chunk c + 1 lands under the MFMAs of chunk c). With 64 output channels that is 116 KB = one workgroup per CU; a
@@ -69,22 +52,22 @@ __global__ __launch_bounds__(256) void conv_halo_f32_kernel(const ConvParams p, 
             const int hi = y0 - d + hy, wi = x0 - d + hx;
             const bool ok = hy < HF_TH + 2 * d && (unsigned)hi < (unsigned)p.H && (unsigned)wi < (unsigned)p.W;
             const unsigned voff = ok ? (unsigned)((((size_t)(b * p.H + hi) * p.W + wi) * p.x_stride + p.x_coff + cc * 16 + c * 4) * 4) : OOB;
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(xrs, (hf_lds_void*)(Xs + ii * 1024), 16, voff, 0, 0, 0);
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(xrs, (lds_void*)(Xs + ii * 1024), 16, voff, 0, 0, 0);
         }
         for (int ii = wave; ii < WINSTR; ii += 4) {                // 16 weight rows (tap, co) x 64 B
             const int row = ii * 16 + (lane >> 2);                 // = tap * (FN * 16) + co
             const int c = (lane & 3) ^ ((row >> 2) & 3);
             const int tap = row / (FN * 16), co = row - tap * (FN * 16);
             const unsigned voff = (unsigned)(((size_t)co * p.Kpad + tap * p.Cin + cc * 16 + c * 4) * 4);
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(wrs, (hf_lds_void*)(Ws + ii * 1024), 16, voff, 0, 0, 0);
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(wrs, (lds_void*)(Ws + ii * 1024), 16, voff, 0, 0, 0);
         }
     };
 
-    hf_f32x4 acc[FN][4];
+    f32x4 acc[FN][4];
 #pragma unroll
     for (int a = 0; a < FN; ++a)
 #pragma unroll
-        for (int q = 0; q < 4; ++q) acc[a][q] = hf_f32x4{0.f, 0.f, 0.f, 0.f};
+        for (int q = 0; q < 4; ++q) acc[a][q] = f32x4{0.f, 0.f, 0.f, 0.f};
 
     // this wave's four pixel fragments: tile rows 2 * wave and 2 * wave + 1, columns 0..15 / 16..31; patch pixel of (row, col) at tap
     // (ky, kx) = (row + ky * d) * PW + col + kx * d
@@ -107,12 +90,12 @@ __global__ __launch_bounds__(256) void conv_halo_f32_kernel(const ConvParams p, 
 #pragma unroll
             for (int a = 0; a < FN; ++a) {
                 const int row = tap * (FN * 16) + a * 16 + fr;
-                wv[set][a] = hf_read16(Ws + row * 64 + ((g ^ ((row >> 2) & 3)) * 16));
+                wv[set][a] = lds_read16_async<float4>(Ws + row * 64 + ((g ^ ((row >> 2) & 3)) * 16));
             }
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
                 const int hp = pbase[q] + (ky * PW + kx) * d;
-                xv[set][q] = hf_read16(Xs + hp * 64 + ((g ^ ((hp >> 2) & 3)) * 16));
+                xv[set][q] = lds_read16_async<float4>(Xs + hp * 64 + ((g ^ ((hp >> 2) & 3)) * 16));
             }
         };
         if (p.dbg == 3) continue;                                  // (timing ablation: no fragment reads, no MFMAs)
@@ -151,10 +134,10 @@ __global__ __launch_bounds__(256) void conv_halo_f32_kernel(const ConvParams p, 
             for (int a = 0; a < FN; ++a) {
                 const int co = a * 16 + 4 * g;
                 float4 v;
-                v.x = hf_act(acc[a][q][0] + (co + 0 < p.Cout ? p.bias[co + 0] : 0.f), p.act);
-                v.y = hf_act(acc[a][q][1] + (co + 1 < p.Cout ? p.bias[co + 1] : 0.f), p.act);
-                v.z = hf_act(acc[a][q][2] + (co + 2 < p.Cout ? p.bias[co + 2] : 0.f), p.act);
-                v.w = hf_act(acc[a][q][3] + (co + 3 < p.Cout ? p.bias[co + 3] : 0.f), p.act);
+                v.x = act_fdiv(acc[a][q][0] + (co + 0 < p.Cout ? p.bias[co + 0] : 0.f), p.act);
+                v.y = act_fdiv(acc[a][q][1] + (co + 1 < p.Cout ? p.bias[co + 1] : 0.f), p.act);
+                v.z = act_fdiv(acc[a][q][2] + (co + 2 < p.Cout ? p.bias[co + 2] : 0.f), p.act);
+                v.w = act_fdiv(acc[a][q][3] + (co + 3 < p.Cout ? p.bias[co + 3] : 0.f), p.act);
                 const int px = q * 16 + fr;
                 *(float4*)(T + (px * CH + ((a * 4 + g) ^ (px & (CH - 1)))) * 16) = v;
             }
@@ -190,7 +173,7 @@ __global__ __launch_bounds__(256) void conv_halo_f32_kernel(const ConvParams p, 
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 if (co + j < p.Cout) {
-                    v[j] = hf_act(v[j] + p.bias[co + j], p.act);
+                    v[j] = act_fdiv(v[j] + p.bias[co + j], p.act);
                     if (rp) v[j] += rp[j];
                 }
             }
@@ -223,7 +206,7 @@ bool conv_halo_f32_valid(const ConvParams& p, int dtype) {
 hipError_t launch_conv_halo_f32(const ConvParams& p_in, int dtype, hipStream_t st) {
     if (!conv_halo_f32_valid(p_in, dtype)) return hipErrorInvalidValue;
     ConvParams p = p_in;
-    static const int dbg = [] { const char* s = getenv("YOLOP_HF_DBG"); return s ? atoi(s) : 0; }();      // 2 / 3: timing ablations (wrong results)
+    static const int dbg = env_int("YOLOP_HF_DBG", 0);      // 2 / 3: timing ablations (wrong results)
     if (dbg) p.dbg = dbg;
     const int d = p.dil > 0 ? p.dil : 1;
     const int fn = p.Cout <= 16 ? 1 : p.Cout <= 32 ? 2 : 4;
@@ -231,14 +214,10 @@ hipError_t launch_conv_halo_f32(const ConvParams& p_in, int dtype, hipStream_t s
     const int B = p.M / (p.Ho * p.Wo);
     const size_t sh = hf_lds(d, fn);
     const dim3 grid((unsigned)(B * tiles_h * tiles_w)), blk(256);
-    static bool attr[3] = {false, false, false};
+    static size_t granted[3] = {0, 0, 0};
     const int ai = fn == 1 ? 0 : fn == 2 ? 1 : 2;
     const void* fptr = fn == 1 ? (const void*)conv_halo_f32_kernel<1> : fn == 2 ? (const void*)conv_halo_f32_kernel<2> : (const void*)conv_halo_f32_kernel<4>;
-    if (!attr[ai]) {
-        hipError_t e = hipFuncSetAttribute(fptr, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e != hipSuccess) return e;
-        attr[ai] = true;
-    }
+    if (hipError_t e = allow_dynamic_lds(fptr, sh, granted[ai])) return e;
     const int xi = hf_xinstr(d);
     if (fn == 1) hipLaunchKernelGGL(conv_halo_f32_kernel<1>, grid, blk, sh, st, p, tiles_w, tiles_h, xi);
     else if (fn == 2) hipLaunchKernelGGL(conv_halo_f32_kernel<2>, grid, blk, sh, st, p, tiles_w, tiles_h, xi);

@@ -17,17 +17,6 @@
 
 namespace yp {
 
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-typedef __attribute__((address_space(3))) void lds_void;
-
-__device__ __forceinline__ float silu_fast(float x) { return x * __builtin_amdgcn_rcpf(1.0f + __expf(-x)); }
-template <int N> __device__ __forceinline__ void wait_vmc() {
-    static_assert(N >= 0 && N < 64, "vmcnt range");
-    __builtin_amdgcn_s_waitcnt((N & 0xF) | (7 << 4) | (0xF << 8) | (((N >> 4) & 3) << 14));
-}
-__device__ __forceinline__ int pswz(int row) { return ((row >> 2) & 1) << 1; }
-
 template <int FM, int FN, int WGM, int WGN, int NSH, bool HAS_RES, bool OUT_F32>
 __global__ __launch_bounds__(WGM * WGN * 64) void conv_halo_p_kernel(const ConvParams p, const int tiles_h, const int tiles_w,
                                                                     const int ntiles, const int G) {
@@ -53,11 +42,7 @@ __global__ __launch_bounds__(WGM * WGN * 64) void conv_halo_p_kernel(const ConvP
     const int fr = lane & 15, fc = lane >> 4;
     const int nchunk = p.Cin >> 5;
 
-    int bid = blockIdx.x;
-    {
-        const int nwg = gridDim.x, q = nwg >> 3, r = nwg & 7, xcd = bid & 7, j = bid >> 3;
-        bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + j;
-    }
+    const int bid = xcd_remap(blockIdx.x, gridDim.x);
     const int nt = bid % ntiles, j0 = bid / ntiles;
     const int n0 = nt * BN;
     const int B = p.M / (p.Ho * p.Wo);
@@ -83,7 +68,7 @@ __global__ __launch_bounds__(WGM * WGN * 64) void conv_halo_p_kernel(const ConvP
         for (int ii = wave; ii < ninstr; ii += NW) {
             const int s = ii * 64 + lane;
             const int rg = s >> 2, pc = s & 3;
-            const int c8 = pc ^ pswz(rg);
+            const int c8 = pc ^ cswz64(rg);
             const int n = rg % BN, q = rg / BN;
             const int tap = q % 9, ch = q / 9;
             const unsigned voff = (unsigned)(((n0 + n) * p.Kpad + tap * p.Cin + ch * 32 + c8 * 8) * 2);
@@ -104,7 +89,7 @@ __global__ __launch_bounds__(WGM * WGN * 64) void conv_halo_p_kernel(const ConvP
             const int ii = wave * LH + j;
             const int s = ii * 64 + lane;
             const int hp = s >> 2, pc = s & 3;
-            const int c8 = pc ^ pswz(hp);
+            const int c8 = pc ^ cswz64(hp);
             const int hy = hp / 18, hx = hp - hy * 18;
             const int hi = h0 - 1 + hy, wi = w0 - 1 + hx;
             const bool ok = (tile < num_tiles) && (ii < H_INSTR) && (hp < HP) && ((unsigned)hi < (unsigned)p.H) && ((unsigned)wi < (unsigned)p.W);
@@ -132,7 +117,7 @@ __global__ __launch_bounds__(WGM * WGN * 64) void conv_halo_p_kernel(const ConvP
 
 #pragma unroll
     for (int s = 0; s < NSH - 1; ++s) issue_next();
-    wait_vmc<0>();                      // weights + first chunks landed (once per workgroup)
+    wait_vmcnt<0>();                      // weights + first chunks landed (once per workgroup)
     __builtin_amdgcn_s_barrier();
 
     int rd_slot = 0;
@@ -148,9 +133,9 @@ __global__ __launch_bounds__(WGM * WGN * 64) void conv_halo_p_kernel(const ConvP
         for (int c = 0; c < nchunk; ++c) {
             if (!first_iter) {
                 const int k = __builtin_popcount(epmask & ((1u << (NSH - 1)) - 1u));
-                if (k == 0) wait_vmc<(NSH - 2) * LH>();
-                else if (k == 1) wait_vmc<(NSH - 2) * LH + S>();
-                else wait_vmc<(NSH - 2) * LH + 2 * S>();
+                if (k == 0) wait_vmcnt<(NSH - 2) * LH>();
+                else if (k == 1) wait_vmcnt<(NSH - 2) * LH + S>();
+                else wait_vmcnt<(NSH - 2) * LH + 2 * S>();
                 __builtin_amdgcn_s_barrier();
             }
             first_iter = false;
@@ -239,7 +224,7 @@ __global__ __launch_bounds__(WGM * WGN * 64) void conv_halo_p_kernel(const ConvP
         }
         epmask |= 1u;
     }
-    wait_vmc<0>();
+    wait_vmcnt<0>();
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -294,12 +279,8 @@ static hipError_t launch_halo_p_var(const ConvParams& p, const HaloPCfg& k, hipS
     if (G < 1) G = 1;
     if (G > num_tiles) G = num_tiles;
     auto kern = conv_halo_p_kernel<FM, FN, WGM, WGN, 3, HAS_RES, OUT_F32>;
-    static size_t attr = 0;
-    if (sh > attr) {
-        hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(160 * 1024));
-        if (e != hipSuccess) return e;
-        attr = 160 * 1024;
-    }
+    static size_t granted = 0;
+    if (hipError_t e = allow_dynamic_lds((const void*)kern, sh, granted)) return e;
     hipLaunchKernelGGL(kern, dim3(G * ntiles), dim3(WGM * WGN * 64), sh, st, p, tiles_h, tiles_w, ntiles, G);
     return hipGetLastError();
 }

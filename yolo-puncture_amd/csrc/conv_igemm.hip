@@ -16,9 +16,6 @@
 
 namespace yp {
 
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-
 template <typename T> struct TT;
 template <> struct TT<__bf16> {
     static constexpr int ES = 2;
@@ -48,10 +45,8 @@ template <> struct TT<float> {
 // derivation in DESIGN.md "conv_igemm LDS image".
 __device__ __forceinline__ int swz(int row, int c) { return c ^ ((4 - ((row >> 2) & 3)) & 3); }
 
-// (fp32 parity mode and the register-staged bf16 fallback: the library expf and an IEEE division - the LDS-DMA kernels of the bf16 hot path
-// have their own packed form, common.h silu4_packed)
-__device__ __forceinline__ float silu(float x) { return x / (1.0f + expf(-x)); }
-
+// (SiLU here is silu_ieee - fp32 parity mode and the register-staged bf16 fallback: the library expf and an IEEE division; the LDS-DMA kernels
+// of the bf16 hot path have their own packed form, silu4_packed)
 template <typename T, int BM, int BN, int WGM, int WGN>
 __global__ __launch_bounds__(256) void conv_igemm_kernel(const ConvParams p) {
     constexpr int ES = TT<T>::ES;
@@ -209,7 +204,7 @@ __global__ __launch_bounds__(256) void conv_igemm_kernel(const ConvParams p) {
             for (int r = 0; r < 4; ++r) {
                 const int c = co + r;
                 float t = acc[a][b][r] + ((c < p.Cout) ? p.bias[c] : 0.f);
-                if (p.act == ACT_SILU) t = silu(t);
+                if (p.act == ACT_SILU) t = silu_ieee(t);
                 else if (p.act == ACT_RELU) t = fmaxf(t, 0.f);
                 v[r] = t;
             }

@@ -12,11 +12,6 @@
 
 namespace yp {
 
-typedef __attribute__((ext_vector_type(8))) __bf16 ks_bf16x8;
-typedef __attribute__((ext_vector_type(4))) float ks_f32x4;
-
-__device__ __forceinline__ float ks_silu(float x) { return x * __builtin_amdgcn_rcpf(1.0f + __expf(-x)); }
-
 template <int FN, int PXF, int UB, bool HAS_RES, bool OUT_F32>
 __global__ __launch_bounds__(256) void conv_ks_kernel(const ConvParams p) {
     __shared__ float4 part[4][FN * PXF][64];
@@ -43,11 +38,11 @@ __global__ __launch_bounds__(256) void conv_ks_kernel(const ConvParams p) {
     const __bf16* xb = (const __bf16*)p.x + p.x_coff + 8 * g;
     const __bf16* wb = (const __bf16*)p.w + (size_t)(n0 + fr) * p.Kpad + 8 * g;
 
-    ks_f32x4 acc[FN][PXF];
+    f32x4 acc[FN][PXF];
 #pragma unroll
     for (int a = 0; a < FN; ++a)
 #pragma unroll
-        for (int b = 0; b < PXF; ++b) acc[a][b] = ks_f32x4{0.f, 0.f, 0.f, 0.f};
+        for (int b = 0; b < PXF; ++b) acc[a][b] = f32x4{0.f, 0.f, 0.f, 0.f};
 
     for (int u0 = wave; u0 < units; u0 += 4 * UB) {
         uint4 xv[UB][PXF], wv[UB][FN];
@@ -77,7 +72,7 @@ __global__ __launch_bounds__(256) void conv_ks_kernel(const ConvParams p) {
             for (int a = 0; a < FN; ++a)
 #pragma unroll
                 for (int b = 0; b < PXF; ++b) {
-                    union { uint4 u; ks_bf16x8 v; } w, x;
+                    union { uint4 u; bf16x8 v; } w, x;
                     w.u = wv[i][a]; x.u = xv[i][b];
                     acc[a][b] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w.v, x.v, acc[a][b], 0, 0, 0);
                 }
@@ -105,7 +100,7 @@ __global__ __launch_bounds__(256) void conv_ks_kernel(const ConvParams p) {
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             v[j] += (co + j < p.Cout) ? p.bias[co + j] : 0.f;
-            if (p.act == ACT_SILU) v[j] = ks_silu(v[j]);
+            if (p.act == ACT_SILU) v[j] = silu_rcp(v[j]);
             else if (p.act == ACT_RELU) v[j] = fmaxf(v[j], 0.f);
         }
         if (HAS_RES) {

@@ -16,15 +16,6 @@
 
 namespace yp {
 
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-typedef __attribute__((address_space(3))) void lds_void;
-
-template <int N> __device__ __forceinline__ void px_wait_vmc() {
-    static_assert(N >= 0 && N < 64, "vmcnt range");
-    __builtin_amdgcn_s_waitcnt((N & 0xF) | (7 << 4) | (0xF << 8) | (((N >> 4) & 3) << 14));
-}
-
 template <int PXW, int FN, int WGM, int WGN, bool HAS_RES, bool OUT_F32>
 __global__ __launch_bounds__(WGM * WGN * 64) void conv_pxd_kernel(const ConvParams p, const int mtiles, const int BMe) {
     constexpr int NW = WGM * WGN;
@@ -45,11 +36,7 @@ __global__ __launch_bounds__(WGM * WGN * 64) void conv_pxd_kernel(const ConvPara
     const int wm = wave % WGM, wn = wave / WGM;
     const int fr = lane & 15, fc = lane >> 4;
 
-    int bid = blockIdx.x;
-    {
-        const int nwg = gridDim.x, q = nwg >> 3, r = nwg & 7, xcd = bid & 7, j = bid >> 3;
-        bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + j;
-    }
+    const int bid = xcd_remap(blockIdx.x, gridDim.x);
     const int mt = bid % mtiles, nt = bid / mtiles;
     // BMe <= BM rows of a tile are in use: the host sizes the tiles so that the launch is whole rounds of workgroups (a 40x40 map at batch 32
     // is 200 tiles of 256 pixels on 256 CUs; 256 tiles of 200 pixels keep every CU busy and finish a fifth earlier)
@@ -275,12 +262,8 @@ static hipError_t launch_pxd_var(const ConvParams& p, hipStream_t st) {
     const int mtiles = (p.M + BMe - 1) / BMe;
     const size_t sh = (size_t)3 * (BN * 8 / 64) * 1024 + 1024;
     auto kern = conv_pxd_kernel<PXW, FN, WGM, WGN, HAS_RES, OUT_F32>;
-    static bool attr = false;
-    if (!attr && sh > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh);
-        if (e != hipSuccess) return e;
-        attr = true;
-    }
+    static size_t granted = 0;
+    if (hipError_t e = allow_dynamic_lds((const void*)kern, sh, granted)) return e;
     hipLaunchKernelGGL(kern, dim3(mtiles * ntiles), dim3(WGM * WGN * 64), sh, st, p, mtiles, BMe);
     return hipGetLastError();
 }

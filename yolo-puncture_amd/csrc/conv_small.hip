@@ -19,14 +19,7 @@
 
 namespace yp {
 
-typedef __attribute__((ext_vector_type(4))) float cs_f32x4;
 typedef __attribute__((ext_vector_type(4))) __bf16 cs_bf16x4;
-
-__device__ __forceinline__ float cs_act(float v, int act) {
-    if (act == ACT_RELU) return fmaxf(v, 0.f);
-    if (act == ACT_SILU) return v / (1.0f + __expf(-v));
-    return v;
-}
 
 // element type: fp32 -> one float4 per lane and unit, four `v_mfma_f32_16x16x4_f32`; bf16 -> 8 bytes per lane and unit, one
 // `v_mfma_f32_16x16x16_bf16` (a lane's four k values are its four consecutive channels in both forms)
@@ -40,7 +33,7 @@ template <> struct CsT<float> {
         return make_float4(ly0 * (lx0 * a.x + lx1 * b.x) + ly1 * (lx0 * c.x + lx1 * d.x), ly0 * (lx0 * a.y + lx1 * b.y) + ly1 * (lx0 * c.y + lx1 * d.y),
                            ly0 * (lx0 * a.z + lx1 * b.z) + ly1 * (lx0 * c.z + lx1 * d.z), ly0 * (lx0 * a.w + lx1 * b.w) + ly1 * (lx0 * c.w + lx1 * d.w));
     }
-    static __device__ __forceinline__ void mma(cs_f32x4& acc, const Vec& w, const Vec& x) {
+    static __device__ __forceinline__ void mma(f32x4& acc, const Vec& w, const Vec& x) {
         acc = __builtin_amdgcn_mfma_f32_16x16x4f32(w.x, x.x, acc, 0, 0, 0);
         acc = __builtin_amdgcn_mfma_f32_16x16x4f32(w.y, x.y, acc, 0, 0, 0);
         acc = __builtin_amdgcn_mfma_f32_16x16x4f32(w.z, x.z, acc, 0, 0, 0);
@@ -65,23 +58,12 @@ template <> struct CsT<__bf16> {
     static __device__ __forceinline__ Vec lerp(const Vec& a, const Vec& b, const Vec& c, const Vec& d, float ly0, float ly1, float lx0, float lx1) {
         return make_uint2(lerp2(a.x, b.x, c.x, d.x, ly0, ly1, lx0, lx1), lerp2(a.y, b.y, c.y, d.y, ly0, ly1, lx0, lx1));
     }
-    static __device__ __forceinline__ void mma(cs_f32x4& acc, const Vec& w, const Vec& x) {
+    static __device__ __forceinline__ void mma(f32x4& acc, const Vec& w, const Vec& x) {
         union { uint2 u; cs_bf16x4 v; } a, b;
         a.u = w; b.u = x;
         acc = __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(a.v, b.v, acc, 0, 0, 0);
     }
 };
-
-// F.upsample(size=..., mode='bilinear') = upsample_bilinear2d, align_corners=False: src = scale*(dst+0.5)-0.5 clamped at 0 (as u2net.hip u2_bil)
-__device__ __forceinline__ void cs_bil(int dst, int n_in, int n_out, int& i0, int& i1, float& l0, float& l1) {
-    const float scale = (float)n_in / (float)n_out;
-    float f = scale * ((float)dst + 0.5f) - 0.5f;
-    f = fmaxf(f, 0.f);
-    i0 = (int)f;
-    i1 = i0 + ((i0 < n_in - 1) ? 1 : 0);
-    l1 = f - (float)i0;
-    l0 = 1.f - l1;
-}
 
 // MODE 0: plain; 1: the 2x2 ceil-mode max pool in front of the convolution taken while loading; 2: input channels [0, x2_C) are the
 // bilinear resize of the low-resolution tensor x2 to the convolution's input size, taken while loading (the up-sample launch and its
@@ -112,9 +94,9 @@ __global__ __launch_bounds__(256) void conv_small_kernel(const ConvParams p) {
     const T* x2b = UP ? (const T*)p.x2 + p.x2_coff + 4 * g : nullptr;
     const int up_units = UP ? p.x2_C >> 4 : 0, bimg = valid ? m / HoWo : 0;
 
-    cs_f32x4 acc[FN];
+    f32x4 acc[FN];
 #pragma unroll
-    for (int a = 0; a < FN; ++a) acc[a] = cs_f32x4{0.f, 0.f, 0.f, 0.f};
+    for (int a = 0; a < FN; ++a) acc[a] = f32x4{0.f, 0.f, 0.f, 0.f};
 
     for (int u0 = wave; u0 < units; u0 += 4 * UB) {
         Vec xv[UB], wv[UB][FN];
@@ -144,8 +126,8 @@ __global__ __launch_bounds__(256) void conv_small_kernel(const ConvParams p) {
                     } else if (UP && cc < up_units) {
                         int ya, yb, xa, xc;
                         float ly0, ly1, lx0, lx1;
-                        cs_bil(hi, p.x2_H, p.H, ya, yb, ly0, ly1);
-                        cs_bil(wi, p.x2_W, p.W, xa, xc, lx0, lx1);
+                        bilinear_tap(hi, p.x2_H, p.H, ya, yb, ly0, ly1);
+                        bilinear_tap(wi, p.x2_W, p.W, xa, xc, lx0, lx1);
                         const T* q0 = x2b + (size_t)((bimg * p.x2_H + ya) * p.x2_W) * p.x2_stride + cc * 16;
                         const T* q1 = x2b + (size_t)((bimg * p.x2_H + yb) * p.x2_W) * p.x2_stride + cc * 16;
                         xv[i] = CsT<T>::lerp(*(const Vec*)(q0 + (size_t)xa * p.x2_stride), *(const Vec*)(q0 + (size_t)xc * p.x2_stride),
@@ -185,7 +167,7 @@ __global__ __launch_bounds__(256) void conv_small_kernel(const ConvParams p) {
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 if (co + j < p.Cout) {
-                    v[j] = cs_act(v[j] + p.bias[co + j], p.act);
+                    v[j] = act_fdiv(v[j] + p.bias[co + j], p.act);
                     if (rp) v[j] += (float)rp[j];
                 }
             }

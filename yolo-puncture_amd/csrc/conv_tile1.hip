@@ -18,16 +18,6 @@
 
 namespace yp {
 
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-typedef __attribute__((address_space(3))) void lds_void;
-
-template <int N> __device__ __forceinline__ void wait_vt1() {
-    static_assert(N >= 0 && N < 64, "vmcnt range");
-    __builtin_amdgcn_s_waitcnt((N & 0xF) | (7 << 4) | (0xF << 8) | (((N >> 4) & 3) << 14));
-}
-__device__ __forceinline__ int tswz(int row) { return ((row >> 2) & 1) << 1; }
-
 constexpr int T1_FMX = 7;        // pixel fragments per wave (2 waves in M: tiles of up to 224 pixels)
 constexpr int T1_NS = 3;         // weight ring slots; a stage is one tap ROW (3 taps x [BN][32]) so that a barrier covers 6*FMX MFMAs per wave
 
@@ -85,7 +75,7 @@ __global__ __launch_bounds__(512) void conv_tile1_kernel(const ConvParams p, con
         const int HR = g.TR + 2, npx = HR * HC;
         for (int pi = wave; pi < g.ppc; pi += NW) {
             const int hp = pi * 16 + (lane >> 2), pc = lane & 3;
-            const int c8 = pc ^ tswz(hp);
+            const int c8 = pc ^ cswz64(hp);
             const int hy = hp / HC, hx = hp - hy * HC;
             const int hi = r0 - 1 + hy, wi = c0 - 1 + hx;
             const bool ok = hp < npx && (unsigned)hi < (unsigned)p.H && (unsigned)wi < (unsigned)p.W;
@@ -105,7 +95,7 @@ __global__ __launch_bounds__(512) void conv_tile1_kernel(const ConvParams p, con
         const int q = wave + j * NW;                                         // piece id within the stage: kx = q / WP, rows (q % WP) * 16 ..
         wlive[j] = q < 3 * WP;
         const int kx = q / WP, n = (q % WP) * 16 + (lane >> 2), pc = lane & 3;
-        const int c8 = pc ^ tswz(n);
+        const int c8 = pc ^ cswz64(n);
         wbase[j] = (unsigned)(((n0 + n) * p.Kpad + kx * p.Cin + c8 * 8) * 2);
     }
     const bool full = wlive[LPW - 1];                                        // this wave carries LPW pieces per stage (else LPW - 1)
@@ -147,7 +137,7 @@ __global__ __launch_bounds__(512) void conv_tile1_kernel(const ConvParams p, con
 #pragma unroll
         for (int a = 0; a < FN; ++a) {
             const int rw = kx * BN + wn * (FN * 16) + a * 16 + fr;
-            wl[kx][a] = (unsigned)(rw * 64 + ((fc ^ tswz(rw)) * 16));
+            wl[kx][a] = (unsigned)(rw * 64 + ((fc ^ cswz64(rw)) * 16));
         }
     const int myf = max(0, min(per_wave, g.nfr - f0));                       // fragments that exist for this wave (wave-uniform)
 
@@ -157,8 +147,8 @@ __global__ __launch_bounds__(512) void conv_tile1_kernel(const ConvParams p, con
 #pragma unroll
         for (int f = 0; f < T1_FMX; ++f) acc[a][f] = f32x4{bias[a][0], bias[a][1], bias[a][2], bias[a][3]};
 
-    if (full) wait_vt1<(T1_NS - 1) * LPW>();         // the patch has landed (only the ring's weight pieces may still be in flight)
-    else wait_vt1<(T1_NS - 1) * (LPW - 1)>();
+    if (full) wait_vmcnt<(T1_NS - 1) * LPW>();         // the patch has landed (only the ring's weight pieces may still be in flight)
+    else wait_vmcnt<(T1_NS - 1) * (LPW - 1)>();
     __builtin_amdgcn_s_barrier();
     T1_STAMP(1);
 
@@ -188,8 +178,8 @@ __global__ __launch_bounds__(512) void conv_tile1_kernel(const ConvParams p, con
     };
     auto stage = [&](int st, auto Pc) {
         constexpr int P = decltype(Pc)::value;           // register set that holds this stage's first tap
-        if (full) wait_vt1<(T1_NS - 2) * LPW>();         // this wave's pieces of stage st have landed
-        else wait_vt1<(T1_NS - 2) * (LPW - 1)>();
+        if (full) wait_vmcnt<(T1_NS - 2) * LPW>();         // this wave's pieces of stage st have landed
+        else wait_vmcnt<(T1_NS - 2) * (LPW - 1)>();
         __builtin_amdgcn_s_barrier();
         const int ch = st / 3, ky = st - ch * 3;
         if (ky == 0 && ch + 1 < nchunk) issue_x(ch + 1);
@@ -300,7 +290,7 @@ __global__ __launch_bounds__(512) void conv_tile1w_kernel(const ConvParams p, co
             for (int j = 0; j < xpw; ++j) {
                 const int pi = min(lw + 4 * j, g.ppc - 1);              // (a surplus instruction rewrites the plane's last piece with the same bytes)
                 const int hp = pi * 16 + (lane >> 2), pc = lane & 3;
-                const int c8 = pc ^ tswz(hp);
+                const int c8 = pc ^ cswz64(hp);
                 const int hy = hp / HC, hx = hp - hy * HC;
                 const int hi = r0 - 1 + hy, wi = c0 - 1 + hx;
                 const bool ok = hp < npx && (unsigned)hi < (unsigned)p.H && (unsigned)wi < (unsigned)p.W;
@@ -313,7 +303,7 @@ __global__ __launch_bounds__(512) void conv_tile1w_kernel(const ConvParams p, co
         for (int j = 0; j < 6; ++j) {
             const int q = lw + 4 * j;                                       // piece of the stage: tap kx = q / 8, rows (q % 8) * 16 ..
             const int kx = q >> 3, n = (q & 7) * 16 + (lane >> 2), pc = lane & 3;
-            const int c8 = pc ^ tswz(n);
+            const int c8 = pc ^ cswz64(n);
             wbase[j] = (unsigned)((n * p.Kpad + kx * p.Cin + c8 * 8) * 2);
         }
         auto issue_stage = [&](int stage) {
@@ -330,13 +320,13 @@ __global__ __launch_bounds__(512) void conv_tile1w_kernel(const ConvParams p, co
         issue_stage(1);
         for (int st = 0; st < nst; ++st) {
             // stage st (and every plane issued before it) has landed once at most the 6 pieces of stage st + 1 are in flight
-            wait_vt1<6>();
+            wait_vmcnt<6>();
             __builtin_amdgcn_s_barrier();
             const int ch = st / 3, ky = st - ch * 3;
             if (ky == 0 && ch + 1 < nchunk) issue_x(ch + 1);                // lands two stages before its first use: the wait above covers it (in-order counter)
             issue_stage(st + 2);                                            // slot of stage st - 1: every consumer passed this barrier, so it is done with it
         }
-        wait_vt1<0>();
+        wait_vmcnt<0>();
         return;
     }
 
@@ -366,7 +356,7 @@ __global__ __launch_bounds__(512) void conv_tile1w_kernel(const ConvParams p, co
 #pragma unroll
         for (int a = 0; a < FN; ++a) {
             const int rw = kx * BN + wn * (FN * 16) + a * 16 + fr;
-            wl[kx][a] = (unsigned)(rw * 64 + ((fc ^ tswz(rw)) * 16));
+            wl[kx][a] = (unsigned)(rw * 64 + ((fc ^ cswz64(rw)) * 16));
         }
     const int myf = max(0, min(per_wave, g.nfr - f0));
     f32x4 acc[FN][FM];
@@ -506,19 +496,15 @@ static hipError_t launch_tile1_var(const ConvParams& p, hipStream_t st) {
     const int B = p.M / (p.Ho * p.Wo);
     const int tiles = B * g.tiles_h * g.tiles_w * ((p.Cout + BN - 1) / BN);
     auto kern = conv_tile1_kernel<WGN, HAS_RES, OUT_F32>;
-    static bool attr = false;
-    if (!attr) {
-        hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(160 * 1024));
-        if (e != hipSuccess) return e;
-        attr = true;
-    }
+    static size_t granted = 0;
+    if (hipError_t e = allow_dynamic_lds((const void*)kern, sh, granted)) return e;
     if constexpr (WGN == 4 && !HAS_RES && !OUT_F32) {
-        static const bool clocks = [] { const char* v = std::getenv("YOLOP_T1_CLOCKS"); return v && *v == '1'; }();
+        static const bool clocks = env_on("YOLOP_T1_CLOCKS");
         if (clocks) {
             auto kc = conv_tile1_kernel<4, false, false, true>;
-            { const char* v = std::getenv("YOLOP_T1_ABL"); const int ab = v ? atoi(v) : 0; (void)hipMemcpyToSymbol(HIP_SYMBOL(g_t1_abl), &ab, sizeof(int)); }
-            static bool attr_c = false;
-            if (!attr_c) { (void)hipFuncSetAttribute((const void*)kc, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(160 * 1024)); attr_c = true; }
+            { const int ab = env_int("YOLOP_T1_ABL", 0); (void)hipMemcpyToSymbol(HIP_SYMBOL(g_t1_abl), &ab, sizeof(int)); }
+            static size_t granted_c = 0;
+            (void)allow_dynamic_lds((const void*)kc, sh, granted_c);
             hipLaunchKernelGGL(kc, dim3(tiles), dim3(512), sh, st, p, g);
             hipError_t e = hipStreamSynchronize(st);
             if (e != hipSuccess) return e;
@@ -543,12 +529,8 @@ static hipError_t launch_tile1w_var(const ConvParams& p, hipStream_t st) {
     const int B = p.M / (p.Ho * p.Wo);
     const int tiles = B * g.tiles_h * g.tiles_w;
     auto kern = conv_tile1w_kernel<T1_FMX, HAS_RES, OUT_F32>;
-    static bool attr = false;
-    if (!attr) {
-        hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(160 * 1024));
-        if (e != hipSuccess) return e;
-        attr = true;
-    }
+    static size_t granted = 0;
+    if (hipError_t e = allow_dynamic_lds((const void*)kern, sh, granted)) return e;
     hipLaunchKernelGGL(kern, dim3(tiles), dim3(512), sh, st, p, g);
     return hipGetLastError();
 }

@@ -23,15 +23,6 @@
 
 namespace yp {
 
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-typedef __attribute__((address_space(3))) void lds_void;
-
-template <int N> __device__ __forceinline__ void wr_wait_vmc() {
-    static_assert(N >= 0 && N < 64, "vmcnt range");
-    __builtin_amdgcn_s_waitcnt((N & 0xF) | (7 << 4) | (0xF << 8) | (((N >> 4) & 3) << 14));
-}
-__device__ __forceinline__ int wr_pswz(int row) { return ((row >> 2) & 1) << 1; }
 template <int... Is, typename F> __device__ __forceinline__ void wr_static_for_impl(std::integer_sequence<int, Is...>, F&& f) {
     (f(std::integral_constant<int, Is>{}), ...);
 }
@@ -71,6 +62,8 @@ __global__ __launch_bounds__(WGM * WGN * 64) void conv_wreg_kernel(const ConvPar
     const int pcol = (TW == 16) ? fr : (((fr & 7) + 6 * (fr >> 3)) & 7);
     const int ppos = prow * PW + pcol;
 
+    // xcd_remap(blockIdx.x, gridDim.x), written out: through the helper `bid >> 3` ends up behind the select and this kernel's scalar
+    // register allocation changes (kernel_util.h)
     int bid = blockIdx.x;
     {
         const int nwg = gridDim.x, q = nwg >> 3, r = nwg & 7, xcd = bid & 7, j = bid >> 3;
@@ -104,7 +97,7 @@ __global__ __launch_bounds__(WGM * WGN * 64) void conv_wreg_kernel(const ConvPar
         const int ii = wave * LH + j;
         const int s = ii * 64 + lane;
         const int hp = s >> 2, pc = s & 3;
-        const int c8 = pc ^ wr_pswz(hp);
+        const int c8 = pc ^ cswz64(hp);
         const int hy = hp / PW, hx = hp - hy * PW;
         hyx[j] = (ii < H_INSTR && hp < HP) ? ((hy << 16) | hx) : -1;
         hrel[j] = (unsigned)(((hy * p.W + hx) * p.x_stride) * 2 + c8 * 16);
@@ -162,19 +155,19 @@ __global__ __launch_bounds__(WGM * WGN * 64) void conv_wreg_kernel(const ConvPar
                 ii = ii >= W_INSTR ? ii - W_INSTR : ii;
                 const int s = ii * 64 + lane;
                 const int rg = s >> 2, pc = s & 3;
-                const int c8 = pc ^ wr_pswz(rg);
+                const int c8 = pc ^ cswz64(rg);
                 const int t = rg / BN, n = rg - t * BN;
                 const unsigned voff = (unsigned)((n * p.Kpad + t * p.Cin + c * 32 + c8 * 8) * 2);
                 __builtin_amdgcn_raw_ptr_buffer_load_lds(wrs, (lds_void*)(Wst + ii * 1024), 16, voff, 0, 0, 0);
             }
-            wr_wait_vmc<0>();
+            wait_vmcnt<0>();
             __builtin_amdgcn_s_barrier();
 #pragma unroll
             for (int t = 0; t < 9; ++t)
 #pragma unroll
                 for (int a = 0; a < FN; ++a) {
                     const int rw = t * BN + wn * (FN * 16) + a * 16 + fr;
-                    wf[c][t][a] = *(const bf16x8*)(Wst + rw * 64 + ((fc ^ wr_pswz(rw)) * 16));
+                    wf[c][t][a] = *(const bf16x8*)(Wst + rw * 64 + ((fc ^ cswz64(rw)) * 16));
                 }
             if (c + 1 < NCH) {
                 __builtin_amdgcn_s_waitcnt(0xc07f);           // lgkmcnt(0): the fragments are in registers before the image is overwritten
@@ -198,9 +191,9 @@ __global__ __launch_bounds__(WGM * WGN * 64) void conv_wreg_kernel(const ConvPar
         for (int c = 0; c < NCH; ++c) {
             if (!first_iter) {
                 const int k = __builtin_popcount(epmask & ((1u << (NSH - 1)) - 1u));
-                if (k == 0) wr_wait_vmc<(NSH - 2) * LH>();
-                else if (k == 1) wr_wait_vmc<(NSH - 2) * LH + S>();
-                else wr_wait_vmc<(NSH - 2) * LH + 2 * S>();
+                if (k == 0) wait_vmcnt<(NSH - 2) * LH>();
+                else if (k == 1) wait_vmcnt<(NSH - 2) * LH + S>();
+                else wait_vmcnt<(NSH - 2) * LH + 2 * S>();
                 __builtin_amdgcn_s_barrier();
             }
             first_iter = false;
@@ -215,7 +208,7 @@ __global__ __launch_bounds__(WGM * WGN * 64) void conv_wreg_kernel(const ConvPar
             auto read_frag = [&](int i) -> bf16x8 {
                 const int kx = i / NH, h = i - kx * NH;
                 const int hp = (wm * FM * RPF + h) * PW + kx + ppos;
-                return *(const bf16x8*)(hsl + hp * 64 + ((fc ^ wr_pswz(hp)) * 16));
+                return *(const bf16x8*)(hsl + hp * 64 + ((fc ^ cswz64(hp)) * 16));
             };
             bf16x8 xf = read_frag(0);
             wr_static_for<3 * NH>([&](auto I) {
@@ -293,7 +286,7 @@ __global__ __launch_bounds__(WGM * WGN * 64) void conv_wreg_kernel(const ConvPar
         epmask |= 1u;
         WR_STAMP(4)
     }
-    wr_wait_vmc<0>();
+    wait_vmcnt<0>();
     if (p.clk && lane == 0)
         for (int i = 0; i < 5; ++i) p.clk[((size_t)blockIdx.x * NW + wave) * 5 + i] = clk[i];
 #undef WR_STAMP
@@ -356,13 +349,9 @@ static hipError_t launch_wreg_var(const ConvParams& p, const WregCfg& k, hipStre
     int G = (num_tiles + rounds - 1) / rounds;
     if (G < 1) G = 1;
     auto kern = conv_wreg_kernel<NCH, FM, FN, WGM, WGN, TW, HAS_RES, OUT_F32>;
-    static bool attr = false;
-    if (!attr) {
-        hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(160 * 1024));
-        if (e != hipSuccess) return e;
-        attr = true;
-    }
-    static const bool clocks = [] { const char* v = std::getenv("YOLOP_WREG_CLOCKS"); return v && *v == '1'; }();   // debug: per-phase s_memtime sums
+    static size_t granted = 0;
+    if (hipError_t e = allow_dynamic_lds((const void*)kern, sh, granted)) return e;
+    static const bool clocks = env_on("YOLOP_WREG_CLOCKS");   // debug: per-phase s_memtime sums
     if (clocks) {
         ConvParams q = p;
         const size_t n = (size_t)G * WGM * WGN * 5;

@@ -18,17 +18,8 @@
 
 namespace yp {
 
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-typedef __attribute__((address_space(3))) void lds_void;
-
 constexpr int WR_NW = 8;
 constexpr int WR_MAXNF = 8;             // channel fragments of a block (NB <= 128)
-
-template <int N> __device__ __forceinline__ void wr_wait_vm() {
-    static_assert(N >= 0 && N < 64, "vmcnt range");
-    __builtin_amdgcn_s_waitcnt((N & 0xF) | (7 << 4) | (0xF << 8) | (((N >> 4) & 3) << 14));
-}
 
 // the fragment set (xs, ws) has landed once at most N younger LDS reads are outstanding; its registers pass through empty asm statements
 // behind the wait, so no use of them moves above it (volatile asm statements keep their order)
@@ -137,7 +128,7 @@ __global__ __launch_bounds__(WR_NW * 64) void conv_wres_kernel(const ConvParams 
     // iteration (runtime piece counts) and otherwise puts `s_waitcnt vmcnt(0)` in front of the accumulators' initialisation - in every
     // iteration, behind the next tile's loads: no prefetch at all. Waited for here, then passed through an empty asm statement (a value
     // that comes out of one is no memory result to wait for).
-    wr_wait_vm<0>();
+    wait_vmcnt<0>();
 #pragma unroll
     for (int i = 0; i < NFW; ++i)
 #pragma unroll
@@ -145,8 +136,8 @@ __global__ __launch_bounds__(WR_NW * 64) void conv_wres_kernel(const ConvParams 
 
     for (int it = 0; tile < ntiles; tile += Gt, ++it) {
         // this tile's rows (first time: the weights too) have landed; the FM * NFW stores of the previous tile, issued behind them, may still fly
-        if (it == 0) wr_wait_vm<0>();
-        else wr_wait_vm<FM * NFW>();
+        if (it == 0) wait_vmcnt<0>();
+        else wait_vmcnt<FM * NFW>();
         __builtin_amdgcn_s_barrier();
         if (tile + Gt < ntiles) issue_tile(tile + Gt, Xs + ((it & 1) ^ 1) * xtile);
         const unsigned char* const XA = Xs + (it & 1) * xtile;
@@ -222,7 +213,7 @@ __global__ __launch_bounds__(WR_NW * 64) void conv_wres_kernel(const ConvParams 
             }
         }
     }
-    wr_wait_vm<0>();
+    wait_vmcnt<0>();
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------------------
@@ -268,12 +259,8 @@ static hipError_t launch_wres_t(const ConvParams& p, const WresCfg& k, hipStream
     wres_blocks(p, k, NB, nblk);
     const size_t sh = wres_lds(p, k);
     auto kern = conv_wres_kernel<TP, WGN, HAS_RES>;
-    static bool attr = false;
-    if (!attr) {
-        hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e != hipSuccess) return e;
-        attr = true;
-    }
+    static size_t granted = 0;
+    if (hipError_t e = allow_dynamic_lds((const void*)kern, sh, granted)) return e;
     const int ntiles = (p.M + TP - 1) / TP;
     // an HBM-bound kernel: as many workgroups as fit (two per CU when the tiles are small), tile lanes in whole XCD rounds
     const int gmax = sh <= 78 * 1024 ? 512 : 256;

@@ -17,16 +17,7 @@
 
 namespace yp {
 
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-typedef __attribute__((address_space(3))) void lds_void;
-
 constexpr int WS_NW = 8;
-
-template <int N> __device__ __forceinline__ void ws_wait_vm() {
-    static_assert(N >= 0 && N < 64, "vmcnt range");
-    __builtin_amdgcn_s_waitcnt((N & 0xF) | (7 << 4) | (0xF << 8) | (((N >> 4) & 3) << 14));
-}
 
 template <int NKS, int NFW, int TP>
 __global__ __launch_bounds__(WS_NW * 64) void conv_wrs_kernel(const ConvParams p, const int G) {
@@ -130,7 +121,7 @@ __global__ __launch_bounds__(WS_NW * 64) void conv_wrs_kernel(const ConvParams p
     // Weights and bias must be KNOWN to be complete before the loop (the compiler cannot count a loop iteration's vector-memory
     // operations and would wait `vmcnt(0)` in front of their first use in every iteration - behind the next tile's loads): waited for
     // here, then passed through empty asm statements (see conv_wres.hip).
-    ws_wait_vm<0>();
+    wait_vmcnt<0>();
 #pragma unroll
     for (int ks = 0; ks < NKS; ++ks)
 #pragma unroll
@@ -143,8 +134,8 @@ __global__ __launch_bounds__(WS_NW * 64) void conv_wrs_kernel(const ConvParams p
     WS_STAMP(0)
     for (int it = 0; tile < ntiles; tile += G, ++it) {
         // this tile's rows have landed; the NFW * FM stores of the previous tile, issued behind them, may still fly
-        if (it == 0) ws_wait_vm<0>();
-        else ws_wait_vm<NFW * FM>();
+        if (it == 0) wait_vmcnt<0>();
+        else wait_vmcnt<NFW * FM>();
         __builtin_amdgcn_s_barrier();
         WS_STAMP(1)
         if (tile + G < ntiles) issue_tile(tile + G, Xs + ((it & 1) ^ 1) * xtile);
@@ -190,7 +181,7 @@ __global__ __launch_bounds__(WS_NW * 64) void conv_wrs_kernel(const ConvParams p
         }
         WS_STAMP(4)
     }
-    ws_wait_vm<0>();
+    wait_vmcnt<0>();
     if (p.clk && lane == 0)
         for (int i = 0; i < 5; ++i) p.clk[((size_t)blockIdx.x * WS_NW + wave) * 5 + i] = clk[i];
 #undef WS_STAMP
@@ -240,15 +231,11 @@ template <int NKS, int NFW, int TP>
 static hipError_t launch_wrs_t(const ConvParams& p, hipStream_t st) {
     const size_t sh = (size_t)2 * TP * p.Cin * 2;
     auto kern = conv_wrs_kernel<NKS, NFW, TP>;
-    static bool attr = false;
-    if (!attr) {
-        hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e != hipSuccess) return e;
-        attr = true;
-    }
+    static size_t granted = 0;
+    if (hipError_t e = allow_dynamic_lds((const void*)kern, sh, granted)) return e;
     const int ntiles = (p.M + TP - 1) / TP;
     const int G = ntiles < 256 ? ntiles : 256;                     // one workgroup per CU (its waves hold the weights: 2 per SIMD)
-    static const bool clocks = [] { const char* v = std::getenv("YOLOP_WRS_CLOCKS"); return v && *v == '1'; }();   // debug: per-phase s_memtime sums
+    static const bool clocks = env_on("YOLOP_WRS_CLOCKS");   // debug: per-phase s_memtime sums
     if (clocks) {
         ConvParams q = p;
         const size_t n = (size_t)G * WS_NW * 5;

@@ -17,13 +17,6 @@
 
 namespace yp {
 
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-typedef __attribute__((address_space(3))) void lds_void;
-
-__device__ __forceinline__ float silu_m(float x) { return x * __builtin_amdgcn_rcpf(1.0f + __expf(-x)); }
-__device__ __forceinline__ int mswz(int row) { return ((row >> 2) & 1) << 1; }
-
 constexpr int DWM_MAXP = 7;      // patches per wave (4 waves -> maps up to 28 patches = 448 pixels)
 
 static inline int dwm_pitch(int W, int KS) {
@@ -54,7 +47,7 @@ __global__ __launch_bounds__(256) void dwconv_mfma_kernel(const DwParams p, cons
     for (int ii = wave; ii < x_instr; ii += 4) {
         const int s = ii * 64 + lane;
         const int hp = s >> 2, pc = s & 3;
-        const int c8 = pc ^ mswz(hp);
+        const int c8 = pc ^ cswz64(hp);
         const int hy = hp / P, hx = hp - hy * P;
         const int hi = hy - pad, wi = hx - pad;
         const bool ok = (hy < HP) && ((unsigned)hi < (unsigned)p.H) && ((unsigned)wi < (unsigned)p.W);
@@ -141,7 +134,7 @@ __global__ __launch_bounds__(256) void dwconv_mfma_kernel(const DwParams p, cons
             for (int h = 0; h < 2; ++h) {
                 __attribute__((aligned(8))) __bf16 o[4];
 #pragma unroll
-                for (int j = 0; j < 4; ++j) o[j] = (__bf16)(p.act == ACT_SILU ? silu_m(acc[i][h][j]) : acc[i][h][j]);
+                for (int j = 0; j < 4; ++j) o[j] = (__bf16)(p.act == ACT_SILU ? silu_rcp(acc[i][h][j]) : acc[i][h][j]);
                 *(uint2*)(yb + (size_t)(yy * p.W + xx) * p.y_stride + 16 * h) = *(const uint2*)o;
             }
         }
@@ -167,13 +160,9 @@ bool dwconv_mfma_valid(const DwParams& p, int dtype) {
 hipError_t launch_dwconv_mfma(const DwParams& p, hipStream_t st) {
     int x_instr = 0;
     const size_t sh = dwm_lds(p, &x_instr);
-    static bool attr = false;
-    if (!attr) {
-        hipError_t e = hipFuncSetAttribute((const void*)dwconv_mfma_kernel<7, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 72 * 1024);
-        if (e == hipSuccess) e = hipFuncSetAttribute((const void*)dwconv_mfma_kernel<7, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 72 * 1024);
-        if (e != hipSuccess) return e;
-        attr = true;
-    }
+    static size_t granted[2] = {0, 0};
+    if (hipError_t e = allow_dynamic_lds((const void*)dwconv_mfma_kernel<7, false>, sh, granted[0])) return e;
+    if (hipError_t e = allow_dynamic_lds((const void*)dwconv_mfma_kernel<7, true>, sh, granted[1])) return e;
     // few (image, channel block) pairs: split each map's patches over up to 4 workgroups (every one stages the whole map - it is L2-resident)
     const int wgs = p.B * (p.C / 32);
     const int psplit = wgs >= 256 ? 1 : wgs >= 128 ? 2 : 4;

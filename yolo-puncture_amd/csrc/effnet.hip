@@ -50,8 +50,6 @@ constexpr int DW_ROWS = 1;           // output rows per depthwise workgroup (= t
 // ---------------------------------------------------------------------------------------------------------------------------------------
 // device helpers
 // ---------------------------------------------------------------------------------------------------------------------------------------
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(4))) float f32x4;
 
 __device__ __forceinline__ float d_bf2f(uint16_t h) { return __uint_as_float((uint32_t)h << 16); }
 __device__ __forceinline__ uint16_t d_f2bf(float f) {       // round to nearest even (NaN stays NaN)
@@ -59,8 +57,6 @@ __device__ __forceinline__ uint16_t d_f2bf(float f) {       // round to nearest 
     if ((u & 0x7fffffffu) > 0x7f800000u) return (uint16_t)((u >> 16) | 0x40);
     return (uint16_t)((u + 0x7fffu + ((u >> 16) & 1u)) >> 16);
 }
-__device__ __forceinline__ float d_swish(float x) { return x / (1.f + expf(-x)); }
-__device__ __forceinline__ float d_sigmoid(float x) { return 1.f / (1.f + expf(-x)); }
 
 template <typename T> __device__ __forceinline__ float ld(const T* p, size_t i);
 template <> __device__ __forceinline__ float ld<float>(const float* p, size_t i) { return p[i]; }
@@ -145,7 +141,7 @@ __global__ __launch_bounds__(256) void cls_stem_kernel(StemArgs a) {
     }
     T* y = (T*)a.y + ((size_t)b * a.Ho * a.Wo + pix) * STEM_C;
 #pragma unroll
-    for (int o = 0; o < STEM_C; ++o) st(y, o, d_swish(acc[o] + sb[o]));
+    for (int o = 0; o < STEM_C; ++o) st(y, o, silu_ieee(acc[o] + sb[o]));
 }
 
 // debug tap only (YOLOP_CLS_TAP_INPUT=1): the normalised 380^2 crop the stem reads, from the same roi_value
@@ -238,7 +234,7 @@ __global__ __launch_bounds__(256) void cls_pw_kernel(PwArgs a) {
             for (int r = 0; r < 4; ++r) {
                 const int row = row0 + i * 16 + 4 * lg + r;
                 float v = acc[i][j][r] + bias;
-                if (a.act) v = d_swish(v);
+                if (a.act) v = silu_ieee(v);
                 if (a.pool) {
                     if (row < a.HW) colsum += v;
                 } else if (cok && row < a.HW) {
@@ -289,7 +285,7 @@ __global__ __launch_bounds__(256) void cls_dw_kernel(DwArgs a) {
                     acc = fmaf(ld(x, ((size_t)iy * a.W + ix) * a.C + c), a.w[(ky * a.k + kx) * a.C + c], acc);
                 }
             }
-            const float v = d_swish(acc + bias);
+            const float v = silu_ieee(acc + bias);
             st(y, ((size_t)oy * a.Wo + ox) * a.C + c, v);
             sum += rnd(T{}, v);
         }
@@ -325,13 +321,13 @@ __global__ __launch_bounds__(256) void cls_se_kernel(SeArgs a) {
         float t = 0.f;
         for (int c = lane; c < a.C; c += 64) t = fmaf(a.wr[(size_t)j * a.C + c], mean[c], t);
         for (int o = 32; o > 0; o >>= 1) t += __shfl_xor(t, o);
-        if (lane == 0) s[j] = d_swish(t + a.br[j]);
+        if (lane == 0) s[j] = silu_ieee(t + a.br[j]);
     }
     __syncthreads();
     for (int c = threadIdx.x; c < a.C; c += 256) {
         float t = 0.f;
         for (int j = 0; j < a.sq; ++j) t = fmaf(a.we[(size_t)c * a.sq + j], s[j], t);
-        a.gate[(size_t)b * a.C + c] = d_sigmoid(t + a.be[c]);
+        a.gate[(size_t)b * a.C + c] = sigmoid_ieee(t + a.be[c]);
     }
 }
 

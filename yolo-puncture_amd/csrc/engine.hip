@@ -823,7 +823,7 @@ static int make_plan(yp_engine& e, int B, int H, int W) {
     for (auto& o : e.ops) o.cfg = -1;
     static const char* kn[] = {"stem_kernel", "", "dwconv_kernel", "pool5_kernel", "upsample2_kernel", "attention_kernel", "head_select_kernel", "", "sppf_pool3_kernel", "anchor_max_level_kernel"};
     for (auto& o : e.ops) { o.form = FORM_PLAIN; o.skip = false; o.folded = false; o.pw_store = false; o.sparse_box = false; o.sparse_cf = false; }
-    static const bool no_fold = [] { const char* v = std::getenv("YOLOP_NO_FOLD"); return v && *v == '1'; }();   // A/B switch
+    static const bool no_fold = env_on("YOLOP_NO_FOLD");   // A/B switch
     for (auto& o : e.ops) {
         if (o.kind != OP_CONV || o.fold_up < 0 || e.dtype != DT_BF16 || no_fold) continue;
         o.folded = true;                                   // tentatively, so that conv_params describes the folded form
@@ -841,7 +841,7 @@ static int make_plan(yp_engine& e, int B, int H, int W) {
             if (c >= 0) {
                 e.ops[o.fuse_pre].skip = true; o.cfg = conv_halo_s2_family.base + c; o.kernel = conv_halo_s2_family.symbol(q, c);
                 // ... and with the stem in front of it, when the stem's output has no other reader
-                static const bool no_front = [] { const char* v = std::getenv("YOLOP_NO_FRONT"); return v && *v == '1'; }();   // A/B switch
+                static const bool no_front = env_on("YOLOP_NO_FRONT");   // A/B switch
                 const Op& c1 = e.ops[o.fuse_pre];
                 int stem = -1, readers = 0;
                 for (size_t j = 0; j < e.ops.size(); ++j) {
@@ -856,7 +856,7 @@ static int make_plan(yp_engine& e, int B, int H, int W) {
             }
             o.form = FORM_PLAIN;
         }
-        static const bool no_c2f = [] { const char* v = std::getenv("YOLOP_NO_C2F"); return v && *v == '1'; }();   // A/B switch
+        static const bool no_c2f = env_on("YOLOP_NO_C2F");   // A/B switch
         if (o.kind == OP_CONV && o.c2f_m1 >= 0 && e.dtype == DT_BF16 && e.fuse && !no_c2f && c2f_fused_valid(c2f_params(e, o))) {
             o.form = FORM_C2F; e.ops[o.c2f_m1].skip = true; e.ops[o.c2f_m2].skip = true; o.kernel = "c2f_fused_kernel";
             continue;
@@ -889,7 +889,7 @@ static int make_plan(yp_engine& e, int B, int H, int W) {
             p.Kpad = (o.in.C + 31) / 32 * 32; p.cfg = o.cfg;
             o.kernel = conv_kernel_name(p, e.dtype);
         } else if (o.kind == OP_DWCONV) {
-            static const bool no_scd = [] { const char* v = std::getenv("YOLOP_NO_SCD"); return v && *v == '1'; }();   // A/B switch
+            static const bool no_scd = env_on("YOLOP_NO_SCD");   // A/B switch
             if (o.scd_pre >= 0 && e.dtype == DT_BF16 && e.fuse && !no_scd && scdown_fused_valid(scd_params(e, o))) {
                 o.form = FORM_SCDOWN; e.ops[o.scd_pre].skip = true; o.kernel = scdown_fused_kernel_name(scd_params(e, o));
                 continue;
@@ -951,7 +951,7 @@ static int make_plan(yp_engine& e, int B, int H, int W) {
     // op launches the kernel; the conv's own output is written as well when anything else reads it. Not when an op that still launches
     // sits between the two and reads the conv's output (the kernel runs at the SPATIAL op's place in the order).
     {
-        static const bool no_pwsp = [] { const char* v = std::getenv("YOLOP_NO_PWSP"); return v && *v == '1'; }();   // A/B switch
+        static const bool no_pwsp = env_on("YOLOP_NO_PWSP");   // A/B switch
         for (size_t i = 0; i < e.ops.size(); ++i) {
             Op& d = e.ops[i];
             if (d.pw_pre < 0 || e.dtype != DT_BF16 || !e.fuse || no_pwsp || d.skip || d.form != FORM_PLAIN) continue;
@@ -984,7 +984,7 @@ static int make_plan(yp_engine& e, int B, int H, int W) {
     }
     // class logits + class-max keys in one launch (cls_out_kernel): the OP_AMAX op is skipped
     {
-        static const bool no_co = [] { const char* v = std::getenv("YOLOP_NO_CLSOUT"); return v && *v == '1'; }();   // A/B switch
+        static const bool no_co = env_on("YOLOP_NO_CLSOUT");   // A/B switch
         for (auto& o : e.ops) {
             if (o.kind != OP_CONV || o.amax_post < 0 || e.dtype != DT_BF16 || !e.fuse || no_co) continue;
             if (!plain_conv(o) || o.folded || e.ops[o.amax_post].skip) continue;
@@ -1427,9 +1427,6 @@ static hipError_t run_op(yp_engine& e, const Op& o, const RunArgs& a, hipStream_
 // Plan-time autotuner: for every dense conv that the LDS-DMA kernel supports, time each valid tile configuration on
 // the real tensors (weights are loaded, activations hold whatever the arena holds - timing does not depend on values
 // up to DVFS) and keep the fastest. Runs once per (B,H,W) plan, outside any graph capture.
-static bool views_overlap(const View& a, const View& b);
-static void op_views(const yp_engine& e, const Op& o, std::vector<View>& rd, std::vector<View>& wr);
-
 static int autotune(yp_engine& e) {
     if (e.dtype != DT_BF16) return YP_OK;
     hipEvent_t e0, e1;
@@ -1444,7 +1441,7 @@ static int autotune(yp_engine& e) {
     // replayed graph leaves it (fresh in the Infinity Cache, partly in the producing XCDs' L2) - neither as warm as mode 0 nor as cold
     // as mode 1. Measured end to end (same box, two runs each): mode 1 15.37 / 15.43 k img/s, mode 2 15.27 / 15.21 k - the cold ranking
     // stays the default
-    static const int cold_mode = [] { const char* v = std::getenv("YOLOP_TUNE_COLD"); return v ? atoi(v) : 1; }();
+    static const int cold_mode = env_int("YOLOP_TUNE_COLD", 1);
     void* flush = nullptr;
     const size_t flush_bytes = (size_t)320 << 20;
     if (cold_mode) HIPCHK(hipMalloc(&flush, flush_bytes));
@@ -1502,8 +1499,7 @@ static int autotune(yp_engine& e) {
         static const std::vector<bool> family_on = [] {
             std::vector<bool> v;
             for (const ConvFamily* f : kConvFamilies) {
-                const char* s = f->tune_env ? std::getenv(f->tune_env) : nullptr;
-                v.push_back((s && *s == '1') == f->opt_in);          // A/B switch (YOLOP_NO_*) or opt-in
+                v.push_back((f->tune_env && env_on(f->tune_env)) == f->opt_in);          // A/B switch (YOLOP_NO_*) or opt-in
             }
             return v;
         }();
@@ -1514,7 +1510,7 @@ static int autotune(yp_engine& e) {
             for (int c = 0; c < f.num_cfgs; ++c)
                 if ((f.two_source || p.x2_C == 0) && f.valid(p, c)) cands.push_back(f.base + c);
         }
-        static const bool no_ps = [] { const char* v = std::getenv("YOLOP_NO_PWSP"); return v && *v == '1'; }();     // A/B switch
+        static const bool no_ps = env_on("YOLOP_NO_PWSP");     // A/B switch
         if (o.kind == OP_CONV && !no_ps && !o.folded && p.x2_C == 0 && pwsp_valid(pwsp_params(e, o))) cands.push_back(PWSP_CFG);
         for (int cc : cands) {
             o.cfg = cc;
@@ -1561,8 +1557,7 @@ static const int TUNE_TABLE_VERSION = 5;
 // or a table this build cannot launch, falls through to the tuner as before. YOLOP_NO_TUNE_TABLES=1 ignores them.
 static std::string packaged_table_prefix() {
     static const std::string pre = [] {
-        const char* off = std::getenv("YOLOP_NO_TUNE_TABLES");
-        if (off && *off == '1') return std::string();
+        if (env_on("YOLOP_NO_TUNE_TABLES")) return std::string();
         Dl_info info;
         if (!dladdr((const void*)&packaged_table_prefix, &info) || !info.dli_fname) return std::string();
         std::string dir(info.dli_fname);
@@ -2010,9 +2005,9 @@ int yp_create(const yp_model_desc* desc, int device, yp_engine** out) {
     install_fatal_handlers();
     std::unique_ptr<yp_engine> e(new yp_engine());
     e->desc = *desc; e->device = device; e->dtype = desc->dtype;
-    { const char* nf = std::getenv("YOLOP_NO_FUSE"); e->fuse = !(nf && *nf == '1'); }
-    { const char* tf = std::getenv("YOLOP_TAIL"); e->tail = tf && *tf == '1'; }
-    { const char* dh = std::getenv("YOLOP_DENSE_HEAD"); e->sparse_head = !(dh && *dh == '1'); }
+    e->fuse = !env_on("YOLOP_NO_FUSE");
+    e->tail = env_on("YOLOP_TAIL");
+    e->sparse_head = !env_on("YOLOP_DENSE_HEAD");
     int rc = build_graph(*e);
     if (rc != YP_OK) return rc;
     for (const Op& o : e->ops)
@@ -2320,7 +2315,7 @@ static int forward_replay(yp_engine* e, const uint8_t* in_dev, int B, int H, int
     const bool same_plan = e->gexec && e->gkey.B == B && e->gkey.H == H && e->gkey.W == W && e->gkey.in == (const void*)in_dev;
     if (e->direct_out && same_plan && (e->gkey.det != det_out || e->gkey.idx != idx_out || e->gkey.coeff != cf) && ++e->out_changes >= 2)
         e->direct_out = false;                        // this caller rotates its output buffers: engine-owned results + copy-out from now on
-    static const int own_mode = [] { const char* v = std::getenv("YOLOP_REPLAY_OWN_STREAM"); return v ? atoi(v) : 0; }();   // A/B switch: 1 = round 2's path, 2 = own stream + direct outputs
+    static const int own_mode = env_int("YOLOP_REPLAY_OWN_STREAM", 0);   // A/B switch: 1 = round 2's path, 2 = own stream + direct outputs
     const bool own = own_mode != 0 || st == nullptr;
     const bool direct = own_mode != 1 && e->direct_out && det_out && idx_out && (!seg || cf);
     RunArgs ag = direct ? RunArgs{in_dev, det_out, idx_out, cf} : RunArgs{in_dev, e->o_det, e->o_idx, seg ? e->o_coeff : nullptr};
@@ -2395,7 +2390,7 @@ int yp_forward(yp_engine* e, const uint8_t* in_dev, int B, int H, int W, float* 
             ms[mode] += now_ms();
         }
         it = e->auto_replay.emplace(std::array<int, 3>{B, H, W}, ms[1] < ms[0]).first;
-        static const bool say = [] { const char* v = std::getenv("YOLOP_VERBOSE"); return v && *v == '1'; }();
+        static const bool say = env_on("YOLOP_VERBOSE");
         if (say) fprintf(stderr, "[yolop] %dx%dx%d: eager %.3f ms, replay %.3f ms per call -> %s\n", B, H, W, ms[0] / 6, ms[1] / 6, it->second ? "replay" : "eager");
         return YP_OK;                                   // (the timed calls produced this call's outputs)
     }

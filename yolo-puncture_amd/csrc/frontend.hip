@@ -20,14 +20,6 @@
 
 namespace yp {
 
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-typedef __attribute__((address_space(3))) void lds_void;
-
-__device__ __forceinline__ float silu_fe(float x) { return x * __builtin_amdgcn_rcpf(1.0f + __expf(-x)); }
-__device__ __forceinline__ void silu4(float* v) { silu4_packed(v); }
-__device__ __forceinline__ int fswz(int row) { return ((row >> 2) & 1) << 1; }
-
 constexpr int FE_TH = 8;                         // output rows per tile (4 waves in M x 2 rows)
 constexpr int FE_HR = 2 * FE_TH + 1;             // 17 stem rows
 constexpr int FE_HP = FE_HR * 33;                // 561 stem pixels per tile
@@ -79,7 +71,7 @@ __device__ __forceinline__ void fe_row(const FeRows& r, int sx, unsigned char* d
     }
     const uint4* r4 = (const uint4*)row;
 #pragma unroll
-    for (int c = 0; c < 4; ++c) *(uint4*)(dst + hp * 64 + ((c ^ fswz(hp)) * 16)) = r4[c];
+    for (int c = 0; c < 4; ++c) *(uint4*)(dst + hp * 64 + ((c ^ cswz64(hp)) * 16)) = r4[c];
 }
 
 __global__ __launch_bounds__(FE_NW * 64) void frontend_kernel(const FrontParams p, const int tiles_h, const int tiles_w, const int G) {
@@ -100,11 +92,7 @@ __global__ __launch_bounds__(FE_NW * 64) void frontend_kernel(const FrontParams 
     const int fr = lane & 15, fc = lane >> 4;
     const int num_tiles = p.B * tiles_h * tiles_w;
 
-    int bid = blockIdx.x;
-    {
-        const int nwg = gridDim.x, q = nwg >> 3, r = nwg & 7, xcd = bid & 7, j = bid >> 3;
-        bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + j;
-    }
+    const int bid = xcd_remap(blockIdx.x, gridDim.x);
 
     const __amdgpu_buffer_rsrc_t w1rs = __builtin_amdgcn_make_buffer_rsrc((void*)p.w1, 0, (int)p.w1_bytes, 0x00020000);
     const __amdgpu_buffer_rsrc_t w2rs = __builtin_amdgcn_make_buffer_rsrc((void*)p.w2, 0, (int)p.w2_bytes, 0x00020000);
@@ -127,7 +115,7 @@ __global__ __launch_bounds__(FE_NW * 64) void frontend_kernel(const FrontParams 
     for (int ii = wave; ii < 9 * BN * 64 / 1024; ii += FE_NW) {          // model.1: row rg = tap*BN + n
         const int s = ii * 64 + lane;
         const int rg = s >> 2, pc = s & 3;
-        const int c8 = pc ^ fswz(rg);
+        const int c8 = pc ^ cswz64(rg);
         const int n = rg % BN, tap = rg / BN;
         const unsigned voff = (unsigned)((n * p.Kpad1 + tap * 32 + c8 * 8) * 2);
         __builtin_amdgcn_raw_ptr_buffer_load_lds(w1rs, (lds_void*)(W1s + ii * 1024), 16, voff, 0, 0, 0);
@@ -142,7 +130,7 @@ __global__ __launch_bounds__(FE_NW * 64) void frontend_kernel(const FrontParams 
     for (int ii = wave; ii < 2; ii += FE_NW) {                           // stem: [32 co][32 k]
         const int s = ii * 64 + lane;
         const int row = s >> 2, pc = s & 3;
-        const int c8 = pc ^ fswz(row);
+        const int c8 = pc ^ cswz64(row);
         const unsigned voff = (unsigned)((row * 32 + c8 * 8) * 2);
         __builtin_amdgcn_raw_ptr_buffer_load_lds(w0rs, (lds_void*)(W0s + ii * 1024), 16, voff, 0, 0, 0);
     }
@@ -227,10 +215,10 @@ __global__ __launch_bounds__(FE_NW * 64) void frontend_kernel(const FrontParams 
                 for (int h = 0; h < 2; ++h) {
                     __attribute__((aligned(8))) __bf16 o[4];
                     float sv[4] = {acc[j][h][0], acc[j][h][1], acc[j][h][2], acc[j][h][3]};
-                    if (p.act0 == ACT_SILU) silu4(sv);
+                    if (p.act0 == ACT_SILU) silu4_packed(sv);
 #pragma unroll
                     for (int i = 0; i < 4; ++i) o[i] = (__bf16)(in[j] ? sv[i] : 0.f);
-                    if (hp < FE_HP) *(uint2*)(Hs + hp * 64 + (((2 * h + (fc >> 1)) ^ fswz(hp)) * 16) + (fc & 1) * 8) = *(const uint2*)o;
+                    if (hp < FE_HP) *(uint2*)(Hs + hp * 64 + (((2 * h + (fc >> 1)) ^ cswz64(hp)) * 16) + (fc & 1) * 8) = *(const uint2*)o;
                 }
             }
         };
@@ -289,7 +277,7 @@ __global__ __launch_bounds__(FE_NW * 64) void frontend_kernel(const FrontParams 
                 const int co = wn * (FN * 16) + a * 16 + fc * 4;
                 __attribute__((aligned(8))) __bf16 o[4];
                 float sv[4] = {acc[a][r][0], acc[a][r][1], acc[a][r][2], acc[a][r][3]};
-                if (p.act1 == ACT_SILU) silu4(sv);
+                if (p.act1 == ACT_SILU) silu4_packed(sv);
 #pragma unroll
                 for (int i = 0; i < 4; ++i) o[i] = (__bf16)sv[i];
                 *(uint2*)(Hs + px * 128 + (((co >> 3) ^ ((px >> 1) & 7)) * 16) + (co & 7) * 2) = *(const uint2*)o;
@@ -332,7 +320,7 @@ __global__ __launch_bounds__(FE_NW * 64) void frontend_kernel(const FrontParams 
             for (int a = 0; a < FN; ++a) {
                 const int co = wn * (FN * 16) + a * 16 + fc * 4;
                 float v[4] = {acc[a][r][0], acc[a][r][1], acc[a][r][2], acc[a][r][3]};
-                if (p.act2 == ACT_SILU) silu4(v);
+                if (p.act2 == ACT_SILU) silu4_packed(v);
                 const unsigned off = pix_ok ? (m * (unsigned)p.y_stride + (unsigned)(p.y_coff + co)) * 2u : OOB;
                 __attribute__((aligned(8))) __bf16 o[4] = {(__bf16)v[0], (__bf16)v[1], (__bf16)v[2], (__bf16)v[3]};
                 __builtin_amdgcn_raw_buffer_store_b64(*(const __attribute__((ext_vector_type(2))) unsigned*)o, yrs, off, 0, 0);
@@ -364,13 +352,9 @@ hipError_t launch_frontend(const FrontParams& p, hipStream_t st) {
     const int num_tiles = p.B * tiles_h * tiles_w;
     int G = 256;
     if (G > num_tiles) G = num_tiles;
-    static bool attr = false;
-    if (!attr) {
-        hipError_t e = hipFuncSetAttribute((const void*)frontend_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(160 * 1024));
-        if (e != hipSuccess) return e;
-        attr = true;
-    }
-    static const bool clocks = [] { const char* v = std::getenv("YOLOP_FRONT_CLOCKS"); return v && *v == '1'; }();   // debug: per-stage s_memtime sums
+    static size_t granted = 0;
+    if (hipError_t e = allow_dynamic_lds((const void*)frontend_kernel, sh, granted)) return e;
+    static const bool clocks = env_on("YOLOP_FRONT_CLOCKS");   // debug: per-stage s_memtime sums
     if (clocks) {
         FrontParams q = p;
         const size_t n = (size_t)G * FE_NW * 6;

@@ -23,7 +23,6 @@ constexpr int MAXK = 512;        // max top-k supported (rank-sorted in one step
 __device__ unsigned long long g_head_clk[8];
 #define HEAD_STAMP(i) do { if (blockIdx.x == 0 && threadIdx.x == 0) g_head_clk[i] = wall_clock64(); } while (0)
 
-__device__ __forceinline__ float sigmoidf_(float x) { return 1.0f / (1.0f + expf(-x)); }
 __device__ __forceinline__ unsigned long long make_key(float score, unsigned flat) {
     return ((unsigned long long)__float_as_uint(score) << 32) | (unsigned long long)(0xFFFFFFFFu - flat);
 }
@@ -55,7 +54,7 @@ __global__ __launch_bounds__(256) void anchor_max_kernel(const HeadParams p, uns
     }
 #pragma unroll
     for (int o = 8; o >= 1; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o, 16));
-    if (sub == 0 && item < total) mkey[item] = __float_as_uint(sigmoidf_(mx));
+    if (sub == 0 && item < total) mkey[item] = __float_as_uint(sigmoid_ieee(mx));
 }
 
 // nc % 4 == 0 form: a workgroup owns 64 consecutive anchors of one level of one image = 16*nc consecutive float4s, read
@@ -85,7 +84,7 @@ __global__ __launch_bounds__(256) void anchor_max4_kernel(const HeadParams p, un
         for (int j = sub; j < q; j += 4) mx = fmaxf(mx, part[a * q + j]);
     mx = fmaxf(mx, __shfl_xor(mx, 1, 64));
     mx = fmaxf(mx, __shfl_xor(mx, 2, 64));
-    if (a < na && sub == 0) mkey[(size_t)b * p.A + abase + a0 + a] = __float_as_uint(sigmoidf_(mx));
+    if (a < na && sub == 0) mkey[(size_t)b * p.A + abase + a0 + a] = __float_as_uint(sigmoid_ieee(mx));
 }
 
 // one level, one launch (OP_AMAX): the class-max pass of a level runs on that level's class lane as soon as its logits exist,
@@ -115,7 +114,7 @@ __global__ __launch_bounds__(256) void anchor_max_level_kernel(const float* __re
     }
     mx = fmaxf(mx, __shfl_xor(mx, 1, 64));
     mx = fmaxf(mx, __shfl_xor(mx, 2, 64));
-    if (a < na && sub == 0) out[(size_t)b * HW + a0 + a] = __float_as_uint(sigmoidf_(mx));
+    if (a < na && sub == 0) out[(size_t)b * HW + a0 + a] = __float_as_uint(sigmoid_ieee(mx));
 }
 
 hipError_t launch_anchor_max_level(const float* cls, int B, int HW, int nc, unsigned* out, hipStream_t st) {
@@ -494,7 +493,7 @@ __global__ __launch_bounds__(HT) void head_select_kernel(const HeadParams p, con
             __syncthreads();
             for (int j = before + tid; j < (int)nfill; j += HT) {   // the survivors' scores, on the dense list
                 const unsigned long long e = keys[j];
-                keys[j] = make_key(sigmoidf_(__uint_as_float((unsigned)(e >> 32))), (unsigned)(e & 0xFFFFFFFFull));
+                keys[j] = make_key(sigmoid_ieee(__uint_as_float((unsigned)(e >> 32))), (unsigned)(e & 0xFFFFFFFFull));
             }
             __syncthreads();
             f0 += take;
@@ -588,15 +587,10 @@ size_t head_scratch_bytes(int B, int A) { return (size_t)B * A * sizeof(unsigned
 
 static hipError_t head_attrs() {
     const size_t sh = (size_t)(CAP + 1536 + HT) * 8 + MAXK * 4 + MAXK * 8;
-    static bool attr_set = false;
-    if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute((const void*)head_select_kernel<0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh);
-        if (e == hipSuccess) e = hipFuncSetAttribute((const void*)head_select_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh);
-        if (e == hipSuccess) e = hipFuncSetAttribute((const void*)head_select_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh);
-        if (e != hipSuccess) return e;
-        attr_set = true;
-    }
-    return hipSuccess;
+    static size_t granted[3] = {0, 0, 0};
+    if (hipError_t e = allow_dynamic_lds((const void*)head_select_kernel<0>, sh, granted[0])) return e;
+    if (hipError_t e = allow_dynamic_lds((const void*)head_select_kernel<1>, sh, granted[1])) return e;
+    return allow_dynamic_lds((const void*)head_select_kernel<2>, sh, granted[2]);
 }
 
 hipError_t launch_head(const HeadParams& p, hipStream_t st) {

@@ -28,15 +28,8 @@
 
 namespace yp {
 
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-typedef __attribute__((address_space(3))) void lds_void;
 typedef const __attribute__((address_space(1))) bf16x8* gfrag;       // weight fragments: GLOBAL loads (a generic pointer would make them flat_load,
                                                                       // which also counts in lgkmcnt and drags the LDS waits along)
-
-__device__ __forceinline__ void hb_write8(unsigned char* dst, uint2 v) {
-    asm volatile("ds_write_b64 %0, %1" ::"v"((unsigned)(size_t)(__attribute__((address_space(3))) unsigned char*)dst), "v"(*(const unsigned long long*)&v) : "memory");
-}
 
 // phase timestamps (100 MHz) of workgroup 0's first tile in the last head_pos_kernel launch (yp_debug_head_branch_clocks)
 __device__ unsigned long long g_hb_clk[8];
@@ -212,7 +205,7 @@ __global__ __launch_bounds__(256) void head_win_kernel(const HeadBranchParams p)
         if (p.act1 == ACT_SILU) silu4_packed(v);
         __attribute__((aligned(8))) __bf16 o[4] = {(__bf16)v[0], (__bf16)v[1], (__bf16)v[2], (__bf16)v[3]};
         const int c8 = (2 * (cf & 1) + (fc >> 1)) & 3;
-        hb_write8(T1 + (size_t)(cf >> 1) * 16 * 64 + swz64((unsigned)(fr * 64 + c8 * 16)) + (fc & 1) * 8, *(const uint2*)o);
+        lds_write8(T1 + (size_t)(cf >> 1) * 16 * 64 + swz64((unsigned)(fr * 64 + c8 * 16)) + (fc & 1) * 8, *(const uint2*)o);
     } else {
         __builtin_amdgcn_s_waitcnt(0 | (7 << 4) | (0xF << 8));
         __builtin_amdgcn_s_barrier();
@@ -249,13 +242,9 @@ bool head_branch_valid(const HeadBranchParams& p) {
 hipError_t launch_head_branch(const HeadBranchParams& p, hipStream_t st) {
     if (!p.plist || !p.pcount || !p.t0) return hipErrorInvalidValue;
     const dim3 grid((unsigned)((p.max_det + 15) / 16), 3, (unsigned)p.B);
-    static bool attr = false;
-    if (!attr) {
-        hipError_t e = hipFuncSetAttribute((const void*)head_pos_kernel<64>, hipFuncAttributeMaxDynamicSharedMemorySize, 3 * 9 * 64 * 64);
-        if (e == hipSuccess) e = hipFuncSetAttribute((const void*)head_pos_kernel<32>, hipFuncAttributeMaxDynamicSharedMemorySize, 3 * 9 * 64 * 64);
-        if (e != hipSuccess) return e;
-        attr = true;
-    }
+    static size_t granted[2] = {0, 0};
+    if (hipError_t e = allow_dynamic_lds((const void*)head_pos_kernel<64>, 3 * 9 * 64 * 64, granted[0])) return e;
+    if (hipError_t e = allow_dynamic_lds((const void*)head_pos_kernel<32>, 3 * 9 * 64 * 64, granted[1])) return e;
     if (p.cmid == 64) {
         hipLaunchKernelGGL((head_pos_kernel<64>), dim3((unsigned)p.pos_grid), dim3(256), 3 * 9 * 64 * 64, st, p);
         hipLaunchKernelGGL((head_win_kernel<64, 64>), grid, dim3(256), 2 * 10 * 1024, st, p);

@@ -16,8 +16,6 @@ constexpr int NT = 1024;
 constexpr int NCAP = 16384;           // sorted-key capacity (power of two >= the 12288-anchor limit of the plan)
 constexpr int NMAXK = 512;
 
-__device__ __forceinline__ float nms_sigmoid(float x) { return 1.0f / (1.0f + expf(-x)); }
-
 struct NmsLocate {
     int A0, A1, A2;
     __device__ __forceinline__ void operator()(int a, int& l, int& loc, int& HWl) const {
@@ -44,14 +42,14 @@ __global__ __launch_bounds__(256) void head_nms_decode_kernel(const HeadParams p
     // the sigmoid is evaluated for those alone
     float m = -INFINITY;
     for (int c = 0; c < p.nc; ++c) m = fmaxf(m, cp[c]);
-    const float sm = nms_sigmoid(m);
+    const float sm = sigmoid_ieee(m);
     const float lo = (sm >= 1.0f) ? 15.0f : m - fmaxf(1e-3f, 1e-4f * fabsf(m));
     float best = -1.f;
     int cls = 0;
     for (int c = 0; c < p.nc; ++c) {
         const float v = cp[c];
         if (v >= lo) {
-            const float s = nms_sigmoid(v);
+            const float s = sigmoid_ieee(v);
             if (s > best) { best = s; cls = c; }
         }
     }
@@ -214,12 +212,8 @@ size_t head_nms_scratch_bytes(int B, int A) { return (size_t)B * A * 8 * sizeof(
 hipError_t launch_head_nms(const HeadParams& p, hipStream_t st) {
     if (p.A > 12288 || p.max_det > NMAXK || !p.mk[0] || !p.nms_params || !p.nms_ws) return hipErrorInvalidValue;
     const size_t sh = (size_t)NCAP * 8;
-    static bool attr_set = false;
-    if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute((const void*)head_nms_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh);
-        if (e != hipSuccess) return e;
-        attr_set = true;
-    }
+    static size_t granted = 0;
+    if (hipError_t e = allow_dynamic_lds((const void*)head_nms_kernel, sh, granted)) return e;
     const long items = (long)p.B * p.A;
     hipLaunchKernelGGL(head_nms_decode_kernel, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, st, p);
     hipLaunchKernelGGL(head_nms_kernel, dim3(p.B), dim3(NT), sh, st, p);

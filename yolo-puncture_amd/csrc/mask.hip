@@ -61,7 +61,6 @@ __global__ __launch_bounds__(256) void mask_gemm_kernel(const MaskParams p, floa
 // proto[pixel][k] with v_mfma_f32_16x16x4_f32 - exact fp32 FMAs accumulated in k order, i.e. the very chain
 // fmaf(c[k], p[k], acc) of the scalar kernel above, so the two give the same bits (tests compare the tail with the oracle
 // either way). One wave = 16 pixels x all masks, 16 masks per accumulator; coefficients are read from LDS as the A operand.
-typedef __attribute__((ext_vector_type(4))) float mf32x4;
 template <typename T>
 __device__ __forceinline__ void mask_gemm_mfma_body(const MaskParams& p, float* M, float* cs) {
     // cs: dynamic LDS [ceil16(n)][32], rows >= n zero
@@ -80,7 +79,7 @@ __device__ __forceinline__ void mask_gemm_mfma_body(const MaskParams& p, float* 
 #pragma unroll
     for (int j = 0; j < 8; ++j) b[j] = (float)pp[4 * j + fk];
     for (int m0 = 0; m0 < npad; m0 += 16) {
-        mf32x4 acc = {0.f, 0.f, 0.f, 0.f};
+        f32x4 acc = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int j = 0; j < 8; ++j) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(cs[(m0 + fr) * 32 + 4 * j + fk], b[j], acc, 0, 0, 0);
         if (pix0 + fr < npix) {
@@ -269,7 +268,7 @@ hipError_t launch_masks(const MaskParams& p, int dtype, hipStream_t st) {
     hipError_t e = hipMemsetAsync(area, 0, (size_t)p.n * sizeof(int32_t), st);
     if (e != hipSuccess) return e;
     const int npix = p.ch * p.cw;
-    static const bool valu_gemm = [] { const char* v = std::getenv("YOLOP_MASK_VALU"); return v && *v == '1'; }();   // A/B: scalar form
+    static const bool valu_gemm = env_on("YOLOP_MASK_VALU");   // A/B: scalar form
     if (valu_gemm) {
         const size_t sh = (size_t)p.n * 32 * sizeof(float);
         if (dtype == DT_BF16) hipLaunchKernelGGL(mask_gemm_kernel<__bf16>, dim3((npix + 255) / 256), dim3(256), sh, st, p, M);
@@ -410,7 +409,7 @@ hipError_t launch_masks_frames(const MaskFramesParams& f, float* M, int dtype, h
     if (f.k == 0) return hipSuccess;
     const MaskParams& p = f.p;
     const int npix = p.ch * p.cw;
-    static const bool valu_gemm = [] { const char* v = std::getenv("YOLOP_MASK_VALU"); return v && *v == '1'; }();   // as launch_masks
+    static const bool valu_gemm = env_on("YOLOP_MASK_VALU");   // as launch_masks
     if (valu_gemm) {
         const size_t sh = (size_t)p.n * 32 * sizeof(float);
         if (dtype == DT_BF16) hipLaunchKernelGGL(mask_frames_gemm_kernel<__bf16>, dim3((npix + 255) / 256, f.k), dim3(256), sh, st, f, M);

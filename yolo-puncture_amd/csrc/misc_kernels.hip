@@ -6,11 +6,6 @@
 
 namespace yp {
 
-__device__ __forceinline__ float silu_f(float x) { return x / (1.0f + expf(-x)); }   // fp32 parity mode: library expf, IEEE division
-// bf16 storage: v_rcp_f32 (1 ulp) instead of the IEEE division sequence (~12 instructions) - same form as the conv epilogues
-__device__ __forceinline__ float silu_q(float x) { return x * __builtin_amdgcn_rcpf(1.0f + __expf(-x)); }
-template <typename T> __device__ __forceinline__ float silu_t(float x) { return sizeof(T) == 2 ? silu_q(x) : silu_f(x); }
-
 template <typename T> struct Vec8;
 template <> struct Vec8<__bf16> {
     uint4 raw;
@@ -52,10 +47,6 @@ template <> struct Vec8<float> {
         a = make_float4(f[0], f[1], f[2], f[3]); b = make_float4(f[4], f[5], f[6], f[7]);
     }
 };
-
-template <typename T> __device__ __forceinline__ float round_to(float x);
-template <> __device__ __forceinline__ float round_to<__bf16>(float x) { return (float)(__bf16)x; }
-template <> __device__ __forceinline__ float round_to<float>(float x) { return x; }
 
 // ---------------------------------------------------------------------------------------------------------
 // stem: uint8 BGR NHWC -> Conv(3->C0, k3 s2 p1)+bias+SiLU. x/255 (IEEE division, as `im.float()/255`),
@@ -100,7 +91,7 @@ __global__ __launch_bounds__(256) void stem_kernel(const StemParams p) {
     }
     if (p.act == ACT_SILU) {
 #pragma unroll
-        for (int j = 0; j < 8; ++j) acc[j] = silu_f(acc[j]);
+        for (int j = 0; j < 8; ++j) acc[j] = silu_ieee(acc[j]);
     }
     Vec8<T> o;
     o.pack(acc);
@@ -112,9 +103,6 @@ __global__ __launch_bounds__(256) void stem_kernel(const StemParams p) {
 // (27 taps of uint8 -> x/255 -> bf16, zero-padded to K=32) straight into LDS, then 4 waves run
 // D[cout][pixel] = W[cout][32] * X[pixel][32] with MFMA 16x16x32 and store 4 consecutive couts per lane.
 // ---------------------------------------------------------------------------------------------------------
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8_t;
-typedef __attribute__((ext_vector_type(4))) float f32x4_t;
-__device__ __forceinline__ int swz32(int row) { return ((row >> 2) & 1) << 1; }
 
 template <int FN>
 __global__ __launch_bounds__(256) void stem_mfma_kernel(const StemParams p, const __bf16* __restrict__ wpk) {
@@ -170,26 +158,26 @@ __global__ __launch_bounds__(256) void stem_mfma_kernel(const StemParams p, cons
         }
         const uint4* r4 = (const uint4*)row;
 #pragma unroll
-        for (int c = 0; c < 4; ++c) *(uint4*)(Xs + tid * 64 + ((c ^ swz32(tid)) * 16)) = r4[c];
+        for (int c = 0; c < 4; ++c) *(uint4*)(Xs + tid * 64 + ((c ^ cswz64(tid)) * 16)) = r4[c];
     }
     for (int i = tid; i < FN * 16 * 4; i += 256) {
         const int r = i >> 2, c = i & 3;
-        *(uint4*)(Ws + r * 64 + ((c ^ swz32(r)) * 16)) = *(const uint4*)(wpk + r * 32 + c * 8);
+        *(uint4*)(Ws + r * 64 + ((c ^ cswz64(r)) * 16)) = *(const uint4*)(wpk + r * 32 + c * 8);
     }
     __syncthreads();
     const int fr = lane & 15, fc = lane >> 4;
-    bf16x8_t wf[FN], xf[4];
+    bf16x8 wf[FN], xf[4];
 #pragma unroll
-    for (int a = 0; a < FN; ++a) { const int r = a * 16 + fr; wf[a] = *(const bf16x8_t*)(Ws + r * 64 + ((fc ^ swz32(r)) * 16)); }
+    for (int a = 0; a < FN; ++a) { const int r = a * 16 + fr; wf[a] = *(const bf16x8*)(Ws + r * 64 + ((fc ^ cswz64(r)) * 16)); }
 #pragma unroll
-    for (int b = 0; b < 4; ++b) { const int r = wave * 64 + b * 16 + fr; xf[b] = *(const bf16x8_t*)(Xs + r * 64 + ((fc ^ swz32(r)) * 16)); }
+    for (int b = 0; b < 4; ++b) { const int r = wave * 64 + b * 16 + fr; xf[b] = *(const bf16x8*)(Xs + r * 64 + ((fc ^ cswz64(r)) * 16)); }
 #pragma unroll
     for (int a = 0; a < FN; ++a) {
         const int co = a * 16 + fc * 4;
         const float4 bs = *(const float4*)(p.bias + co);
 #pragma unroll
         for (int b = 0; b < 4; ++b) {
-            f32x4_t acc = {0.f, 0.f, 0.f, 0.f};
+            f32x4 acc = {0.f, 0.f, 0.f, 0.f};
             acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[a], xf[b], acc, 0, 0, 0);
             const int mm = (int)blockIdx.x * 256 + wave * 64 + b * 16 + fr;
             if (mm >= M) continue;
@@ -488,19 +476,6 @@ __global__ __launch_bounds__(256) void sppf_pool3_kernel(const PoolParams p) {
 // bf16 fast form: 32 channels (four 16-B pieces) of one image per workgroup, separable 5x5 max (row pass, column pass),
 // values kept in LDS as order-preserving int16 keys (k = x ^ ((x >> 15) & 0x7fff), an involution) so that one
 // v_pk_max_i16 handles two channels; clamped neighbour indices replace the -inf padding (max ignores duplicates).
-typedef short short2v __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ unsigned bf16x2_key(unsigned d) {
-    const unsigned s = (d >> 15) & 0x00010001u;
-    return d ^ ((s << 15) - s);
-}
-__device__ __forceinline__ uint4 key4(const uint4 v) { return make_uint4(bf16x2_key(v.x), bf16x2_key(v.y), bf16x2_key(v.z), bf16x2_key(v.w)); }
-__device__ __forceinline__ unsigned pkmax(unsigned a, unsigned b) {
-    const short2v r = __builtin_elementwise_max(__builtin_bit_cast(short2v, a), __builtin_bit_cast(short2v, b));
-    return __builtin_bit_cast(unsigned, r);
-}
-__device__ __forceinline__ uint4 pkmax4(const uint4 a, const uint4 b) {
-    return make_uint4(pkmax(a.x, b.x), pkmax(a.y, b.y), pkmax(a.z, b.z), pkmax(a.w, b.w));
-}
 
 __global__ __launch_bounds__(256) void sppf_pool3_bf16_kernel(const PoolParams p) {
     extern __shared__ __attribute__((aligned(16))) unsigned char plds[];
@@ -514,7 +489,7 @@ __global__ __launch_bounds__(256) void sppf_pool3_bf16_kernel(const PoolParams p
     const int items = HW * 4;
     for (int i = threadIdx.x; i < items; i += 256) {
         const uint4 v = *(const uint4*)(xb + (size_t)(i >> 2) * p.x_stride + (i & 3) * 8);
-        *(uint4*)(bufA + i * 16) = key4(v);
+        *(uint4*)(bufA + i * 16) = bf16x8_key(v);
     }
     __syncthreads();
     for (int stage = 0; stage < 3; ++stage) {
@@ -543,7 +518,7 @@ __global__ __launch_bounds__(256) void sppf_pool3_bf16_kernel(const PoolParams p
             m = pkmax4(m, *(const uint4*)(col + (size_t)(y3 * W) * 64));
             m = pkmax4(m, *(const uint4*)(col + (size_t)(y4 * W) * 64));
             *(uint4*)(dst + i * 16) = m;
-            *(uint4*)(yb + (size_t)px * p.y_stride + (i & 3) * 8) = key4(m);
+            *(uint4*)(yb + (size_t)px * p.y_stride + (i & 3) * 8) = bf16x8_key(m);
         }
         __syncthreads();
     }
@@ -560,12 +535,8 @@ hipError_t launch_sppf_pool3(const PoolParams& p, int dtype, hipStream_t st) {
     if (!sppf_pool3_fits(p, dtype)) return hipErrorInvalidValue;
     if (dtype == DT_BF16 && (p.C & 31) == 0 && (p.x_stride & 7) == 0 && (p.x_coff & 7) == 0 && (p.y_stride & 7) == 0 && (p.y_coff & 7) == 0) {
         const size_t sh = (size_t)p.H * p.W * 192;
-        static bool attr = false;
-        if (!attr) {
-            hipError_t e = hipFuncSetAttribute((const void*)sppf_pool3_bf16_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
-            if (e != hipSuccess) return e;
-            attr = true;
-        }
+        static size_t granted = 0;
+        if (hipError_t e = allow_dynamic_lds((const void*)sppf_pool3_bf16_kernel, sh, granted)) return e;
         hipLaunchKernelGGL(sppf_pool3_bf16_kernel, dim3((unsigned)(p.B * (p.C / 32))), dim3(256), sh, st, p);
         return hipGetLastError();
     }

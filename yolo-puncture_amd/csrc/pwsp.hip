@@ -24,24 +24,7 @@
 
 namespace yp {
 
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(4))) float f32x4;
 typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
-typedef __attribute__((address_space(3))) void lds_void;
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef short short2v __attribute__((ext_vector_type(2)));
-
-__device__ __forceinline__ unsigned ps_key2(unsigned d) {               // bf16 pair -> order-preserving int16 pair (an involution)
-    const unsigned s = (d >> 15) & 0x00010001u;
-    return d ^ ((s << 15) - s);
-}
-__device__ __forceinline__ uint4 ps_key4(const uint4 v) { return make_uint4(ps_key2(v.x), ps_key2(v.y), ps_key2(v.z), ps_key2(v.w)); }
-__device__ __forceinline__ unsigned ps_max2(unsigned a, unsigned b) {
-    const short2v r = __builtin_elementwise_max(__builtin_bit_cast(short2v, a), __builtin_bit_cast(short2v, b));
-    return __builtin_bit_cast(unsigned, r);
-}
-__device__ __forceinline__ uint4 ps_max4(const uint4 a, const uint4 b) { return make_uint4(ps_max2(a.x, b.x), ps_max2(a.y, b.y), ps_max2(a.z, b.z), ps_max2(a.w, b.w)); }
-__device__ __forceinline__ float ps_silu(float x) { return x * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(x * -1.4426950408889634f)); }
 
 // phase stamps (core clock, s_memtime) of workgroup 0 / wave 0 in the last launch: [0] start, [1] prologue issued, [2] GEMM done, [3] epilogue
 // done, [4] behind the barrier, [5] spatial stage done; [8 + g] at the top of k-step g (g < 16). yp_debug_pwsp_clocks reads them.
@@ -312,7 +295,7 @@ __global__ __launch_bounds__(PS_NT) void pwsp_kernel(const PwSpParams p) {
                 for (int j = 0; j < DW_PW; ++j) {
                     if (oy0 + i >= p.H || ox0 + j >= p.W) continue;
                     float v0 = o[i][j][0], v1 = o[i][j][1];
-                    if (p.actd == ACT_SILU) { v0 = ps_silu(v0); v1 = ps_silu(v1); }
+                    if (p.actd == ACT_SILU) { v0 = silu_rcp(v0); v1 = silu_rcp(v1); }
                     const unsigned pix = pix0 + (unsigned)(i * p.W + j);
                     if (p.res) {
                         const unsigned rr = *(const unsigned*)((const __bf16*)p.res + (size_t)(pix * (unsigned)p.res_stride + (unsigned)(p.res_coff + c)));
@@ -328,7 +311,7 @@ __global__ __launch_bounds__(PS_NT) void pwsp_kernel(const PwSpParams p) {
         unsigned char* const bufB = img + (size_t)HW * 64;
         unsigned char* const tmp = img + (size_t)HW * 128;
         const int items = HW * 4, W = p.W, H = p.H;
-        for (int i = tid; i < items; i += PS_NT) *(uint4*)(bufA + i * 16) = ps_key4(*(const uint4*)(bufA + i * 16));
+        for (int i = tid; i < items; i += PS_NT) *(uint4*)(bufA + i * 16) = bf16x8_key(*(const uint4*)(bufA + i * 16));
         __syncthreads();
         for (int stage = 0; stage < 3; ++stage) {
             const unsigned char* src = (stage & 1) ? bufB : bufA;
@@ -338,10 +321,10 @@ __global__ __launch_bounds__(PS_NT) void pwsp_kernel(const PwSpParams p) {
                 const int x0 = max(x - 2, 0), x1 = max(x - 1, 0), x3 = min(x + 1, W - 1), x4 = min(x + 2, W - 1);
                 const unsigned char* row = src + (size_t)(y * W) * 64 + (i & 3) * 16;
                 uint4 m = *(const uint4*)(row + x * 64);
-                m = ps_max4(m, *(const uint4*)(row + x0 * 64));
-                m = ps_max4(m, *(const uint4*)(row + x1 * 64));
-                m = ps_max4(m, *(const uint4*)(row + x3 * 64));
-                m = ps_max4(m, *(const uint4*)(row + x4 * 64));
+                m = pkmax4(m, *(const uint4*)(row + x0 * 64));
+                m = pkmax4(m, *(const uint4*)(row + x1 * 64));
+                m = pkmax4(m, *(const uint4*)(row + x3 * 64));
+                m = pkmax4(m, *(const uint4*)(row + x4 * 64));
                 *(uint4*)(tmp + i * 16) = m;
             }
             __syncthreads();
@@ -351,12 +334,12 @@ __global__ __launch_bounds__(PS_NT) void pwsp_kernel(const PwSpParams p) {
                 const int y0 = max(y - 2, 0), y1 = max(y - 1, 0), y3 = min(y + 1, H - 1), y4 = min(y + 2, H - 1);
                 const unsigned char* col = tmp + (size_t)x * 64 + (i & 3) * 16;
                 uint4 m = *(const uint4*)(col + (size_t)(y * W) * 64);
-                m = ps_max4(m, *(const uint4*)(col + (size_t)(y0 * W) * 64));
-                m = ps_max4(m, *(const uint4*)(col + (size_t)(y1 * W) * 64));
-                m = ps_max4(m, *(const uint4*)(col + (size_t)(y3 * W) * 64));
-                m = ps_max4(m, *(const uint4*)(col + (size_t)(y4 * W) * 64));
+                m = pkmax4(m, *(const uint4*)(col + (size_t)(y0 * W) * 64));
+                m = pkmax4(m, *(const uint4*)(col + (size_t)(y1 * W) * 64));
+                m = pkmax4(m, *(const uint4*)(col + (size_t)(y3 * W) * 64));
+                m = pkmax4(m, *(const uint4*)(col + (size_t)(y4 * W) * 64));
                 *(uint4*)(dst + i * 16) = m;
-                *(uint4*)(yb + (size_t)pxl * p.y2_stride + (i & 3) * 8) = ps_key4(m);
+                *(uint4*)(yb + (size_t)pxl * p.y2_stride + (i & 3) * 8) = bf16x8_key(m);
             }
             __syncthreads();
         }
@@ -381,7 +364,7 @@ static size_t pwsp_lds_bytes(const PwSpParams& p, int NS) {
 int pwsp_slice(const PwSpParams& p) {
     // 64-channel slices while that still gives every CU a workgroup, else 32 (the pool form is written for 32)
     if (p.sp == 3) return 32;
-    static const int force = [] { const char* v = std::getenv("YOLOP_PWSP_NS"); return v ? atoi(v) : 0; }();      // experiment: slice width
+    static const int force = env_int("YOLOP_PWSP_NS", 0);      // experiment: slice width
     if (force == 32) return 32;
     if (force == 64 && (p.C1 % 64) == 0 && (p.sp == 0 || ((p.sp_c0 % 64) == 0 && (p.Csp % 64) == 0))) return 64;
     // (>= 96 workgroups: the wider slice halves the redundant reads of the image's pixels - every slice's workgroup pulls all of them through its
@@ -420,12 +403,8 @@ template <int NS, int SP>
 static hipError_t launch_pwsp_t(const PwSpParams& p, hipStream_t st) {
     const size_t sh = pwsp_lds_bytes(p, NS);
     auto kern = pwsp_kernel<NS, SP>;
-    static size_t attr = 0;
-    if (sh > attr && sh > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e != hipSuccess) return e;
-        attr = 160 * 1024;
-    }
+    static size_t granted = 0;
+    if (hipError_t e = allow_dynamic_lds((const void*)kern, sh, granted)) return e;
     hipLaunchKernelGGL(kern, dim3((unsigned)(p.B * (p.C1 / NS))), dim3(PS_NT), sh, st, p);
     return hipGetLastError();
 }

@@ -19,10 +19,6 @@
 
 namespace yp {
 
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-typedef __attribute__((address_space(3))) void lds_void;
-
 constexpr int SD_NW = 8;
 constexpr int SD_TH = 4, SD_TW = 8;                     // output tile
 constexpr int SD_RH = 2 * SD_TH + 1, SD_RW = 2 * SD_TW + 1;   // 9 x 17 patch of the 1x1's output / input
@@ -32,11 +28,6 @@ constexpr int SD_XB = SD_XP * 1024;
 constexpr int SD_TB = 160 * 128;                        // t: [160 px][64 ch]
 constexpr int SD_WB = 64 * 256;                         // one group's 1x1 weights [64 co][128 k]
 constexpr int SD_LDS = 2 * SD_XB + 2 * SD_TB + 2 * SD_WB + 5120 + 2048;   // 160768 B
-
-// (LDS accesses next to in-flight LDS-DMA go through inline asm: see conv_dwpw.hip)
-__device__ __forceinline__ void sd_write8(unsigned char* dst, unsigned long long v) {
-    asm volatile("ds_write_b64 %0, %1" ::"v"((unsigned)(size_t)(__attribute__((address_space(3))) unsigned char*)dst), "v"(v) : "memory");
-}
 
 __global__ __launch_bounds__(SD_NW * 64) void scdown_fused_kernel(const ScdParams p, const int tiles_h, const int tiles_w, const int G) {
     constexpr unsigned OOB = 0x80000000u;
@@ -53,11 +44,7 @@ __global__ __launch_bounds__(SD_NW * 64) void scdown_fused_kernel(const ScdParam
     const int num_tiles = p.B * tiles_h * tiles_w;
     const int ngroups = p.C >> 6;
 
-    int bid = blockIdx.x;
-    {
-        const int nwg = gridDim.x, q = nwg >> 3, r = nwg & 7, xcd = bid & 7, j = bid >> 3;
-        bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + j;
-    }
+    const int bid = xcd_remap(blockIdx.x, gridDim.x);
 
     const __amdgpu_buffer_rsrc_t xrs = __builtin_amdgcn_make_buffer_rsrc((void*)p.x, 0, (int)p.x_bytes, 0x00020000);
     const __amdgpu_buffer_rsrc_t wrs = __builtin_amdgcn_make_buffer_rsrc((void*)p.w1, 0, (int)p.w1_bytes, 0x00020000);
@@ -205,7 +192,7 @@ __global__ __launch_bounds__(SD_NW * 64) void scdown_fused_kernel(const ScdParam
 #pragma unroll
                     for (int i = 0; i < 4; ++i) ob[i] = (__bf16)(in ? v[i] : 0.f);
                     const int ch = cf * 16 + fc * 4;
-                    sd_write8(Tg + qq * 128 + (((ch >> 3) ^ ((qq >> 1) & 7)) * 16) + (ch & 7) * 2, *(const unsigned long long*)ob);
+                    lds_write8(Tg + qq * 128 + (((ch >> 3) ^ ((qq >> 1) & 7)) * 16) + (ch & 7) * 2, *(const unsigned long long*)ob);
                 }
             }
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
@@ -240,13 +227,9 @@ hipError_t launch_scdown_fused(const ScdParams& p, hipStream_t st) {
     const int num_tiles = p.B * tiles_h * tiles_w;
     int G = 256;
     if (G > num_tiles) G = num_tiles;
-    static bool attr = false;
-    if (!attr) {
-        hipError_t e = hipFuncSetAttribute((const void*)scdown_fused_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(160 * 1024));
-        if (e != hipSuccess) return e;
-        attr = true;
-    }
-    static const bool clocks = [] { const char* v = std::getenv("YOLOP_SCD_CLOCKS"); return v && *v == '1'; }();   // debug: per-stage s_memtime sums
+    static size_t granted = 0;
+    if (hipError_t e = allow_dynamic_lds((const void*)scdown_fused_kernel, (size_t)SD_LDS, granted)) return e;
+    static const bool clocks = env_on("YOLOP_SCD_CLOCKS");   // debug: per-stage s_memtime sums
     if (clocks) {
         ScdParams q = p;
         const size_t n = (size_t)G * SD_NW * 4;

@@ -17,11 +17,6 @@
 
 namespace yp {
 
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-typedef __attribute__((ext_vector_type(2))) float f32x2;
-typedef __attribute__((address_space(3))) void lds_void;
-
 constexpr int SS_NW = 8;
 constexpr int SS_T = 4;                               // 4 x 4 output pixels per tile
 constexpr int SS_R = 2 * SS_T + 1;                    // 9 x 9 patch
@@ -29,12 +24,6 @@ constexpr int SS_RP = SS_R * SS_R;                    // 81 patch pixels
 constexpr int SS_FM = 6;                              // pixel fragments (96 rows; rows 81.. are nothing)
 constexpr int SS_C = 256;                             // intermediate / output channels
 constexpr int SS_TB = SS_FM * 16 * SS_C * 2;          // t: [96 px][256 ch] bf16 = 48 KB
-
-template <int N> __device__ __forceinline__ void ss_wait_vm() {
-    static_assert(N >= 0 && N < 64, "vmcnt range");
-    __builtin_amdgcn_s_waitcnt((N & 0xF) | (7 << 4) | (0xF << 8) | (((N >> 4) & 3) << 14));
-}
-__device__ __forceinline__ unsigned ss_lds_addr(const void* p) { return (unsigned)(size_t)(const __attribute__((address_space(3))) unsigned char*)p; }
 
 template <int NKS>
 __global__ __launch_bounds__(SS_NW * 64, 2) void scdown_stream_kernel(const ScdParams p, const int tiles_h, const int tiles_w, const int num_tiles, const int G) {
@@ -109,7 +98,7 @@ __global__ __launch_bounds__(SS_NW * 64, 2) void scdown_stream_kernel(const ScdP
         bd = f32x2{p.biasd[2 * cp], p.biasd[2 * cp + 1]};
     }
     // (known complete before the loop, then passed through empty asm statements: see conv_wres.hip)
-    ss_wait_vm<0>();
+    wait_vmcnt<0>();
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
 #pragma unroll
@@ -121,11 +110,11 @@ __global__ __launch_bounds__(SS_NW * 64, 2) void scdown_stream_kernel(const ScdP
     for (int t = 0; t < 9; ++t) asm volatile("" : "+v"(wd[t]));
     asm volatile("" : "+v"(bd));
 
-    const unsigned ts_l = ss_lds_addr(Ts);
+    const unsigned ts_l = lds_addr(Ts);
     for (int it = 0; tile < num_tiles; tile += G, ++it) {
         // (a) this tile's patch has landed (issued in front of the previous tile's stores, which may still fly)
-        if (it == 0) ss_wait_vm<0>();
-        else ss_wait_vm<NST>();
+        if (it == 0) wait_vmcnt<0>();
+        else wait_vmcnt<NST>();
         __builtin_amdgcn_s_barrier();
         const int slot = it & 1;
         issue_tile(tile + G, slot ^ 1);
@@ -205,16 +194,16 @@ __global__ __launch_bounds__(SS_NW * 64, 2) void scdown_stream_kernel(const ScdP
             }
         }
     }
-    ss_wait_vm<0>();
+    wait_vmcnt<0>();
 }
 
 bool scdown_stream_valid(const ScdParams& p) {
-    static const bool off = [] { const char* v = std::getenv("YOLOP_NO_SCD_STREAM"); return v && *v == '1'; }();   // A/B switch
+    static const bool off = env_on("YOLOP_NO_SCD_STREAM");   // A/B switch
     if (off || p.clk) return false;
     // K = 128 (`model.5`: 59.5 us stand-alone against 66-67.5, same-box A/B of the step -9 us). K = 256 (`model.20`: 32.4 us against 22.4 + 12.7
     // for the two kernels it replaces) costs a lone batch 7 us per step and GAINS 12 us with two batches in flight (1.4302 against 1.4422 ms,
     // three tunings each: one launch holds the CUs for less time than two) - on, since the ring is how batches are run. YOLOP_SCD_STREAM_K=128 / 256: one width only.
-    static const int only_k = [] { const char* v = std::getenv("YOLOP_SCD_STREAM_K"); return v ? atoi(v) : 0; }();
+    static const int only_k = env_int("YOLOP_SCD_STREAM_K", 0);
     if (only_k && p.K != only_k) return false;
     if ((p.K != 128 && p.K != 256) || p.Kpad1 != p.K || p.C != SS_C) return false;
     if ((p.x_stride & 7) || (p.x_coff & 7) || (p.y_stride & 1) || (p.y_coff & 1)) return false;
@@ -233,12 +222,8 @@ template <int NKS>
 static hipError_t launch_scdown_stream_t(const ScdParams& p, hipStream_t st) {
     const size_t sh = (size_t)2 * SS_FM * 16 * NKS * 64 + SS_TB;
     auto kern = scdown_stream_kernel<NKS>;
-    static bool attr = false;
-    if (!attr) {
-        hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e != hipSuccess) return e;
-        attr = true;
-    }
+    static size_t granted = 0;
+    if (hipError_t e = allow_dynamic_lds((const void*)kern, sh, granted)) return e;
     const int tiles_h = (p.Ho + SS_T - 1) / SS_T, tiles_w = (p.Wo + SS_T - 1) / SS_T;
     const int num_tiles = p.B * tiles_h * tiles_w;
     const int G = num_tiles < 256 ? num_tiles : 256;

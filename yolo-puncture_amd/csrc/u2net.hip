@@ -359,16 +359,6 @@ __global__ __launch_bounds__(256) void u2_pool_kernel(const T* __restrict__ x, i
     for (int q = 0; q < 4; ++q) o[q] = (T)m[q];
 }
 
-// F.upsample(size=..., mode='bilinear') = upsample_bilinear2d, align_corners=False: src = scale*(dst+0.5)-0.5 clamped at 0
-__device__ __forceinline__ void u2_bil(int dst, int n_in, int n_out, int& i0, int& i1, float& l0, float& l1) {
-    const float scale = (float)n_in / (float)n_out;
-    float f = scale * ((float)dst + 0.5f) - 0.5f;
-    f = fmaxf(f, 0.f);
-    i0 = (int)f;
-    i1 = i0 + ((i0 < n_in - 1) ? 1 : 0);
-    l1 = f - (float)i0;
-    l0 = 1.f - l1;
-}
 template <typename T>
 __global__ __launch_bounds__(256) void u2_up_kernel(const T* __restrict__ x, int xs, int xc, T* __restrict__ y, int ys, int yc, int B, int H, int W,
                                                    int Ho, int Wo, int C) {
@@ -389,8 +379,8 @@ __global__ __launch_bounds__(256) void u2_up_kernel(const T* __restrict__ x, int
     }
     int y0, y1, x0, x1;
     float ly0, ly1, lx0, lx1;
-    u2_bil(ho, H, Ho, y0, y1, ly0, ly1);
-    u2_bil(wo, W, Wo, x0, x1, lx0, lx1);
+    bilinear_tap(ho, H, Ho, y0, y1, ly0, ly1);
+    bilinear_tap(wo, W, Wo, x0, x1, lx0, lx1);
     const T* p00 = x + ((size_t)(b * H + y0) * W + x0) * xs + xc + c;
     const T* p01 = x + ((size_t)(b * H + y0) * W + x1) * xs + xc + c;
     const T* p10 = x + ((size_t)(b * H + y1) * W + x0) * xs + xc + c;
@@ -429,8 +419,8 @@ __global__ __launch_bounds__(256) void u2_tail_kernel(const U2Tail t) {
             else {
                 int y0, y1, x0, x1;
                 float ly0, ly1, lx0, lx1;
-                u2_bil(ho, t.h[k], t.H, y0, y1, ly0, ly1);
-                u2_bil(wo, t.w[k], t.W, x0, x1, lx0, lx1);
+                bilinear_tap(ho, t.h[k], t.H, y0, y1, ly0, ly1);
+                bilinear_tap(wo, t.w[k], t.W, x0, x1, lx0, lx1);
                 v = ly0 * (lx0 * s[y0 * t.w[k] + x0] + lx1 * s[y0 * t.w[k] + x1]) + ly1 * (lx0 * s[y1 * t.w[k] + x0] + lx1 * s[y1 * t.w[k] + x1]);
             }
             acc = fmaf(t.fuse[k], v, acc);
