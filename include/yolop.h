@@ -227,6 +227,14 @@ int yp_u2net_set_graph(yp_u2net* e, int enable);   /* hipGraph replay of the for
 int yp_u2net_tensor_count(const yp_u2net* e);
 int yp_u2net_tensor_info(const yp_u2net* e, int i, char* name, int name_cap, int dims[4] /*B,H,W,C*/);
 int yp_u2net_tensor_read(yp_u2net* e, int i, float* host_out);   /* sync copy NHWC -> fp32 host (debug taps) */
+/*    Read-only view of the plan (per-op tests): yp_u2net_op_info writes op i's name and up to info_cap of its YP_U2_OP_INFO = 17 fields
+ *      [kind (0 input, 1 conv, 2 pool, 3 up), in (tensor, coff, C), out (tensor, coff, C), res (tensor or -1, coff, C), dil, act (0 none,
+ *      2 ReLU), logical Cin, impl (-1 not chosen yet, 0 conv_igemm, 1 conv_small, 2 conv_small taking its pool / up-sample while loading,
+ *      3 conv_halo_f32), pool_op, up_op, consumer (op indices or -1)] and returns 17. impl is that of the current plan: final once a
+ *      forward of the shape has run. A pool / up op whose consumer has impl 2 does not launch (its output tensor is not written). */
+#define YP_U2_OP_INFO 17
+int yp_u2net_op_count(const yp_u2net* e);
+int yp_u2net_op_info(const yp_u2net* e, int i, char* name, int name_cap, int32_t* info, int info_cap);
 
 /* -- EfficientNet-B3 needle classifier: the third network of the reference's video loop, `load_classify_net` +
  *    `predict_and_find_start_inserted` (yolo_seg/app.py:116-123 -> yolo_seg/tasks/needle_clasify.py:41-199), efficientnet_pytorch's

@@ -110,7 +110,8 @@ def test_unet_predict_surface():
 
 
 def test_bf16_mode_is_close():
-    """bf16 storage / fp32 accumulation: not the parity mode; the fused map stays within a few 1e-2 of the fp32 reference path"""
+    """bf16 storage / fp32 accumulation: not the parity mode; the fused map stays within a few 1e-2 of the fp32 reference path
+    (end-to-end closeness only: the bf16 parity check is the per-op suite, test_gpu_u2net_perop.py)"""
     st = synthetic_state("p", 0)
     im = rand_image((1, 160, 160, 3), seed=3)
     x = im.flip(-1).permute(0, 3, 1, 2).float() / 255.0
@@ -145,7 +146,8 @@ def test_conv_kernel_choice_forced(small_max, dtype, monkeypatch):
     """The engine times conv_igemm, the K-split small-map kernel (conv_small.hip) and the halo-tile kernel for large maps
     (conv_halo_f32.hip) per layer; here each is forced for every layer it can run (YOLOP_U2_SMALL_MAX, read at create: 0 = conv_igemm
     everywhere, otherwise conv_small up to that many output pixels and the halo kernel above) and held to the reference fixture: fp32 to the 1e-3 bound of the other
-    tests (both kernels are fp32 FMA chains, they differ in summation order only), bf16 to the bf16 mode's closeness bound."""
+    tests (both kernels are fp32 FMA chains, they differ in summation order only), bf16 to the bf16 mode's closeness bound
+    (the parity check of every forced kernel, per op and in both dtypes, is test_gpu_u2net_perop.py)."""
     monkeypatch.setenv("YOLOP_U2_SMALL_MAX", small_max)
     z = np.load(os.path.join(GOLD, "u2netp_b.npz"))
     B, H, W = (int(v) for v in z["shape"])

@@ -133,6 +133,22 @@ int main() {
             CHECK(yp_u2net_forward_crops(u, frame_stub, 2, 720, 1280, w, ok_idx, 1, 380, 380, nullptr, nullptr, nullptr, nullptr) == YP_ERR_ARG);
         // valid arguments: refused only because no weights were finalized (no device here)
         CHECK(yp_u2net_forward_crops(u, frame_stub, 2, 720, 1280, ok_win, dup_idx, 2, 380, 380, nullptr, nullptr, nullptr, nullptr) == YP_ERR_STATE);
+        // the plan's read-only view (yp_u2net_op_info): input + 112 REBNCONVs + 6 side convs + pools + up-samples, short buffers respected
+        const int nops = yp_u2net_op_count(u);
+        int nconv = 0;
+        for (int i = 0; i < nops; ++i) {
+            char on[8];
+            int32_t info[YP_U2_OP_INFO + 1];
+            info[YP_U2_OP_INFO] = 12345;
+            CHECK(yp_u2net_op_info(u, i, on, sizeof(on), info, YP_U2_OP_INFO) == YP_U2_OP_INFO && info[YP_U2_OP_INFO] == 12345);
+            CHECK(info[13] == -1);                                       // impl: nothing is chosen before a plan's first pass
+            nconv += info[0] == 1;
+            int32_t two[3] = {-7, -7, -7};
+            CHECK(yp_u2net_op_info(u, i, nullptr, 0, two, 2) == YP_U2_OP_INFO && two[0] == info[0] && two[2] == -7);
+        }
+        CHECK(nconv == 118);
+        CHECK(yp_u2net_op_info(u, nops, nullptr, 0, nullptr, 0) == YP_ERR_ARG && yp_u2net_op_info(u, -1, nullptr, 0, nullptr, 0) == YP_ERR_ARG);
+        CHECK(yp_u2net_op_count(nullptr) == YP_ERR_ARG);
         CHECK(yp_u2net_destroy(u) == YP_OK);
     }
     // clip form of the YOLO segmentation pass (yp_masks_frames, yp_masks_frames_input, yp_letterbox_batch): bad arguments fail before

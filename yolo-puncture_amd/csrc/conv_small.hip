@@ -28,10 +28,10 @@ template <> struct CsT<float> {
     typedef float4 Vec;
     static __device__ __forceinline__ Vec zero() { return make_float4(0.f, 0.f, 0.f, 0.f); }
     static __device__ __forceinline__ Vec vmax(const Vec& a, const Vec& b) { return make_float4(fmaxf(a.x, b.x), fmaxf(a.y, b.y), fmaxf(a.z, b.z), fmaxf(a.w, b.w)); }
-    // bilinear tap, the expression of u2_up_kernel (u2net.hip)
+    // bilinear tap: the operations of u2_up_kernel (u2net.hip), bit for bit (bilinear_blend)
     static __device__ __forceinline__ Vec lerp(const Vec& a, const Vec& b, const Vec& c, const Vec& d, float ly0, float ly1, float lx0, float lx1) {
-        return make_float4(ly0 * (lx0 * a.x + lx1 * b.x) + ly1 * (lx0 * c.x + lx1 * d.x), ly0 * (lx0 * a.y + lx1 * b.y) + ly1 * (lx0 * c.y + lx1 * d.y),
-                           ly0 * (lx0 * a.z + lx1 * b.z) + ly1 * (lx0 * c.z + lx1 * d.z), ly0 * (lx0 * a.w + lx1 * b.w) + ly1 * (lx0 * c.w + lx1 * d.w));
+        return make_float4(bilinear_blend(a.x, b.x, c.x, d.x, ly0, ly1, lx0, lx1), bilinear_blend(a.y, b.y, c.y, d.y, ly0, ly1, lx0, lx1),
+                           bilinear_blend(a.z, b.z, c.z, d.z, ly0, ly1, lx0, lx1), bilinear_blend(a.w, b.w, c.w, d.w, ly0, ly1, lx0, lx1));
     }
     static __device__ __forceinline__ void mma(f32x4& acc, const Vec& w, const Vec& x) {
         acc = __builtin_amdgcn_mfma_f32_16x16x4f32(w.x, x.x, acc, 0, 0, 0);
@@ -49,10 +49,10 @@ template <> struct CsT<__bf16> {
     }
     static __device__ __forceinline__ Vec vmax(const Vec& a, const Vec& b) { return make_uint2(max2(a.x, b.x), max2(a.y, b.y)); }
     static __device__ __forceinline__ unsigned lerp2(unsigned a, unsigned b, unsigned c, unsigned d, float ly0, float ly1, float lx0, float lx1) {
-        const float lo = ly0 * (lx0 * __uint_as_float(a << 16) + lx1 * __uint_as_float(b << 16)) + ly1 * (lx0 * __uint_as_float(c << 16) + lx1 * __uint_as_float(d << 16));
-        const float hi = ly0 * (lx0 * __uint_as_float(a & 0xffff0000u) + lx1 * __uint_as_float(b & 0xffff0000u)) +
-                         ly1 * (lx0 * __uint_as_float(c & 0xffff0000u) + lx1 * __uint_as_float(d & 0xffff0000u));
-        __attribute__((aligned(4))) __bf16 o[2] = {(__bf16)lo, (__bf16)hi};                 // (rounded as the stand-alone kernel stores it)
+        const float lo = bilinear_blend(__uint_as_float(a << 16), __uint_as_float(b << 16), __uint_as_float(c << 16), __uint_as_float(d << 16), ly0, ly1, lx0, lx1);
+        const float hi = bilinear_blend(__uint_as_float(a & 0xffff0000u), __uint_as_float(b & 0xffff0000u), __uint_as_float(c & 0xffff0000u),
+                                        __uint_as_float(d & 0xffff0000u), ly0, ly1, lx0, lx1);
+        __attribute__((aligned(4))) __bf16 o[2] = {(__bf16)lo, (__bf16)hi};                 // (rounded as the stand-alone kernel stores it: same operations, same bits)
         return *(const unsigned*)o;
     }
     static __device__ __forceinline__ Vec lerp(const Vec& a, const Vec& b, const Vec& c, const Vec& d, float ly0, float ly1, float lx0, float lx1) {

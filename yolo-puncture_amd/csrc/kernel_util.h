@@ -107,7 +107,11 @@ template <> __device__ __forceinline__ float round_to<float>(float x) { return x
 
 // F.upsample(size=..., mode='bilinear') = upsample_bilinear2d, align_corners=False: src = scale*(dst+0.5)-0.5 clamped at 0.
 // Source indices i0, i1 and their weights l0, l1 for destination index dst of an n_in -> n_out resize.
+// This and bilinear_blend are ONE fixed sequence of IEEE fp32 operations (no contraction into FMAs, which the compiler would choose per
+// call site): every kernel that resizes - stand-alone, while loading a convolution's operand, in the tail - gets the same bits, and a host
+// restatement with one rounding per operation gets them too (tests/perop_u2net.py: bilinear_f32).
 __device__ __forceinline__ void bilinear_tap(int dst, int n_in, int n_out, int& i0, int& i1, float& l0, float& l1) {
+#pragma clang fp contract(off)
     const float scale = (float)n_in / (float)n_out;
     float f = scale * ((float)dst + 0.5f) - 0.5f;
     f = fmaxf(f, 0.f);
@@ -115,6 +119,13 @@ __device__ __forceinline__ void bilinear_tap(int dst, int n_in, int n_out, int& 
     i1 = i0 + ((i0 < n_in - 1) ? 1 : 0);
     l1 = f - (float)i0;
     l0 = 1.f - l1;
+}
+// the four taps (a b / c d) blended: along each row first, then the two rows
+__device__ __forceinline__ float bilinear_blend(float a, float b, float c, float d, float ly0, float ly1, float lx0, float lx1) {
+#pragma clang fp contract(off)
+    const float top = lx0 * a + lx1 * b;
+    const float bot = lx0 * c + lx1 * d;
+    return ly0 * top + ly1 * bot;
 }
 
 }  // namespace yp

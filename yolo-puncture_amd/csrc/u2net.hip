@@ -91,6 +91,7 @@ struct yp_u2net {
     // conv_small.hip vs conv_igemm.hip per convolution: small_max < 0 = timed per layer in a plan's first pass (default), otherwise
     // conv_small takes every layer it can run with at most small_max output pixels (YOLOP_U2_SMALL_MAX; 0 = never). Read at create.
     long small_max = -1;
+    bool fuse_pool = true;              // conv_small may take a pool / up-sample while loading (YOLOP_U2_FUSE_POOL, 0 = never). Read at create.
     int pB = 0, pH = 0, pW = 0;
     void* arena = nullptr;
     size_t arena_bytes = 0;
@@ -387,7 +388,7 @@ __global__ __launch_bounds__(256) void u2_up_kernel(const T* __restrict__ x, int
     const T* p11 = x + ((size_t)(b * H + y1) * W + x1) * xs + xc + c;
 #pragma unroll
     for (int q = 0; q < 4; ++q)
-        o[q] = (T)(ly0 * (lx0 * (float)p00[q] + lx1 * (float)p01[q]) + ly1 * (lx0 * (float)p10[q] + lx1 * (float)p11[q]));
+        o[q] = (T)bilinear_blend((float)p00[q], (float)p01[q], (float)p10[q], (float)p11[q], ly0, ly1, lx0, lx1);
 }
 
 struct U2Tail {
@@ -421,7 +422,7 @@ __global__ __launch_bounds__(256) void u2_tail_kernel(const U2Tail t) {
                 float ly0, ly1, lx0, lx1;
                 bilinear_tap(ho, t.h[k], t.H, y0, y1, ly0, ly1);
                 bilinear_tap(wo, t.w[k], t.W, x0, x1, lx0, lx1);
-                v = ly0 * (lx0 * s[y0 * t.w[k] + x0] + lx1 * s[y0 * t.w[k] + x1]) + ly1 * (lx0 * s[y1 * t.w[k] + x0] + lx1 * s[y1 * t.w[k] + x1]);
+                v = bilinear_blend(s[y0 * t.w[k] + x0], s[y0 * t.w[k] + x1], s[y1 * t.w[k] + x0], s[y1 * t.w[k] + x1], ly0, ly1, lx0, lx1);
             }
             acc = fmaf(t.fuse[k], v, acc);
         }
@@ -590,9 +591,8 @@ static int u2_tune_op(yp_u2net& e, U2Op& o, hipStream_t st) {
     const ConvParams p = u2_conv_params(e, o);
     const bool can_small = conv_small_valid(p, e.dtype), can_halo = conv_halo_f32_valid(p, e.dtype);
     if (!can_small && !can_halo) { o.impl = 0; return YP_OK; }
-    static const bool fuse_pool = [] { const char* s = getenv("YOLOP_U2_FUSE_POOL"); return !(s && s[0] == '0'); }();
     const int pre_op = o.pool_op >= 0 ? o.pool_op : o.up_op;      // the pool / up-sample this conv could take while loading (at most one)
-    const bool can_fuse = can_small && fuse_pool && pre_op >= 0 && conv_small_valid(u2_conv_params(e, o, true), e.dtype);
+    const bool can_fuse = can_small && e.fuse_pool && pre_op >= 0 && conv_small_valid(u2_conv_params(e, o, true), e.dtype);
     if (e.small_max >= 0) {                              // forced (tests): conv_small up to small_max pixels, the halo kernel above it
         o.impl = (can_small && u2_default_impl(e, p)) ? (can_fuse ? 2 : 1) : ((can_halo && e.small_max > 0) ? 3 : 0);
         return YP_OK;
@@ -656,6 +656,7 @@ int yp_u2net_create(int variant, int dtype, int device, yp_u2net** out) {
     std::unique_ptr<yp_u2net> e(new yp_u2net());
     e->variant = variant; e->dtype = dtype; e->device = device;
     if (const char* sm = getenv("YOLOP_U2_SMALL_MAX")) e->small_max = atol(sm);
+    if (const char* fp = getenv("YOLOP_U2_FUSE_POOL")) e->fuse_pool = fp[0] != '0';
     const int rc = build_u2net(*e);
     if (rc != YP_OK) return rc;
     *out = e.release();
@@ -949,6 +950,18 @@ int yp_u2net_tensor_read(yp_u2net* e, int i, float* host_out) {
         for (size_t j = 0; j < n; ++j) host_out[j] = bf2f(tmp[j]);
     }
     return YP_OK;
+}
+
+int yp_u2net_op_count(const yp_u2net* e) { return e ? (int)e->ops.size() : u2fail(YP_ERR_ARG, "null engine"); }
+
+int yp_u2net_op_info(const yp_u2net* e, int i, char* name, int cap, int32_t* info, int info_cap) {
+    if (!e || i < 0 || i >= (int)e->ops.size()) return u2fail(YP_ERR_ARG, "bad op index");
+    const U2Op& o = e->ops[i];
+    if (name && cap > 0) snprintf(name, cap, "%s", o.name.c_str());
+    const int32_t f[YP_U2_OP_INFO] = {o.kind, o.in.t, o.in.coff, o.in.C, o.out.t, o.out.coff, o.out.C, o.res.t, o.res.coff, o.res.C, o.dil, o.act,
+                                      o.widx >= 0 ? e->weights[o.widx].cin : 0, o.impl, o.pool_op, o.up_op, o.consumer};
+    for (int k = 0; info && k < info_cap && k < YP_U2_OP_INFO; ++k) info[k] = f[k];
+    return YP_U2_OP_INFO;
 }
 
 }  // extern "C"

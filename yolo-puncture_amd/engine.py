@@ -130,6 +130,7 @@ EXPORTS = ["yp_last_error", "yp_create", "yp_destroy", "yp_weight_count", "yp_we
            "yp_mask_contours_scaled", "yp_mask_contours_large_workspace", "yp_mask_contours_large", "yp_comm_unique_id", "yp_comm_create", "yp_allgather", "yp_comm_destroy",
            "yp_u2net_create", "yp_u2net_destroy", "yp_u2net_weight_count", "yp_u2net_weight_info", "yp_u2net_set_weight", "yp_u2net_finalize",
            "yp_u2net_forward", "yp_u2net_forward_crops", "yp_u2net_set_graph", "yp_u2net_tensor_count", "yp_u2net_tensor_info", "yp_u2net_tensor_read",
+           "yp_u2net_op_count", "yp_u2net_op_info",
            "yp_cls_create", "yp_cls_destroy", "yp_cls_weight_count", "yp_cls_weight_info", "yp_cls_set_weight", "yp_cls_finalize",
            "yp_cls_forward", "yp_cls_set_graph", "yp_cls_tensor_count", "yp_cls_tensor_info", "yp_cls_tensor_read"]
 

@@ -112,8 +112,11 @@ def _declare(lib: C.CDLL) -> None:
     lib.yp_u2net_tensor_count.argtypes = [vp]
     lib.yp_u2net_tensor_info.argtypes = [vp, C.c_int, C.c_char_p, C.c_int, C.POINTER(C.c_int)]
     lib.yp_u2net_tensor_read.argtypes = [vp, C.c_int, vp]
+    lib.yp_u2net_op_count.argtypes = [vp]
+    lib.yp_u2net_op_info.argtypes = [vp, C.c_int, C.c_char_p, C.c_int, C.POINTER(C.c_int32), C.c_int]
     for fn in ("yp_u2net_create", "yp_u2net_destroy", "yp_u2net_weight_count", "yp_u2net_weight_info", "yp_u2net_set_weight",
-               "yp_u2net_finalize", "yp_u2net_forward", "yp_u2net_forward_crops", "yp_u2net_tensor_count", "yp_u2net_tensor_info", "yp_u2net_tensor_read"):
+               "yp_u2net_finalize", "yp_u2net_forward", "yp_u2net_forward_crops", "yp_u2net_tensor_count", "yp_u2net_tensor_info", "yp_u2net_tensor_read",
+               "yp_u2net_op_count", "yp_u2net_op_info"):
         getattr(lib, fn).restype = C.c_int
     lib._u2_declared = True
 
@@ -231,6 +234,25 @@ class U2NetEngine:
         dims = (C.c_int * 4)()
         return [dict(index=i, name=(self._chk(self.lib.yp_u2net_tensor_info(self._h, i, name, 256, dims)), name.value.decode())[1], shape=tuple(dims))
                 for i in range(n)]
+
+    def ops(self) -> List[dict]:
+        """The ops of the current plan, in launch order (read-only): kind 'input' | 'conv' | 'pool' | 'up'; `in`, `out`, `res` = (tensor index,
+        first channel, channels), res[0] < 0 when there is none; dil, act (0 none, 2 ReLU), cin (logical), impl (-1 not chosen yet,
+        0 conv_igemm, 1 conv_small, 2 conv_small taking its pool / up-sample while loading, 3 conv_halo_f32: final after a forward of the
+        shape), pool_op / up_op (convs) and consumer (pools / up-samples): op indices or -1. A pool / up-sample whose consumer has impl 2
+        does not launch."""
+        n = self._chk(self.lib.yp_u2net_op_count(self._h))
+        name = C.create_string_buffer(256)
+        f = (C.c_int32 * 17)()
+        out = []
+        for i in range(n):
+            if self._chk(self.lib.yp_u2net_op_info(self._h, i, name, 256, f, 17)) != 17:
+                raise YolopError("yp_u2net_op_info: this library reports another field count than 17")
+            v = [int(x) for x in f]
+            out.append({"index": i, "name": name.value.decode(), "kind": ("input", "conv", "pool", "up")[v[0]], "in": tuple(v[1:4]),
+                        "out": tuple(v[4:7]), "res": tuple(v[7:10]), "dil": v[10], "act": v[11], "cin": v[12], "impl": v[13],
+                        "pool_op": v[14], "up_op": v[15], "consumer": v[16]})
+        return out
 
     def read_tensor(self, name: str) -> torch.Tensor:
         """Debug tap: NHWC fp32 host copy of an activation of the last forward."""
