@@ -322,6 +322,11 @@ int yp_debug_force_conv_cfg(int cfg);
    runs as pwsp_kernel, -1 where a heuristic picks or the op has no configuration id (fused forms other than the 3x3 s2 -> 1x1 pair, non-conv
    ops), -2 for a folded upsample no configuration can run. */
 int yp_debug_op_cfg(const yp_engine* e, int i, int* cfg);
+/* Test hook: the store form of the last conv launch of this process whose kernel has both: 1 = 16-byte stores in the paired channel order,
+   0 = the 8-byte form (a launch that misses the alignment or width conditions, or an engine created under YOLOP_NARROW_STORE=1, which keeps
+   the 8-byte stores everywhere), -1 = no such launch since the last call (the call resets it; launches record their form only from the first call on, so call it once
+   before the launch of interest). Read it right after yp_run_op. */
+int yp_debug_last_store_form(void);
 /* Test hook: the conv tile families' configuration id ranges [base, base + num_cfgs), in the autotuner's order. Fills at most cap entries of
    each array (either may be null) and returns the number of families. */
 int yp_debug_conv_families(int* base, int* num_cfgs, int cap);

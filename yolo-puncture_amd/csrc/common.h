@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <atomic>
 #include <cstdlib>
 #include <string>
 #include <vector>
@@ -136,6 +137,9 @@ struct ConvParams {
     int pool_in, src_H, src_W;
     // conv_small only: the x2 channels are a BILINEAR resize (align_corners = False) of x2 to H x W instead of the nearest x2 above
     int up_bilinear;
+    // bf16 epilogues: 1 = the engine asks for the paired channel order (16-byte stores, kernel_util.h). A launcher passes it on to its
+    // kernel only where wide_store_ok holds, so in a kernel it means "this launch is paired": weight fill and epilogue read the same flag
+    int wide;
 };
 
 struct DwParams {
@@ -280,6 +284,26 @@ inline hipError_t allow_dynamic_lds(const void* kern, size_t bytes, size_t& gran
     if (hipError_t e = hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)most)) return e;
     granted = most;
     return hipSuccess;
+}
+
+// The paired (16-byte) store form of a bf16 conv epilogue, decided per launch from the parameters alone (no tuner decision, no
+// configuration id): `frags` = 16-channel fragments per wave, `Cout` etc. of the kernel's FINAL store. It needs fragment pairs (even
+// frags), Cout in whole pairs (32 channels) and 16-byte aligned channel slices of y and of the residual; anything else - v10-N's narrow
+// layers, odd head widths, the fp32 outputs, YOLOP_NARROW_STORE=1 (want = 0) - takes the 8-byte form.
+// Test hook (yp_debug_last_store_form): what the last launch that can take either form took. Recorded only once the hook has been called,
+// so a production launch writes no shared state; atomics, as two engines may launch from two threads.
+inline std::atomic<bool>& store_form_watched() { static std::atomic<bool> v{false}; return v; }
+inline std::atomic<int>& last_store_form() { static std::atomic<int> v{-1}; return v; }
+inline bool wide_store_ok(int want, int frags, int Cout, int y_stride, int y_coff, bool out_f32, const void* res = nullptr, int res_stride = 0, int res_coff = 0) {
+    const bool ok = want && !out_f32 && frags > 0 && (frags & 1) == 0 && (Cout % 32) == 0 && (y_stride & 7) == 0 && (y_coff & 7) == 0 &&
+                    (!res || ((res_stride & 7) == 0 && (res_coff & 7) == 0));
+    if (store_form_watched().load(std::memory_order_relaxed)) last_store_form().store(ok ? 1 : 0, std::memory_order_relaxed);
+    return ok;
+}
+inline ConvParams with_store_form(const ConvParams& p, int frags) {
+    ConvParams q = p;
+    q.wide = wide_store_ok(p.wide, frags, p.Cout, p.y_stride, p.y_coff, p.out_f32 != 0, p.res, p.res_stride, p.res_coff) ? 1 : 0;
+    return q;
 }
 
 // launches (implemented in the .hip files); dtype selects the template instance

@@ -35,6 +35,7 @@ __global__ __launch_bounds__(WGM * WGN * 64) void conv_pxd_kernel(const ConvPara
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wm = wave % WGM, wn = wave / WGM;
     const int fr = lane & 15, fc = lane >> 4;
+    const bool wide = !OUT_F32 && p.wide != 0;                     // paired channel order (kernel_util.h): weight rows, bias, residual and store
 
     const int bid = xcd_remap(blockIdx.x, gridDim.x);
     const int mt = bid % mtiles, nt = bid / mtiles;
@@ -71,7 +72,7 @@ __global__ __launch_bounds__(WGM * WGN * 64) void conv_pxd_kernel(const ConvPara
         const int s = ii * 64 + lane;
         const int row = s >> 3, pc = s & 7;
         const int c = pc ^ ((row >> 1) & 7);
-        wconst[j] = (ii < W_INSTR) ? (unsigned)(((n0 + row) * p.Kpad + c * 8) * 2) : OOB;
+        wconst[j] = (ii < W_INSTR) ? (unsigned)(((n0 + weight_row_channel(row, wide)) * p.Kpad + c * 8) * 2) : OOB;
     }
     auto issue_w = [&](int kt, int slot) {
         unsigned char* dst = smem + slot * SLOT;
@@ -123,7 +124,7 @@ __global__ __launch_bounds__(WGM * WGN * 64) void conv_pxd_kernel(const ConvPara
     {
 #pragma unroll
         for (int a = 0; a < FN; ++a) {
-            const int co = n0 + wn * (FN * 16) + a * 16 + fc * 4;
+            const int co = n0 + wn * (FN * 16) + acc_channel(a, fc, wide);
             f32x4 b4;
 #pragma unroll
             for (int r = 0; r < 4; ++r) b4[r] = (co + r < p.Cout) ? p.bias[co + r] : 0.f;
@@ -188,6 +189,29 @@ __global__ __launch_bounds__(WGM * WGN * 64) void conv_pxd_kernel(const ConvPara
         const int ri = (wm * PXW + f) * 16 + fr;
         const int m = m0 + ri;
         const bool pix_ok = ri < BMe && m < p.M;
+        if (wide) {                                    // a fragment pair (2j, 2j+1) per step: one 16-byte store (and residual read) per lane
+#pragma unroll
+            for (int j = 0; j < FN / 2; ++j) {
+                const int co = n0 + wn * (FN * 16) + acc_channel(2 * j, fc, true);      // 8 channels from here: fragment 2j's four, then 2j+1's
+                const bool ok = pix_ok && (co < p.Cout);
+                float v[2][4];
+#pragma unroll
+                for (int h = 0; h < 2; ++h) {
+#pragma unroll
+                    for (int q = 0; q < 4; ++q) v[h][q] = acc[2 * j + h][f][q];
+                    if (p.act == ACT_SILU) silu4_packed(v[h]);
+                }
+                if (HAS_RES) {
+                    uint2 rr[2];
+                    load_res_bf16x8((const __bf16*)p.res + (size_t)m * p.res_stride + p.res_coff + co, ok, rr[0], rr[1]);
+                    add_res_bf16x4(v[0], rr[0]);
+                    add_res_bf16x4(v[1], rr[1]);
+                }
+                store_bf16x8(v[0], v[1], yrs, ok ? ((unsigned)m * (unsigned)p.y_stride + (unsigned)(p.y_coff + co)) * 2u : OOB);
+            }
+            continue;
+        }
+        // the 8-byte form: one store per fragment, weight rows in natural order
 #pragma unroll
         for (int a = 0; a < FN; ++a) {
             const int co = n0 + wn * (FN * 16) + a * 16 + fc * 4;
@@ -246,7 +270,9 @@ static bool conv_pxd_cfg_valid(const ConvParams& p, int c) {
 static std::string conv_pxd_symbol(const ConvParams& p, int c) { return std::string(kPxd[c].name) + res_f32_args(p) + ">"; }
 
 template <int PXW, int FN, int WGM, int WGN, bool HAS_RES, bool OUT_F32>
-static hipError_t launch_pxd_var(const ConvParams& p, hipStream_t st) {
+static hipError_t launch_pxd_var(const ConvParams& p_in, hipStream_t st) {
+    static_assert(FN % 2 == 0, "fragment pairs");
+    const ConvParams p = with_store_form(p_in, FN);
     constexpr int BM = WGM * PXW * 16, BN = WGN * FN * 16;
     const int ntiles = (p.Cout + BN - 1) / BN;
     // whole rounds of 256 workgroups: the rounds the full tiles need, then the tile height that fills exactly those rounds

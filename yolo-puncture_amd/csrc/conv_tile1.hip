@@ -24,8 +24,9 @@ constexpr int T1_NS = 3;         // weight ring slots; a stage is one tap ROW (3
 struct Tile1Geo { int TR, TC, tiles_h, tiles_w, nfr, ppc; };   // ppc: 16-pixel pieces per chunk plane of the patch
 
 // debug (YOLOP_T1_CLOCKS=1, the <4,false,false> instantiation only): 100-MHz stamps of workgroup 0's waves - [0] start, [1] patch plane 0 and the
-// first weight stages landed (first barrier passed), [2] main loop done, [3] epilogue stores issued
-__device__ unsigned long long g_t1_clk[8][4];
+// first weight stages landed (first barrier passed), [2] main loop done, [3] every SiLU done (the stamped form takes them all before the first store), [4] last store issued,
+// [5] vmcnt(0) behind the stores
+__device__ unsigned long long g_t1_clk[8][6];
 __device__ int g_t1_abl;      // timing ablations of the stamped instantiation (YOLOP_T1_ABL, results become wrong): 1 no weight pieces in the loop, 2 no MFMAs, 4 no fragment reads
 
 template <int WGN, bool HAS_RES, bool OUT_F32, bool CLK = false>
@@ -46,6 +47,7 @@ __global__ __launch_bounds__(512) void conv_tile1_kernel(const ConvParams p, con
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wm = wave % WGM, wn = wave / WGM;
     const int fr = lane & 15, fc = lane >> 4;
+    const bool wide = !OUT_F32 && p.wide != 0;         // paired channel order (kernel_util.h): weight rows, bias, residual and store
 
     const int ntn = (p.Cout + BN - 1) / BN;
     int bid = blockIdx.x;
@@ -64,7 +66,7 @@ __global__ __launch_bounds__(512) void conv_tile1_kernel(const ConvParams p, con
     float bias[FN][4];
 #pragma unroll
     for (int a = 0; a < FN; ++a) {
-        const int co = n0 + wn * (FN * 16) + a * 16 + fc * 4;
+        const int co = n0 + wn * (FN * 16) + acc_channel(a, fc, wide);
 #pragma unroll
         for (int r = 0; r < 4; ++r) bias[a][r] = (co + r < p.Cout) ? p.bias[co + r] : 0.f;
     }
@@ -96,7 +98,7 @@ __global__ __launch_bounds__(512) void conv_tile1_kernel(const ConvParams p, con
         wlive[j] = q < 3 * WP;
         const int kx = q / WP, n = (q % WP) * 16 + (lane >> 2), pc = lane & 3;
         const int c8 = pc ^ cswz64(n);
-        wbase[j] = (unsigned)(((n0 + n) * p.Kpad + kx * p.Cin + c8 * 8) * 2);
+        wbase[j] = (unsigned)(((n0 + weight_row_channel(n, wide)) * p.Kpad + kx * p.Cin + c8 * 8) * 2);
     }
     const bool full = wlive[LPW - 1];                                        // this wave carries LPW pieces per stage (else LPW - 1)
     int it = 0;
@@ -213,6 +215,22 @@ __global__ __launch_bounds__(512) void conv_tile1_kernel(const ConvParams p, con
 
     // ---- epilogue ---------------------------------------------------------------------------------------------------------------
     T1_STAMP(2);
+    if constexpr (CLK) {
+        // the stamped instantiation splits the epilogue: every SiLU first, then nothing but address arithmetic, conversions and stores
+        if (p.act == ACT_SILU) {
+#pragma unroll
+            for (int f = 0; f < T1_FMX; ++f)
+#pragma unroll
+                for (int a = 0; a < FN; ++a) {
+                    float v[4] = {acc[a][f][0], acc[a][f][1], acc[a][f][2], acc[a][f][3]};
+                    silu4_packed(v);
+                    acc[a][f] = f32x4{v[0], v[1], v[2], v[3]};
+                }
+        }
+        asm volatile("" ::: "memory");
+        __builtin_amdgcn_sched_barrier(0);
+        T1_STAMP(3);
+    }
 #pragma unroll
     for (int f = 0; f < T1_FMX; ++f) {
         if (f >= myf) continue;
@@ -221,12 +239,35 @@ __global__ __launch_bounds__(512) void conv_tile1_kernel(const ConvParams p, con
         const int ho = r0 + r, wo = c0 + c;
         const bool pix_ok = pp < npix && ho < p.Ho && wo < p.Wo;
         const unsigned m = (unsigned)((b * p.Ho + ho) * p.Wo + wo);
+        if (wide) {                                    // a fragment pair (2j, 2j+1) per step: one 16-byte store (and residual read) per lane
+#pragma unroll
+            for (int j = 0; j < FN / 2; ++j) {
+                const int co = n0 + wn * (FN * 16) + acc_channel(2 * j, fc, true);      // 8 channels from here: fragment 2j's four, then 2j+1's
+                const bool ok = pix_ok && co < p.Cout;
+                float v[2][4];
+#pragma unroll
+                for (int h = 0; h < 2; ++h) {
+#pragma unroll
+                    for (int q = 0; q < 4; ++q) v[h][q] = acc[2 * j + h][f][q];
+                    if (p.act == ACT_SILU && !CLK) silu4_packed(v[h]);
+                }
+                if (HAS_RES) {
+                    uint2 rr[2];
+                    load_res_bf16x8((const __bf16*)p.res + (size_t)m * p.res_stride + p.res_coff + co, ok, rr[0], rr[1]);
+                    add_res_bf16x4(v[0], rr[0]);
+                    add_res_bf16x4(v[1], rr[1]);
+                }
+                store_bf16x8(v[0], v[1], yrs, ok ? (m * (unsigned)p.y_stride + (unsigned)(p.y_coff + co)) * 2u : OOB);
+            }
+            continue;
+        }
+        // the 8-byte form: one store per fragment, weight rows in natural order
 #pragma unroll
         for (int a = 0; a < FN; ++a) {
             const int co = n0 + wn * (FN * 16) + a * 16 + fc * 4;
             const bool ok = pix_ok && co < p.Cout;
             float v[4] = {acc[a][f][0], acc[a][f][1], acc[a][f][2], acc[a][f][3]};
-            if (p.act == ACT_SILU) silu4_packed(v);
+            if (p.act == ACT_SILU && !CLK) silu4_packed(v);
             if (HAS_RES) {
                 const uint2 rr = ok ? *(const uint2*)((const __bf16*)p.res + (size_t)m * p.res_stride + p.res_coff + co) : make_uint2(0u, 0u);
                 v[0] += __uint_as_float(rr.x << 16); v[1] += __uint_as_float(rr.x & 0xffff0000u);
@@ -242,7 +283,11 @@ __global__ __launch_bounds__(512) void conv_tile1_kernel(const ConvParams p, con
             }
         }
     }
-    T1_STAMP(3);
+    if constexpr (CLK) {
+        T1_STAMP(4);                       // the last store is issued
+        wait_vmcnt<0>();
+        T1_STAMP(5);                       // ... and every store has left the wave
+    }
 #undef T1_STAMP
 }
 
@@ -488,7 +533,8 @@ static bool conv_tile1_cfg_valid(const ConvParams& p, int c) {
 }
 
 template <int WGN, bool HAS_RES, bool OUT_F32>
-static hipError_t launch_tile1_var(const ConvParams& p, hipStream_t st) {
+static hipError_t launch_tile1_var(const ConvParams& p_in, hipStream_t st) {
+    const ConvParams p = with_store_form(p_in, 2);
     constexpr int BN = WGN * 32;
     Tile1Geo g;
     size_t sh;
@@ -508,12 +554,13 @@ static hipError_t launch_tile1_var(const ConvParams& p, hipStream_t st) {
             hipLaunchKernelGGL(kc, dim3(tiles), dim3(512), sh, st, p, g);
             hipError_t e = hipStreamSynchronize(st);
             if (e != hipSuccess) return e;
-            unsigned long long h[8][4];
+            unsigned long long h[8][6];
             (void)hipMemcpyFromSymbol(h, HIP_SYMBOL(g_t1_clk), sizeof(h));
-            double ph[3] = {0, 0, 0};
-            for (int w = 0; w < 8; ++w) for (int i = 0; i < 3; ++i) ph[i] += (double)(h[w][i + 1] - h[w][i]) / 100.0 / 8.0;
-            fprintf(stderr, "[tile1 clocks] Cin %d Cout %d %dx%d tiles %d (TR %d TC %d): fill %.2f us, main loop %.2f us, epilogue %.2f us (workgroup 0, mean of 8 waves)\n",
-                    p.Cin, p.Cout, p.Ho, p.Wo, tiles, g.TR, g.TC, ph[0], ph[1], ph[2]);
+            double ph[5] = {0, 0, 0, 0, 0};
+            for (int w = 0; w < 8; ++w) for (int i = 0; i < 5; ++i) ph[i] += (double)(h[w][i + 1] - h[w][i]) / 100.0 / 8.0;
+            fprintf(stderr, "[tile1 clocks] Cin %d Cout %d %dx%d tiles %d (TR %d TC %d) %s stores: fill %.2f us, main loop %.2f us, epilogue: SiLU %.2f us, store issue %.2f us, "
+                    "store drain %.2f us (workgroup 0, mean of 8 waves)\n",
+                    p.Cin, p.Cout, p.Ho, p.Wo, tiles, g.TR, g.TC, p.wide ? "16-byte" : "8-byte", ph[0], ph[1], ph[2], ph[3], ph[4]);
             return hipSuccess;
         }
     }

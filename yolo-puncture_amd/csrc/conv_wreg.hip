@@ -28,6 +28,14 @@ template <int... Is, typename F> __device__ __forceinline__ void wr_static_for_i
 }
 template <int N, typename F> __device__ __forceinline__ void wr_static_for(F&& f) { wr_static_for_impl(std::make_integer_sequence<int, N>{}, f); }
 
+// Which instantiations carry the paired (16-byte) store form beside the 8-byte one (kernel and launcher ask the same function). Fragment pairs
+// need an even FN. Two shapes stay on the 8-byte form alone - their code is then exactly what it was - because both epilogues together no
+// longer fit their registers: the 512-register waves with 16 accumulator fragments (ids 700, 702: 15-36 spilled registers against 0) and the
+// 256-register waves with 8 fragments, which spill as they are (id 707: 8 -> 13 registers with both forms).
+template <int FM, int FN, int WGM, int WGN> constexpr bool wreg_paired() {
+    return (FN % 2 == 0) && FM * FN < 16 && !(WGM * WGN == 8 && FM * FN >= 8);
+}
+
 template <int NCH, int FM, int FN, int WGM, int WGN, int TW, bool HAS_RES, bool OUT_F32>
 __global__ __launch_bounds__(WGM * WGN * 64) void conv_wreg_kernel(const ConvParams p, const int tiles_h, const int tiles_w, const int G) {
     constexpr int NW = WGM * WGN;
@@ -57,6 +65,7 @@ __global__ __launch_bounds__(WGM * WGN * 64) void conv_wreg_kernel(const ConvPar
 #define WR_STAMP(i) if (p.clk) { const unsigned long long now = __builtin_amdgcn_s_memtime(); clk[i] += now - last; last = now; }
     const int wm = wave % WGM, wn = wave / WGM;
     const int fr = lane & 15, fc = lane >> 4;
+    const bool wide = !OUT_F32 && wreg_paired<FM, FN, WGM, WGN>() && p.wide != 0;   // paired channel order (kernel_util.h): weight rows, bias, residual and store
     // this lane's pixel inside a fragment: (row, col) and its position offset in the halo image
     const int prow = (TW == 16) ? 0 : (fr >> 3);
     const int pcol = (TW == 16) ? fr : (((fr & 7) + 6 * (fr >> 3)) & 7);
@@ -80,7 +89,7 @@ __global__ __launch_bounds__(WGM * WGN * 64) void conv_wreg_kernel(const ConvPar
     float bias[FN][4];
 #pragma unroll
     for (int a = 0; a < FN; ++a) {
-        const int co = wn * (FN * 16) + a * 16 + fc * 4;
+        const int co = wn * (FN * 16) + acc_channel(a, fc, wide);
 #pragma unroll
         for (int r = 0; r < 4; ++r) bias[a][r] = (co + r < p.Cout) ? p.bias[co + r] : 0.f;
     }
@@ -157,7 +166,7 @@ __global__ __launch_bounds__(WGM * WGN * 64) void conv_wreg_kernel(const ConvPar
                 const int rg = s >> 2, pc = s & 3;
                 const int c8 = pc ^ cswz64(rg);
                 const int t = rg / BN, n = rg - t * BN;
-                const unsigned voff = (unsigned)((n * p.Kpad + t * p.Cin + c * 32 + c8 * 8) * 2);
+                const unsigned voff = (unsigned)((weight_row_channel(n, wide) * p.Kpad + t * p.Cin + c * 32 + c8 * 8) * 2);
                 __builtin_amdgcn_raw_ptr_buffer_load_lds(wrs, (lds_void*)(Wst + ii * 1024), 16, voff, 0, 0, 0);
             }
             wait_vmcnt<0>();
@@ -192,7 +201,10 @@ __global__ __launch_bounds__(WGM * WGN * 64) void conv_wreg_kernel(const ConvPar
             if (!first_iter) {
                 const int k = __builtin_popcount(epmask & ((1u << (NSH - 1)) - 1u));
                 if (k == 0) wait_vmcnt<(NSH - 2) * LH>();
-                else if (k == 1) wait_vmcnt<(NSH - 2) * LH + S>();
+                else if (wide) {                          // a tile's epilogue issued S / 2 stores
+                    if (k == 1) wait_vmcnt<(NSH - 2) * LH + S / 2>();
+                    else wait_vmcnt<(NSH - 2) * LH + S>();
+                } else if (k == 1) wait_vmcnt<(NSH - 2) * LH + S>();
                 else wait_vmcnt<(NSH - 2) * LH + 2 * S>();
                 __builtin_amdgcn_s_barrier();
             }
@@ -232,7 +244,7 @@ __global__ __launch_bounds__(WGM * WGN * 64) void conv_wreg_kernel(const ConvPar
             WR_STAMP(3)
         }
 
-        // ---- epilogue of `tile`: exactly S buffer stores per wave ---------------------------------------------------------
+        // ---- epilogue of `tile`: exactly S buffer stores per wave (S / 2 in the paired form) ---------------------------------------------------------
         {
             int t = tile;                               // (uniform)
             const int tw = t % tiles_w; t /= tiles_w;
@@ -241,44 +253,83 @@ __global__ __launch_bounds__(WGM * WGN * 64) void conv_wreg_kernel(const ConvPar
             const int row0 = th * TH + (wm * FM) * RPF + prow, wo = tw * TW + pcol;
             const bool col_ok = wo < p.Wo;
             const unsigned m0 = (unsigned)((b * p.Ho + row0) * p.Wo + wo);          // pixel index of fragment 0; fragment r is RPF rows further
-            const int co0 = wn * (FN * 16) + fc * 4;
-            uint2 rres[FM][FN];
-            if (HAS_RES) {
+            if (wide) {
+                // paired form: S / 2 stores per wave and tile (wide is wave-uniform for the launch: the counted waits above count S / 2)
+                const int cw = wn * (FN * 16);                                      // first channel of this wave
+                uint2 rres[FM][FN];
+                if (HAS_RES) {
+                    const __bf16* rp0 = (const __bf16*)p.res + p.res_coff;
+#pragma unroll
+                    for (int r = 0; r < FM; ++r) {
+                        const bool pix_ok = col_ok && (row0 + r * RPF < p.Ho);
+                        const __bf16* rp = rp0 + (size_t)(m0 + (unsigned)(r * RPF * p.Wo)) * p.res_stride;
+#pragma unroll
+                        for (int a = 0; a + 1 < FN; a += 2) {                       // one 16-byte read per fragment pair
+                            const int co = cw + acc_channel(a, fc, true);
+                            load_res_bf16x8(rp + co, pix_ok && co < p.Cout, rres[r][a], rres[r][a + 1]);
+                        }
+                    }
+                }
+                const unsigned off0 = (m0 * (unsigned)p.y_stride + (unsigned)p.y_coff) * 2u;
+                const unsigned roff = (unsigned)(RPF * p.Wo * p.y_stride) * 2u;
 #pragma unroll
                 for (int r = 0; r < FM; ++r) {
                     const bool pix_ok = col_ok && (row0 + r * RPF < p.Ho);
-                    const unsigned m = m0 + (unsigned)(r * RPF * p.Wo);
 #pragma unroll
-                    for (int a = 0; a < FN; ++a) {
-                        const int co = co0 + a * 16;
-                        rres[r][a] = (pix_ok && co < p.Cout)
-                                         ? *(const uint2*)((const __bf16*)p.res + (size_t)m * p.res_stride + p.res_coff + co)
-                                         : make_uint2(0u, 0u);
+                    for (int a = 0; a + 1 < FN; a += 2) {
+                        const int co = cw + acc_channel(a, fc, true);               // 8 channels from here: fragment a's four, then a+1's
+                        float v[2][4];
+#pragma unroll
+                        for (int h = 0; h < 2; ++h) {
+#pragma unroll
+                            for (int q = 0; q < 4; ++q) v[h][q] = acc[a + h][r][q];
+                            if (p.act == ACT_SILU) silu4_packed(v[h]);
+                            if (HAS_RES) add_res_bf16x4(v[h], rres[r][a + h]);
+                        }
+                        store_bf16x8(v[0], v[1], yrs, (pix_ok && co < p.Cout) ? off0 + (unsigned)r * roff + (unsigned)co * 2u : OOB);
                     }
                 }
-            }
-            const unsigned es = OUT_F32 ? 4u : 2u;
-            const unsigned off0 = (m0 * (unsigned)p.y_stride + (unsigned)(p.y_coff + co0)) * es;
-            const unsigned roff = (unsigned)(RPF * p.Wo * p.y_stride) * es;
+            } else {
+                // the 8-byte form: exactly S stores per wave and tile, weight rows in natural order
+                const int co0 = wn * (FN * 16) + fc * 4;
+                uint2 rres[FM][FN];
+                if (HAS_RES) {
 #pragma unroll
-            for (int r = 0; r < FM; ++r) {
-                const bool pix_ok = col_ok && (row0 + r * RPF < p.Ho);
+                    for (int r = 0; r < FM; ++r) {
+                        const bool pix_ok = col_ok && (row0 + r * RPF < p.Ho);
+                        const unsigned m = m0 + (unsigned)(r * RPF * p.Wo);
 #pragma unroll
-                for (int a = 0; a < FN; ++a) {
-                    const bool ok = pix_ok && (co0 + a * 16 < p.Cout);
-                    float v[4] = {acc[a][r][0], acc[a][r][1], acc[a][r][2], acc[a][r][3]};
-                    if (p.act == ACT_SILU) silu4_packed(v);
-                    if (HAS_RES) {
-                        const uint2 rr = rres[r][a];
-                        v[0] += __uint_as_float(rr.x << 16); v[1] += __uint_as_float(rr.x & 0xffff0000u);
-                        v[2] += __uint_as_float(rr.y << 16); v[3] += __uint_as_float(rr.y & 0xffff0000u);
+                        for (int a = 0; a < FN; ++a) {
+                            const int co = co0 + a * 16;
+                            rres[r][a] = (pix_ok && co < p.Cout)
+                                             ? *(const uint2*)((const __bf16*)p.res + (size_t)m * p.res_stride + p.res_coff + co)
+                                             : make_uint2(0u, 0u);
+                        }
                     }
-                    const unsigned off = ok ? off0 + (unsigned)r * roff + (unsigned)(a * 16) * es : OOB;
-                    if (OUT_F32) {
-                        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(__attribute__((ext_vector_type(4))) unsigned, make_float4(v[0], v[1], v[2], v[3])), yrs, off, 0, 0);
-                    } else {
-                        __attribute__((aligned(8))) __bf16 o[4] = {(__bf16)v[0], (__bf16)v[1], (__bf16)v[2], (__bf16)v[3]};
-                        __builtin_amdgcn_raw_buffer_store_b64(*(const __attribute__((ext_vector_type(2))) unsigned*)o, yrs, off, 0, 0);
+                }
+                const unsigned es = OUT_F32 ? 4u : 2u;
+                const unsigned off0 = (m0 * (unsigned)p.y_stride + (unsigned)(p.y_coff + co0)) * es;
+                const unsigned roff = (unsigned)(RPF * p.Wo * p.y_stride) * es;
+#pragma unroll
+                for (int r = 0; r < FM; ++r) {
+                    const bool pix_ok = col_ok && (row0 + r * RPF < p.Ho);
+#pragma unroll
+                    for (int a = 0; a < FN; ++a) {
+                        const bool ok = pix_ok && (co0 + a * 16 < p.Cout);
+                        float v[4] = {acc[a][r][0], acc[a][r][1], acc[a][r][2], acc[a][r][3]};
+                        if (p.act == ACT_SILU) silu4_packed(v);
+                        if (HAS_RES) {
+                            const uint2 rr = rres[r][a];
+                            v[0] += __uint_as_float(rr.x << 16); v[1] += __uint_as_float(rr.x & 0xffff0000u);
+                            v[2] += __uint_as_float(rr.y << 16); v[3] += __uint_as_float(rr.y & 0xffff0000u);
+                        }
+                        const unsigned off = ok ? off0 + (unsigned)r * roff + (unsigned)(a * 16) * es : OOB;
+                        if (OUT_F32) {
+                            __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(__attribute__((ext_vector_type(4))) unsigned, make_float4(v[0], v[1], v[2], v[3])), yrs, off, 0, 0);
+                        } else {
+                            __attribute__((aligned(8))) __bf16 o[4] = {(__bf16)v[0], (__bf16)v[1], (__bf16)v[2], (__bf16)v[3]};
+                            __builtin_amdgcn_raw_buffer_store_b64(*(const __attribute__((ext_vector_type(2))) unsigned*)o, yrs, off, 0, 0);
+                        }
                     }
                 }
             }
@@ -338,7 +389,8 @@ static bool conv_wreg_cfg_valid(const ConvParams& p, int c) {
 static std::string conv_wreg_symbol(const ConvParams& p, int c) { return std::string(kWreg[c].name) + res_f32_args(p) + ">"; }
 
 template <int NCH, int FM, int FN, int WGM, int WGN, int TW, bool HAS_RES, bool OUT_F32>
-static hipError_t launch_wreg_var(const ConvParams& p, const WregCfg& k, hipStream_t st) {
+static hipError_t launch_wreg_var(const ConvParams& p_in, const WregCfg& k, hipStream_t st) {
+    const ConvParams p = with_store_form(p_in, wreg_paired<FM, FN, WGM, WGN>() ? FN : 1);
     constexpr int RPF = 16 / TW, TH = WGM * FM * RPF;
     const size_t sh = wreg_lds(k);
     const int B = p.M / (p.Ho * p.Wo);
@@ -365,8 +417,8 @@ static hipError_t launch_wreg_var(const ConvParams& p, const WregCfg& k, hipStre
         double s5[5] = {0, 0, 0, 0, 0}, mx[5] = {0, 0, 0, 0, 0};
         for (size_t w = 0; w < n / 5; ++w)
             for (int i = 0; i < 5; ++i) { s5[i] += (double)h[w * 5 + i]; mx[i] = std::max(mx[i], (double)h[w * 5 + i]); }
-        fprintf(stderr, "[wreg clocks] %s G=%d tiles=%d  per-wave mean cycles: prologue %.0f  wait+barrier %.0f  issue %.0f  compute %.0f  epilogue %.0f   (max %.0f %.0f %.0f %.0f %.0f)\n",
-                k.name, G, num_tiles, s5[0] / (n / 5), s5[1] / (n / 5), s5[2] / (n / 5), s5[3] / (n / 5), s5[4] / (n / 5), mx[0], mx[1], mx[2], mx[3], mx[4]);
+        fprintf(stderr, "[wreg clocks] %s G=%d tiles=%d  %s stores  per-wave mean cycles: prologue %.0f  wait+barrier %.0f  issue %.0f  compute %.0f  epilogue %.0f   (max %.0f %.0f %.0f %.0f %.0f)\n",
+                k.name, G, num_tiles, p.wide ? "16-byte" : "8-byte", s5[0] / (n / 5), s5[1] / (n / 5), s5[2] / (n / 5), s5[3] / (n / 5), s5[4] / (n / 5), mx[0], mx[1], mx[2], mx[3], mx[4]);
         return hipGetLastError();
     }
     hipLaunchKernelGGL(kern, dim3(G), dim3(WGM * WGN * 64), sh, st, p, tiles_h, tiles_w, G);

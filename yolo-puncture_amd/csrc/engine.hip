@@ -64,6 +64,7 @@ struct yp_engine {
     std::map<std::array<int, 3>, bool> auto_replay;
     bool fuse = true;             // dw->pw fusion (YOLOP_NO_FUSE=1 disables, for A/B)
     bool tail = false;            // conv_dwpw TAIL form (YOLOP_TAIL=1 at yp_create enables; see make_plan)
+    bool narrow_store = false;    // bf16 conv epilogues keep the 8-byte stores everywhere (YOLOP_NARROW_STORE=1 at yp_create; default: 16-byte paired stores where a launch admits them)
     bool sparse_head = true;      // v10 head: box / coefficient branches on the stage-1 winners only (YOLOP_DENSE_HEAD=1 at yp_create disables)
     void* sp_ws = nullptr; size_t sp_ws_bytes = 0;   // winners-only head: sel / wlist / wcount / thr / box rows / coefficient rows
     bool tune = true;             // plan-time autotuning of the conv tile configuration
@@ -1168,6 +1169,7 @@ static ConvParams conv_params(const yp_engine& e, const Op& o) {
     if (o.res.t >= 0) { const TensorDesc& tr = e.tensors[o.res.t]; p.res = tr.ptr ? tr.ptr : (const void*)1; p.res_stride = tr.C; p.res_coff = o.res.coff; }
     p.M = e.pB * to.H * to.W; p.ks = o.k; p.stride = o.s; p.pad = o.k / 2; p.act = o.act;
     p.out_f32 = (to.f32 && e.dtype == DT_BF16) ? 1 : 0;
+    p.wide = (e.dtype == DT_BF16 && !p.out_f32 && !e.narrow_store) ? 1 : 0;      // asked for; the launcher decides (wide_store_ok)
     p.up = 1; p.oy = 0; p.ox = 0;
     p.x_bytes = ti.bytes; p.w_bytes = w.mat_bytes; p.y_bytes = to.bytes; p.cfg = o.cfg; p.dbg = conv_debug_ablation();
     if (o.folded) {
@@ -2008,6 +2010,7 @@ int yp_create(const yp_model_desc* desc, int device, yp_engine** out) {
     e->fuse = !env_on("YOLOP_NO_FUSE");
     e->tail = env_on("YOLOP_TAIL");
     e->sparse_head = !env_on("YOLOP_DENSE_HEAD");
+    e->narrow_store = env_on("YOLOP_NARROW_STORE");
     int rc = build_graph(*e);
     if (rc != YP_OK) return rc;
     for (const Op& o : e->ops)
@@ -2565,6 +2568,11 @@ int yp_debug_ablation(int v) {
 int yp_debug_force_conv_cfg(int cfg) {
     conv_dma_force_cfg(cfg);
     return conv_dma_family.num_cfgs;
+}
+
+int yp_debug_last_store_form(void) {
+    store_form_watched().store(true);       // launches record their form from the first call on
+    return last_store_form().exchange(-1);
 }
 
 int yp_debug_op_cfg(const yp_engine* e, int i, int* cfg) {

@@ -68,6 +68,42 @@ __device__ __forceinline__ void silu4_packed(float* v) {
     }
 }
 
+// ---- paired channel order: 16-byte stores of the bf16 conv epilogues --------------------------------------------------------------
+// A lane of a 16x16 MFMA accumulator holds A-rows fc*4 .. fc*4+3 of its pixel: with the weight rows in natural order that is 4
+// consecutive output channels = one 8-byte store per fragment. The weights are the A operand, so WHICH channel sits in an A-row is
+// chosen where the weight rows are fetched: in the paired order, row i of fragment a of the fragment pair (2j, 2j+1) holds channel
+//   j*32 + (i >> 2)*8 + (a & 1)*4 + (i & 3),
+// lane group fc then holds channels j*32 + fc*8 + 0..3 in fragment 2j and + 4..7 in fragment 2j+1: 8 consecutive bf16 = one 16-byte
+// store per lane and fragment pair, 64 contiguous bytes per pixel and instruction. Every output element is the same dot product in the
+// same k order (bit-identical); the LDS / register images keep their row positions (swizzles, bank behaviour unchanged); only the
+// SOURCE row of the weight fill and the channel index of bias, residual and store change. ConvParams::wide and its conditions: common.h.
+//
+// paired_channel: row of a weight image whose 32-row blocks are fragment pairs -> the channel fetched into it (a bijection of each block;
+// tests/test_wide_store_host.py restates it)
+__host__ __device__ constexpr int paired_channel(int row) { return (row & ~31) | ((row & 12) << 1) | ((row & 16) >> 2) | (row & 3); }
+__device__ __forceinline__ int weight_row_channel(int row, bool wide) { return wide ? paired_channel(row) : row; }
+// first of the 4 channels that lane group fc holds of fragment a, relative to the first channel of the wave's fragment 0
+__device__ __forceinline__ int acc_channel(int a, int fc, bool wide) { return wide ? (a >> 1) * 32 + fc * 8 + (a & 1) * 4 : a * 16 + fc * 4; }
+// v[0..3] += four bf16 residual values
+__device__ __forceinline__ void add_res_bf16x4(float* v, uint2 rr) {
+    v[0] += __uint_as_float(rr.x << 16); v[1] += __uint_as_float(rr.x & 0xffff0000u);
+    v[2] += __uint_as_float(rr.y << 16); v[3] += __uint_as_float(rr.y & 0xffff0000u);
+}
+// the 16-byte residual read of a fragment pair: lo = the 4 channels of fragment 2j, hi = those of fragment 2j+1
+__device__ __forceinline__ void load_res_bf16x8(const __bf16* src, bool ok, uint2& lo, uint2& hi) {
+    const uint4 q = ok ? *(const uint4*)src : make_uint4(0u, 0u, 0u, 0u);
+    lo = make_uint2(q.x, q.y); hi = make_uint2(q.z, q.w);
+}
+__device__ __forceinline__ void store_bf16x4(const float* v, __amdgpu_buffer_rsrc_t rs, unsigned off) {
+    __attribute__((aligned(8))) __bf16 o[4] = {(__bf16)v[0], (__bf16)v[1], (__bf16)v[2], (__bf16)v[3]};
+    __builtin_amdgcn_raw_buffer_store_b64(*(const __attribute__((ext_vector_type(2))) unsigned*)o, rs, off, 0, 0);
+}
+// both fragments of a pair as eight bf16 in one 16-byte store
+__device__ __forceinline__ void store_bf16x8(const float* lo, const float* hi, __amdgpu_buffer_rsrc_t rs, unsigned off) {
+    __attribute__((aligned(16))) __bf16 o[8] = {(__bf16)lo[0], (__bf16)lo[1], (__bf16)lo[2], (__bf16)lo[3], (__bf16)hi[0], (__bf16)hi[1], (__bf16)hi[2], (__bf16)hi[3]};
+    __builtin_amdgcn_raw_buffer_store_b128(*(const __attribute__((ext_vector_type(4))) unsigned*)o, rs, off, 0, 0);
+}
+
 // LDS accesses behind the compiler's back: it cannot tell them from the in-flight LDS-DMA of the next chunk apart and drains vmcnt to 0
 // in front of them (= no prefetch at all). The caller orders the reads with explicit lgkmcnt waits before the first use.
 __device__ __forceinline__ unsigned lds_addr(const void* p) { return (unsigned)(size_t)(const __attribute__((address_space(3))) unsigned char*)p; }
