@@ -284,6 +284,11 @@ int yp_op_input(const yp_engine* e, int i, int* tensor, int* coff, int* C, int* 
    1x1 -> depthwise conv / SPPF pool chain, one workgroup per image and channel slice), or -1; *pre_stored = 1 when that kernel also writes
    the 1x1's own output tensor (it has other readers). The parity tests use it to teacher-force both results of such a launch. */
 int yp_op_fusion(const yp_engine* e, int i, int* pre, int* pre_stored);
+/* Launch form of op i under the current plan: *form = 0 when it launches as its own kernel (or not at all), else the fused form
+   (1 dw -> pw, 2 dw -> pw -> logits, 3 3x3 s2 -> 1x1, 4 stem -> 3x3 s2 -> 1x1, 5 C2f bottleneck -> 1x1, 6 1x1 -> dw s2, 7 1x1 -> dw / pool
+   chain, 8 logits + class-max keys). Returns the number of ops whose work that launch takes over - they launch nothing and report no
+   FLOPs or bytes - and fills absorbed[0 .. min(n, cap)) with their indices (either pointer may be null); < 0 on a bad index. Host only. */
+int yp_debug_op_form(const yp_engine* e, int i, int* form, int* absorbed, int cap);
 /* Debug stepping for per-op parity tests ("teacher forcing"): run ONE op of the current plan, and overwrite a
  * channel slice of an engine tensor from fp32 host data [B,H,W,C] (converted to the tensor's storage type). */
 int yp_run_op(yp_engine* e, int i, const uint8_t* in_dev, float* det_out, int32_t* idx_out, float* coeff_out, void* stream);

@@ -1,5 +1,6 @@
-"""The kernel name a plan reports for a dense conv (yp_op_kernel: bench, profiles and rocprof joins use it) is a kernel symbol that
-libyolop.so really contains: every conv family builds it from the template instance its launcher picks. No GPU needed."""
+"""The kernel name a plan reports for a dense conv, a depthwise conv or the stem (yp_op_kernel: bench, profiles and rocprof joins use it)
+is a kernel symbol that libyolop.so really contains: every conv family, launch_dwconv and launch_stem build it from the template instance
+the launcher picks. No GPU needed."""
 import glob
 import os
 import re
@@ -20,13 +21,17 @@ def _kernel_symbols(lib_path):
     # the host stubs HIP registers for every __global__ instance: "void yp::conv_wres_kernel<64, 2, false>(yp::ConvParams, ...)"
     mangled = [ln.split()[-1] for ln in subprocess.run([NM, "--defined-only", lib_path], capture_output=True, text=True, check=True).stdout.splitlines()
                if ln.split() and ln.split()[-1].startswith("_ZN2yp")]
+    # (binutils' c++filt does not know the mangling of __bf16, "DF16b", and would leave those instances mangled: spell it as a vendor type)
+    mangled = [m.replace("DF16b", "u6__bf16") for m in mangled]
     out = subprocess.run([CXXFILT], input="\n".join(mangled), capture_output=True, text=True, check=True).stdout.splitlines()
     syms = set()
     for d in out:
         d = d.replace(" ", "")
         if d.startswith("void"):
             d = d[4:]
-        syms.add(d.split("(")[0].replace("yp::", ""))
+        d = d.split("(")[0].replace("yp::", "")
+        syms.add(d)
+        syms.add(d.replace("<__bf16", "<bf16").replace("<float", "<f32"))      # the element type as dwconv_kernel_name / stem_kernel_name spell it
     return syms
 
 
@@ -50,6 +55,10 @@ def test_packaged_table_conv_names_are_kernel_symbols(monkeypatch):
                 e.plan(1, 64, 64)                      # (a plan of the same shape is kept as it is: re-plan from scratch)
                 for o in e.plan(B, H, W):
                     k = o["kernel"]
+                    if k.startswith(("dwconv_", "stem_")):          # named by their launchers, whatever id is forced
+                        assert k.replace(" ", "") in syms, (os.path.basename(f), o["name"], k)
+                        checked.add(k.split("<")[0])
+                        continue
                     if table.get(o["name"]) != cfg or not k.startswith("conv_") or k.startswith(("conv_igemm", "conv_dwpw")):
                         continue
                     assert k.replace(" ", "") in syms, (os.path.basename(f), o["name"], cfg, k)
@@ -57,4 +66,5 @@ def test_packaged_table_conv_names_are_kernel_symbols(monkeypatch):
             e.close()
     finally:
         lib.yp_debug_force_conv_cfg(-1)
-    assert {"conv_dma_p_kernel", "conv_dma_lc_kernel", "conv_halo_s2_kernel", "conv_tile1_kernel", "conv_wres_kernel"} <= checked, checked
+    assert {"conv_dma_p_kernel", "conv_dma_lc_kernel", "conv_halo_s2_kernel", "conv_tile1_kernel", "conv_wres_kernel", "dwconv_row_kernel",
+            "stem_mfma_kernel"} <= checked, checked

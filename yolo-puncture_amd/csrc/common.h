@@ -60,7 +60,8 @@ struct WeightDesc {
     size_t mat_bytes = 0;      // bytes of one packed GEMM matrix
 };
 
-// How a launching op runs (a plan decision). The ops whose work a fused form takes over are skipped.
+// How a launching op runs (a plan decision). The ops whose work a fused form takes over are skipped. engine.hip's kForms has one record
+// per value, in this order: candidates, admission, effective views and launch of a form are all there.
 enum Form {
     FORM_PLAIN = 0,       // the op's own kernel
     FORM_DWPW,            // OP_CONV 1x1: the depthwise 3x3 in front (fuse_dw) and this conv as conv_dwpw_kernel
@@ -91,7 +92,7 @@ struct Op {
     Form form = FORM_PLAIN;       // plan decision: launch form
     bool skip = false;            // plan decision: this op's work is done by a fused consumer
     int fuse_pre = -1;            // OP_CONV 1x1: index of the 3x3 stride-2 conv feeding it that can run as the first stage of one kernel
-    int stem_op = -1;             // FORM_FRONTEND: index of the stem op
+    int stem_op = -1;             // OP_CONV 1x1 with fuse_pre: index of the stem op when that 3x3 is the only reader of the stem's output (graph pass)
     int fold_up = -1;             // OP_CONV 1x1 on a [upsampled | skip] concat: index of the nearest-x2 upsample op it can absorb
     bool folded = false;          // plan decision: the upsample is folded into this conv's input gather
     int c2f_m1 = -1, c2f_m2 = -1; // OP_CONV 1x1 closing a C2f with one plain bottleneck: indices of the bottleneck's two 3x3 convs
@@ -342,12 +343,15 @@ constexpr int kNumConvFamilies = 12;
 extern const ConvFamily* const kConvFamilies[kNumConvFamilies];
 int conv_halo_s2_pw_cfg(const ConvParams& p);          // configuration for the fused trailing-1x1 form, or -1
 hipError_t launch_dwconv(const DwParams& p, int dtype, hipStream_t st);
+std::string dwconv_kernel_name(const DwParams& p, int dtype);    // the kernel launch_dwconv runs for p
 hipError_t launch_stem(const StemParams& p, int dtype, hipStream_t st);
+std::string stem_kernel_name(const StemParams& p, int dtype);    // the kernel launch_stem runs for p
 hipError_t launch_pool5(const PoolParams& p, int dtype, hipStream_t st);
 hipError_t launch_sppf_pool3(const PoolParams& p, int dtype, hipStream_t st);
 bool sppf_pool3_fits(const PoolParams& p, int dtype);
 bool dwconv_mfma_valid(const DwParams& p, int dtype);
 hipError_t launch_dwconv_mfma(const DwParams& p, hipStream_t st);
+const char* dwconv_mfma_kernel_name(const DwParams& p);
 hipError_t launch_upsample(const UpParams& p, int dtype, hipStream_t st);
 hipError_t launch_attention(const AttnParams& p, int dtype, hipStream_t st);
 // conv_small.hip: fp32 3x3 for small maps (four waves split K, operands straight from L2)

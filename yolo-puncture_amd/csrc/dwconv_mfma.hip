@@ -157,15 +157,20 @@ bool dwconv_mfma_valid(const DwParams& p, int dtype) {
     return dwm_lds(p, nullptr) <= 72 * 1024;            // two workgroups per CU
 }
 
+// few (image, channel block) pairs: split each map's patches over up to 4 workgroups (every one stages the whole map - it is L2-resident)
+static int dwm_psplit(const DwParams& p) {
+    const int wgs = p.B * (p.C / 32);
+    return wgs >= 256 ? 1 : wgs >= 128 ? 2 : 4;
+}
+const char* dwconv_mfma_kernel_name(const DwParams& p) { return dwm_psplit(p) == 1 ? "dwconv_mfma_kernel<7,false>" : "dwconv_mfma_kernel<7,true>"; }
+
 hipError_t launch_dwconv_mfma(const DwParams& p, hipStream_t st) {
     int x_instr = 0;
     const size_t sh = dwm_lds(p, &x_instr);
     static size_t granted[2] = {0, 0};
     if (hipError_t e = allow_dynamic_lds((const void*)dwconv_mfma_kernel<7, false>, sh, granted[0])) return e;
     if (hipError_t e = allow_dynamic_lds((const void*)dwconv_mfma_kernel<7, true>, sh, granted[1])) return e;
-    // few (image, channel block) pairs: split each map's patches over up to 4 workgroups (every one stages the whole map - it is L2-resident)
-    const int wgs = p.B * (p.C / 32);
-    const int psplit = wgs >= 256 ? 1 : wgs >= 128 ? 2 : 4;
+    const int wgs = p.B * (p.C / 32), psplit = dwm_psplit(p);
     if (psplit == 1) hipLaunchKernelGGL((dwconv_mfma_kernel<7, false>), dim3((unsigned)wgs, 1), dim3(256), sh, st, p, dwm_pitch(p.W, p.ks), x_instr);
     else hipLaunchKernelGGL((dwconv_mfma_kernel<7, true>), dim3((unsigned)wgs, (unsigned)psplit), dim3(256), sh, st, p, dwm_pitch(p.W, p.ks), x_instr);
     return hipGetLastError();

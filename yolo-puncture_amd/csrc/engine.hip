@@ -598,6 +598,17 @@ static int build_graph(yp_engine& e) {
     return finish_graph_passes(e);
 }
 
+static bool views_overlap(const View& a, const View& b) {
+    return a.t >= 0 && a.t == b.t && a.coff < b.coff + b.C && b.coff < a.coff + a.C;
+}
+// the ops other than `except` whose input or residual overlaps v (the graph as built: plan decisions play no part)
+static std::vector<int> readers_of(const yp_engine& e, const View& v, int except = -1) {
+    std::vector<int> r;
+    for (size_t j = 0; j < e.ops.size(); ++j)
+        if ((int)j != except && (views_overlap(e.ops[j].in, v) || views_overlap(e.ops[j].res, v))) r.push_back((int)j);
+    return r;
+}
+
 // graph passes shared by every family: they only look at op kinds, shapes and who reads what
 static int finish_graph_passes(yp_engine& e) {
     // ---- fusion pass: depthwise 3x3 (s1, SiLU) whose only consumer is the next op, a 1x1 conv ------------------------------
@@ -607,28 +618,16 @@ static int finish_graph_passes(yp_engine& e) {
         if (d.kind != OP_DWCONV || d.k != 3 || d.s != 1 || d.res.t >= 0 || d.gs != 0) continue;
         if (c.kind != OP_CONV || c.k != 1 || c.s != 1 || c.res.t >= 0) continue;
         if (c.in.t != d.out.t || c.in.coff != d.out.coff || c.in.C != d.out.C) continue;
-        bool other_reader = false;
-        for (size_t j = 0; j < e.ops.size(); ++j) {
-            if (j == i + 1) continue;
-            const Op& q = e.ops[j];
-            for (const View* v : {&q.in, &q.res})
-                if (v->t == d.out.t && v->coff < d.out.coff + d.out.C && d.out.coff < v->coff + v->C) other_reader = true;
-        }
-        if (!other_reader) c.fuse_dw = (int)i;
+        if (readers_of(e, d.out, (int)i + 1).empty()) c.fuse_dw = (int)i;
     }
     // ---- fold pass: nearest-x2 upsample written into the leading slice of a concat buffer whose only reader is a 1x1 conv ----
     for (size_t i = 0; i < e.ops.size(); ++i) {
         const Op& u = e.ops[i];
         if (u.kind != OP_UPSAMPLE || (u.out.C % 64) != 0) continue;
-        int reader = -1, nread = 0;
-        for (size_t j = 0; j < e.ops.size(); ++j) {
-            const Op& q = e.ops[j];
-            for (const View* v : {&q.in, &q.res})
-                if (v->t == u.out.t && v->coff < u.out.coff + u.out.C && u.out.coff < v->coff + v->C) { reader = (int)j; ++nread; }
-        }
-        if (nread != 1) continue;
-        Op& c = e.ops[reader];
-        if (c.kind != OP_CONV || c.k != 1 || c.s != 1 || c.in.t != u.out.t || c.in.coff != u.out.coff || c.in.C <= u.out.C) continue;
+        const std::vector<int> readers = readers_of(e, u.out);
+        if (readers.size() != 1) continue;
+        Op& c = e.ops[readers[0]];
+        if (c.kind != OP_CONV || c.k != 1 || c.s != 1 || views_overlap(c.res, u.out) || c.in.t != u.out.t || c.in.coff != u.out.coff || c.in.C <= u.out.C) continue;
         c.fold_up = (int)i;
     }
     // ---- 3x3 stride-2 conv whose only consumer is the next op, a 1x1 conv: candidates for conv_halo_s2's fused trailing 1x1 -----
@@ -638,14 +637,11 @@ static int finish_graph_passes(yp_engine& e) {
         if (a.kind != OP_CONV || a.k != 3 || a.s != 2 || a.res.t >= 0) continue;
         if (c.kind != OP_CONV || c.k != 1 || c.s != 1 || c.res.t >= 0 || c.fold_up >= 0 || c.fuse_dw >= 0) continue;
         if (c.in.t != a.out.t || c.in.coff != a.out.coff || c.in.C != a.out.C) continue;
-        bool other_reader = false;
-        for (size_t j = 0; j < e.ops.size(); ++j) {
-            if (j == i + 1) continue;
-            const Op& q = e.ops[j];
-            for (const View* v : {&q.in, &q.res})
-                if (v->t == a.out.t && v->coff < a.out.coff + a.out.C && a.out.coff < v->coff + v->C) other_reader = true;
-        }
-        if (!other_reader) c.fuse_pre = (int)i;
+        if (!readers_of(e, a.out, (int)i + 1).empty()) continue;
+        c.fuse_pre = (int)i;
+        // ... and the stem in front of the 3x3, when nothing else reads the stem's tensor: candidates for frontend_kernel
+        for (size_t j = 0; j < e.ops.size(); ++j)
+            if (e.ops[j].kind == OP_STEM && e.ops[j].out.t == a.in.t && readers_of(e, View{a.in.t, 0, e.tensors[a.in.t].C}, (int)i).empty()) c.stem_op = (int)j;
     }
     // ---- 1x1 logit conv (no activation, fp32 output) behind a dw -> pw pair, optionally followed by the class-max op: candidates for the
     //      third stage of conv_dwpw's TAIL form (the class branch of the v10 / YOLO11 heads: dw -> pw -> dw -> [pw -> 1x1 logits -> max]) -----
@@ -656,14 +652,7 @@ static int finish_graph_passes(yp_engine& e) {
         if (!e.tensors[c2.out.t].f32 || c2.out.coff != 0 || c2.out.C != e.tensors[c2.out.t].C) continue;
         if (c1.kind != OP_CONV || c1.fuse_dw < 0 || c1.res.t >= 0) continue;
         if (c2.in.t != c1.out.t || c2.in.coff != c1.out.coff || c2.in.C != c1.out.C) continue;
-        bool other_reader = false;
-        for (size_t j = 0; j < e.ops.size(); ++j) {
-            if (j == i) continue;
-            const Op& q = e.ops[j];
-            for (const View* v : {&q.in, &q.res})
-                if (v->t == c1.out.t && v->coff < c1.out.coff + c1.out.C && c1.out.coff < v->coff + v->C) other_reader = true;
-        }
-        if (other_reader) continue;
+        if (!readers_of(e, c1.out, (int)i).empty()) continue;
         c2.fuse_tail = (int)i - 1;
         if (i + 1 < e.ops.size() && e.ops[i + 1].kind == OP_AMAX && e.ops[i + 1].in.t == c2.out.t) c2.tail_amax = (int)i + 1;
     }
@@ -686,8 +675,7 @@ static int finish_graph_passes(yp_engine& e) {
         if (!dw && d.kind != OP_POOL3) continue;
         int c = -1;
         for (size_t j = i; j-- > 0;) {                               // the latest earlier op that writes what d reads
-            const Op& q = e.ops[j];
-            if (q.out.t == d.in.t && q.out.coff < d.in.coff + d.in.C && d.in.coff < q.out.coff + q.out.C) { c = (int)j; break; }
+            if (views_overlap(e.ops[j].out, d.in)) { c = (int)j; break; }
         }
         if (c < 0) continue;
         const Op& pw = e.ops[c];
@@ -699,451 +687,18 @@ static int finish_graph_passes(yp_engine& e) {
     return YP_OK;
 }
 
-// ---------------------------------------------------------------------------------------------------------
-// plan: resolve shapes for (B,H,W), compute algorithmic flops/bytes
-// ---------------------------------------------------------------------------------------------------------
-static ConvParams conv_params(const yp_engine& e, const Op& o);
-// Releases the replay executable and the graph it was instantiated from. Callers have made sure no replay of it is in flight
-// (ev_done synchronised, or a device synchronisation): see the lifetime rule at forward_replay.
-static void drop_graph(yp_engine& e) {
-    if (e.gexec) { (void)hipGraphExecDestroy(e.gexec); e.gexec = nullptr; }
-    if (e.gsrc) { (void)hipGraphDestroy(e.gsrc); e.gsrc = nullptr; }
-}
-static DwPwParams dwpw_params(const yp_engine& e, const Op& c);
-static FrontParams front_params(const yp_engine& e, const Op& o, const uint8_t* img);
-static C2fParams c2f_params(const yp_engine& e, const Op& o);
-static ScdParams scd_params(const yp_engine& e, const Op& o);
-static PwSpParams pwsp_params(const yp_engine& e, const Op& o);
-static ClsOutParams cls_out_params(const yp_engine& e, const Op& o);
-static bool views_overlap(const View& a, const View& b);
-static void op_views(const yp_engine& e, const Op& o, std::vector<View>& rd, std::vector<View>& wr);
 // a conv that launches as itself through launch_conv (or pwsp_kernel under PWSP_CFG): its configuration id is the tuner's to choose
 static bool plain_conv(const Op& o) { return (o.kind == OP_CONV || o.kind == OP_CONVT) && !o.skip && o.form == FORM_PLAIN; }
 static size_t tensor_elem_bytes(const yp_engine& e, const TensorDesc& t) { return (t.f32 || e.dtype == DT_F32) ? 4 : 2; }
-
-// ---- winners-only head (head_branch.hip): workspace layout and parameter blocks -----------------------------------------------------------------
-struct SparseWs {
-    size_t sel, wlist, wcount, thr, box, cf, pcount, plist, t0box, t0cf, total;
-    int plist_off[3], plist_cap[3];          // per level: first entry / capacity of its position list
-    size_t t0_off[3];                        // per level: first (image, pixel) row of the position-addressed maps, in rows
-    size_t rows;                             // B * anchors
-};
-static SparseWs sparse_ws_layout(int B, int max_det, const int (&HWl)[3]) {
-    SparseWs w{};
-    size_t off = 0;
-    auto take = [&](size_t bytes) { const size_t o = off; off += (bytes + 255) & ~(size_t)255; return o; };
-    w.sel = take((size_t)B * HEAD_MAXK * 4); w.wlist = take((size_t)B * 3 * HEAD_MAXK * 4); w.wcount = take((size_t)B * 3 * 4); w.thr = take((size_t)B * 4);
-    w.box = take((size_t)B * max_det * 64 * 4); w.cf = take((size_t)B * max_det * 32 * 4);
-    w.pcount = take(8 * 4);                  // [0..3) live counters, [4..7) the counts of the last forward (head stage 2 saves them)
-    size_t ents = 0, rows = 0;
-    for (int l = 0; l < 3; ++l) {
-        w.plist_off[l] = (int)ents; w.plist_cap[l] = B * std::min(HWl[l], 9 * max_det);   // a winner's 3x3 neighbourhood, never more than the level has
-        ents += (size_t)(w.plist_cap[l] + 63) & ~(size_t)63;
-        w.t0_off[l] = rows; rows += (size_t)B * HWl[l];
-    }
-    w.rows = rows;
-    w.plist = take(ents * 4);
-    w.t0box = take(rows * 64 * 2); w.t0cf = take(rows * 32 * 2);
-    w.total = off;
-    return w;
-}
-static SparseWs sparse_ws_layout(const yp_engine& e) {
-    const int hw[3] = {(e.pH / 8) * (e.pW / 8), (e.pH / 16) * (e.pW / 16), (e.pH / 32) * (e.pW / 32)};
-    return sparse_ws_layout(e.pB, e.desc.max_det, hw);
-}
-// which: 0 = box branch (one2one_cv2), 1 = mask-coefficient branch (cv4)
-static HeadBranchParams head_branch_params(const yp_engine& e, const Op& h, int which) {
-    HeadBranchParams p{};
-    const SparseWs ws = sparse_ws_layout(e);
-    char* base = (char*)e.sp_ws;
-    for (int l = 0; l < 3; ++l) {
-        const int* ids = which == 0 ? h.hb_box[l] : h.hb_cf[l];
-        if (ids[0] < 0) { p.cmid = 0; return p; }
-        const Op &c0 = e.ops[ids[0]], &c1 = e.ops[ids[1]], &c2 = e.ops[ids[2]];
-        const WeightDesc &w0 = e.weights[c0.widx], &w1 = e.weights[c1.widx], &w2 = e.weights[c2.widx];
-        const TensorDesc& ti = e.tensors[c0.in.t];
-        p.x[l] = ti.ptr; p.x_stride[l] = ti.C; p.x_coff[l] = c0.in.coff; p.H[l] = ti.H; p.W[l] = ti.W; p.Cin[l] = c0.in.C; p.x_bytes[l] = ti.bytes;
-        p.w0[l] = w0.d_w; p.Kpad0[l] = w0.Kpad; p.b0[l] = w0.d_b;
-        p.w1[l] = w1.d_w; p.Kpad1[l] = w1.Kpad; p.b1[l] = w1.d_b;
-        p.w2[l] = w2.d_w; p.Kpad2[l] = w2.Kpad; p.b2[l] = w2.d_b;
-        if (l == 0) { p.cmid = c0.out.C; p.cout = c2.out.C; p.act0 = c0.act; p.act1 = c1.act; }
-        // the shape the kernel is written for: 3x3 s1 -> 3x3 s1 -> 1x1 without activation, no residuals, equal widths on every level
-        if (c0.k != 3 || c1.k != 3 || c2.k != 1 || c0.s != 1 || c1.s != 1 || c2.s != 1 || c0.res.t >= 0 || c1.res.t >= 0 || c2.res.t >= 0 || c2.act != ACT_NONE ||
-            c0.out.C != p.cmid || c1.out.C != p.cmid || c1.in.C != p.cmid || c2.in.C != p.cmid || c2.out.C != p.cout || c0.act != p.act0 || c1.act != p.act1 ||
-            w0.cin_pad != c0.in.C || w1.cin_pad != p.cmid) { p.cmid = 0; return p; }
-    }
-    p.B = e.pB; p.max_det = e.desc.max_det; p.maxk = HEAD_MAXK;
-    p.A0 = p.H[0] * p.W[0]; p.A1 = p.H[1] * p.W[1];
-    auto at = [&](size_t off) -> char* { return base ? base + off : nullptr; };      // (plan time: the workspace does not exist yet)
-    p.sel = (const int*)at(ws.sel); p.wlist = (const int*)at(ws.wlist); p.wcount = (const int*)at(ws.wcount);
-    p.out = (float*)at(which == 0 ? ws.box : ws.cf);
-    p.plist = (const int*)at(ws.plist); p.pcount = (const int*)at(ws.pcount);
-    p.t0 = at(which == 0 ? ws.t0box : ws.t0cf); p.t0_bytes = ws.rows * (size_t)p.cmid * 2;
-    for (int l = 0; l < 3; ++l) { p.plist_off[l] = ws.plist_off[l]; p.plist_cap[l] = ws.plist_cap[l]; p.t0_off[l] = ws.t0_off[l] * (size_t)p.cmid; }
-    p.pos_grid = 256;                        // one workgroup per CU (its three plane slots fill most of a CU's LDS)
-    return p;
-}
-
-static int make_plan(yp_engine& e, int B, int H, int W) {
-    if (B <= 0 || H <= 0 || W <= 0 || (H % 32) || (W % 32)) return fail(YP_ERR_ARG, "input must be [B,H,W,3] with H,W multiples of 32 (got %d,%d,%d)", B, H, W);
-    if (e.planned && e.pB == B && e.pH == H && e.pW == W) return YP_OK;
-    size_t A = 0;
-    for (int l = 0; l < 3; ++l) A += (size_t)(H / (8 << l)) * (W / (8 << l));
-    if (A > 12288) return fail(YP_ERR_ARG, "input %dx%d has %zu anchors; the LDS top-k supports at most 12288", H, W, A);
-    for (auto& t : e.tensors) {
-        t.H = H / t.sdiv; t.W = W / t.sdiv;
-        t.bytes = (size_t)B * t.H * t.W * t.C * tensor_elem_bytes(e, t);
-    }
-    for (auto& o : e.ops) {
-        const double es = e.es();
-        auto vbytes = [&](const View& v) {
-            if (v.t < 0) return 0.0;
-            const TensorDesc& t = e.tensors[v.t];
-            return (double)B * t.H * t.W * v.C * (double)tensor_elem_bytes(e, t);
-        };
-        o.flops = 0; o.bytes = vbytes(o.in) + vbytes(o.out) + vbytes(o.res);
-        if (o.kind == OP_CONV || o.kind == OP_DWCONV || o.kind == OP_STEM || o.kind == OP_CONVT) {
-            const TensorDesc& to = e.tensors[o.out.t];
-            const WeightDesc& w = e.weights[o.widx];
-            const double px = (double)B * to.H * to.W;
-            if (o.kind == OP_CONVT) o.flops = 2.0 * px * w.cout * w.cin_g;   // one tap per output pixel
-            else o.flops = 2.0 * px * w.cout * w.cin_g * w.k * w.k;
-            o.bytes += (double)w.cout * w.cin_g * w.k * w.k * es;
-            if (o.kind == OP_STEM) o.bytes += (double)B * H * W * 3;
-        } else if (o.kind == OP_ATTN) {
-            const TensorDesc& ti = e.tensors[o.in.t];
-            const double Nn = (double)ti.H * ti.W;
-            o.flops = 2.0 * B * o.nh * Nn * Nn * (o.kd + o.hd);
-        } else if (o.kind == OP_HEAD) {
-            o.bytes = 0;                       // class-max keys + the winners' class / box rows + the outputs
-            for (int l = 0; l < 3; ++l) o.bytes += (o.amax[l].t >= 0) ? vbytes(o.amax[l]) : vbytes(o.cls[l]);
-            o.bytes += (double)B * e.desc.max_det * (e.desc.nc + 64 + 6 + 1) * 4;
-        }
-    }
-    e.pB = B; e.pH = H; e.pW = W; e.planned = true; e.allocated = false; e.warmed = false;
-    for (auto& o : e.ops) o.cfg = -1;
-    static const char* kn[] = {"stem_kernel", "", "dwconv_kernel", "pool5_kernel", "upsample2_kernel", "attention_kernel", "head_select_kernel", "", "sppf_pool3_kernel", "anchor_max_level_kernel"};
-    for (auto& o : e.ops) { o.form = FORM_PLAIN; o.skip = false; o.folded = false; o.pw_store = false; o.sparse_box = false; o.sparse_cf = false; }
-    static const bool no_fold = env_on("YOLOP_NO_FOLD");   // A/B switch
-    for (auto& o : e.ops) {
-        if (o.kind != OP_CONV || o.fold_up < 0 || e.dtype != DT_BF16 || no_fold) continue;
-        o.folded = true;                                   // tentatively, so that conv_params describes the folded form
-        const ConvParams q = conv_params(e, o);
-        bool any = false;
-        for (int c = 0; c < conv_dma_p_family.num_cfgs && !any; ++c) any = conv_dma_p_family.valid(q, c);
-        if (any) e.ops[o.fold_up].skip = true;
-        else o.folded = false;
-    }
-    for (auto& o : e.ops) {
-        if (o.kind == OP_CONV && o.fuse_pre >= 0 && e.dtype == DT_BF16 && e.fuse) {
-            o.form = FORM_S2PW;                            // tentatively, so that conv_params describes the fused form
-            const ConvParams q = conv_params(e, o);
-            const int c = conv_halo_s2_pw_cfg(q);
-            if (c >= 0) {
-                e.ops[o.fuse_pre].skip = true; o.cfg = conv_halo_s2_family.base + c; o.kernel = conv_halo_s2_family.symbol(q, c);
-                // ... and with the stem in front of it, when the stem's output has no other reader
-                static const bool no_front = env_on("YOLOP_NO_FRONT");   // A/B switch
-                const Op& c1 = e.ops[o.fuse_pre];
-                int stem = -1, readers = 0;
-                for (size_t j = 0; j < e.ops.size(); ++j) {
-                    if (e.ops[j].kind == OP_STEM && e.ops[j].out.t == c1.in.t) stem = (int)j;
-                    for (const View* v : {&e.ops[j].in, &e.ops[j].res}) if (v->t == c1.in.t) ++readers;
-                }
-                if (stem >= 0 && readers == 1 && !no_front && e.weights[e.ops[stem].widx].d_w2 != nullptr) {
-                    o.stem_op = stem;
-                    if (frontend_valid(front_params(e, o, nullptr))) { o.form = FORM_FRONTEND; e.ops[stem].skip = true; o.kernel = "frontend_kernel"; }
-                }
-                continue;
-            }
-            o.form = FORM_PLAIN;
-        }
-        static const bool no_c2f = env_on("YOLOP_NO_C2F");   // A/B switch
-        if (o.kind == OP_CONV && o.c2f_m1 >= 0 && e.dtype == DT_BF16 && e.fuse && !no_c2f && c2f_fused_valid(c2f_params(e, o))) {
-            o.form = FORM_C2F; e.ops[o.c2f_m1].skip = true; e.ops[o.c2f_m2].skip = true; o.kernel = "c2f_fused_kernel";
-            continue;
-        }
-        if (o.kind == OP_CONV && o.fuse_dw >= 0 && e.dtype == DT_BF16 && e.fuse) {
-            const DwPwParams q = dwpw_params(e, o);
-            if (conv_dwpw_valid(q)) { o.form = FORM_DWPW; e.ops[o.fuse_dw].skip = true; o.kernel = conv_dwpw_kernel_name(q); continue; }
-        }
-        // TAIL form (logit conv + class-max keys as a third stage of the last dw -> pw pair): opt-in, YOLOP_TAIL=1. Alone it takes 33 us less
-        // than the three launches it replaces (213 -> 180 us over the P3 / P4 class branches, -105 MB of HBM traffic), but in the replayed
-        // graph the step is 0.7 % SLOWER with it (1.936 vs 1.922 ms, same box, three alternating runs): the 1x1 conv and the max pass it
-        // removes were HBM-bound and ran beside the VALU-bound kernels of the other head lanes for free, while the longer fused kernel holds
-        // its statically assigned CUs for longer.
-        if (o.kind == OP_CONV && o.fuse_tail >= 0 && e.dtype == DT_BF16 && e.fuse && e.tail && e.ops[o.fuse_tail].form == FORM_DWPW) {
-            // (ops are visited in order: the pointwise conv in front has already been decided)
-            o.form = FORM_DWPW_TAIL;
-            const DwPwParams q = dwpw_params(e, o);
-            if (conv_dwpw_valid(q)) {
-                e.ops[o.fuse_tail].skip = true;
-                if (o.tail_amax >= 0) e.ops[o.tail_amax].skip = true;
-                o.kernel = conv_dwpw_kernel_name(q);
-                continue;
-            }
-            o.form = FORM_PLAIN;
-        }
-        if (o.kind == OP_CONV) o.kernel = conv_kernel_name(conv_params(e, o), e.dtype);
-        else if (o.kind == OP_CONVT) {
-            ConvParams p{};
-            p.Cout = o.out.C; p.M = B * e.tensors[o.in.t].H * e.tensors[o.in.t].W; p.Cin = o.in.C; p.ks = 1;
-            p.Kpad = (o.in.C + 31) / 32 * 32; p.cfg = o.cfg;
-            o.kernel = conv_kernel_name(p, e.dtype);
-        } else if (o.kind == OP_DWCONV) {
-            static const bool no_scd = env_on("YOLOP_NO_SCD");   // A/B switch
-            if (o.scd_pre >= 0 && e.dtype == DT_BF16 && e.fuse && !no_scd && scdown_fused_valid(scd_params(e, o))) {
-                o.form = FORM_SCDOWN; e.ops[o.scd_pre].skip = true; o.kernel = scdown_fused_kernel_name(scd_params(e, o));
-                continue;
-            }
-            const char* t = e.dtype == DT_BF16 ? "bf16" : "f32";
-            char buf[64];
-            DwParams q{};
-            q.H = q.Ho = e.tensors[o.in.t].H; q.W = q.Wo = e.tensors[o.in.t].W; q.C = o.out.C; q.ks = o.k; q.stride = o.s; q.gs = o.gs;
-            q.x_stride = e.tensors[o.in.t].C; q.x_coff = o.in.coff; q.y_stride = e.tensors[o.out.t].C; q.y_coff = o.out.coff;
-            q.res = o.res.t >= 0 ? (const void*)1 : nullptr;
-            q.x_bytes = (size_t)B * q.H * q.W * q.x_stride * 2;
-            if (dwconv_mfma_valid(q, e.dtype)) snprintf(buf, sizeof(buf), "dwconv_mfma_kernel<%d,%s>", o.k, B * (q.C / 32) >= 256 ? "false" : "true");
-            else if (o.k == 3 && o.s == 1) snprintf(buf, sizeof(buf), "dwconv_row_kernel<%s,3,1,4>", t);
-            else if (o.k == 3 && o.s == 2) snprintf(buf, sizeof(buf), "dwconv_row_kernel<%s,3,2,2>", t);
-            else if (o.k == 7 && o.s == 1) snprintf(buf, sizeof(buf), "dwconv_row_kernel<%s,7,1,2>", t);
-            else snprintf(buf, sizeof(buf), "dwconv_kernel<%s>", t);
-            o.kernel = buf;
-        } else if (o.kind == OP_STEM) {
-            char buf[64];
-            if (e.dtype == DT_BF16) snprintf(buf, sizeof(buf), "stem_mfma_kernel<%d>", o.out.C / 16);
-            else snprintf(buf, sizeof(buf), "stem_kernel<f32>");
-            o.kernel = buf;
-        } else if (o.kind == OP_POOL3 && e.dtype == DT_BF16 && (o.in.C & 31) == 0) o.kernel = "sppf_pool3_bf16_kernel";
-        else o.kernel = (o.kind == OP_HEAD && o.nms) ? "head_nms_kernel" : kn[o.kind];
-    }
-    // winners-only head (v10 top-k head, bf16): the box / coefficient branches run on the stage-1 winners inside the head op; their dense
-    // convolutions stay in the op list (yp_run_op steps them, the fp32 parity mode and YOLOP_DENSE_HEAD=1 run them) but launch nothing here
-    for (auto& o : e.ops) {
-        if (o.kind != OP_HEAD || o.nms || e.dtype != DT_BF16 || !e.sparse_head || e.desc.max_det > HEAD_MAXK || o.amax[0].t < 0) continue;
-        for (int which = 0; which < 2; ++which) {
-            const HeadBranchParams q = head_branch_params(e, o, which);
-            if (q.cmid == 0 || !head_branch_valid(q)) continue;
-            if (which == 1 && !o.sparse_box) continue;              // (stage 2 reads the coefficient rows by rank only beside winners-only box rows)
-            // the branch's tensors must have no reader outside the branch and the head op (they are never written in this mode)
-            bool outside = false;
-            for (int l = 0; l < 3 && !outside; ++l)
-                for (int j = 0; j < 3 && !outside; ++j) {
-                    const int oi = (which == 0 ? o.hb_box : o.hb_cf)[l][j];
-                    const View& w = e.ops[oi].out;
-                    for (size_t r = 0; r < e.ops.size() && !outside; ++r) {
-                        const Op& q2 = e.ops[r];
-                        if (&q2 == &o) continue;
-                        bool member = false;
-                        for (int l2 = 0; l2 < 3; ++l2) for (int j2 = 0; j2 < 3; ++j2) member |= (int)r == (which == 0 ? o.hb_box : o.hb_cf)[l2][j2];
-                        if (member) continue;
-                        for (const View* v : {&q2.in, &q2.res}) outside |= v->t >= 0 && v->t == w.t && v->coff < w.coff + w.C && w.coff < v->coff + v->C;
-                    }
-                }
-            if (outside) continue;
-            (which == 0 ? o.sparse_box : o.sparse_cf) = true;
-            for (int l = 0; l < 3; ++l)
-                for (int j = 0; j < 3; ++j) {
-                    Op& c = e.ops[(which == 0 ? o.hb_box : o.hb_cf)[l][j]];
-                    c.skip = true;
-                }
-        }
-    }
-    // 1x1 -> depthwise / pool chain as pwsp_kernel (decided last: it looks at which ops still launch). The 1x1 conv is skipped, the spatial
-    // op launches the kernel; the conv's own output is written as well when anything else reads it. Not when an op that still launches
-    // sits between the two and reads the conv's output (the kernel runs at the SPATIAL op's place in the order).
-    {
-        static const bool no_pwsp = env_on("YOLOP_NO_PWSP");   // A/B switch
-        for (size_t i = 0; i < e.ops.size(); ++i) {
-            Op& d = e.ops[i];
-            if (d.pw_pre < 0 || e.dtype != DT_BF16 || !e.fuse || no_pwsp || d.skip || d.form != FORM_PLAIN) continue;
-            Op& c = e.ops[d.pw_pre];
-            if (!plain_conv(c) || c.folded) continue;
-            // from the effective read / write sets of the ops that still launch: the conv's output read anywhere else = other readers;
-            // moved to the spatial op's place, the conv must not pass an op that reads or writes its output, writes its input or residual,
-            // or touches the spatial op's output / residual
-            bool between = false, other = false;
-            std::vector<View> rd, wr;
-            auto any_overlap = [](const std::vector<View>& vs, const View& v) {
-                for (const View& x : vs) if (views_overlap(x, v)) return true;
-                return false;
-            };
-            for (size_t j = 0; j < e.ops.size(); ++j) {
-                if (j == i || (int)j == d.pw_pre || e.ops[j].skip) continue;
-                op_views(e, e.ops[j], rd, wr);
-                const bool reads = any_overlap(rd, c.out);
-                other |= reads;
-                if ((int)j > d.pw_pre && j < i)
-                    between |= reads || any_overlap(wr, c.out) || any_overlap(wr, c.in) || any_overlap(wr, c.res) || any_overlap(wr, d.out) || any_overlap(wr, d.res) ||
-                               any_overlap(rd, d.out);
-            }
-            if (between) continue;
-            d.form = FORM_PWSP; d.pw_store = other;
-            if (!pwsp_valid(pwsp_params(e, d))) { d.form = FORM_PLAIN; d.pw_store = false; continue; }
-            c.skip = true;
-            d.kernel = pwsp_kernel_name(pwsp_params(e, d));
-        }
-    }
-    // class logits + class-max keys in one launch (cls_out_kernel): the OP_AMAX op is skipped
-    {
-        static const bool no_co = env_on("YOLOP_NO_CLSOUT");   // A/B switch
-        for (auto& o : e.ops) {
-            if (o.kind != OP_CONV || o.amax_post < 0 || e.dtype != DT_BF16 || !e.fuse || no_co) continue;
-            if (!plain_conv(o) || o.folded || e.ops[o.amax_post].skip) continue;
-            if (!cls_out_valid(cls_out_params(e, o))) continue;
-            o.form = FORM_CLS_OUT; e.ops[o.amax_post].skip = true;
-            o.kernel = cls_out_kernel_name(cls_out_params(e, o));
-        }
-    }
-    // algorithmic work of the graph as it runs: an op whose work moved into a fused consumer reports nothing and launches
-    // nothing; the consumer reports the FLOPs of all its stages and the bytes of what it reads and writes (the intermediates
-    // never reach HBM), a conv with a folded upsample reads the low-resolution tensor instead of its upsampled copy
-    {
-        const double es = e.es();
-        auto vb = [&](const View& v) {
-            if (v.t < 0) return 0.0;
-            const TensorDesc& t = e.tensors[v.t];
-            return (double)B * t.H * t.W * v.C * (double)tensor_elem_bytes(e, t);
-        };
-        auto wb = [&](const Op& q) { const WeightDesc& w = e.weights[q.widx]; return (double)w.cout * w.cin_g * w.k * w.k * es; };
-        for (auto& o : e.ops) {
-            switch (o.form) {
-                case FORM_PLAIN: break;
-                case FORM_SCDOWN: { const Op& c1 = e.ops[o.scd_pre]; o.flops += c1.flops; o.bytes = vb(c1.in) + vb(o.out) + wb(c1) + wb(o); break; }
-                case FORM_PWSP: {
-                    const Op& c1 = e.ops[o.pw_pre];
-                    o.flops += c1.flops;
-                    o.bytes = vb(c1.in) + (o.pw_store ? vb(c1.out) : 0.0) + vb(o.out) + vb(o.res) + wb(c1) + (o.kind == OP_DWCONV ? wb(o) : 0.0);
-                    break;
-                }
-                case FORM_DWPW: { const Op& d = e.ops[o.fuse_dw]; o.flops += d.flops; o.bytes = vb(d.in) + vb(d.res) + vb(o.out) + wb(d) + wb(o); break; }
-                case FORM_DWPW_TAIL: {                 // (its pointwise conv, visited before, already carries the depthwise stage's FLOPs)
-                    const Op& c1 = e.ops[o.fuse_tail];
-                    const Op& d = e.ops[c1.fuse_dw];
-                    o.flops += c1.flops;
-                    o.bytes = vb(d.in) + vb(o.out) + wb(d) + wb(c1) + wb(o) + (o.tail_amax >= 0 ? vb(e.ops[o.tail_amax].out) : 0.0);
-                    break;
-                }
-                case FORM_FRONTEND: {
-                    const Op &c1 = e.ops[o.fuse_pre], &st = e.ops[o.stem_op];
-                    o.flops += c1.flops + st.flops; o.bytes = (double)B * H * W * 3 + vb(o.out) + wb(st) + wb(c1) + wb(o);
-                    break;
-                }
-                case FORM_S2PW: { const Op& c1 = e.ops[o.fuse_pre]; o.flops += c1.flops; o.bytes = vb(c1.in) + vb(o.out) + wb(c1) + wb(o); break; }
-                case FORM_C2F: {
-                    const Op &m1 = e.ops[o.c2f_m1], &m2 = e.ops[o.c2f_m2];
-                    o.flops += m1.flops + m2.flops;
-                    o.bytes = vb(View{o.in.t, o.in.coff, 2 * m1.in.C}) + vb(o.out) + wb(m1) + wb(m2) + wb(o);
-                    break;
-                }
-                case FORM_CLS_OUT: o.bytes += vb(e.ops[o.amax_post].out); break;
-            }
-            if (o.folded) { const Op& u = e.ops[o.fold_up]; o.bytes += vb(u.in) - vb(u.out); }
-        }
-        for (auto& o : e.ops) {
-            if (o.kind != OP_HEAD) continue;
-            for (int which = 0; which < 2; ++which) {
-                if (!(which == 0 ? o.sparse_box : o.sparse_cf)) continue;
-                const HeadBranchParams q = head_branch_params(e, o, which);
-                for (int l = 0; l < 3; ++l) {        // (which level a winner lies on is data: a third each, neighbourhoods disjoint unless the level is full)
-                    const double nw = (double)B * e.desc.max_det / 3.0;
-                    const double npos = std::min(9.0 * nw, (double)B * q.H[l] * q.W[l]);
-                    o.flops += 2.0 * (npos * 9.0 * q.Cin[l] * q.cmid + nw * (9.0 * q.cmid * q.cmid + (double)q.cmid * q.cout));
-                    o.bytes += npos * (9.0 * q.Cin[l] * 2 + 2.0 * q.cmid * 2) + nw * q.cout * 4 + (9.0 * q.Cin[l] * q.cmid + 9.0 * q.cmid * q.cmid + q.cmid * q.cout) * 2;
-                }
-            }
-            if (o.sparse_box || o.sparse_cf) o.kernel = "head_select_kernel<1> + head_pos_kernel + head_win_kernel + head_select_kernel<2>";
-        }
-        for (auto& o : e.ops)
-            if (o.skip) { o.flops = 0; o.bytes = 0; o.kernel = "-"; }
-    }
-    return YP_OK;
-}
-
-static int allocate_plan(yp_engine& e) {
-    if (e.allocated) return YP_OK;
-    // A dense conv packed with padded taps (WeightDesc::cin_pad > Cin, see conv_params) reads cin_pad channels per pixel and multiplies the
-    // surplus by zero weights: the surplus bytes are the next channels of the same pixel (in a concat buffer: a slice a LATER op writes), the
-    // next pixel, or - at the last pixel of the last image - up to (cin_pad - Cin) * 2 < 64 bytes past the end of the tensor. Every one of
-    // those bytes must be a finite bf16 pattern (NaN * 0 = NaN on the matrix cores; a NaN output then lands in the very slice the next
-    // forward over-reads, i.e. it would never heal). So (i) a tensor read by such a conv owns a 64-byte tail inside its slot, and (ii) the
-    // whole region of a layout is zeroed on EVERY layout, not only when the arena grows: a re-plan into the kept arena puts bf16 tensors
-    // over stale fp32 logits / u32 keys, whose low halves read as bf16 NaN once in 256.
-    std::vector<char> tail(e.tensors.size(), 0);
-    for (const auto& o : e.ops)
-        if (o.kind == OP_CONV && o.widx >= 0 && o.in.t >= 0 && e.weights[o.widx].cin_pad > o.in.C) tail[o.in.t] = 1;
-    auto slot = [&](size_t i) { return (e.tensors[i].bytes + (tail[i] ? 64 : 0) + 255) & ~(size_t)255; };
-    size_t total = 0;
-    for (size_t i = 0; i < e.tensors.size(); ++i) total += slot(i);
-    HIPCHK(hipSetDevice(e.device));
-    total += 4096;                                   // (slack behind the last tensor: padded-tap reads of conv_igemm's plain loads)
-    if (total > e.arena_bytes) {
-        if (e.arena) HIPCHK(hipFree(e.arena));
-        e.arena = nullptr;
-        HIPCHK(hipMalloc(&e.arena, total));
-        e.arena_bytes = total;
-    }
-    HIPCHK(hipMemset(e.arena, 0, total));            // (2.9 GB at S / bs 32: ~1 ms, once per plan)
-    size_t off = 0;
-    for (size_t i = 0; i < e.tensors.size(); ++i) {
-        e.tensors[i].ptr = (char*)e.arena + off;
-        off += slot(i);
-    }
-    {
-        size_t A = 0;
-        for (int l = 0; l < 3; ++l) A += (size_t)(e.pH / (8 << l)) * (e.pW / (8 << l));
-        const size_t need = head_scratch_bytes(e.pB, (int)A);
-        if (need > e.head_ws_bytes) {
-            if (e.head_ws) HIPCHK(hipFree(e.head_ws));
-            e.head_ws = nullptr;
-            HIPCHK(hipMalloc(&e.head_ws, need));
-            e.head_ws_bytes = need;
-        }
-    }
-    {
-        bool sparse = false;
-        for (const auto& o : e.ops) sparse |= o.kind == OP_HEAD && (o.sparse_box || o.sparse_cf);
-        const size_t need = sparse ? sparse_ws_layout(e).total : 0;
-        if (need > e.sp_ws_bytes) {
-            if (e.sp_ws) HIPCHK(hipFree(e.sp_ws));
-            e.sp_ws = nullptr; e.sp_ws_bytes = 0;
-            HIPCHK(hipMalloc(&e.sp_ws, need));
-            e.sp_ws_bytes = need;
-        }
-        // zeroed for every plan, not only when it grows: the layout moves with B, so the head's live position counters (which every
-        // forward empties behind itself) can land on rows the previous plan left behind - garbage counts index the lists out of bounds
-        if (need) HIPCHK(hipMemset(e.sp_ws, 0, need));
-    }
-    if (e.desc.family != YP_FAMILY_V10) {
-        size_t A = 0;
-        for (int l = 0; l < 3; ++l) A += (size_t)(e.pH / (8 << l)) * (e.pW / (8 << l));
-        const size_t need = head_nms_scratch_bytes(e.pB, (int)A);
-        if (need > e.nms_ws_bytes) {
-            if (e.nms_ws) HIPCHK(hipFree(e.nms_ws));
-            e.nms_ws = nullptr; e.nms_ws_bytes = 0;
-            HIPCHK(hipMalloc(&e.nms_ws, need));
-            e.nms_ws_bytes = need;
-        }
-        if (!e.d_nms) {
-            HIPCHK(hipMalloc((void**)&e.d_nms, 2 * sizeof(float)));
-            const float v[2] = {e.nms_conf, e.nms_iou};
-            HIPCHK(hipMemcpy(e.d_nms, v, sizeof(v), hipMemcpyHostToDevice));
-        }
-    }
-    if ((size_t)e.pB > e.o_cap) {
-        if (e.o_det) { HIPCHK(hipFree(e.o_det)); HIPCHK(hipFree(e.o_idx)); HIPCHK(hipFree(e.o_coeff)); }
-        const size_t rows = (size_t)e.pB * e.desc.max_det;
-        HIPCHK(hipMalloc(&e.o_det, rows * 6 * sizeof(float)));
-        HIPCHK(hipMalloc(&e.o_idx, rows * sizeof(int32_t)));
-        HIPCHK(hipMalloc(&e.o_coeff, rows * 32 * sizeof(float)));
-        e.o_cap = (size_t)e.pB;
-    }
-    if (e.gexec) { (void)hipDeviceSynchronize(); drop_graph(e); }   // (never under a running replay)
-    e.allocated = true;
-    return YP_OK;
+// bytes of a view under the current plan (0 for no view)
+static double view_bytes(const yp_engine& e, const View& v) {
+    if (v.t < 0) return 0.0;
+    const TensorDesc& t = e.tensors[v.t];
+    return (double)e.pB * t.H * t.W * v.C * (double)tensor_elem_bytes(e, t);
 }
 
 // ---------------------------------------------------------------------------------------------------------
-// op launch
+// parameter blocks of the launches, built from the op and the current plan
 // ---------------------------------------------------------------------------------------------------------
 struct RunArgs { const uint8_t* in; float* det; int32_t* idx; float* coeff; };
 
@@ -1285,15 +840,539 @@ static ConvParams convt_params(const yp_engine& e, const Op& o, int dy, int dx) 
     return p;
 }
 
+static DwPwParams dwpw_params(const yp_engine& e, const Op& c) {
+    if (c.form == FORM_DWPW_TAIL) {      // the dw -> pw pair in front with this 1x1 (and the class-max keys) as the third stage
+        DwPwParams p = dwpw_params(e, e.ops[c.fuse_tail]);
+        const WeightDesc& w3 = e.weights[c.widx];
+        const TensorDesc& to = e.tensors[c.out.t];
+        p.w3 = w3.d_w ? w3.d_w : (const void*)1; p.Kpad3 = w3.Kpad; p.w3_bytes = w3.mat_bytes; p.b3 = w3.d_b ? w3.d_b : (const float*)1; p.C3 = c.out.C;
+        p.y3 = to.ptr ? (float*)to.ptr : (float*)1; p.y3_stride = to.C; p.y3_coff = c.out.coff; p.y3_bytes = to.bytes;
+        p.keys = c.tail_amax >= 0 ? (unsigned*)e.tensors[e.ops[c.tail_amax].out.t].ptr : nullptr;
+        p.out_f32 = 0;
+        return p;
+    }
+    const Op& d = e.ops[c.fuse_dw];
+    const WeightDesc &wd = e.weights[d.widx], &wp = e.weights[c.widx];
+    const TensorDesc &ti = e.tensors[d.in.t], &to = e.tensors[c.out.t];
+    DwPwParams p{};
+    p.x = ti.ptr; p.x_stride = ti.C; p.x_coff = d.in.coff; p.B = e.pB; p.H = ti.H; p.W = ti.W; p.C = d.in.C; p.x_bytes = ti.bytes;
+    p.w_dw = wd.d_w; p.b_dw = wd.d_b; p.act_dw = d.act;
+    p.w_pw = wp.d_w; p.Kpad = wp.Kpad; p.wpw_bytes = wp.mat_bytes; p.b_pw = wp.d_b; p.act_pw = c.act;
+    p.y = to.ptr; p.y_stride = to.C; p.y_coff = c.out.coff; p.y_bytes = to.bytes; p.Cout = c.out.C;
+    p.out_f32 = (to.f32 && e.dtype == DT_BF16) ? 1 : 0;
+    return p;
+}
+
+// the depthwise conv's own launch (launch_dwconv); at plan time, before the arena exists, for the kernel name (dwconv_kernel_name)
+static DwParams dw_params(const yp_engine& e, const Op& o) {
+    const WeightDesc& w = e.weights[o.widx];
+    const TensorDesc &ti = e.tensors[o.in.t], &to = e.tensors[o.out.t];
+    DwParams p{};
+    p.x = ti.ptr; p.x_stride = ti.C; p.x_coff = o.in.coff; p.H = ti.H; p.W = ti.W; p.C = o.out.C;
+    p.w = w.d_w; p.bias = w.d_b;
+    p.y = to.ptr; p.y_stride = to.C; p.y_coff = o.out.coff; p.Ho = to.H; p.Wo = to.W;
+    if (o.res.t >= 0) { const TensorDesc& tr = e.tensors[o.res.t]; p.res = tr.ptr ? tr.ptr : (const void*)1; p.res_stride = tr.C; p.res_coff = o.res.coff; }
+    p.B = e.pB; p.ks = o.k; p.stride = o.s; p.pad = o.k / 2; p.act = o.act; p.gs = o.gs; p.gstride = o.gstride;
+    p.x_bytes = ti.bytes;
+    return p;
+}
+
+static StemParams stem_params(const yp_engine& e, const Op& o, const uint8_t* img) {
+    const WeightDesc& w = e.weights[o.widx];
+    const TensorDesc& to = e.tensors[o.out.t];
+    StemParams p{};
+    p.x = img; p.H = e.pH; p.W = e.pW; p.w = (const float*)w.d_w; p.wpk = w.d_w2; p.bias = w.d_b;
+    p.y = to.ptr; p.y_stride = to.C; p.y_coff = o.out.coff; p.Ho = to.H; p.Wo = to.W; p.C0 = o.out.C; p.B = e.pB; p.act = o.act;
+    return p;
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// The fused launch forms: one record per Form, kForms[form]. Everything the planner, the byte accounting, the lane schedule, the
+// launch and the introspection calls know about a form is in its record; only yp_op_fusion, which reports the pwsp pair, names one.
+//   absorbed: the ops whose work the form takes over, from the launching op's graph links (0 = o is no candidate); make_plan skips them
+//   admit:    o.form is the record's: build the parameter block, ask the kernel's predicate; the kernel's name (S2PW: and its cfg), "" = refused
+//   views:    what the launch reads in place of o.in (`in` arrives as o.in; t < 0 = nothing) and the second tensor it writes
+//   launch:   the launch itself
+// The gate in front of admit is the same for all: a bf16 engine, fusion on (YOLOP_NO_FUSE), the record's own A/B switch off.
+//
+// The ORDER in which make_plan tries the forms is behaviour and is not in the table. One pass over the ops, in op order, decides
+// S2PW -> FRONTEND (only on top of an admitted S2PW), then C2F, DWPW and DWPW_TAIL for a conv and SCDOWN for a depthwise conv; DWPW_TAIL
+// relies on the pointwise conv in front of it having been decided earlier in that same pass. Then comes the winners-only head, then PWSP,
+// which looks at which ops still launch, and last CLS_OUT, which must see PWSP's and the head's skips.
+// ---------------------------------------------------------------------------------------------------------
+struct FormRec {
+    const char* off_env;          // A/B switch: set to 1 it keeps the form's ops apart; null = none
+    bool own_cfg;                 // Op::cfg is the launch's configuration id (yp_debug_op_cfg); the other forms have none
+    bool reads_frames;            // the launch reads the caller's frames: B*H*W*3 bytes, and the tuner can run it only when it has them
+    int (*absorbed)(const yp_engine& e, const Op& o, int m[3]);
+    std::string (*admit)(const yp_engine& e, const Op& o, int& cfg);
+    void (*views)(const yp_engine& e, const Op& o, View& in, View& extra);
+    hipError_t (*launch)(const yp_engine& e, const Op& o, const RunArgs& a, hipStream_t st);
+};
+static int link1(int i, int m[3]) { m[0] = i; return i >= 0 ? 1 : 0; }
+
+// conv_dwpw_kernel: the depthwise 3x3 in front (fuse_dw) -> this 1x1
+static int dwpw_absorbed(const yp_engine&, const Op& o, int m[3]) { return link1(o.fuse_dw, m); }
+static std::string dwpw_admit(const yp_engine& e, const Op& o, int&) {
+    const DwPwParams q = dwpw_params(e, o);
+    return conv_dwpw_valid(q) ? conv_dwpw_kernel_name(q) : "";
+}
+static void dwpw_views(const yp_engine& e, const Op& o, View& in, View&) { in = e.ops[o.fuse_dw].in; }
+static hipError_t dwpw_launch(const yp_engine& e, const Op& o, const RunArgs&, hipStream_t st) { return launch_conv_dwpw(dwpw_params(e, o), st); }
+
+// its TAIL form: dw -> pw (fuse_tail, itself a DWPW) -> this logit conv (+ the class-max keys of tail_amax). Opt-in, YOLOP_TAIL=1: alone it
+// takes 33 us less than the three launches it replaces (213 -> 180 us over the P3 / P4 class branches, -105 MB of HBM traffic), but in the
+// replayed graph the step is 0.7 % SLOWER with it (1.936 vs 1.922 ms, same box, three alternating runs): the 1x1 conv and the max pass it
+// removes were HBM-bound and ran beside the VALU-bound kernels of the other head lanes for free, while the longer fused kernel holds its
+// statically assigned CUs for longer.
+static int tail_absorbed(const yp_engine& e, const Op& o, int m[3]) {
+    if (o.fuse_tail < 0) return 0;
+    m[0] = e.ops[o.fuse_tail].fuse_dw; m[1] = o.fuse_tail; m[2] = o.tail_amax;
+    return o.tail_amax >= 0 ? 3 : 2;
+}
+static std::string tail_admit(const yp_engine& e, const Op& o, int& cfg) {
+    return e.tail && e.ops[o.fuse_tail].form == FORM_DWPW ? dwpw_admit(e, o, cfg) : "";
+}
+static void tail_views(const yp_engine& e, const Op& o, View& in, View& extra) {
+    in = e.ops[e.ops[o.fuse_tail].fuse_dw].in;
+    if (o.tail_amax >= 0) extra = e.ops[o.tail_amax].out;
+}
+
+// conv_halo_s2's PW2 form: the 3x3 s2 conv in front (fuse_pre) -> this 1x1
+static int s2pw_absorbed(const yp_engine&, const Op& o, int m[3]) { return link1(o.fuse_pre, m); }
+static std::string s2pw_admit(const yp_engine& e, const Op& o, int& cfg) {
+    const ConvParams q = conv_params(e, o);
+    const int c = conv_halo_s2_pw_cfg(q);
+    if (c < 0) return "";
+    cfg = conv_halo_s2_family.base + c;
+    return conv_halo_s2_family.symbol(q, c);
+}
+static void s2pw_views(const yp_engine& e, const Op& o, View& in, View&) { in = e.ops[o.fuse_pre].in; }
+static hipError_t s2pw_launch(const yp_engine& e, const Op& o, const RunArgs&, hipStream_t st) {
+    return conv_halo_s2_family.launch(conv_params(e, o), o.cfg - conv_halo_s2_family.base, st);
+}
+
+// frontend_kernel: stem (stem_op) -> 3x3 s2 (fuse_pre) -> this 1x1; needs the stem's uploaded GEMM layout, so never before yp_finalize
+static int front_absorbed(const yp_engine&, const Op& o, int m[3]) {
+    m[0] = o.stem_op; m[1] = o.fuse_pre;
+    return o.stem_op >= 0 && o.fuse_pre >= 0 ? 2 : 0;
+}
+static std::string front_admit(const yp_engine& e, const Op& o, int&) {
+    return e.weights[e.ops[o.stem_op].widx].d_w2 && frontend_valid(front_params(e, o, nullptr)) ? "frontend_kernel" : "";
+}
+static void front_views(const yp_engine&, const Op&, View& in, View&) { in = View{}; }
+static hipError_t front_launch(const yp_engine& e, const Op& o, const RunArgs& a, hipStream_t st) { return launch_frontend(front_params(e, o, a.in), st); }
+
+// c2f_fused_kernel: the bottleneck's two 3x3 convs (c2f_m1, c2f_m2) -> this 1x1 over [a | b | c]; it reads a and b only
+static int c2f_absorbed(const yp_engine&, const Op& o, int m[3]) {
+    m[0] = o.c2f_m1; m[1] = o.c2f_m2;
+    return o.c2f_m1 >= 0 ? 2 : 0;
+}
+static std::string c2f_admit(const yp_engine& e, const Op& o, int&) { return c2f_fused_valid(c2f_params(e, o)) ? "c2f_fused_kernel" : ""; }
+static void c2f_views(const yp_engine& e, const Op& o, View& in, View&) { in = View{o.in.t, o.in.coff, 2 * e.ops[o.c2f_m1].in.C}; }
+static hipError_t c2f_launch(const yp_engine& e, const Op& o, const RunArgs&, hipStream_t st) { return launch_c2f_fused(c2f_params(e, o), st); }
+
+// scdown_fused_kernel: the 1x1 in front (scd_pre) -> this depthwise 3x3 s2
+static int scd_absorbed(const yp_engine&, const Op& o, int m[3]) { return link1(o.scd_pre, m); }
+static std::string scd_admit(const yp_engine& e, const Op& o, int&) {
+    const ScdParams q = scd_params(e, o);
+    return scdown_fused_valid(q) ? scdown_fused_kernel_name(q) : "";
+}
+static void scd_views(const yp_engine& e, const Op& o, View& in, View&) { in = e.ops[o.scd_pre].in; }
+static hipError_t scd_launch(const yp_engine& e, const Op& o, const RunArgs&, hipStream_t st) { return launch_scdown_fused(scd_params(e, o), st); }
+
+// pwsp_kernel: the 1x1 in front (pw_pre) -> this depthwise conv / pool chain; the 1x1's own output too when it has other readers (pw_store)
+static int pwsp_absorbed(const yp_engine&, const Op& o, int m[3]) { return link1(o.pw_pre, m); }
+static std::string pwsp_admit(const yp_engine& e, const Op& o, int&) {
+    const PwSpParams q = pwsp_params(e, o);
+    return pwsp_valid(q) ? pwsp_kernel_name(q) : "";
+}
+static void pwsp_views(const yp_engine& e, const Op& o, View& in, View& extra) {
+    in = e.ops[o.pw_pre].in;
+    if (o.pw_store) extra = e.ops[o.pw_pre].out;
+}
+static hipError_t pwsp_launch(const yp_engine& e, const Op& o, const RunArgs&, hipStream_t st) { return launch_pwsp(pwsp_params(e, o), st); }
+
+// cls_out_kernel: this logit conv and the class-max keys of amax_post
+static int clsout_absorbed(const yp_engine&, const Op& o, int m[3]) { return link1(o.amax_post, m); }
+static std::string clsout_admit(const yp_engine& e, const Op& o, int&) {
+    const ClsOutParams q = cls_out_params(e, o);
+    return cls_out_valid(q) ? cls_out_kernel_name(q) : "";
+}
+static void clsout_views(const yp_engine& e, const Op& o, View&, View& extra) { extra = e.ops[o.amax_post].out; }
+static hipError_t clsout_launch(const yp_engine& e, const Op& o, const RunArgs&, hipStream_t st) { return launch_cls_out(cls_out_params(e, o), st); }
+
+static const FormRec kForms[] = {     // indexed by Form
+    /* FORM_PLAIN */     {nullptr, false, false, nullptr, nullptr, nullptr, nullptr},
+    /* FORM_DWPW */      {nullptr, false, false, dwpw_absorbed, dwpw_admit, dwpw_views, dwpw_launch},
+    /* FORM_DWPW_TAIL */ {nullptr, false, false, tail_absorbed, tail_admit, tail_views, dwpw_launch},
+    /* FORM_S2PW */      {nullptr, true, false, s2pw_absorbed, s2pw_admit, s2pw_views, s2pw_launch},
+    /* FORM_FRONTEND */  {"YOLOP_NO_FRONT", false, true, front_absorbed, front_admit, front_views, front_launch},
+    /* FORM_C2F */       {"YOLOP_NO_C2F", false, false, c2f_absorbed, c2f_admit, c2f_views, c2f_launch},
+    /* FORM_SCDOWN */    {"YOLOP_NO_SCD", false, false, scd_absorbed, scd_admit, scd_views, scd_launch},
+    /* FORM_PWSP */      {"YOLOP_NO_PWSP", false, false, pwsp_absorbed, pwsp_admit, pwsp_views, pwsp_launch},
+    /* FORM_CLS_OUT */   {"YOLOP_NO_CLSOUT", false, false, clsout_absorbed, clsout_admit, clsout_views, clsout_launch},
+};
+constexpr int kNumForms = (int)(sizeof(kForms) / sizeof(kForms[0]));
+static_assert(kNumForms == FORM_CLS_OUT + 1, "one record per Form, in the enum's order");
+// the record of the fused form o launches as; null for an op that launches as itself or not at all
+static const FormRec* fused(const Op& o) { return (o.skip || o.form == FORM_PLAIN) ? nullptr : &kForms[o.form]; }
+// the fused launch's parameter block, built from the current plan and dropped: admit builds it to ask the kernel's predicate (host selftest)
+static void build_form_params(const yp_engine& e, const Op& o) { int cfg; (void)kForms[o.form].admit(e, o, cfg); }
+
+// What a launch reads and writes: drives the lane schedule, PWSP's legality and the tuner's producer search.
+static void op_views(const yp_engine& e, const Op& o, std::vector<View>& rd, std::vector<View>& wr) {
+    rd.clear(); wr.clear();
+    if (o.skip) return;
+    View in = o.in, extra;                                 // extra: a second tensor the fused form writes
+    if (const FormRec* r = fused(o)) r->views(e, o, in, extra);
+    if (in.t >= 0) rd.push_back(in);
+    if (o.folded) rd.push_back(e.ops[o.fold_up].in);      // (besides the concat buffer, whose skip part it still reads)
+    if (o.res.t >= 0) rd.push_back(o.res);
+    if (o.out.t >= 0) wr.push_back(o.out);
+    if (extra.t >= 0) wr.push_back(extra);
+    if (o.kind == OP_HEAD)
+        for (int l = 0; l < 3; ++l) {
+            if (o.sparse_box) rd.push_back(e.ops[o.hb_box[l][0]].in);              // the level's feature map instead of the dense box map
+            else if (o.box[l].t >= 0) rd.push_back(o.box[l]);
+            if (o.cls[l].t >= 0) rd.push_back(o.cls[l]);
+            if (o.sparse_cf) rd.push_back(e.ops[o.hb_cf[l][0]].in);
+            else if (o.cf[l].t >= 0) rd.push_back(o.cf[l]);
+            if (o.amax[l].t >= 0) rd.push_back(o.amax[l]);
+        }
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// plan: resolve shapes for (B,H,W), compute algorithmic flops/bytes
+// ---------------------------------------------------------------------------------------------------------
+// Releases the replay executable and the graph it was instantiated from. Callers have made sure no replay of it is in flight
+// (ev_done synchronised, or a device synchronisation): see the lifetime rule at forward_replay.
+static void drop_graph(yp_engine& e) {
+    if (e.gexec) { (void)hipGraphExecDestroy(e.gexec); e.gexec = nullptr; }
+    if (e.gsrc) { (void)hipGraphDestroy(e.gsrc); e.gsrc = nullptr; }
+}
+// ---- winners-only head (head_branch.hip): workspace layout and parameter blocks -----------------------------------------------------------------
+struct SparseWs {
+    size_t sel, wlist, wcount, thr, box, cf, pcount, plist, t0box, t0cf, total;
+    int plist_off[3], plist_cap[3];          // per level: first entry / capacity of its position list
+    size_t t0_off[3];                        // per level: first (image, pixel) row of the position-addressed maps, in rows
+    size_t rows;                             // B * anchors
+};
+static SparseWs sparse_ws_layout(int B, int max_det, const int (&HWl)[3]) {
+    SparseWs w{};
+    size_t off = 0;
+    auto take = [&](size_t bytes) { const size_t o = off; off += (bytes + 255) & ~(size_t)255; return o; };
+    w.sel = take((size_t)B * HEAD_MAXK * 4); w.wlist = take((size_t)B * 3 * HEAD_MAXK * 4); w.wcount = take((size_t)B * 3 * 4); w.thr = take((size_t)B * 4);
+    w.box = take((size_t)B * max_det * 64 * 4); w.cf = take((size_t)B * max_det * 32 * 4);
+    w.pcount = take(8 * 4);                  // [0..3) live counters, [4..7) the counts of the last forward (head stage 2 saves them)
+    size_t ents = 0, rows = 0;
+    for (int l = 0; l < 3; ++l) {
+        w.plist_off[l] = (int)ents; w.plist_cap[l] = B * std::min(HWl[l], 9 * max_det);   // a winner's 3x3 neighbourhood, never more than the level has
+        ents += (size_t)(w.plist_cap[l] + 63) & ~(size_t)63;
+        w.t0_off[l] = rows; rows += (size_t)B * HWl[l];
+    }
+    w.rows = rows;
+    w.plist = take(ents * 4);
+    w.t0box = take(rows * 64 * 2); w.t0cf = take(rows * 32 * 2);
+    w.total = off;
+    return w;
+}
+static SparseWs sparse_ws_layout(const yp_engine& e) {
+    const int hw[3] = {(e.pH / 8) * (e.pW / 8), (e.pH / 16) * (e.pW / 16), (e.pH / 32) * (e.pW / 32)};
+    return sparse_ws_layout(e.pB, e.desc.max_det, hw);
+}
+// which: 0 = box branch (one2one_cv2), 1 = mask-coefficient branch (cv4)
+static HeadBranchParams head_branch_params(const yp_engine& e, const Op& h, int which) {
+    HeadBranchParams p{};
+    const SparseWs ws = sparse_ws_layout(e);
+    char* base = (char*)e.sp_ws;
+    for (int l = 0; l < 3; ++l) {
+        const int* ids = which == 0 ? h.hb_box[l] : h.hb_cf[l];
+        if (ids[0] < 0) { p.cmid = 0; return p; }
+        const Op &c0 = e.ops[ids[0]], &c1 = e.ops[ids[1]], &c2 = e.ops[ids[2]];
+        const WeightDesc &w0 = e.weights[c0.widx], &w1 = e.weights[c1.widx], &w2 = e.weights[c2.widx];
+        const TensorDesc& ti = e.tensors[c0.in.t];
+        p.x[l] = ti.ptr; p.x_stride[l] = ti.C; p.x_coff[l] = c0.in.coff; p.H[l] = ti.H; p.W[l] = ti.W; p.Cin[l] = c0.in.C; p.x_bytes[l] = ti.bytes;
+        p.w0[l] = w0.d_w; p.Kpad0[l] = w0.Kpad; p.b0[l] = w0.d_b;
+        p.w1[l] = w1.d_w; p.Kpad1[l] = w1.Kpad; p.b1[l] = w1.d_b;
+        p.w2[l] = w2.d_w; p.Kpad2[l] = w2.Kpad; p.b2[l] = w2.d_b;
+        if (l == 0) { p.cmid = c0.out.C; p.cout = c2.out.C; p.act0 = c0.act; p.act1 = c1.act; }
+        // the shape the kernel is written for: 3x3 s1 -> 3x3 s1 -> 1x1 without activation, no residuals, equal widths on every level
+        if (c0.k != 3 || c1.k != 3 || c2.k != 1 || c0.s != 1 || c1.s != 1 || c2.s != 1 || c0.res.t >= 0 || c1.res.t >= 0 || c2.res.t >= 0 || c2.act != ACT_NONE ||
+            c0.out.C != p.cmid || c1.out.C != p.cmid || c1.in.C != p.cmid || c2.in.C != p.cmid || c2.out.C != p.cout || c0.act != p.act0 || c1.act != p.act1 ||
+            w0.cin_pad != c0.in.C || w1.cin_pad != p.cmid) { p.cmid = 0; return p; }
+    }
+    p.B = e.pB; p.max_det = e.desc.max_det; p.maxk = HEAD_MAXK;
+    p.A0 = p.H[0] * p.W[0]; p.A1 = p.H[1] * p.W[1];
+    auto at = [&](size_t off) -> char* { return base ? base + off : nullptr; };      // (plan time: the workspace does not exist yet)
+    p.sel = (const int*)at(ws.sel); p.wlist = (const int*)at(ws.wlist); p.wcount = (const int*)at(ws.wcount);
+    p.out = (float*)at(which == 0 ? ws.box : ws.cf);
+    p.plist = (const int*)at(ws.plist); p.pcount = (const int*)at(ws.pcount);
+    p.t0 = at(which == 0 ? ws.t0box : ws.t0cf); p.t0_bytes = ws.rows * (size_t)p.cmid * 2;
+    for (int l = 0; l < 3; ++l) { p.plist_off[l] = ws.plist_off[l]; p.plist_cap[l] = ws.plist_cap[l]; p.t0_off[l] = ws.t0_off[l] * (size_t)p.cmid; }
+    p.pos_grid = 256;                        // one workgroup per CU (its three plane slots fill most of a CU's LDS)
+    return p;
+}
+
+static int make_plan(yp_engine& e, int B, int H, int W) {
+    if (B <= 0 || H <= 0 || W <= 0 || (H % 32) || (W % 32)) return fail(YP_ERR_ARG, "input must be [B,H,W,3] with H,W multiples of 32 (got %d,%d,%d)", B, H, W);
+    if (e.planned && e.pB == B && e.pH == H && e.pW == W) return YP_OK;
+    size_t A = 0;
+    for (int l = 0; l < 3; ++l) A += (size_t)(H / (8 << l)) * (W / (8 << l));
+    if (A > 12288) return fail(YP_ERR_ARG, "input %dx%d has %zu anchors; the LDS top-k supports at most 12288", H, W, A);
+    for (auto& t : e.tensors) {
+        t.H = H / t.sdiv; t.W = W / t.sdiv;
+        t.bytes = (size_t)B * t.H * t.W * t.C * tensor_elem_bytes(e, t);
+    }
+    e.pB = B; e.pH = H; e.pW = W; e.planned = true; e.allocated = false; e.warmed = false;
+    const double es = e.es();
+    for (auto& o : e.ops) {
+        o.flops = 0; o.bytes = view_bytes(e, o.in) + view_bytes(e, o.out) + view_bytes(e, o.res);
+        if (o.kind == OP_CONV || o.kind == OP_DWCONV || o.kind == OP_STEM || o.kind == OP_CONVT) {
+            const TensorDesc& to = e.tensors[o.out.t];
+            const WeightDesc& w = e.weights[o.widx];
+            const double px = (double)B * to.H * to.W;
+            if (o.kind == OP_CONVT) o.flops = 2.0 * px * w.cout * w.cin_g;   // one tap per output pixel
+            else o.flops = 2.0 * px * w.cout * w.cin_g * w.k * w.k;
+            o.bytes += (double)w.cout * w.cin_g * w.k * w.k * es;
+            if (o.kind == OP_STEM) o.bytes += (double)B * H * W * 3;
+        } else if (o.kind == OP_ATTN) {
+            const TensorDesc& ti = e.tensors[o.in.t];
+            const double Nn = (double)ti.H * ti.W;
+            o.flops = 2.0 * B * o.nh * Nn * Nn * (o.kd + o.hd);
+        } else if (o.kind == OP_HEAD) {
+            o.bytes = 0;                       // class-max keys + the winners' class / box rows + the outputs
+            for (int l = 0; l < 3; ++l) o.bytes += (o.amax[l].t >= 0) ? view_bytes(e, o.amax[l]) : view_bytes(e, o.cls[l]);
+            o.bytes += (double)B * e.desc.max_det * (e.desc.nc + 64 + 6 + 1) * 4;
+        }
+    }
+    for (auto& o : e.ops) o.cfg = -1;
+    static const char* kn[] = {"stem_kernel", "", "dwconv_kernel", "pool5_kernel", "upsample2_kernel", "attention_kernel", "head_select_kernel", "", "sppf_pool3_kernel", "anchor_max_level_kernel"};
+    for (auto& o : e.ops) { o.form = FORM_PLAIN; o.skip = false; o.folded = false; o.pw_store = false; o.sparse_box = false; o.sparse_cf = false; }
+    static const bool no_fold = env_on("YOLOP_NO_FOLD");   // A/B switch
+    for (auto& o : e.ops) {
+        if (o.kind != OP_CONV || o.fold_up < 0 || e.dtype != DT_BF16 || no_fold) continue;
+        o.folded = true;                                   // tentatively, so that conv_params describes the folded form
+        const ConvParams q = conv_params(e, o);
+        bool any = false;
+        for (int c = 0; c < conv_dma_p_family.num_cfgs && !any; ++c) any = conv_dma_p_family.valid(q, c);
+        if (any) e.ops[o.fold_up].skip = true;
+        else o.folded = false;
+    }
+    // the fused forms (kForms; the order they are tried in is described there)
+    static const std::array<bool, kNumForms> form_off = [] {
+        std::array<bool, kNumForms> v{};
+        for (int f = 0; f < kNumForms; ++f) v[f] = kForms[f].off_env && env_on(kForms[f].off_env);   // A/B switches
+        return v;
+    }();
+    // o takes form f if its links make it a candidate, the gate is open and the kernel admits it: its absorbed ops are skipped then
+    auto try_form = [&](Op& o, Form f) {
+        const FormRec& rec = kForms[f];
+        int m[3];
+        const int n = rec.absorbed(e, o, m);
+        if (n == 0 || e.dtype != DT_BF16 || !e.fuse || form_off[f]) return false;
+        const Form was = o.form;
+        o.form = f;                                        // tentatively, so that the parameter builders describe the fused form
+        const std::string kernel = rec.admit(e, o, o.cfg);
+        if (kernel.empty()) { o.form = was; return false; }
+        o.kernel = kernel;
+        for (int i = 0; i < n; ++i) e.ops[m[i]].skip = true;
+        return true;
+    };
+    for (auto& o : e.ops) {
+        if (o.kind == OP_CONV) {
+            if (try_form(o, FORM_S2PW)) { try_form(o, FORM_FRONTEND); continue; }      // ... and with the stem in front of it
+            if (try_form(o, FORM_C2F) || try_form(o, FORM_DWPW) || try_form(o, FORM_DWPW_TAIL)) continue;
+            o.kernel = conv_kernel_name(conv_params(e, o), e.dtype);
+        } else if (o.kind == OP_CONVT) o.kernel = conv_kernel_name(convt_params(e, o, 0, 0), e.dtype);      // (the four sub-positions share a shape)
+        else if (o.kind == OP_DWCONV) {
+            if (!try_form(o, FORM_SCDOWN)) o.kernel = dwconv_kernel_name(dw_params(e, o), e.dtype);
+        } else if (o.kind == OP_STEM) o.kernel = stem_kernel_name(stem_params(e, o, nullptr), e.dtype);
+        else if (o.kind == OP_POOL3 && e.dtype == DT_BF16 && (o.in.C & 31) == 0) o.kernel = "sppf_pool3_bf16_kernel";
+        else o.kernel = (o.kind == OP_HEAD && o.nms) ? "head_nms_kernel" : kn[o.kind];
+    }
+    // winners-only head (v10 top-k head, bf16): the box / coefficient branches run on the stage-1 winners inside the head op; their dense
+    // convolutions stay in the op list (yp_run_op steps them, the fp32 parity mode and YOLOP_DENSE_HEAD=1 run them) but launch nothing here
+    for (auto& o : e.ops) {
+        if (o.kind != OP_HEAD || o.nms || e.dtype != DT_BF16 || !e.sparse_head || e.desc.max_det > HEAD_MAXK || o.amax[0].t < 0) continue;
+        for (int which = 0; which < 2; ++which) {
+            const HeadBranchParams q = head_branch_params(e, o, which);
+            if (q.cmid == 0 || !head_branch_valid(q)) continue;
+            if (which == 1 && !o.sparse_box) continue;              // (stage 2 reads the coefficient rows by rank only beside winners-only box rows)
+            // the branch's tensors must have no reader outside the branch and the head op (they are never written in this mode)
+            const int *first = which == 0 ? &o.hb_box[0][0] : &o.hb_cf[0][0], *last = first + 9;      // the branch's nine convs
+            bool outside = false;
+            for (const int* m = first; m != last; ++m)
+                for (int r : readers_of(e, e.ops[*m].out, (int)(&o - e.ops.data()))) outside |= std::find(first, last, r) == last;
+            if (outside) continue;
+            (which == 0 ? o.sparse_box : o.sparse_cf) = true;
+            for (const int* m = first; m != last; ++m) e.ops[*m].skip = true;
+        }
+    }
+    // 1x1 -> depthwise / pool chain as pwsp_kernel (decided last: it looks at which ops still launch). The 1x1 conv is skipped, the spatial
+    // op launches the kernel; the conv's own output is written as well when anything else reads it. Not when an op that still launches
+    // sits between the two and reads the conv's output (the kernel runs at the SPATIAL op's place in the order).
+    for (size_t i = 0; i < e.ops.size(); ++i) {
+        Op& d = e.ops[i];
+        if (d.pw_pre < 0 || d.skip || fused(d)) continue;
+        const Op& c = e.ops[d.pw_pre];
+        if (!plain_conv(c) || c.folded) continue;
+        // from the effective read / write sets of the ops that still launch: the conv's output read anywhere else = other readers;
+        // moved to the spatial op's place, the conv must not pass an op that reads or writes its output, writes its input or residual,
+        // or touches the spatial op's output / residual
+        bool between = false, other = false;
+        std::vector<View> rd, wr;
+        auto any_overlap = [](const std::vector<View>& vs, const View& v) {
+            for (const View& x : vs) if (views_overlap(x, v)) return true;
+            return false;
+        };
+        for (size_t j = 0; j < e.ops.size(); ++j) {
+            if (j == i || (int)j == d.pw_pre || e.ops[j].skip) continue;
+            op_views(e, e.ops[j], rd, wr);
+            const bool reads = any_overlap(rd, c.out);
+            other |= reads;
+            if ((int)j > d.pw_pre && j < i)
+                between |= reads || any_overlap(wr, c.out) || any_overlap(wr, c.in) || any_overlap(wr, c.res) || any_overlap(wr, d.out) || any_overlap(wr, d.res) ||
+                           any_overlap(rd, d.out);
+        }
+        if (between) continue;
+        d.pw_store = other;
+        if (!try_form(d, FORM_PWSP)) d.pw_store = false;
+    }
+    // class logits + class-max keys in one launch (cls_out_kernel): the OP_AMAX op is skipped
+    for (auto& o : e.ops)
+        if (o.amax_post >= 0 && plain_conv(o) && !o.folded && !e.ops[o.amax_post].skip) try_form(o, FORM_CLS_OUT);
+    // algorithmic work of the graph as it runs: an op whose work moved into a fused consumer reports nothing and launches
+    // nothing; the consumer reports the FLOPs of all its stages and the bytes of what it reads and writes (the intermediates
+    // never reach HBM), a conv with a folded upsample reads the low-resolution tensor instead of its upsampled copy
+    {
+        auto wb = [&](const Op& q) {
+            if (q.widx < 0) return 0.0;
+            const WeightDesc& w = e.weights[q.widx];
+            return (double)w.cout * w.cin_g * w.k * w.k * es;
+        };
+        for (auto& o : e.ops) {
+            if (const FormRec* r = fused(o)) {             // (an absorbed op that is itself fused - the TAIL form's pointwise conv - stays as it was)
+                int m[3];
+                const int n = r->absorbed(e, o, m);
+                View in = o.in, extra;
+                r->views(e, o, in, extra);
+                o.bytes = view_bytes(e, in) + view_bytes(e, o.res) + view_bytes(e, o.out) + view_bytes(e, extra) + wb(o) + (r->reads_frames ? (double)B * H * W * 3 : 0.0);
+                for (int i = 0; i < n; ++i) { o.flops += e.ops[m[i]].flops; o.bytes += wb(e.ops[m[i]]); }
+            }
+            if (o.folded) { const Op& u = e.ops[o.fold_up]; o.bytes += view_bytes(e, u.in) - view_bytes(e, u.out); }
+        }
+        for (auto& o : e.ops) {
+            if (o.kind != OP_HEAD) continue;
+            for (int which = 0; which < 2; ++which) {
+                if (!(which == 0 ? o.sparse_box : o.sparse_cf)) continue;
+                const HeadBranchParams q = head_branch_params(e, o, which);
+                for (int l = 0; l < 3; ++l) {        // (which level a winner lies on is data: a third each, neighbourhoods disjoint unless the level is full)
+                    const double nw = (double)B * e.desc.max_det / 3.0;
+                    const double npos = std::min(9.0 * nw, (double)B * q.H[l] * q.W[l]);
+                    o.flops += 2.0 * (npos * 9.0 * q.Cin[l] * q.cmid + nw * (9.0 * q.cmid * q.cmid + (double)q.cmid * q.cout));
+                    o.bytes += npos * (9.0 * q.Cin[l] * 2 + 2.0 * q.cmid * 2) + nw * q.cout * 4 + (9.0 * q.Cin[l] * q.cmid + 9.0 * q.cmid * q.cmid + q.cmid * q.cout) * 2;
+                }
+            }
+            if (o.sparse_box || o.sparse_cf) o.kernel = "head_select_kernel<1> + head_pos_kernel + head_win_kernel + head_select_kernel<2>";
+        }
+        for (auto& o : e.ops)
+            if (o.skip) { o.flops = 0; o.bytes = 0; o.kernel = "-"; }
+    }
+    return YP_OK;
+}
+
+static int allocate_plan(yp_engine& e) {
+    if (e.allocated) return YP_OK;
+    // A dense conv packed with padded taps (WeightDesc::cin_pad > Cin, see conv_params) reads cin_pad channels per pixel and multiplies the
+    // surplus by zero weights: the surplus bytes are the next channels of the same pixel (in a concat buffer: a slice a LATER op writes), the
+    // next pixel, or - at the last pixel of the last image - up to (cin_pad - Cin) * 2 < 64 bytes past the end of the tensor. Every one of
+    // those bytes must be a finite bf16 pattern (NaN * 0 = NaN on the matrix cores; a NaN output then lands in the very slice the next
+    // forward over-reads, i.e. it would never heal). So (i) a tensor read by such a conv owns a 64-byte tail inside its slot, and (ii) the
+    // whole region of a layout is zeroed on EVERY layout, not only when the arena grows: a re-plan into the kept arena puts bf16 tensors
+    // over stale fp32 logits / u32 keys, whose low halves read as bf16 NaN once in 256.
+    std::vector<char> tail(e.tensors.size(), 0);
+    for (const auto& o : e.ops)
+        if (o.kind == OP_CONV && o.widx >= 0 && o.in.t >= 0 && e.weights[o.widx].cin_pad > o.in.C) tail[o.in.t] = 1;
+    auto slot = [&](size_t i) { return (e.tensors[i].bytes + (tail[i] ? 64 : 0) + 255) & ~(size_t)255; };
+    size_t total = 0;
+    for (size_t i = 0; i < e.tensors.size(); ++i) total += slot(i);
+    HIPCHK(hipSetDevice(e.device));
+    total += 4096;                                   // (slack behind the last tensor: padded-tap reads of conv_igemm's plain loads)
+    if (total > e.arena_bytes) {
+        if (e.arena) HIPCHK(hipFree(e.arena));
+        e.arena = nullptr;
+        HIPCHK(hipMalloc(&e.arena, total));
+        e.arena_bytes = total;
+    }
+    HIPCHK(hipMemset(e.arena, 0, total));            // (2.9 GB at S / bs 32: ~1 ms, once per plan)
+    size_t off = 0;
+    for (size_t i = 0; i < e.tensors.size(); ++i) {
+        e.tensors[i].ptr = (char*)e.arena + off;
+        off += slot(i);
+    }
+    {
+        size_t A = 0;
+        for (int l = 0; l < 3; ++l) A += (size_t)(e.pH / (8 << l)) * (e.pW / (8 << l));
+        const size_t need = head_scratch_bytes(e.pB, (int)A);
+        if (need > e.head_ws_bytes) {
+            if (e.head_ws) HIPCHK(hipFree(e.head_ws));
+            e.head_ws = nullptr;
+            HIPCHK(hipMalloc(&e.head_ws, need));
+            e.head_ws_bytes = need;
+        }
+    }
+    {
+        bool sparse = false;
+        for (const auto& o : e.ops) sparse |= o.kind == OP_HEAD && (o.sparse_box || o.sparse_cf);
+        const size_t need = sparse ? sparse_ws_layout(e).total : 0;
+        if (need > e.sp_ws_bytes) {
+            if (e.sp_ws) HIPCHK(hipFree(e.sp_ws));
+            e.sp_ws = nullptr; e.sp_ws_bytes = 0;
+            HIPCHK(hipMalloc(&e.sp_ws, need));
+            e.sp_ws_bytes = need;
+        }
+        // zeroed for every plan, not only when it grows: the layout moves with B, so the head's live position counters (which every
+        // forward empties behind itself) can land on rows the previous plan left behind - garbage counts index the lists out of bounds
+        if (need) HIPCHK(hipMemset(e.sp_ws, 0, need));
+    }
+    if (e.desc.family != YP_FAMILY_V10) {
+        size_t A = 0;
+        for (int l = 0; l < 3; ++l) A += (size_t)(e.pH / (8 << l)) * (e.pW / (8 << l));
+        const size_t need = head_nms_scratch_bytes(e.pB, (int)A);
+        if (need > e.nms_ws_bytes) {
+            if (e.nms_ws) HIPCHK(hipFree(e.nms_ws));
+            e.nms_ws = nullptr; e.nms_ws_bytes = 0;
+            HIPCHK(hipMalloc(&e.nms_ws, need));
+            e.nms_ws_bytes = need;
+        }
+        if (!e.d_nms) {
+            HIPCHK(hipMalloc((void**)&e.d_nms, 2 * sizeof(float)));
+            const float v[2] = {e.nms_conf, e.nms_iou};
+            HIPCHK(hipMemcpy(e.d_nms, v, sizeof(v), hipMemcpyHostToDevice));
+        }
+    }
+    if ((size_t)e.pB > e.o_cap) {
+        if (e.o_det) { HIPCHK(hipFree(e.o_det)); HIPCHK(hipFree(e.o_idx)); HIPCHK(hipFree(e.o_coeff)); }
+        const size_t rows = (size_t)e.pB * e.desc.max_det;
+        HIPCHK(hipMalloc(&e.o_det, rows * 6 * sizeof(float)));
+        HIPCHK(hipMalloc(&e.o_idx, rows * sizeof(int32_t)));
+        HIPCHK(hipMalloc(&e.o_coeff, rows * 32 * sizeof(float)));
+        e.o_cap = (size_t)e.pB;
+    }
+    if (e.gexec) { (void)hipDeviceSynchronize(); drop_graph(e); }   // (never under a running replay)
+    e.allocated = true;
+    return YP_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// op launch
+// ---------------------------------------------------------------------------------------------------------
 // The configuration id run_op launches o with (yp_debug_op_cfg): every branch here mirrors one of run_op's.
 static int op_launch_cfg(const yp_engine& e, const Op& o) {
     if (o.kind == OP_CONVT) return conv_launch_cfg(convt_params(e, o, 0, 0), e.dtype);      // (the four sub-positions share a shape)
+    if (const FormRec* r = fused(o)) return r->own_cfg ? o.cfg : -1;
     if (o.kind != OP_CONV) return -1;
-    switch (o.form) {
-        case FORM_DWPW: case FORM_DWPW_TAIL: case FORM_FRONTEND: case FORM_C2F: case FORM_CLS_OUT: return -1;
-        case FORM_S2PW: return o.cfg;
-        default: break;
-    }
     if (o.cfg == PWSP_CFG) return PWSP_CFG;
     if (conv_dma_forced_cfg() == PWSP_CFG && e.dtype == DT_BF16 && !o.folded) {
         const PwSpParams q = pwsp_params(e, o);
@@ -1305,24 +1384,10 @@ static int op_launch_cfg(const yp_engine& e, const Op& o) {
 static hipError_t run_op(yp_engine& e, const Op& o, const RunArgs& a, hipStream_t st) {
     auto T = [&](const View& v) -> const TensorDesc& { return e.tensors[v.t]; };
     const int B = e.pB;
+    if (const FormRec* r = fused(o)) return r->launch(e, o, a, st);
     switch (o.kind) {
-        case OP_STEM: {
-            const WeightDesc& w = e.weights[o.widx];
-            const TensorDesc& to = T(o.out);
-            StemParams p{};
-            p.x = a.in; p.H = e.pH; p.W = e.pW; p.w = (const float*)w.d_w; p.wpk = w.d_w2; p.bias = w.d_b;
-            p.y = to.ptr; p.y_stride = to.C; p.y_coff = o.out.coff; p.Ho = to.H; p.Wo = to.W; p.C0 = o.out.C; p.B = B; p.act = o.act;
-            return launch_stem(p, e.dtype, st);
-        }
+        case OP_STEM: return launch_stem(stem_params(e, o, a.in), e.dtype, st);
         case OP_CONV:
-            switch (o.form) {
-                case FORM_DWPW: case FORM_DWPW_TAIL: return launch_conv_dwpw(dwpw_params(e, o), st);
-                case FORM_FRONTEND: return launch_frontend(front_params(e, o, a.in), st);
-                case FORM_C2F: return launch_c2f_fused(c2f_params(e, o), st);
-                case FORM_S2PW: return conv_halo_s2_family.launch(conv_params(e, o), o.cfg - conv_halo_s2_family.base, st);
-                case FORM_CLS_OUT: return launch_cls_out(cls_out_params(e, o), st);
-                default: break;
-            }
             if (o.cfg == PWSP_CFG) return launch_pwsp(pwsp_params(e, o), st);
             if (conv_dma_forced_cfg() == PWSP_CFG && e.dtype == DT_BF16 && !o.folded) {          // test hook (yp_debug_force_conv_cfg): every 1x1 that admits it
                 const PwSpParams q = pwsp_params(e, o);
@@ -1337,20 +1402,7 @@ static hipError_t run_op(yp_engine& e, const Op& o, const RunArgs& a, hipStream_
                 }
             return hipSuccess;
         }
-        case OP_DWCONV: {
-            if (o.form == FORM_SCDOWN) return launch_scdown_fused(scd_params(e, o), st);
-            if (o.form == FORM_PWSP) return launch_pwsp(pwsp_params(e, o), st);
-            const WeightDesc& w = e.weights[o.widx];
-            const TensorDesc &ti = T(o.in), &to = T(o.out);
-            DwParams p{};
-            p.x = ti.ptr; p.x_stride = ti.C; p.x_coff = o.in.coff; p.H = ti.H; p.W = ti.W; p.C = o.out.C;
-            p.w = w.d_w; p.bias = w.d_b;
-            p.y = to.ptr; p.y_stride = to.C; p.y_coff = o.out.coff; p.Ho = to.H; p.Wo = to.W;
-            if (o.res.t >= 0) { p.res = T(o.res).ptr; p.res_stride = T(o.res).C; p.res_coff = o.res.coff; }
-            p.B = B; p.ks = o.k; p.stride = o.s; p.pad = o.k / 2; p.act = o.act; p.gs = o.gs; p.gstride = o.gstride;
-            p.x_bytes = ti.bytes;
-            return launch_dwconv(p, e.dtype, st);
-        }
+        case OP_DWCONV: return launch_dwconv(dw_params(e, o), e.dtype, st);
         case OP_POOL5: {
             const TensorDesc &ti = T(o.in), &to = T(o.out);
             PoolParams p{};
@@ -1360,7 +1412,6 @@ static hipError_t run_op(yp_engine& e, const Op& o, const RunArgs& a, hipStream_
         }
         case OP_POOL3: {
             const TensorDesc &ti = T(o.in), &to = T(o.out);
-            if (o.form == FORM_PWSP) return launch_pwsp(pwsp_params(e, o), st);
             PoolParams p{};
             p.x = ti.ptr; p.x_stride = ti.C; p.x_coff = o.in.coff; p.y = to.ptr; p.y_stride = to.C; p.y_coff = o.out.coff;
             p.B = B; p.H = ti.H; p.W = ti.W; p.C = o.in.C;
@@ -1426,6 +1477,9 @@ static hipError_t run_op(yp_engine& e, const Op& o, const RunArgs& a, hipStream_
     return hipErrorInvalidValue;
 }
 
+// the launch a tunable conv's configuration is chosen for (a ConvTranspose: its four sub-positions share a shape)
+static ConvParams tune_params(const yp_engine& e, const Op& o) { return o.kind == OP_CONV ? conv_params(e, o) : convt_params(e, o, 0, 0); }
+
 // Plan-time autotuner: for every dense conv that the LDS-DMA kernel supports, time each valid tile configuration on
 // the real tensors (weights are loaded, activations hold whatever the arena holds - timing does not depend on values
 // up to DVFS) and keep the fastest. Runs once per (B,H,W) plan, outside any graph capture.
@@ -1464,7 +1518,7 @@ static int autotune(yp_engine& e) {
     auto time_cfg = [&](Op& o, float& tmin) -> hipError_t {
         tmin = 1e30f;
         const Op* prod = (cold_mode == 2) ? producer_of(o) : nullptr;
-        if (prod && (prod->kind == OP_STEM || prod->form == FORM_FRONTEND) && !tune_in) prod = nullptr;      // (needs the caller's frames)
+        if (prod && (prod->kind == OP_STEM || (fused(*prod) && fused(*prod)->reads_frames)) && !tune_in) prod = nullptr;      // (needs the caller's frames)
         for (int rep = 0; rep < 4; ++rep) {
             if (flush && rep > 0 && (cold_mode == 1 || !prod)) { hipError_t fe = hipMemsetAsync(flush, rep, flush_bytes, nullptr); if (fe != hipSuccess) return fe; }
             if (prod) {
@@ -1486,10 +1540,7 @@ static int autotune(yp_engine& e) {
     };
     for (Op& o : e.ops) {
         if (!plain_conv(o)) continue;
-        ConvParams p{};
-        if (o.kind == OP_CONV) p = conv_params(e, o);
-        else { p.Cin = o.in.C; p.Cout = o.out.C; p.ks = 1; p.Kpad = e.weights[o.widx].Kpad; p.M = e.pB * e.tensors[o.in.t].H * e.tensors[o.in.t].W;
-               p.x_bytes = e.tensors[o.in.t].bytes; p.w_bytes = e.weights[o.widx].mat_bytes; }
+        const ConvParams p = tune_params(e, o);
         if (!conv_dma_supported(p)) continue;
         float best = 1e30f;
         int bestc = -1;
@@ -1540,9 +1591,7 @@ static int autotune(yp_engine& e) {
             }
         }
         o.cfg = bestc;
-        if (o.cfg == PWSP_CFG) o.kernel = pwsp_kernel_name(pwsp_params(e, o));
-        else if (o.kind == OP_CONV) o.kernel = conv_kernel_name(conv_params(e, o), e.dtype);
-        else { p.cfg = o.cfg; o.kernel = conv_kernel_name(p, e.dtype); }
+        o.kernel = o.cfg == PWSP_CFG ? pwsp_kernel_name(pwsp_params(e, o)) : conv_kernel_name(tune_params(e, o), e.dtype);
     }
     (void)hipEventDestroy(e0);
     (void)hipEventDestroy(e1);
@@ -1583,13 +1632,6 @@ static std::string tune_cache_path(const yp_engine& e, bool packaged = false) {
 }
 // Install tile configurations that did not come from this process's tuner (cache file, yp_tuning_import): one id per op of the current
 // plan (ignored for ops that are not tunable convs). Every id is checked with the predicates the tuner itself uses; all or nothing.
-static ConvParams tune_params(const yp_engine& e, const Op& o) {
-    if (o.kind == OP_CONV) return conv_params(e, o);
-    ConvParams p{};
-    p.Cin = o.in.C; p.Cout = o.out.C; p.ks = 1; p.Kpad = e.weights[o.widx].Kpad; p.M = e.pB * e.tensors[o.in.t].H * e.tensors[o.in.t].W;
-    p.x_bytes = e.tensors[o.in.t].bytes; p.w_bytes = e.weights[o.widx].mat_bytes;
-    return p;
-}
 static bool apply_tuning(yp_engine& e, const int* cfgs, int n) {
     if (n != (int)e.ops.size()) return false;
     for (size_t i = 0; i < e.ops.size(); ++i) {
@@ -1638,74 +1680,12 @@ static void save_tune_cache(const yp_engine& e) {
         if (o.kind == OP_CONV || o.kind == OP_CONVT) f << o.name << " " << o.cfg << "\n";
 }
 
-static DwPwParams dwpw_params(const yp_engine& e, const Op& c) {
-    if (c.form == FORM_DWPW_TAIL) {      // the dw -> pw pair in front with this 1x1 (and the class-max keys) as the third stage
-        DwPwParams p = dwpw_params(e, e.ops[c.fuse_tail]);
-        const WeightDesc& w3 = e.weights[c.widx];
-        const TensorDesc& to = e.tensors[c.out.t];
-        p.w3 = w3.d_w ? w3.d_w : (const void*)1; p.Kpad3 = w3.Kpad; p.w3_bytes = w3.mat_bytes; p.b3 = w3.d_b ? w3.d_b : (const float*)1; p.C3 = c.out.C;
-        p.y3 = to.ptr ? (float*)to.ptr : (float*)1; p.y3_stride = to.C; p.y3_coff = c.out.coff; p.y3_bytes = to.bytes;
-        p.keys = c.tail_amax >= 0 ? (unsigned*)e.tensors[e.ops[c.tail_amax].out.t].ptr : nullptr;
-        p.out_f32 = 0;
-        return p;
-    }
-    const Op& d = e.ops[c.fuse_dw];
-    const WeightDesc &wd = e.weights[d.widx], &wp = e.weights[c.widx];
-    const TensorDesc &ti = e.tensors[d.in.t], &to = e.tensors[c.out.t];
-    DwPwParams p{};
-    p.x = ti.ptr; p.x_stride = ti.C; p.x_coff = d.in.coff; p.B = e.pB; p.H = ti.H; p.W = ti.W; p.C = d.in.C; p.x_bytes = ti.bytes;
-    p.w_dw = wd.d_w; p.b_dw = wd.d_b; p.act_dw = d.act;
-    p.w_pw = wp.d_w; p.Kpad = wp.Kpad; p.wpw_bytes = wp.mat_bytes; p.b_pw = wp.d_b; p.act_pw = c.act;
-    p.y = to.ptr; p.y_stride = to.C; p.y_coff = c.out.coff; p.y_bytes = to.bytes; p.Cout = c.out.C;
-    p.out_f32 = (to.f32 && e.dtype == DT_BF16) ? 1 : 0;
-    return p;
-}
-
 // ---------------------------------------------------------------------------------------------------------
 // Multi-lane launch for graph capture: ops carry a lane; every lane is a stream. Dependencies are derived from the
 // tensor views (RAW / WAR / WAW on overlapping channel ranges); a dependency that crosses lanes becomes an event
 // record on the producer's stream + a wait on the consumer's. Captured from lane 0's stream this yields a hipGraph
 // whose independent head branches (box / class / coefficient per level, prototypes) overlap with the rest of the neck.
 // ---------------------------------------------------------------------------------------------------------
-static bool views_overlap(const View& a, const View& b) {
-    return a.t >= 0 && a.t == b.t && a.coff < b.coff + b.C && b.coff < a.coff + a.C;
-}
-static void op_views(const yp_engine& e, const Op& o, std::vector<View>& rd, std::vector<View>& wr) {
-    rd.clear(); wr.clear();
-    if (o.skip) return;
-    View extra;                                            // a second tensor the fused form writes
-    switch (o.form) {
-        case FORM_DWPW: rd.push_back(e.ops[o.fuse_dw].in); break;
-        case FORM_DWPW_TAIL:
-            rd.push_back(e.ops[e.ops[o.fuse_tail].fuse_dw].in);
-            if (o.tail_amax >= 0) extra = e.ops[o.tail_amax].out;
-            break;
-        case FORM_SCDOWN: rd.push_back(e.ops[o.scd_pre].in); break;
-        case FORM_PWSP:
-            rd.push_back(e.ops[o.pw_pre].in);
-            if (o.pw_store) extra = e.ops[o.pw_pre].out;
-            break;
-        case FORM_C2F: rd.push_back(View{o.in.t, o.in.coff, 2 * e.ops[o.c2f_m1].in.C}); break;
-        case FORM_FRONTEND: break;                         // (reads the caller's frames only)
-        case FORM_S2PW: rd.push_back(e.ops[o.fuse_pre].in); break;
-        case FORM_CLS_OUT: extra = e.ops[o.amax_post].out; [[fallthrough]];
-        case FORM_PLAIN: if (o.in.t >= 0) rd.push_back(o.in); break;
-    }
-    if (o.folded) rd.push_back(e.ops[o.fold_up].in);      // (besides the concat buffer, whose skip part it still reads)
-    if (o.res.t >= 0) rd.push_back(o.res);
-    if (o.out.t >= 0) wr.push_back(o.out);
-    if (extra.t >= 0) wr.push_back(extra);
-    if (o.kind == OP_HEAD)
-        for (int l = 0; l < 3; ++l) {
-            if (o.sparse_box) rd.push_back(e.ops[o.hb_box[l][0]].in);              // the level's feature map instead of the dense box map
-            else if (o.box[l].t >= 0) rd.push_back(o.box[l]);
-            if (o.cls[l].t >= 0) rd.push_back(o.cls[l]);
-            if (o.sparse_cf) rd.push_back(e.ops[o.hb_cf[l][0]].in);
-            else if (o.cf[l].t >= 0) rd.push_back(o.cf[l]);
-            if (o.amax[l].t >= 0) rd.push_back(o.amax[l]);
-        }
-}
-
 // Pure host step: the launch order with its cross-lane waits / records for the current plan. Kept apart from the HIP calls so
 // that (i) it runs once per plan instead of once per capture and (ii) the CPU-only sanitizer build can exercise it.
 static int build_lane_schedule(yp_engine& e) {
@@ -2124,9 +2104,23 @@ int yp_op_kernel(const yp_engine* e, int i, char* name, int cap) {
 int yp_op_fusion(const yp_engine* e, int i, int* pre, int* pre_stored) {
     if (!e || i < 0 || i >= (int)e->ops.size()) return fail(YP_ERR_ARG, "bad op index");
     const Op& o = e->ops[i];
-    if (pre) *pre = o.form == FORM_PWSP ? o.pw_pre : -1;
-    if (pre_stored) *pre_stored = (o.form == FORM_PWSP && o.pw_store) ? 1 : 0;
+    const FormRec* r = fused(o);
+    int m[3] = {-1, -1, -1};
+    if (r == &kForms[FORM_PWSP]) r->absorbed(*e, o, m);      // (this call reports the pwsp pair only; yp_debug_op_form reports every form)
+    if (pre) *pre = m[0];
+    if (pre_stored) *pre_stored = (m[0] >= 0 && o.pw_store) ? 1 : 0;
     return YP_OK;
+}
+
+int yp_debug_op_form(const yp_engine* e, int i, int* form, int* absorbed, int cap) {
+    if (!e || i < 0 || i >= (int)e->ops.size()) return fail(YP_ERR_ARG, "bad op index");
+    const Op& o = e->ops[i];
+    const FormRec* r = fused(o);
+    int m[3];
+    const int n = r ? r->absorbed(*e, o, m) : 0;
+    if (form) *form = r ? (int)o.form : (int)FORM_PLAIN;
+    for (int k = 0; absorbed && k < n && k < cap; ++k) absorbed[k] = m[k];
+    return n;
 }
 
 int yp_op_output(const yp_engine* e, int i, int* tensor, int* coff, int* C) {
@@ -2605,14 +2599,8 @@ int yp_debug_host_selftest(yp_engine* e) {
         }
     for (const Op& o : e->ops) {
         if (o.skip) continue;
-        switch (o.form) {
-            case FORM_DWPW: case FORM_DWPW_TAIL: acc += (size_t)dwpw_params(*e, o).Cout; break;
-            case FORM_FRONTEND: acc += (size_t)front_params(*e, o, nullptr).C2; break;
-            case FORM_C2F: acc += (size_t)c2f_params(*e, o).Cout; break;
-            case FORM_SCDOWN: acc += (size_t)scd_params(*e, o).C; break;
-            case FORM_PWSP: acc += (size_t)pwsp_params(*e, o).C1; break;
-            default: if (o.kind == OP_CONV) acc += (size_t)conv_params(*e, o).Cout;
-        }
+        if (fused(o)) build_form_params(*e, o);
+        else if (o.kind == OP_CONV) acc += (size_t)conv_params(*e, o).Cout;
     }
     save_tune_cache(*e);
     (void)load_tune_cache(*e);

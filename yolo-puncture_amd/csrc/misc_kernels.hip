@@ -189,11 +189,22 @@ __global__ __launch_bounds__(256) void stem_mfma_kernel(const StemParams p, cons
     }
 }
 
+// the MFMA stem's shapes: bf16, 16..80 output channels in whole fragments, 8-byte aligned stores, 32-bit pixel indices
+static bool stem_mfma_shape(const StemParams& p, int dtype) {
+    return dtype == DT_BF16 && (p.C0 % 16) == 0 && p.C0 <= 80 && (p.y_stride & 3) == 0 && (p.y_coff & 3) == 0 &&
+           (long)p.B * p.Ho * p.Wo + 256 < (1l << 31);
+}
+// The name does not ask for the GEMM weight layout (p.wpk), which the launch needs: a plan is named before the weights are uploaded, and
+// a bf16 upload always brings that layout.
+std::string stem_kernel_name(const StemParams& p, int dtype) {
+    if (stem_mfma_shape(p, dtype)) return "stem_mfma_kernel<" + std::to_string(p.C0 / 16) + ">";
+    return dtype == DT_BF16 ? "stem_kernel<bf16>" : "stem_kernel<f32>";
+}
+
 hipError_t launch_stem(const StemParams& p, int dtype, hipStream_t st) {
     const long total = (long)p.B * p.Ho * p.Wo * (p.C0 / 8);
     const int blk = 256;
-    if (dtype == DT_BF16 && p.wpk && (p.C0 % 16) == 0 && p.C0 <= 80 && (p.y_stride & 3) == 0 && (p.y_coff & 3) == 0 &&
-        (long)p.B * p.Ho * p.Wo + 256 < (1l << 31)) {
+    if (stem_mfma_shape(p, dtype) && p.wpk) {
         const long M = (long)p.B * p.Ho * p.Wo;
         const unsigned grid = (unsigned)((M + 255) / 256);
         const __bf16* w = (const __bf16*)p.wpk;
@@ -358,12 +369,24 @@ static void launch_dw_row(const DwParams& p, hipStream_t st) {
     hipLaunchKernelGGL((dwconv_row_kernel<T, KS, S, NOUT>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, p);
 }
 
+// The row kernel's instances: the launch and the template arguments as the symbol spells them, both from one list of numbers.
+template <typename T>
+struct DwRow { int ks, stride; const char* args; void (*launch)(const DwParams&, hipStream_t); };
+#define DW_ROW(KS, S, NOUT) {KS, S, #KS "," #S "," #NOUT, launch_dw_row<T, KS, S, NOUT>}
+// the instance for p, or null: the generic kernel (other shapes; tensors beyond 32-bit buffer offsets)
+template <typename T>
+static const DwRow<T>* dw_row(const DwParams& p) {
+    static const DwRow<T> rows[] = {DW_ROW(3, 1, 4), DW_ROW(3, 2, 2), DW_ROW(7, 1, 2)};
+    if (p.x_bytes >= (1ull << 31)) return nullptr;
+    for (const DwRow<T>& r : rows)
+        if (r.ks == p.ks && r.stride == p.stride) return &r;
+    return nullptr;
+}
+#undef DW_ROW
+
 template <typename T>
 static hipError_t launch_dwconv_t(const DwParams& p, hipStream_t st) {
-    const bool small = p.x_bytes < (1ull << 31);      // 32-bit buffer offsets
-    if (small && p.ks == 3 && p.stride == 1) launch_dw_row<T, 3, 1, 4>(p, st);
-    else if (small && p.ks == 3 && p.stride == 2) launch_dw_row<T, 3, 2, 2>(p, st);
-    else if (small && p.ks == 7 && p.stride == 1) launch_dw_row<T, 7, 1, 2>(p, st);
+    if (const DwRow<T>* r = dw_row<T>(p)) r->launch(p, st);
     else {
         const long total = (long)p.B * p.Ho * p.Wo * (p.C / 8);
         hipLaunchKernelGGL(dwconv_kernel<T>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, p);
@@ -374,6 +397,12 @@ static hipError_t launch_dwconv_t(const DwParams& p, hipStream_t st) {
 hipError_t launch_dwconv(const DwParams& p, int dtype, hipStream_t st) {
     if (dwconv_mfma_valid(p, dtype)) return launch_dwconv_mfma(p, st);
     return dtype == DT_BF16 ? launch_dwconv_t<__bf16>(p, st) : launch_dwconv_t<float>(p, st);
+}
+std::string dwconv_kernel_name(const DwParams& p, int dtype) {
+    if (dwconv_mfma_valid(p, dtype)) return dwconv_mfma_kernel_name(p);
+    const std::string t = dtype == DT_BF16 ? "bf16" : "f32";
+    const DwRow<float>* r = dw_row<float>(p);              // (the arguments are the same for both element types)
+    return r ? "dwconv_row_kernel<" + t + "," + r->args + ">" : "dwconv_kernel<" + t + ">";
 }
 
 // ---------------------------------------------------------------------------------------------------------

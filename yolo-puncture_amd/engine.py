@@ -21,6 +21,7 @@ LIB_PATH = os.environ.get("YOLOP_LIB") or os.path.join(_HERE, "libyolop.so")    
 YP_BF16, YP_F32 = 0, 1
 TASK_DETECT, TASK_SEGMENT = 0, 1
 OP_KINDS = {0: "stem", 1: "conv", 2: "dwconv", 3: "pool5", 4: "upsample", 5: "attn", 6: "head", 7: "convT", 8: "pool3", 9: "amax"}
+FORMS = ("plain", "dwpw", "dwpw_tail", "s2pw", "frontend", "c2f", "scdown", "pwsp", "cls_out")   # enum Form of csrc/common.h
 
 
 class ModelDesc(C.Structure):
@@ -69,6 +70,8 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     lib.yp_op_kernel.argtypes = [vp, C.c_int, C.c_char_p, C.c_int]
     lib.yp_op_fusion.argtypes = [vp, C.c_int, ip, ip]
     lib.yp_op_fusion.restype = C.c_int
+    lib.yp_debug_op_form.argtypes = [vp, C.c_int, ip, ip, C.c_int]
+    lib.yp_debug_op_form.restype = C.c_int
     lib.yp_run_op.argtypes = [vp, C.c_int, vp, vp, vp, vp, vp]
     lib.yp_tensor_write.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp]
     lib.yp_tensor_count.argtypes = [vp]
@@ -128,7 +131,7 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
 EXPORTS = ["yp_last_error", "yp_create", "yp_destroy", "yp_weight_count", "yp_weight_info", "yp_set_weight",
            "yp_finalize", "yp_forward", "yp_proto", "yp_masks", "yp_id_mask_resized", "yp_plan", "yp_op_info", "yp_op_output", "yp_op_input", "yp_op_fusion",
            "yp_tensor_count", "yp_tensor_info", "yp_tensor_read", "yp_profile", "yp_set_graph", "yp_run_op",
-           "yp_tensor_write", "yp_op_kernel", "yp_set_autotune", "yp_tuning_export", "yp_tuning_import", "yp_set_nms", "yp_debug_force_conv_cfg", "yp_debug_op_cfg", "yp_debug_last_store_form", "yp_debug_conv_families", "yp_debug_ablation", "yp_debug_head_clocks", "yp_debug_head_branch_clocks", "yp_debug_head_winners", "yp_debug_contour_clocks", "yp_debug_pwsp_clocks", "yp_debug_host_selftest", "yp_debug_graph_info", "yp_tuning_source", "yp_debug_head_positions", "yp_debug_marker", "yp_letterbox", "yp_letterbox_batch", "yp_masks_frames", "yp_masks_frames_input", "yp_mask_contours",
+           "yp_tensor_write", "yp_op_kernel", "yp_set_autotune", "yp_tuning_export", "yp_tuning_import", "yp_set_nms", "yp_debug_force_conv_cfg", "yp_debug_op_cfg", "yp_debug_op_form", "yp_debug_last_store_form", "yp_debug_conv_families", "yp_debug_ablation", "yp_debug_head_clocks", "yp_debug_head_branch_clocks", "yp_debug_head_winners", "yp_debug_contour_clocks", "yp_debug_pwsp_clocks", "yp_debug_host_selftest", "yp_debug_graph_info", "yp_tuning_source", "yp_debug_head_positions", "yp_debug_marker", "yp_letterbox", "yp_letterbox_batch", "yp_masks_frames", "yp_masks_frames_input", "yp_mask_contours",
            "yp_mask_contours_scaled", "yp_mask_contours_large_workspace", "yp_mask_contours_large", "yp_comm_unique_id", "yp_comm_create", "yp_allgather", "yp_comm_destroy",
            "yp_u2net_create", "yp_u2net_destroy", "yp_u2net_weight_count", "yp_u2net_weight_info", "yp_u2net_set_weight", "yp_u2net_finalize",
            "yp_u2net_forward", "yp_u2net_forward_crops", "yp_u2net_set_graph", "yp_u2net_tensor_count", "yp_u2net_tensor_info", "yp_u2net_tensor_read",
@@ -523,6 +526,9 @@ class Engine:
             rec["pre"], rec["pre_stored"] = pre.value, bool(stored.value)     # pwsp_kernel: the 1x1 conv fused in front (or -1), and whether its output is written too
             self._chk(self.lib.yp_debug_op_cfg(self._h, i, C.byref(pre)))
             rec["cfg"] = pre.value          # the tile configuration id run_op launches it with under the forced id (-1: a heuristic picks)
+            absorbed = (C.c_int * 3)()
+            n_abs = self._chk(self.lib.yp_debug_op_form(self._h, i, C.byref(pre), absorbed, 3))
+            rec["form"], rec["absorbed"] = FORMS[pre.value], list(absorbed[:n_abs])   # the fused launch form and the ops whose work it takes over
             ops.append(rec)
         return ops
 
