@@ -272,6 +272,17 @@ int yp_allgather(yp_comm* c, const void* send_dev, void* recv_dev, size_t bytes_
 int yp_comm_destroy(yp_comm* c);
 
 /* -- introspection (tests, bench): the planned op list for an input shape; host only. */
+/* Input size limits. All of them are checked by yp_plan (and by everything that plans: yp_forward, yp_tuning_import), before any launch,
+ * with a message that names the quantity and the largest value that fits (YP_ERR_ARG):
+ *   anchors  (H/8 * W/8 + H/16 * W/16 + H/32 * W/32) <= YP_MAX_ANCHORS. Up to 12288 anchors the heads select inside one workgroup's LDS;
+ *            beyond, chunks of 12288 anchors select in parallel and one workgroup per image merges the chunk winners (v10), or the
+ *            candidates above `conf` are gathered into a global list first (NMS families; at most the 16384 best-scoring candidates of
+ *            an image enter NMS, where ultralytics' max_nms is 30000).
+ *   attention tokens (H/32 * W/32, v10 and 11 only): above 400 the PSA block runs a generic kernel that keeps 16 x tokens scores in LDS,
+ *            which ends at 2368 tokens for 32-wide keys. v8 has no attention.
+ *   bytes    every activation stays below 2^31 bytes: yp_max_batch(e, H, W) is the largest B that plans at HxW (callers split to it). */
+#define YP_MAX_ANCHORS 294912   /* 12288 * (12288 / 512): covers 3840x2176 (214200) */
+int yp_max_batch(const yp_engine* e, int H, int W);
 int yp_plan(yp_engine* e, int B, int H, int W);            /* (re)build the plan; returns #ops or <0 */
 int yp_op_info(const yp_engine* e, int i, char* name, int name_cap, int* kind, double* flops,
                double* bytes);                                 /* algorithmic FLOPs / HBM bytes of op i */
@@ -341,6 +352,13 @@ int yp_debug_ablation(int v);
    [0] start, [1] keys loaded, [2] stage-1 lower bound found, [3] stage-1 select done, [4] stage-2 candidates scanned,
    [5] stage-2 select done, [6] decoded; [7] = stage-2 rounds << 32 | candidates that entered the last round's select. */
 int yp_debug_head_clocks(uint64_t* out8);
+/* Test hook: stage 1 of the top-k head alone (the top k anchors by score descending, anchor index ascending) on caller-made class-max keys,
+   through the kernels an engine takes for that anchor count: head_select_kernel<1> up to 12288 anchors, head_chunk_topk_kernel +
+   head_select_large_kernel<1> beyond. mk_dev[l]: device uint32 [B][hw[l][0] * hw[l][1]], the bits of the anchors' best sigmoid scores as
+   the class-max pass leaves them (non-negative floats); 1 <= k <= 512. sel_out_dev: device int32 [B][512], the winners' anchor ids in rank
+   order in the first min(k, anchors) slots; thr_out_dev: device uint32 [B], the score bits of the last winner. Returns after the stream
+   has drained. YP_ERR_ARG (nothing launched) on null pointers, B < 1, k out of range, an empty level or more than YP_MAX_ANCHORS anchors. */
+int yp_debug_topk_anchors(const uint32_t* const mk_dev[3], int B, const int hw[3][2], int k, int32_t* sel_out_dev, uint32_t* thr_out_dev, void* stream);
 /* The same for the position kernel of the winners-only head (workgroup 0's first tile, last launch): [0] tile start, [1] position list read,
    [2] first patch plane landed, [3] all channel chunks done, [4] activations stored; [5] = level << 32 | channel chunks of that tile,
    [6] = tiles of the launch (64 positions each), [7] = listed positions of the launch (all levels, all images). */

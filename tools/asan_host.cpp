@@ -72,9 +72,43 @@ int main() {
                 // back to the first shape: the per-shape memo path
                 CHECK(yp_plan(e, shapes[0][0], shapes[0][1], shapes[0][2]) > 0);
                 CHECK(yp_debug_host_selftest(e) > 0);
+                // beyond 12288 anchors: the heads' large forms plan; what no kernel holds is refused by yp_plan and leaves the plan as it was
+                CHECK(yp_plan(e, 1, 800, 768) > 0);
+                CHECK(yp_debug_host_selftest(e) > 0);
+                CHECK(yp_plan(e, 1, 3776, 3840) == YP_ERR_ARG && strstr(yp_last_error(), "anchors"));                    // one row past YP_MAX_ANCHORS
+                if (fam != YP_FAMILY_V8) CHECK(yp_plan(e, 1, 2560, 1472) == YP_ERR_ARG && strstr(yp_last_error(), "attention tokens"));
+                else CHECK(yp_plan(e, 1, 2560, 1472) > 0);
+                {
+                    const int mb = yp_max_batch(e, 1280, 1280);
+                    CHECK(mb >= 1 && yp_max_batch(e, 640, 640) >= mb);
+                    CHECK(yp_plan(e, mb, 1280, 1280) > 0);
+                    CHECK(yp_plan(e, mb + 1, 1280, 1280) == YP_ERR_ARG && strstr(yp_last_error(), "2^31"));
+                    CHECK(yp_debug_host_selftest(e) > 0);                                                                  // (the plan at mb still stands)
+                    CHECK(yp_max_batch(nullptr, 640, 640) == YP_ERR_ARG && yp_max_batch(e, 100, 640) == YP_ERR_ARG && yp_max_batch(e, 640, 0) == YP_ERR_ARG);
+                }
+                CHECK(yp_plan(e, shapes[0][0], shapes[0][1], shapes[0][2]) > 0);
                 CHECK(yp_forward(e, nullptr, 1, 64, 64, nullptr, nullptr, nullptr, nullptr) < 0);
                 CHECK(yp_destroy(e) == YP_OK);
             }
+    {   // yp_debug_topk_anchors: every argument is checked before anything touches the device
+        static uint32_t stub[4];
+        const uint32_t* mk[3] = {stub, stub, stub};
+        const uint32_t* mk_hole[3] = {stub, nullptr, stub};
+        const int hw[3][2] = {{100, 96}, {50, 48}, {25, 24}};
+        const int hw_zero[3][2] = {{100, 96}, {0, 48}, {25, 24}};
+        const int hw_big[3][2] = {{512, 512}, {128, 256}, {1, 1}};                      // YP_MAX_ANCHORS + 1
+        int32_t* sel = (int32_t*)stub;
+        CHECK(yp_debug_topk_anchors(nullptr, 1, hw, 300, sel, stub, nullptr) == YP_ERR_ARG);
+        CHECK(yp_debug_topk_anchors(mk, 1, nullptr, 300, sel, stub, nullptr) == YP_ERR_ARG);
+        CHECK(yp_debug_topk_anchors(mk, 1, hw, 300, nullptr, stub, nullptr) == YP_ERR_ARG);
+        CHECK(yp_debug_topk_anchors(mk, 1, hw, 300, sel, nullptr, nullptr) == YP_ERR_ARG);
+        CHECK(yp_debug_topk_anchors(mk, 0, hw, 300, sel, stub, nullptr) == YP_ERR_ARG);
+        CHECK(yp_debug_topk_anchors(mk, 1, hw, 0, sel, stub, nullptr) == YP_ERR_ARG);
+        CHECK(yp_debug_topk_anchors(mk, 1, hw, 513, sel, stub, nullptr) == YP_ERR_ARG);
+        CHECK(yp_debug_topk_anchors(mk_hole, 1, hw, 300, sel, stub, nullptr) == YP_ERR_ARG);
+        CHECK(yp_debug_topk_anchors(mk, 1, hw_zero, 300, sel, stub, nullptr) == YP_ERR_ARG);
+        CHECK(yp_debug_topk_anchors(mk, 1, hw_big, 300, sel, stub, nullptr) == YP_ERR_ARG);
+    }
     yp_model_desc bad{'q', 80, 0, 0, 300, 0};
     yp_engine* e = nullptr;
     CHECK(yp_create(&bad, 0, &e) < 0);

@@ -281,9 +281,24 @@ __global__ __launch_bounds__(A_MAXW * 64) void attention_mfma_kernel(const AttnP
     }
 }
 
+// the matrix-core form: every key of a head in one workgroup's LDS (N <= 400)
+static bool attention_takes_mfma(const AttnParams& p, int dtype) {
+    const size_t qkv_bytes = (size_t)p.B * p.N * p.q_stride * 2;
+    return dtype == DT_BF16 && p.kd == 32 && p.hd == 64 && p.N <= 16 * A_NT && (p.q_stride & 7) == 0 && (p.q_coff & 7) == 0 && qkv_bytes < (1ull << 31);
+}
+static size_t attention_generic_lds(int kd, int N) { return (size_t)(QT * kd + QT * N) * sizeof(float); }
+
+// Whether launch_attention has a kernel for p (the planner asks before anything launches); *max_tokens = the largest N it has one for
+// with p's head sizes: the generic kernel keeps a query tile's QT x N scores in LDS.
+bool attention_fits(const AttnParams& p, int dtype, int* max_tokens) {
+    if (max_tokens) *max_tokens = (int)((150 * 1024 / sizeof(float) - (size_t)QT * p.kd) / QT);
+    if (attention_takes_mfma(p, dtype)) return true;
+    return attention_generic_lds(p.kd, p.N) <= 150 * 1024 && !(p.kd & 3) && !(p.hd & 3);
+}
+
 hipError_t launch_attention(const AttnParams& p, int dtype, hipStream_t st) {
     const size_t qkv_bytes = (size_t)p.B * p.N * p.q_stride * 2;
-    if (dtype == DT_BF16 && p.kd == 32 && p.hd == 64 && p.N <= 16 * A_NT && (p.q_stride & 7) == 0 && (p.q_coff & 7) == 0 && qkv_bytes < (1ull << 31)) {
+    if (attention_takes_mfma(p, dtype)) {
         // query tiles per workgroup: as long as possible (K/V are staged once per workgroup) while the grid still covers the chip
         static const int target = [] { const int v = env_int("YOLOP_ATTN_WGS", 0); return v > 0 ? v : 256; }();
         const int ntiles = (p.N + 15) / 16, BH = p.B * p.nh;
@@ -293,8 +308,8 @@ hipError_t launch_attention(const AttnParams& p, int dtype, hipStream_t st) {
         hipLaunchKernelGGL(attention_mfma_kernel, dim3((unsigned)nsplit, (unsigned)BH), dim3(A_MAXW * 64), 0, st, p, tpw, (unsigned)qkv_bytes);
         return hipGetLastError();
     }
-    const size_t sh = (size_t)(QT * p.kd + QT * p.N) * sizeof(float);
-    if (sh > 150 * 1024 || (p.kd & 3) || (p.hd & 3)) return hipErrorInvalidValue;
+    const size_t sh = attention_generic_lds(p.kd, p.N);
+    if (!attention_fits(p, dtype, nullptr)) return hipErrorInvalidValue;
     dim3 grid((p.N + QT - 1) / QT, p.B * p.nh);
     static size_t granted[2] = {0, 0};
     if (dtype == DT_BF16) {

@@ -266,6 +266,7 @@ bool head_branch_valid(const HeadBranchParams& p);
 hipError_t launch_head_branch(const HeadBranchParams& p, hipStream_t st);
 hipError_t launch_head_nms(const HeadParams& p, hipStream_t st);
 size_t head_nms_scratch_bytes(int B, int A);
+hipError_t launch_head_nms_large(const HeadParams& p, hipStream_t st);             // head_large.hip: A > HEAD_LDS_ANCHORS
 
 // Experiment switches (YOLOP_* environment variables). env_on: set and its first character is '1'; env_int: atoi of the value, dflt when
 // unset. A launcher keeps the result in a function-local static, so a switch is read once, at the first use of that function.
@@ -354,6 +355,7 @@ hipError_t launch_dwconv_mfma(const DwParams& p, hipStream_t st);
 const char* dwconv_mfma_kernel_name(const DwParams& p);
 hipError_t launch_upsample(const UpParams& p, int dtype, hipStream_t st);
 hipError_t launch_attention(const AttnParams& p, int dtype, hipStream_t st);
+bool attention_fits(const AttnParams& p, int dtype, int* max_tokens);      // the predicate of launch_attention, for the planner
 // conv_small.hip: fp32 3x3 for small maps (four waves split K, operands straight from L2)
 bool conv_small_valid(const ConvParams& p, int dtype);
 hipError_t launch_conv_small(const ConvParams& p, int dtype, hipStream_t st);
@@ -366,6 +368,14 @@ hipError_t launch_letterbox(const uint8_t* src, int h0, int w0, uint8_t* dst, in
 hipError_t launch_letterbox_batch(const uint8_t* src, int n, int h0, int w0, uint8_t* dst, int out_h, int out_w, int new_h, int new_w,
                                   int top, int left, int pad, hipStream_t st);
 size_t head_scratch_bytes(int B, int A);
+// More anchors than one workgroup's LDS holds (head_large.hip): chunks of HEAD_LDS_ANCHORS select in parallel, one workgroup per image merges
+// their winners - at most HEAD_LDS_ANCHORS of them, HEAD_MAXK per chunk, hence the bound on A.
+constexpr int HEAD_LDS_ANCHORS = 12288;
+constexpr int HEAD_MAX_ANCHORS = HEAD_LDS_ANCHORS * (HEAD_LDS_ANCHORS / HEAD_MAXK);
+inline int head_large_chunks(int A) { return (A + HEAD_LDS_ANCHORS - 1) / HEAD_LDS_ANCHORS; }
+inline size_t head_large_ckeys_offset(int B, int A) { return ((size_t)B * A * sizeof(unsigned) + 255) & ~(size_t)255; }      // in HeadParams::scratch
+hipError_t launch_head_large(const HeadParams& p, int mode, hipStream_t st);      // mode 0: whole head, 1: stage 1 (winners hand-over)
+const char* head_large_kernel_name(int mode);
 hipError_t head_read_clocks(unsigned long long* out8);
 hipError_t head_branch_read_clocks(unsigned long long* out8);
 hipError_t launch_copy_out(const float* det, float* det_out, const int32_t* idx, int32_t* idx_out, const float* coeff, float* coeff_out,

@@ -1114,12 +1114,39 @@ static HeadBranchParams head_branch_params(const yp_engine& e, const Op& h, int 
     return p;
 }
 
+// The largest batch at HxW whose every activation tensor stays below 2^31 bytes: the kernels build buffer resources and byte offsets from
+// 32-bit byte counts.
+static_assert(HEAD_MAX_ANCHORS == YP_MAX_ANCHORS, "the public bound is the large forms'");
+static int max_batch(const yp_engine& e, int H, int W) {
+    size_t per = 1;
+    for (const auto& t : e.tensors) per = std::max(per, (size_t)(H / t.sdiv) * (W / t.sdiv) * t.C * tensor_elem_bytes(e, t));
+    return (int)std::min<size_t>(((1ull << 31) - 1) / per, 1u << 20);
+}
+
 static int make_plan(yp_engine& e, int B, int H, int W) {
     if (B <= 0 || H <= 0 || W <= 0 || (H % 32) || (W % 32)) return fail(YP_ERR_ARG, "input must be [B,H,W,3] with H,W multiples of 32 (got %d,%d,%d)", B, H, W);
     if (e.planned && e.pB == B && e.pH == H && e.pW == W) return YP_OK;
+    // every refusal happens here, before the plan changes and before any launch
     size_t A = 0;
     for (int l = 0; l < 3; ++l) A += (size_t)(H / (8 << l)) * (W / (8 << l));
-    if (A > 12288) return fail(YP_ERR_ARG, "input %dx%d has %zu anchors; the LDS top-k supports at most 12288", H, W, A);
+    if (A > (size_t)YP_MAX_ANCHORS)
+        return fail(YP_ERR_ARG, "input %dx%d has %zu anchors; the heads' chunked selection supports at most %d (YP_MAX_ANCHORS)", H, W, A, YP_MAX_ANCHORS);
+    for (const auto& o : e.ops) {
+        if (o.kind != OP_ATTN) continue;
+        const TensorDesc& ti = e.tensors[o.in.t];
+        AttnParams q{};
+        q.q_stride = ti.C; q.q_coff = o.in.coff; q.B = B; q.N = (H / ti.sdiv) * (W / ti.sdiv); q.nh = o.nh; q.kd = o.kd; q.hd = o.hd;
+        int max_tokens = 0;
+        if (!attention_fits(q, e.dtype, &max_tokens))
+            return fail(YP_ERR_ARG, "input %dx%d gives %s %d attention tokens; the attention kernels hold at most %d (a streaming form is not built)", H, W,
+                        o.name.c_str(), q.N, max_tokens);
+    }
+    {
+        const int mb = max_batch(e, H, W);
+        if (B > mb)
+            return fail(YP_ERR_ARG, "batch %d at %dx%d: the largest activation would reach 2^31 bytes (32-bit byte offsets in the kernels); the largest batch that fits is %d (yp_max_batch)",
+                        B, H, W, mb);
+    }
     for (auto& t : e.tensors) {
         t.H = H / t.sdiv; t.W = W / t.sdiv;
         t.bytes = (size_t)B * t.H * t.W * t.C * tensor_elem_bytes(e, t);
@@ -1189,6 +1216,7 @@ static int make_plan(yp_engine& e, int B, int H, int W) {
             if (!try_form(o, FORM_SCDOWN)) o.kernel = dwconv_kernel_name(dw_params(e, o), e.dtype);
         } else if (o.kind == OP_STEM) o.kernel = stem_kernel_name(stem_params(e, o, nullptr), e.dtype);
         else if (o.kind == OP_POOL3 && e.dtype == DT_BF16 && (o.in.C & 31) == 0) o.kernel = "sppf_pool3_bf16_kernel";
+        else if (o.kind == OP_HEAD && A > (size_t)HEAD_LDS_ANCHORS) o.kernel = o.nms ? "head_nms_gather_kernel + head_nms_large_kernel" : head_large_kernel_name(0);
         else o.kernel = (o.kind == OP_HEAD && o.nms) ? "head_nms_kernel" : kn[o.kind];
     }
     // winners-only head (v10 top-k head, bf16): the box / coefficient branches run on the stage-1 winners inside the head op; their dense
@@ -1274,7 +1302,9 @@ static int make_plan(yp_engine& e, int B, int H, int W) {
                     o.bytes += npos * (9.0 * q.Cin[l] * 2 + 2.0 * q.cmid * 2) + nw * q.cout * 4 + (9.0 * q.Cin[l] * q.cmid + 9.0 * q.cmid * q.cmid + q.cmid * q.cout) * 2;
                 }
             }
-            if (o.sparse_box || o.sparse_cf) o.kernel = "head_select_kernel<1> + head_pos_kernel + head_win_kernel + head_select_kernel<2>";
+            if (o.sparse_box || o.sparse_cf)
+                o.kernel = (A > (size_t)HEAD_LDS_ANCHORS ? std::string(head_large_kernel_name(1)) : std::string("head_select_kernel<1>")) +
+                           " + head_pos_kernel + head_win_kernel + head_select_kernel<2>";
         }
         for (auto& o : e.ops)
             if (o.skip) { o.flops = 0; o.bytes = 0; o.kernel = "-"; }
@@ -2085,6 +2115,12 @@ int yp_plan(yp_engine* e, int B, int H, int W) {
     return rc == YP_OK ? (int)e->ops.size() : rc;
 }
 
+int yp_max_batch(const yp_engine* e, int H, int W) {
+    if (!e) return fail(YP_ERR_ARG, "null engine");
+    if (H <= 0 || W <= 0 || (H % 32) || (W % 32)) return fail(YP_ERR_ARG, "yp_max_batch: H,W must be positive multiples of 32 (got %d,%d)", H, W);
+    return max_batch(*e, H, W);
+}
+
 int yp_op_info(const yp_engine* e, int i, char* name, int cap, int* kind, double* flops, double* bytes) {
     if (!e || i < 0 || i >= (int)e->ops.size()) return fail(YP_ERR_ARG, "bad op index");
     const Op& o = e->ops[i];
@@ -2497,6 +2533,35 @@ int yp_debug_head_winners(yp_engine* e, int32_t* sel_host, float* box_host, floa
     if (box_host && h->sparse_box) HIPCHK(hipMemcpy(box_host, base + ws.box, (size_t)e->pB * e->desc.max_det * 64 * 4, hipMemcpyDeviceToHost));
     if (coeff_host && h->sparse_cf) HIPCHK(hipMemcpy(coeff_host, base + ws.cf, (size_t)e->pB * e->desc.max_det * 32 * 4, hipMemcpyDeviceToHost));
     return (h->sparse_box ? 1 : 0) | (h->sparse_cf ? 2 : 0);
+}
+
+int yp_debug_topk_anchors(const uint32_t* const mk_dev[3], int B, const int hw[3][2], int k, int32_t* sel_out_dev, uint32_t* thr_out_dev, void* stream) {
+    if (!mk_dev || !hw || !sel_out_dev || !thr_out_dev) return fail(YP_ERR_ARG, "yp_debug_topk_anchors: null argument");
+    if (B < 1 || B > 4096) return fail(YP_ERR_ARG, "yp_debug_topk_anchors: B = %d (1 .. 4096)", B);
+    if (k < 1 || k > HEAD_MAXK) return fail(YP_ERR_ARG, "yp_debug_topk_anchors: k = %d (1 .. %d)", k, HEAD_MAXK);
+    HeadParams p{};
+    size_t A = 0;
+    for (int l = 0; l < 3; ++l) {
+        if (!mk_dev[l]) return fail(YP_ERR_ARG, "yp_debug_topk_anchors: level %d has no keys", l);
+        if (hw[l][0] < 1 || hw[l][1] < 1 || hw[l][0] > 65536 || hw[l][1] > 65536) return fail(YP_ERR_ARG, "yp_debug_topk_anchors: level %d is %dx%d", l, hw[l][0], hw[l][1]);
+        p.mk[l] = mk_dev[l]; p.hw[l][0] = hw[l][0]; p.hw[l][1] = hw[l][1];
+        A += (size_t)hw[l][0] * hw[l][1];
+    }
+    if (A > (size_t)YP_MAX_ANCHORS) return fail(YP_ERR_ARG, "yp_debug_topk_anchors: %zu anchors; at most %d (YP_MAX_ANCHORS)", A, YP_MAX_ANCHORS);
+    p.nlev = 3; p.A = (int)A; p.B = B; p.nc = 1; p.max_det = k;
+    // stage 1 as the winners-only head launches it (no position lists): sel [B][512] | wlist [B][3][512] | wcount [B][3] | scratch of the large form
+    const size_t sel_b = (size_t)B * HEAD_MAXK * 4, wl_b = 3 * sel_b, wc_b = ((size_t)B * 3 * 4 + 255) & ~(size_t)255;
+    char* ws = nullptr;
+    HIPCHK(hipMalloc((void**)&ws, sel_b + wl_b + wc_b + head_scratch_bytes(B, (int)A)));
+    p.sp_sel = (int*)ws; p.sp_wlist = (int*)(ws + sel_b); p.sp_wcount = (int*)(ws + sel_b + wl_b); p.sp_thr = thr_out_dev;
+    p.scratch = ws + sel_b + wl_b + wc_b;
+    hipStream_t st = (hipStream_t)stream;
+    hipError_t err = launch_head_stage1(p, st);
+    if (err == hipSuccess) err = hipMemcpyAsync(sel_out_dev, p.sp_sel, sel_b, hipMemcpyDeviceToDevice, st);
+    if (err == hipSuccess) err = hipStreamSynchronize(st);
+    (void)hipFree(ws);
+    if (err != hipSuccess) return fail(YP_ERR_HIP, "yp_debug_topk_anchors: %s", hipGetErrorString(err));
+    return YP_OK;
 }
 
 int yp_tuning_source(const yp_engine* e) {

@@ -65,6 +65,10 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
                                            C.c_size_t, vp]
     lib.yp_mask_contours_large.restype = C.c_int
     lib.yp_plan.argtypes = [vp, C.c_int, C.c_int, C.c_int]
+    lib.yp_max_batch.argtypes = [vp, C.c_int, C.c_int]
+    lib.yp_max_batch.restype = C.c_int
+    lib.yp_debug_topk_anchors.argtypes = [C.POINTER(vp), C.c_int, C.POINTER(C.c_int), C.c_int, vp, vp, vp]
+    lib.yp_debug_topk_anchors.restype = C.c_int
     lib.yp_op_info.argtypes = [vp, C.c_int, C.c_char_p, C.c_int, ip, C.POINTER(C.c_double), C.POINTER(C.c_double)]
     lib.yp_op_output.argtypes = [vp, C.c_int, ip, ip, ip]
     lib.yp_op_kernel.argtypes = [vp, C.c_int, C.c_char_p, C.c_int]
@@ -131,13 +135,38 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
 EXPORTS = ["yp_last_error", "yp_create", "yp_destroy", "yp_weight_count", "yp_weight_info", "yp_set_weight",
            "yp_finalize", "yp_forward", "yp_proto", "yp_masks", "yp_id_mask_resized", "yp_plan", "yp_op_info", "yp_op_output", "yp_op_input", "yp_op_fusion",
            "yp_tensor_count", "yp_tensor_info", "yp_tensor_read", "yp_profile", "yp_set_graph", "yp_run_op",
-           "yp_tensor_write", "yp_op_kernel", "yp_set_autotune", "yp_tuning_export", "yp_tuning_import", "yp_set_nms", "yp_debug_force_conv_cfg", "yp_debug_op_cfg", "yp_debug_op_form", "yp_debug_last_store_form", "yp_debug_conv_families", "yp_debug_ablation", "yp_debug_head_clocks", "yp_debug_head_branch_clocks", "yp_debug_head_winners", "yp_debug_contour_clocks", "yp_debug_pwsp_clocks", "yp_debug_host_selftest", "yp_debug_graph_info", "yp_tuning_source", "yp_debug_head_positions", "yp_debug_marker", "yp_letterbox", "yp_letterbox_batch", "yp_masks_frames", "yp_masks_frames_input", "yp_mask_contours",
+           "yp_tensor_write", "yp_op_kernel", "yp_set_autotune", "yp_tuning_export", "yp_tuning_import", "yp_set_nms", "yp_debug_force_conv_cfg", "yp_debug_op_cfg", "yp_debug_op_form", "yp_debug_last_store_form", "yp_debug_conv_families", "yp_debug_ablation", "yp_debug_head_clocks", "yp_debug_head_branch_clocks", "yp_debug_head_winners", "yp_debug_contour_clocks", "yp_debug_pwsp_clocks", "yp_debug_host_selftest", "yp_debug_graph_info", "yp_tuning_source", "yp_debug_head_positions", "yp_debug_marker", "yp_max_batch", "yp_debug_topk_anchors", "yp_letterbox", "yp_letterbox_batch", "yp_masks_frames", "yp_masks_frames_input", "yp_mask_contours",
            "yp_mask_contours_scaled", "yp_mask_contours_large_workspace", "yp_mask_contours_large", "yp_comm_unique_id", "yp_comm_create", "yp_allgather", "yp_comm_destroy",
            "yp_u2net_create", "yp_u2net_destroy", "yp_u2net_weight_count", "yp_u2net_weight_info", "yp_u2net_set_weight", "yp_u2net_finalize",
            "yp_u2net_forward", "yp_u2net_forward_crops", "yp_u2net_set_graph", "yp_u2net_tensor_count", "yp_u2net_tensor_info", "yp_u2net_tensor_read",
            "yp_u2net_op_count", "yp_u2net_op_info",
            "yp_cls_create", "yp_cls_destroy", "yp_cls_weight_count", "yp_cls_weight_info", "yp_cls_set_weight", "yp_cls_finalize",
            "yp_cls_forward", "yp_cls_set_graph", "yp_cls_tensor_count", "yp_cls_tensor_info", "yp_cls_tensor_read"]
+
+
+MAX_ANCHORS = 294912      # YP_MAX_ANCHORS
+
+
+def topk_anchors(mk: List[torch.Tensor], hw, k: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Debug: stage 1 of the top-k head alone (yp_debug_topk_anchors) on caller-made class-max keys. mk[l]: device uint32-as-int32 [B, H_l * W_l]
+    (bits of non-negative float scores), hw: three (H_l, W_l). Returns (winners int32 [B, 512] - anchor ids by rank in the first
+    min(k, anchors) slots - and the threshold's score bits int32 [B]), on the device. Runs the kernels an engine takes for that anchor count."""
+    lib = load_library()
+    if len(mk) != 3 or len(hw) != 3:
+        raise ValueError("three levels")
+    B = int(mk[0].shape[0])
+    dev = mk[0].device
+    for t, (h, w) in zip(mk, hw):
+        if t.dtype != torch.int32 or not t.is_contiguous() or t.device != dev or tuple(t.shape) != (B, int(h) * int(w)):
+            raise ValueError("mk[l] must be contiguous int32 [B, H_l * W_l] on one device")
+    sel = torch.full((B, 512), -1, dtype=torch.int32, device=dev)
+    thr = torch.zeros((B,), dtype=torch.int32, device=dev)
+    ptrs = (C.c_void_p * 3)(*[t.data_ptr() for t in mk])
+    hwa = (C.c_int * 6)(*[int(v) for pair in hw for v in pair])
+    rc = lib.yp_debug_topk_anchors(ptrs, B, hwa, int(k), C.c_void_p(sel.data_ptr()), C.c_void_p(thr.data_ptr()), C.c_void_p(_stream_ptr(dev)))
+    if rc < 0:
+        raise YolopError(lib.yp_last_error().decode())
+    return sel, thr
 
 
 def conv_families() -> List[Tuple[int, int]]:
@@ -531,6 +560,10 @@ class Engine:
             rec["form"], rec["absorbed"] = FORMS[pre.value], list(absorbed[:n_abs])   # the fused launch form and the ops whose work it takes over
             ops.append(rec)
         return ops
+
+    def max_batch(self, H: int, W: int) -> int:
+        """The largest batch that plans at HxW (every activation below 2^31 bytes); callers split larger groups to it."""
+        return self._chk(self.lib.yp_max_batch(self._h, int(H), int(W)))
 
     def tensors(self) -> List[dict]:
         n = self._chk(self.lib.yp_tensor_count(self._h))

@@ -445,7 +445,12 @@ class YOLO:
             geos.append(geo)
             groups.setdefault((geo["out_h"], geo["out_w"]), []).append(i)
         out_by_index: Dict[int, Results] = {}
+        # ... in runs of at most the engine's largest batch at that shape (Engine.max_batch: large inputs reach the kernels' 32-bit byte offsets)
+        runs: List[Tuple[Tuple[int, int], List[int]]] = []
         for (H, W), idxs in groups.items():
+            mb = eng.max_batch(H, W)
+            runs += [((H, W), idxs[s0:s0 + mb]) for s0 in range(0, len(idxs), mb)]
+        for (H, W), idxs in runs:
             # the raw frame goes up once; resize + pad-114 run on the device straight into the batch tensor (yp_letterbox)
             # (one persistent batch buffer per shape: the engine's hipGraph is specialised on the input pointer)
             bcache = self.__dict__.setdefault("_batch_cache", {})
@@ -538,11 +543,10 @@ class YOLO:
             return ClipResults([], [], [], [], [], [])
         if H <= 0 or W <= 0:
             raise ValueError(f"empty frames ({H}x{W})")
-        B, chunks = hostops.clip_plan(N, batch_size)
         geo = hostops.letterbox_geometry(H, W, imgsz)
         Hl, Wl = geo["out_h"], geo["out_w"]
-
         eng = self._engine()
+        B, chunks = hostops.clip_plan(N, min(int(batch_size), eng.max_batch(Hl, Wl)))      # (no chunk larger than the engine plans at this shape)
         if self.family != "v10":
             eng.set_nms(conf, iou)
         mode = os.environ.get("YOLOP_PREDICT_GRAPH", "auto")
