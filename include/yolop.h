@@ -343,6 +343,10 @@ int yp_debug_op_cfg(const yp_engine* e, int i, int* cfg);
    the 8-byte stores everywhere), -1 = no such launch since the last call (the call resets it; launches record their form only from the first call on, so call it once
    before the launch of interest). Read it right after yp_run_op. */
 int yp_debug_last_store_form(void);
+/* Test hook: at most n workgroups for the persistent kernels that wait for a tile with a counted vmcnt (conv_wres: in whole rounds of 8 tile
+   lanes per channel block; conv_dwpw_stream, c2f_fused), 0 = no cap. A small input then makes a workgroup walk several tiles, which is where the counted wait in front of a tile
+   comes into play. Host-side only: the launchers read it, device code is the same. Returns the previous value. */
+int yp_debug_max_workgroups(int n);
 /* Test hook: the conv tile families' configuration id ranges [base, base + num_cfgs), in the autotuner's order. Fills at most cap entries of
    each array (either may be null) and returns the number of families. */
 int yp_debug_conv_families(int* base, int* num_cfgs, int cap);

@@ -42,6 +42,7 @@ __global__ __launch_bounds__(CF_NW * 64) void c2f_fused_kernel(const C2fParams p
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int fr = lane & 15, fc = lane >> 4;
     const int num_tiles = p.B * tiles_h * tiles_w;
+    const bool wide = p.wide != 0;                            // paired channel order (kernel_util.h) of the final 1x1: W3s rows, bias3, the stores of S4 and the counted wait
 
     const int bid = xcd_remap(blockIdx.x, gridDim.x);
 
@@ -88,14 +89,14 @@ __global__ __launch_bounds__(CF_NW * 64) void c2f_fused_kernel(const C2fParams p
         const int rg = s >> 2, pc = s & 3;
         const int c8 = pc ^ cswz64(rg);
         const int n = rg & 63, ch = rg >> 6;
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(w3rs, (lds_void*)(W3s + ii * 1024), 16, (unsigned)((n * p.Kpad3 + ch * 32 + c8 * 8) * 2), 0, 0, 0);
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(w3rs, (lds_void*)(W3s + ii * 1024), 16, (unsigned)((weight_row_channel(n, wide) * p.Kpad3 + ch * 32 + c8 * 8) * 2), 0, 0, 0);
     }
 
     const int cf = wave & 1, wq = wave >> 1;          // stages 2 and 3: channel half, pixel-fragment group
     if (tid < 128) Bs[tid] = tid < 32 ? p.bias1[tid] : tid < 64 ? p.bias2[tid - 32] : p.bias3[tid - 64];
     const float* const bias1 = Bs + cf * 16 + fc * 4;          // (read per stage: the registers are needed for the weight fragments)
     const float* const bias2 = Bs + 32 + cf * 16 + fc * 4;
-    const float* const bias3 = Bs + 64 + cf * 32 + fc * 4;
+    const float* const bias3 = Bs + 64 + cf * 32;              // (+ acc_channel: the wave's two fragments)
 
     int tile = bid;
     issue_ab(tile, ABs);
@@ -122,7 +123,10 @@ __global__ __launch_bounds__(CF_NW * 64) void c2f_fused_kernel(const C2fParams p
         const int th = t % tiles_h;
         const int b = t / tiles_h;
         unsigned char* const AB = ABs + (it & 1) * CF_AB;
-        if (it) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");         // this tile's patch (only the previous tile's 4 stores are younger)
+        if (it) {                                                        // this tile's patch (only the previous tile's 4 stores are younger; 2 in the paired form)
+            if (wide) asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
+            else asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
+        }
         CF_STAMP(0)
         __builtin_amdgcn_s_barrier();                                    // patch complete; every wave is past the previous tile's stage 4
         CF_STAMP(1)
@@ -246,7 +250,7 @@ __global__ __launch_bounds__(CF_NW * 64) void c2f_fused_kernel(const C2fParams p
 #pragma unroll
             for (int j = 0; j < 2; ++j)
 #pragma unroll
-                for (int a = 0; a < 2; ++a) acc[j][a] = *(const f32x4*)(bias3 + a * 16);
+                for (int a = 0; a < 2; ++a) acc[j][a] = *(const f32x4*)(bias3 + acc_channel(a, fc, wide));
 #pragma unroll
             for (int ch = 0; ch < 3; ++ch)
 #pragma unroll
@@ -259,6 +263,19 @@ __global__ __launch_bounds__(CF_NW * 64) void c2f_fused_kernel(const C2fParams p
                 const int ho = th * CF_TH + wq + 4 * j;
                 const bool pix_ok = (ho < p.H) && (wo < p.W);
                 const unsigned m = (unsigned)((b * p.H + ho) * p.W + wo);
+                if (wide) {                                // the wave's fragment pair: one 16-byte store per lane, 2 per wave and tile
+                    float v[2][4];
+#pragma unroll
+                    for (int h = 0; h < 2; ++h) {
+#pragma unroll
+                        for (int q = 0; q < 4; ++q) v[h][q] = acc[j][h][q];
+                        if (p.act3 == ACT_SILU) silu4_packed(v[h]);
+                    }
+                    const int co = cf * 32 + acc_channel(0, fc, true);                     // 8 channels from here: fragment 0's four, then fragment 1's
+                    store_bf16x8(v[0], v[1], yrs, pix_ok ? (m * (unsigned)p.y_stride + (unsigned)(p.y_coff + co)) * 2u : OOB);
+                    continue;
+                }
+                // the 8-byte form: one store per fragment, weight rows in natural order
 #pragma unroll
                 for (int a = 0; a < 2; ++a) {
                     float v[4] = {acc[j][a][0], acc[j][a][1], acc[j][a][2], acc[j][a][3]};
@@ -289,11 +306,14 @@ bool c2f_fused_valid(const C2fParams& p) {
     return true;
 }
 
-hipError_t launch_c2f_fused(const C2fParams& p, hipStream_t st) {
+hipError_t launch_c2f_fused(const C2fParams& p_in, hipStream_t st) {
+    C2fParams p = p_in;
+    p.wide = wide_store_ok(p_in.wide, 2, p_in.Cout, p_in.y_stride, p_in.y_coff, false) ? 1 : 0;     // (two channel fragments per wave in S4)
     const int tiles_h = (p.H + CF_TH - 1) / CF_TH, tiles_w = (p.W + 15) / 16;
     const int num_tiles = p.B * tiles_h * tiles_w;
     int G = 256;
     if (G > num_tiles) G = num_tiles;
+    if (const int cap = debug_max_workgroups()) G = G < cap ? G : cap;
     static size_t granted = 0;
     if (hipError_t e = allow_dynamic_lds((const void*)c2f_fused_kernel, (size_t)CF_LDS, granted)) return e;
     static const bool clocks = env_on("YOLOP_C2F_CLOCKS");   // debug: per-stage s_memtime sums

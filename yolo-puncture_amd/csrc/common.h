@@ -185,6 +185,7 @@ struct C2fParams {
     const void* w3; const float* bias3; int act3, Kpad3, Cout; size_t w3_bytes;   // cv2: packed [Cout^][3*C]
     void* y; int y_stride, y_coff; size_t y_bytes;
     unsigned long long* clk;                                              // debug (YOLOP_C2F_CLOCKS=1): per-wave stage clocks, else null
+    int wide;                                                             // the final 1x1's paired channel order is asked for (ConvParams::wide); the launcher decides
 };
 bool c2f_fused_valid(const C2fParams& p);
 
@@ -308,6 +309,13 @@ inline ConvParams with_store_form(const ConvParams& p, int frags) {
     return q;
 }
 
+// Test hook (yp_debug_max_workgroups): an upper bound on the grid of the persistent kernels with a counted wait in front of a tile
+// (conv_wres, conv_dwpw_stream, c2f_fused), 0 = none.
+// With it a small input makes a workgroup walk several tiles - the counted vmcnt in front of a tile is exercised from the second tile on.
+// Read by the launchers only; a kernel whose workgroup mapping needs whole rounds (conv_wres: 8 tile lanes per channel block) stops there.
+inline std::atomic<int>& debug_max_workgroups_ref() { static std::atomic<int> v{0}; return v; }
+inline int debug_max_workgroups() { return debug_max_workgroups_ref().load(std::memory_order_relaxed); }
+
 // launches (implemented in the .hip files); dtype selects the template instance
 hipError_t launch_conv(const ConvParams& p, int dtype, hipStream_t st);
 hipError_t launch_conv_igemm(const ConvParams& p, int dtype, hipStream_t st);   // always the register-staged kernel (dilation, ReLU, any Cin % 8 == 0)
@@ -388,6 +396,7 @@ struct DwPwParams {                              // fused depthwise 3x3 s1 -> po
     const void* w_pw; int Kpad; size_t wpw_bytes; const float* b_pw; int act_pw;   // pointwise: packed [Cout^][Kpad]
     void* y; int y_stride, y_coff; size_t y_bytes; int Cout; int out_f32;
     unsigned long long* clk;                                    // debug (YOLOP_DWPW_CLOCKS=1): per-wave phase clocks, else null
+    int wide;                                                   // conv_dwpw_stream: the paired channel order is asked for (ConvParams::wide); its launcher decides (wide_store_ok)
     // TAIL form (round 3): a trailing 1x1 (the class branch's logit conv, no activation, fp32 output) runs as a third stage on the tile
     // while it is still in LDS: y3 = W3 . act_pw(pointwise(...)) + b3; the pointwise result itself is NOT written (y is unused). When
     // `keys` is set, the per-pixel class maximum goes out as well: keys[b*H*W + pixel] = bits of sigmoid(max_c y3) (what OP_AMAX makes)
@@ -409,6 +418,7 @@ struct PwSpParams {
     const void* res; int res_stride, res_coff;                                      // added after actd (nullable)
     void* y2; int y2_stride, y2_coff;                                              // spatial result (pool: stage s at channel offset s * Csp)
     int dbg;                                                                        // timing ablations (tools only, results wrong): 1 no MFMAs, 2 no pixel loads, 4 no spatial stage
+    int wide;                                                                       // sp = 0: the paired channel order for the stores to y1 is asked for (ConvParams::wide); the launcher decides
 };
 bool pwsp_valid(const PwSpParams& p);
 const char* pwsp_kernel_name(const PwSpParams& p);

@@ -42,11 +42,22 @@ __global__ __launch_bounds__(NW * 64, 2) void conv_dwpw_stream_kernel(const DwPw
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int fr = lane & 15, fc = lane >> 4;
+    const bool wide = NFW % 2 == 0 && p.wide != 0;                 // paired channel order (kernel_util.h): weight rows, bias, store and the counted wait
 
     const __amdgpu_buffer_rsrc_t xrs = __builtin_amdgcn_make_buffer_rsrc((void*)p.x, 0, (int)p.x_bytes, 0x00020000);
     const __amdgpu_buffer_rsrc_t wrs = __builtin_amdgcn_make_buffer_rsrc((void*)p.w_pw, 0, (int)p.wpw_bytes, 0x00020000);
     const __amdgpu_buffer_rsrc_t yrs = __builtin_amdgcn_make_buffer_rsrc((void*)p.y, 0, (int)p.y_bytes, 0x00020000);
 
+    // halo position (row, column) of this lane's pixel in each of its pieces, packed into one register per piece: unpacked behind an empty asm
+    // statement at every use, so the compiler cannot keep both halves live across the tile loop (with four waves that is 24 registers, and
+    // the kernel then spills - a reload between two pieces waits for the pieces before it)
+    unsigned hyx[DS_PIECES / NW];
+#pragma unroll
+    for (int j = 0; j < DS_PIECES / NW; ++j) {
+        const int hp = ((wave + j * NW) * 64 + lane) >> 4;
+        const int hy = hp / (DS_TW + 2);
+        hyx[j] = (unsigned)((hy << 8) | (hp - hy * (DS_TW + 2)));
+    }
     // six pieces per wave and tile, whether they exist or not (pieces 45..47 and the tiles behind the end read nothing)
     auto issue_tile = [&](int tile, int slot) {
         int t = tile;
@@ -60,7 +71,9 @@ __global__ __launch_bounds__(NW * 64, 2) void conv_dwpw_stream_kernel(const DwPw
             const int ii = wave + j * NW;
             const int s = ii * 64 + lane;
             const int hp = s >> 4, c = s & 15;
-            const int hy = hp / (DS_TW + 2), hx = hp - hy * (DS_TW + 2);
+            unsigned q = hyx[j];
+            asm volatile("" : "+v"(q));
+            const int hy = (int)(q >> 8), hx = (int)(q & 255u);
             const int hi = h0 + hy, wi = w0 + hx;
             const bool ok = tile < num_tiles && hp < DS_HP && (unsigned)hi < (unsigned)p.H && (unsigned)wi < (unsigned)p.W;
             const unsigned voff = ok ? (unsigned)((((b * p.H + hi) * p.W + wi) * p.x_stride + p.x_coff + c * 8) * 2) : OOB;
@@ -91,12 +104,12 @@ __global__ __launch_bounds__(NW * 64, 2) void conv_dwpw_stream_kernel(const DwPw
     for (int i = 0; i < NFW; ++i) {
 #pragma unroll
         for (int ks = 0; ks < 4; ++ks) {
-            const unsigned voff = (unsigned)((((wave * NFW + i) * 16 + fr) * p.Kpad + (ks >> 1) * 64 + fc * 16 + (ks & 1) * 8) * 2);
+            const unsigned voff = (unsigned)((weight_row_channel((wave * NFW + i) * 16 + fr, wide) * p.Kpad + (ks >> 1) * 64 + fc * 16 + (ks & 1) * 8) * 2);
             const __attribute__((ext_vector_type(4))) unsigned v = __builtin_amdgcn_raw_buffer_load_b128(wrs, voff, 0, 0);
             wreg[ks][i] = __builtin_bit_cast(bf16x8, v);
         }
 #pragma unroll
-        for (int r = 0; r < 4; ++r) { const int co = (wave * NFW + i) * 16 + fc * 4 + r; bpw[i][r] = (co < p.Cout) ? p.b_pw[co] : 0.f; }
+        for (int r = 0; r < 4; ++r) { const int co = wave * NFW * 16 + acc_channel(i, fc, wide) + r; bpw[i][r] = (co < p.Cout) ? p.b_pw[co] : 0.f; }
     }
     // (known complete before the loop, then passed through empty asm statements: see conv_wres.hip)
     wait_vmcnt<0>();
@@ -115,6 +128,7 @@ __global__ __launch_bounds__(NW * 64, 2) void conv_dwpw_stream_kernel(const DwPw
     for (int it = 0; tile < num_tiles; tile += G, ++it) {
         // (a) this tile's rows have landed (issued in front of the previous tile's stores, which may still fly)
         if (it == 0) wait_vmcnt<0>();
+        else if (wide) wait_vmcnt<NST / 2>();                      // a tile's paired epilogue issued half as many stores
         else wait_vmcnt<NST>();
         __builtin_amdgcn_s_barrier();
         const int slot = NSLOT == 2 ? (it & 1) : 0;
@@ -179,6 +193,27 @@ __global__ __launch_bounds__(NW * 64, 2) void conv_dwpw_stream_kernel(const DwPw
                 for (int f = 0; f < DS_TH; ++f) acc[i][f] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wreg[ks][i], xf[f], acc[i][f], 0, 0, 0);
         }
         const int wo = tw * DS_TW + fr;
+        if (wide) {                                                // a fragment pair (2j, 2j+1) per step: one 16-byte store per lane, NST / 2 per wave and tile
+#pragma unroll
+            for (int j = 0; j < NFW / 2; ++j) {
+                const int co = wave * NFW * 16 + acc_channel(2 * j, fc, true);     // 8 channels from here: fragment 2j's four, then 2j+1's
+#pragma unroll
+                for (int f = 0; f < DS_TH; ++f) {
+                    const int ho = th * DS_TH + f;
+                    const bool ok = ho < p.H && wo < p.W;              // (Cout = 128 = the eight waves' channels: dwpw_stream_valid)
+                    float v[2][4];
+#pragma unroll
+                    for (int h = 0; h < 2; ++h) {
+#pragma unroll
+                        for (int q = 0; q < 4; ++q) v[h][q] = acc[2 * j + h][f][q];
+                        if (p.act_pw == ACT_SILU) silu4_packed(v[h]);
+                    }
+                    store_bf16x8(v[0], v[1], yrs, ok ? (unsigned)((((b * p.H + ho) * p.W + wo) * p.y_stride + p.y_coff + co) * 2) : OOB);
+                }
+            }
+            continue;
+        }
+        // the 8-byte form: one store per fragment, weight rows in natural order
 #pragma unroll
         for (int i = 0; i < NFW; ++i) {
             const int co = (wave * NFW + i) * 16 + fc * 4;
@@ -210,7 +245,9 @@ bool dwpw_stream_valid(const DwPwParams& p) {
 }
 
 template <int NW>
-static hipError_t launch_dwpw_stream_t(const DwPwParams& p, hipStream_t st) {
+static hipError_t launch_dwpw_stream_t(const DwPwParams& p_in, hipStream_t st) {
+    DwPwParams p = p_in;
+    p.wide = wide_store_ok(p_in.wide, 8 / NW, p_in.Cout, p_in.y_stride, p_in.y_coff, p_in.out_f32 != 0) ? 1 : 0;      // (one fragment per wave with 8 waves: the 8-byte form)
     const size_t sh = (size_t)(NW == 8 ? 2 : 1) * DS_HB + DS_AB;
     auto kern = conv_dwpw_stream_kernel<NW>;
     static size_t granted = 0;
@@ -218,7 +255,8 @@ static hipError_t launch_dwpw_stream_t(const DwPwParams& p, hipStream_t st) {
     const int tiles_h = (p.H + DS_TH - 1) / DS_TH, tiles_w = (p.W + DS_TW - 1) / DS_TW;
     const int num_tiles = p.B * tiles_h * tiles_w;
     const int gmax = NW == 8 ? 256 : 512;
-    const int G = num_tiles < gmax ? num_tiles : gmax;
+    int G = num_tiles < gmax ? num_tiles : gmax;
+    if (const int cap = debug_max_workgroups()) G = G < cap ? G : cap;
     hipLaunchKernelGGL(kern, dim3((unsigned)G), dim3(NW * 64), sh, st, p, tiles_h, tiles_w, num_tiles, G);
     return hipGetLastError();
 }

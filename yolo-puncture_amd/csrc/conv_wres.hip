@@ -32,8 +32,16 @@ template <int N, int FM, int NFW> __device__ __forceinline__ void wr_wait_lgkm(b
     for (int i = 0; i < NFW; ++i) asm volatile("" : "+v"(ws[i]));
 }
 
-template <int TP, int WGN, bool HAS_RES>
-__global__ __launch_bounds__(WR_NW * 64) void conv_wres_kernel(const ConvParams p, const int NB, const int nblk, const int G, const int TPe) {
+// Which instantiations carry the paired (16-byte) store form beside the 8-byte one (kernel and launcher ask the same function): those whose
+// waves issue at least 8 stores per tile. Measured on the bench step against the parent build, kernel trace / per-op table: <128,2> (8 stores
+// -> 4) 28.0 -> 26.0 us, while <64,2> (4 -> 2) and <32,4> (2 -> 1) came out 0.5 - 0.7 us SLOWER with both epilogues in them than with one, in
+// either form - there is too little to halve. They compile to what they were (same instruction count and registers).
+template <int TP, int WGN> constexpr bool wres_paired() { return (TP / (16 * (WR_NW / WGN))) * (WR_MAXNF / WGN) >= 8; }
+
+// The kernel's body. CLK: the stamped form (debug, YOLOP_WRES_CLOCKS=1, conv_wres_clk_kernel below): per-wave s_memtime sums of prologue /
+// wait + barrier / piece issue / k loop / epilogue, in the style of conv_wreg's; the production kernels carry none of it
+template <int TP, int WGN, bool HAS_RES, bool CLK>
+__device__ __forceinline__ void conv_wres_body(const ConvParams p, const int NB, const int nblk, const int G, const int TPe) {
     constexpr int WGM = WR_NW / WGN;
     constexpr int FM = TP / (16 * WGM);                            // pixel fragments per wave
     constexpr int NFW = WR_MAXNF / WGN;                            // channel fragments per wave at most
@@ -54,10 +62,13 @@ __global__ __launch_bounds__(WR_NW * 64) void conv_wres_kernel(const ConvParams 
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wm = wave % WGM, wn = wave / WGM;
     const int fr = lane & 15, fc = lane >> 4;
+    const bool wide = wres_paired<TP, WGN>() && p.wide != 0;       // paired channel order (kernel_util.h): weight rows, bias, residual, store and the counted wait
     // TPe <= TP rows of a tile are in use: the host sizes the tiles so that every tile lane gets the same number of pixels (a 40x40 map in
     // 64-pixel tiles is 3.1 tiles per lane = four rounds of which the last is mostly idle; four rounds of 50 pixels are not)
     const int ntiles = (p.M + TPe - 1) / TPe;
     const int HoWo = p.Ho * p.Wo;
+    unsigned long long clk[5] = {0, 0, 0, 0, 0}, last = CLK ? __builtin_amdgcn_s_memtime() : 0ull;
+#define WRES_STAMP(i) if constexpr (CLK) { const unsigned long long now = __builtin_amdgcn_s_memtime(); clk[i] += now - last; last = now; }
 
     // workgroup -> (channel block, tile lane): the blocks of one tile lane are neighbours on one XCD (G % (8 * nblk) == 0)
     const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3;
@@ -109,7 +120,7 @@ __global__ __launch_bounds__(WR_NW * 64) void conv_wres_kernel(const ConvParams 
             const int s = ii * 64 + lane;
             const int r = s / cpr, pc = s - r * cpr;
             const int c = pc ^ (r & mW);
-            const unsigned voff = (unsigned)(((n0 + r) * p.Kpad + c * 8) * 2);
+            const unsigned voff = (unsigned)(((n0 + weight_row_channel(r, wide)) * p.Kpad + c * 8) * 2);
             __builtin_amdgcn_raw_ptr_buffer_load_lds(wrs, (lds_void*)(Ws + ii * 1024), 16, voff, 0, 0, 0);
         }
     }
@@ -121,7 +132,7 @@ __global__ __launch_bounds__(WR_NW * 64) void conv_wres_kernel(const ConvParams 
     for (int i = 0; i < NFW; ++i)
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-            const int co = n0 + (wn * nfw + i) * 16 + fc * 4 + r;
+            const int co = wres_paired<TP, WGN>() ? n0 + wn * nfw * 16 + acc_channel(i, fc, wide) + r : n0 + (wn * nfw + i) * 16 + fc * 4 + r;
             bias[i][r] = (i < nfw && co < p.Cout) ? p.bias[co] : 0.f;
         }
     // The bias loads must be KNOWN to be complete before the loop: the compiler cannot count the vector-memory operations of a loop
@@ -134,12 +145,17 @@ __global__ __launch_bounds__(WR_NW * 64) void conv_wres_kernel(const ConvParams 
 #pragma unroll
         for (int r = 0; r < 4; ++r) asm volatile("" : "+v"(bias[i][r]));
 
+    WRES_STAMP(0)
     for (int it = 0; tile < ntiles; tile += Gt, ++it) {
-        // this tile's rows (first time: the weights too) have landed; the FM * NFW stores of the previous tile, issued behind them, may still fly
+        // this tile's rows (first time: the weights too) have landed; the FM * NFW stores of the previous tile (half as many in the paired
+        // form), issued behind them, may still fly
         if (it == 0) wait_vmcnt<0>();
+        else if (wide) wait_vmcnt<FM * NFW / 2>();
         else wait_vmcnt<FM * NFW>();
         __builtin_amdgcn_s_barrier();
+        WRES_STAMP(1)
         if (tile + Gt < ntiles) issue_tile(tile + Gt, Xs + ((it & 1) ^ 1) * xtile);
+        WRES_STAMP(2)
         const unsigned char* const XA = Xs + (it & 1) * xtile;
         const unsigned char* const XB = XA + (size_t)TP * RBA;
         f32x4 acc[NFW][FM];
@@ -191,11 +207,35 @@ __global__ __launch_bounds__(WR_NW * 64) void conv_wres_kernel(const ConvParams 
         };
         if (KA > 0) run_segment(XA, RBA, 0, KA >> 5, mA);
         run_segment(XB, RBB, KA >> 3, KB >> 5, mB);
+        WRES_STAMP(3)
         // ---- activation, residual, bf16 stores ----------------------------------------------------------------------------------
 #pragma unroll
         for (int f = 0; f < FM; ++f) {
             const int ri = (wm * FM + f) * 16 + fr;
             const long m = (long)tile * TPe + ri;
+            if (wide) {                                    // a fragment pair (2j, 2j+1) per step: one 16-byte store (and residual read) per lane; nfw is even
+#pragma unroll
+                for (int j = 0; j < NFW / 2; ++j) {
+                    const int co = n0 + wn * nfw * 16 + acc_channel(2 * j, fc, true);           // 8 channels from here: fragment 2j's four, then 2j+1's
+                    const bool ok = 2 * j < nfw && ri < TPe && m < p.M && co < p.Cout;          // (Cout % 32 == 0: a lane's eight channels exist together)
+                    float v[2][4];
+#pragma unroll
+                    for (int h = 0; h < 2; ++h) {
+#pragma unroll
+                        for (int q = 0; q < 4; ++q) v[h][q] = acc[2 * j + h][f][q];
+                        if (p.act == ACT_SILU && 2 * j < nfw) silu4_packed(v[h]);
+                    }
+                    if (HAS_RES) {
+                        uint2 rr[2];
+                        load_res_bf16x8((const __bf16*)p.res + m * p.res_stride + p.res_coff + co, ok, rr[0], rr[1]);
+                        add_res_bf16x4(v[0], rr[0]);
+                        add_res_bf16x4(v[1], rr[1]);
+                    }
+                    store_bf16x8(v[0], v[1], yrs, ok ? (unsigned)((m * p.y_stride + p.y_coff + co) * 2) : OOB);
+                }
+                continue;
+            }
+            // the 8-byte form: one store per fragment, weight rows in natural order
 #pragma unroll
             for (int i = 0; i < NFW; ++i) {
                 const int co = n0 + (wn * nfw + i) * 16 + fc * 4;
@@ -212,8 +252,23 @@ __global__ __launch_bounds__(WR_NW * 64) void conv_wres_kernel(const ConvParams 
                 __builtin_amdgcn_raw_buffer_store_b64(*(const __attribute__((ext_vector_type(2))) unsigned*)o, yrs, off, 0, 0);
             }
         }
+        WRES_STAMP(4)
     }
     wait_vmcnt<0>();
+    if constexpr (CLK) {
+        if (lane == 0)
+            for (int i = 0; i < 5; ++i) p.clk[((size_t)blockIdx.x * WR_NW + wave) * 5 + i] = clk[i];
+    }
+#undef WRES_STAMP
+}
+
+template <int TP, int WGN, bool HAS_RES>
+__global__ __launch_bounds__(WR_NW * 64) void conv_wres_kernel(const ConvParams p, const int NB, const int nblk, const int G, const int TPe) {
+    conv_wres_body<TP, WGN, HAS_RES, false>(p, NB, nblk, G, TPe);
+}
+template <int TP, int WGN>
+__global__ __launch_bounds__(WR_NW * 64) void conv_wres_clk_kernel(const ConvParams p, const int NB, const int nblk, const int G, const int TPe) {
+    conv_wres_body<TP, WGN, false, true>(p, NB, nblk, G, TPe);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------------------
@@ -254,9 +309,11 @@ static bool conv_wres_cfg_valid(const ConvParams& p, int c) {
 }
 
 template <int TP, int WGN, bool HAS_RES>
-static hipError_t launch_wres_t(const ConvParams& p, const WresCfg& k, hipStream_t st) {
+static hipError_t launch_wres_t(const ConvParams& p_in, const WresCfg& k, hipStream_t st) {
     int NB, nblk;
-    wres_blocks(p, k, NB, nblk);
+    wres_blocks(p_in, k, NB, nblk);
+    // paired stores: whole fragment pairs per wave (then NB, and every block's first channel, is a multiple of 32)
+    const ConvParams p = with_store_form(p_in, wres_paired<TP, WGN>() ? NB / (16 * WGN) : 1);
     const size_t sh = wres_lds(p, k);
     auto kern = conv_wres_kernel<TP, WGN, HAS_RES>;
     static size_t granted = 0;
@@ -267,11 +324,34 @@ static hipError_t launch_wres_t(const ConvParams& p, const WresCfg& k, hipStream
     int lanes8 = gmax / (8 * nblk);                                // tile lanes / 8
     if (lanes8 < 1) lanes8 = 1;
     while (lanes8 > 1 && (lanes8 - 1) * 8 >= ntiles) --lanes8;
+    if (const int cap = debug_max_workgroups()) while (lanes8 > 1 && lanes8 * 8 * nblk > cap) --lanes8;
     const int G = lanes8 * 8 * nblk;
     // equal pixels per tile lane: the rounds the full tiles need, then the tile height that fills exactly those rounds
     const long lanes = (long)lanes8 * 8;
     const int rounds = (int)((p.M + lanes * TP - 1) / (lanes * TP));
     const int TPe = tile_balance_enabled(2) ? (int)((p.M + lanes * rounds - 1) / (lanes * rounds)) : TP;
+    if constexpr (TP == 128 && WGN == 2 && !HAS_RES) {
+        static const bool clocks = env_on("YOLOP_WRES_CLOCKS");   // debug: per-phase s_memtime sums of the stamped instantiation
+        if (clocks) {
+            auto kc = conv_wres_clk_kernel<TP, WGN>;
+            static size_t granted_c = 0;
+            if (hipError_t e = allow_dynamic_lds((const void*)kc, sh, granted_c)) return e;
+            ConvParams q = p;
+            const size_t n = (size_t)G * WR_NW * 5;
+            if (hipMalloc((void**)&q.clk, n * 8) != hipSuccess) return hipErrorOutOfMemory;
+            hipLaunchKernelGGL(kc, dim3((unsigned)G), dim3(WR_NW * 64), sh, st, q, NB, nblk, G, TPe);
+            (void)hipStreamSynchronize(st);
+            std::vector<unsigned long long> h(n);
+            (void)hipMemcpy(h.data(), q.clk, n * 8, hipMemcpyDeviceToHost);
+            (void)hipFree(q.clk);
+            double s5[5] = {0, 0, 0, 0, 0};
+            for (size_t w = 0; w < n / 5; ++w)
+                for (int i = 0; i < 5; ++i) s5[i] += (double)h[w * 5 + i];
+            fprintf(stderr, "[wres clocks] %s G=%d tiles=%d  %s stores  per-wave mean cycles: prologue %.0f  wait+barrier %.0f  issue %.0f  k loop %.0f  epilogue %.0f\n",
+                    k.name, G, (p.M + TPe - 1) / TPe, p.wide ? "16-byte" : "8-byte", s5[0] / (n / 5), s5[1] / (n / 5), s5[2] / (n / 5), s5[3] / (n / 5), s5[4] / (n / 5));
+            return hipGetLastError();
+        }
+    }
     hipLaunchKernelGGL(kern, dim3((unsigned)G), dim3(WR_NW * 64), sh, st, p, NB, nblk, G, TPe);
     return hipGetLastError();
 }

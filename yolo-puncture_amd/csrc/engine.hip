@@ -760,6 +760,7 @@ static C2fParams c2f_params(const yp_engine& e, const Op& o) {
     p.shortcut = m2.res.t >= 0 ? 1 : 0;
     p.w3 = w3.d_w; p.bias3 = w3.d_b; p.act3 = o.act; p.Kpad3 = w3.Kpad; p.Cout = o.out.C; p.w3_bytes = w3.mat_bytes;
     p.y = to.ptr; p.y_stride = to.C; p.y_coff = o.out.coff; p.y_bytes = to.bytes;
+    p.wide = (e.dtype == DT_BF16 && !to.f32 && !e.narrow_store) ? 1 : 0;          // asked for; the launcher decides (wide_store_ok)
     // the kernel's channel map: a = [coff, coff+C), b = the next C (the bottleneck's input and residual), c = the C after that
     if (m1.in.t != o.in.t || m1.in.coff != o.in.coff + p.C || m2.out.t != o.in.t || m2.out.coff != o.in.coff + 2 * p.C || o.in.C != 3 * p.C ||
         m1.k != 3 || m2.k != 3 || m1.s != 1 || m2.s != 1 || m1.out.C != p.C || m2.out.C != p.C || m1.res.t >= 0 ||
@@ -805,6 +806,7 @@ static PwSpParams pwsp_params(const yp_engine& e, const Op& o) {
     p.x = ti.ptr; p.x_stride = ti.C; p.x_coff = c1.in.coff; p.x_bytes = ti.bytes; p.B = e.pB; p.H = ti.H; p.W = ti.W; p.K = c1.in.C;
     p.w1 = w1.d_w; p.bias1 = w1.d_b; p.act1 = c1.act; p.Kpad1 = w1.Kpad; p.C1 = c1.out.C; p.w1_bytes = w1.mat_bytes;
     p.dbg = conv_debug_ablation();
+    p.wide = (e.dtype == DT_BF16 && !t1.f32 && !e.narrow_store) ? 1 : 0;          // asked for; the launcher decides (wide_store_ok)
     if (!pair || o.pw_store) { p.y1 = t1.ptr ? t1.ptr : (void*)1; p.y1_stride = t1.C; p.y1_coff = c1.out.coff; }
     if (!pair) {
         if (c1.res.t >= 0) { const TensorDesc& tr = e.tensors[c1.res.t]; p.res1 = tr.ptr ? tr.ptr : (const void*)1; p.res1_stride = tr.C; p.res1_coff = c1.res.coff; }
@@ -860,6 +862,7 @@ static DwPwParams dwpw_params(const yp_engine& e, const Op& c) {
     p.w_pw = wp.d_w; p.Kpad = wp.Kpad; p.wpw_bytes = wp.mat_bytes; p.b_pw = wp.d_b; p.act_pw = c.act;
     p.y = to.ptr; p.y_stride = to.C; p.y_coff = c.out.coff; p.y_bytes = to.bytes; p.Cout = c.out.C;
     p.out_f32 = (to.f32 && e.dtype == DT_BF16) ? 1 : 0;
+    p.wide = (e.dtype == DT_BF16 && !p.out_f32 && !e.narrow_store) ? 1 : 0;      // asked for; the launcher decides (wide_store_ok)
     return p;
 }
 
@@ -2633,6 +2636,8 @@ int yp_debug_last_store_form(void) {
     store_form_watched().store(true);       // launches record their form from the first call on
     return last_store_form().exchange(-1);
 }
+
+int yp_debug_max_workgroups(int n) { return debug_max_workgroups_ref().exchange(n > 0 ? n : 0); }
 
 int yp_debug_op_cfg(const yp_engine* e, int i, int* cfg) {
     if (!e || i < 0 || i >= (int)e->ops.size() || !cfg) return fail(YP_ERR_ARG, "bad argument");

@@ -58,6 +58,10 @@ __global__ __launch_bounds__(PS_NT) void pwsp_kernel(const PwSpParams p) {
     const int fr = lane & 15, fc = lane >> 4;
     const int HW = p.H * p.W;
     const int nsl = p.C1 / NS;
+    // paired channel order (kernel_util.h): weight rows, bias, residual and the stores to y1 - the plain form only: with a spatial stage behind
+    // the epilogue the second epilogue measured no gain (<64,1> 37.1 -> 36.7 us in the kernel trace, inside its spread) or a loss (<64,2> 30.1 ->
+    // 30.9 us per op), so those instances are exactly what they were
+    const bool wide = SP == 0 && p.wide != 0;
 
     // image -> XCD: workgroup ids go round the 8 XCDs, so the slices of one image take ids of one residue class and share an L2
     int b, sl;
@@ -112,7 +116,7 @@ __global__ __launch_bounds__(PS_NT) void pwsp_kernel(const PwSpParams p) {
         const int row = s_ >> 3, pc = s_ & 7;
         const int c = pc ^ ((row >> 1) & 7);
         w_kc = c * 8;
-        wconst = (wave < W_INSTR) ? (unsigned)(((n0 + row) * p.Kpad1 + c * 8) * 2) : OOB;
+        wconst = (wave < W_INSTR) ? (unsigned)(((n0 + weight_row_channel(row, wide)) * p.Kpad1 + c * 8) * 2) : OOB;
     }
     auto kbyte = [&](int kt) { return (unsigned)(kt * BK) * 2u; };
     auto issue_A = [&](int kt) {
@@ -137,7 +141,7 @@ __global__ __launch_bounds__(PS_NT) void pwsp_kernel(const PwSpParams p) {
     f32x4 acc[FN][PS_MF];
 #pragma unroll
     for (int a = 0; a < FN; ++a) {
-        const float4 b4 = *(const float4*)(p.bias1 + n0 + a * 16 + fc * 4);     // bias rides in the accumulator
+        const float4 b4 = *(const float4*)(p.bias1 + n0 + acc_channel(a, fc, wide));     // bias rides in the accumulator
 #pragma unroll
         for (int f = 0; f < PS_MF; ++f) acc[a][f] = f32x4{b4.x, b4.y, b4.z, b4.w};
     }
@@ -197,6 +201,30 @@ __global__ __launch_bounds__(PS_NT) void pwsp_kernel(const PwSpParams p) {
         const int m = (wave + PS_NW * f) * 16 + fr;
         const bool ok = m < HW;
         const int py = ok ? m / p.W : 0, px = ok ? m - py * p.W : 0;
+        if (wide) {                                        // a fragment pair (a, a+1) per step: one 16-byte store (and residual read) per lane
+#pragma unroll
+            for (int a = 0; a + 1 < FN; a += 2) {
+                const int co = acc_channel(a, fc, true);   // 8 channels from here: fragment a's four, then a+1's
+                float v[2][4];
+#pragma unroll
+                for (int h = 0; h < 2; ++h) {
+#pragma unroll
+                    for (int q = 0; q < 4; ++q) v[h][q] = acc[a + h][f][q];
+                    if (p.act1 == ACT_SILU) silu4_packed(v[h]);
+                }
+                if (SP == 0 && p.res1) {
+                    uint2 rr[2];
+                    load_res_bf16x8((const __bf16*)p.res1 + (size_t)(b * HW + m) * p.res1_stride + p.res1_coff + n0 + co, ok, rr[0], rr[1]);
+                    add_res_bf16x4(v[0], rr[0]);
+                    add_res_bf16x4(v[1], rr[1]);
+                }
+                __attribute__((aligned(16))) __bf16 o[8] = {(__bf16)v[0][0], (__bf16)v[0][1], (__bf16)v[0][2], (__bf16)v[0][3],
+                                                            (__bf16)v[1][0], (__bf16)v[1][1], (__bf16)v[1][2], (__bf16)v[1][3]};
+                if (ok && p.y1) *(uint4*)((__bf16*)p.y1 + (size_t)(b * HW + m) * p.y1_stride + p.y1_coff + n0 + co) = *(const uint4*)o;
+            }
+            continue;
+        }
+        // the 8-byte form: one store per fragment, weight rows in natural order
 #pragma unroll
         for (int a = 0; a < FN; ++a) {
             float v[4] = {acc[a][f][0], acc[a][f][1], acc[a][f][2], acc[a][f][3]};
@@ -400,7 +428,9 @@ const char* pwsp_kernel_name(const PwSpParams& p) {
 }
 
 template <int NS, int SP>
-static hipError_t launch_pwsp_t(const PwSpParams& p, hipStream_t st) {
+static hipError_t launch_pwsp_t(const PwSpParams& p_in, hipStream_t st) {
+    PwSpParams p = p_in;                                // the form of the stores to y1: the plain form has both, the spatial forms the 8-byte one
+    p.wide = (SP == 0 && p_in.y1 && wide_store_ok(p_in.wide, NS / 16, p_in.C1, p_in.y1_stride, p_in.y1_coff, false, p_in.res1, p_in.res1_stride, p_in.res1_coff)) ? 1 : 0;
     const size_t sh = pwsp_lds_bytes(p, NS);
     auto kern = pwsp_kernel<NS, SP>;
     static size_t granted = 0;
