@@ -143,7 +143,6 @@ constexpr int A_MAXW = 8;           // waves per workgroup
 __device__ __forceinline__ int vswz(int row) { return ((row >> 1) & 3) << 1; }      // V image: 128-B rows, 32-B pairs swizzled
 
 __global__ __launch_bounds__(A_MAXW * 64) void attention_mfma_kernel(const AttnParams p, const int tiles_per_wg, const unsigned qkv_bytes) {
-    constexpr unsigned OOB = 0x80000000u;
     __shared__ __attribute__((aligned(1024))) unsigned char lds[A_NPAD * 64 + A_NPAD * 128];
     unsigned char* const Ks = lds;                             // [A_NPAD keys][32] bf16, chunk-swizzled
     unsigned char* const Vs = lds + A_NPAD * 64;               // [A_NPAD keys][64] bf16, pair-swizzled
@@ -159,7 +158,7 @@ __global__ __launch_bounds__(A_MAXW * 64) void attention_mfma_kernel(const AttnP
     const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void*)p.qkv, 0, (int)qkv_bytes, 0x00020000);
     for (int ii = wave; ii < A_NPAD / 16; ii += nw) {          // 16 keys x 64 B per instruction
         const int key = ii * 16 + (lane >> 2), c = (lane & 3) ^ cswz64(key);
-        const unsigned voff = (key < p.N) ? (unsigned)((base_el + (size_t)key * p.q_stride + p.kd + c * 8) * 2) : OOB;
+        const unsigned voff = (key < p.N) ? (unsigned)((base_el + (size_t)key * p.q_stride + p.kd + c * 8) * 2) : kBufferOOB;
         __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (lds_void*)(Ks + ii * 1024), 16, voff, 0, 0, 0);
     }
     // the first tile's query fragment, issued between the K and V rows so that the counted wait below covers it (an asm load: the
@@ -177,7 +176,7 @@ __global__ __launch_bounds__(A_MAXW * 64) void attention_mfma_kernel(const AttnP
     for (int k = 0; k < NV; ++k) {                              // 8 keys x 128 B per instruction
         const int ii = min(wave + k * A_MAXW, A_NPAD / 8 - 1);
         const int key = ii * 8 + (lane >> 3), c = (lane & 7) ^ vswz(key);
-        const unsigned voff = (key < p.N) ? (unsigned)((base_el + (size_t)key * p.q_stride + 2 * p.kd + c * 8) * 2) : OOB;
+        const unsigned voff = (key < p.N) ? (unsigned)((base_el + (size_t)key * p.q_stride + 2 * p.kd + c * 8) * 2) : kBufferOOB;
         __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (lds_void*)(Vs + ii * 1024), 16, voff, 0, 0, 0);
     }
     // K (and the query fragment) first: the V rows may still be in flight while the first tile's scores and softmax run (they are

@@ -28,7 +28,6 @@ constexpr int CF_W33 = 9 * 32 * 64, CF_W3 = 3 * 64 * 64;
 constexpr int CF_LDS = 2 * CF_AB + CF_TS + CF_CS + 2 * CF_W33 + CF_W3 + 512;    // 131584 (+ the three bias vectors)
 
 __global__ __launch_bounds__(CF_NW * 64) void c2f_fused_kernel(const C2fParams p, const int tiles_h, const int tiles_w, const int G) {
-    constexpr unsigned OOB = 0x80000000u;
     extern __shared__ __attribute__((aligned(1024))) unsigned char smem[];
     unsigned char* const ABs = smem;                          // 2 x [240 px][64 ch]   (a = ch 0..31, b = ch 32..63)
     unsigned char* const Ts = ABs + 2 * CF_AB;                // [180 px][32 ch]
@@ -69,7 +68,7 @@ __global__ __launch_bounds__(CF_NW * 64) void c2f_fused_kernel(const C2fParams p
                 const int py = row / CF_PW, px = row - py * CF_PW;
                 const int iy = th * CF_TH - 2 + py, ix = tw * 16 - 2 + px;
                 const bool ok = tv && (unsigned)iy < (unsigned)p.H && (unsigned)ix < (unsigned)p.W;
-                const unsigned voff = ok ? (unsigned)((((b * p.H + iy) * p.W + ix) * p.x_stride + p.x_coff + c8 * 8) * 2) : OOB;
+                const unsigned voff = ok ? (unsigned)((((b * p.H + iy) * p.W + ix) * p.x_stride + p.x_coff + c8 * 8) * 2) : kBufferOOB;
                 __builtin_amdgcn_raw_ptr_buffer_load_lds(xrs, (lds_void*)(dst + ii * 1024), 16, voff, 0, 0, 0);
             }
         }
@@ -218,13 +217,10 @@ __global__ __launch_bounds__(CF_NW * 64) void c2f_fused_kernel(const C2fParams p
                 float v[4] = {acc[j][0], acc[j][1], acc[j][2], acc[j][3]};
                 if (p.act2 == ACT_SILU) silu4_packed(v);
                 if (p.shortcut) {
-                    const unsigned lo = (unsigned)rr[j], hi = (unsigned)(rr[j] >> 32);
-                    v[0] += __uint_as_float(lo << 16); v[1] += __uint_as_float(lo & 0xffff0000u);
-                    v[2] += __uint_as_float(hi << 16); v[3] += __uint_as_float(hi & 0xffff0000u);
+                    add_res_bf16x4(v, make_uint2((unsigned)rr[j], (unsigned)(rr[j] >> 32)));
                 }
                 const int q = (wq + 4 * j) * 16 + fr;
-                __attribute__((aligned(8))) __bf16 o[4] = {(__bf16)v[0], (__bf16)v[1], (__bf16)v[2], (__bf16)v[3]};
-                lds_write8(Cs + q * 64 + (((cf * 2 + (fc >> 1)) ^ cswz64(q)) * 16) + (fc & 1) * 8, *(const unsigned long long*)o);
+                lds_write8(Cs + q * 64 + (((cf * 2 + (fc >> 1)) ^ cswz64(q)) * 16) + (fc & 1) * 8, pack_bf16x4(v));
             }
         }
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
@@ -272,7 +268,7 @@ __global__ __launch_bounds__(CF_NW * 64) void c2f_fused_kernel(const C2fParams p
                         if (p.act3 == ACT_SILU) silu4_packed(v[h]);
                     }
                     const int co = cf * 32 + acc_channel(0, fc, true);                     // 8 channels from here: fragment 0's four, then fragment 1's
-                    store_bf16x8(v[0], v[1], yrs, pix_ok ? (m * (unsigned)p.y_stride + (unsigned)(p.y_coff + co)) * 2u : OOB);
+                    store_bf16x8(v[0], v[1], yrs, pix_ok ? (m * (unsigned)p.y_stride + (unsigned)(p.y_coff + co)) * 2u : kBufferOOB);
                     continue;
                 }
                 // the 8-byte form: one store per fragment, weight rows in natural order
@@ -281,9 +277,8 @@ __global__ __launch_bounds__(CF_NW * 64) void c2f_fused_kernel(const C2fParams p
                     float v[4] = {acc[j][a][0], acc[j][a][1], acc[j][a][2], acc[j][a][3]};
                     if (p.act3 == ACT_SILU) silu4_packed(v);
                     const int co = (cf * 2 + a) * 16 + fc * 4;
-                    const unsigned off = pix_ok ? (m * (unsigned)p.y_stride + (unsigned)(p.y_coff + co)) * 2u : OOB;
-                    __attribute__((aligned(8))) __bf16 o[4] = {(__bf16)v[0], (__bf16)v[1], (__bf16)v[2], (__bf16)v[3]};
-                    __builtin_amdgcn_raw_buffer_store_b64(*(const __attribute__((ext_vector_type(2))) unsigned*)o, yrs, off, 0, 0);
+                    const unsigned off = pix_ok ? (m * (unsigned)p.y_stride + (unsigned)(p.y_coff + co)) * 2u : kBufferOOB;
+                    store_bf16x4(v, yrs, off);
                 }
             }
         }

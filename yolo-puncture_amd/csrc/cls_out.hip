@@ -20,7 +20,6 @@ constexpr int CO_MAXNF = 8;             // up to 128 classes
 template <int TP, int NF>
 __global__ __launch_bounds__(CO_NW * 64) void cls_out_kernel(const ClsOutParams p, const int G, const int TPe) {
     constexpr int FM = TP / (16 * CO_NW);                          // pixel fragments per wave
-    constexpr unsigned OOB = 0x80000000u;
     extern __shared__ __attribute__((aligned(1024))) unsigned char smem[];
     const int RB = p.K * 2;                                        // bytes per row (a multiple of 128)
     const int CPR = RB >> 4;                                       // 16-byte chunks per row
@@ -43,7 +42,7 @@ __global__ __launch_bounds__(CO_NW * 64) void cls_out_kernel(const ClsOutParams 
             const int r = s / CPR, pc = s - r * CPR;
             const int c = pc ^ (r & 7);
             const bool ok = r < nrows && row0 + r < row_lim;
-            const unsigned voff = ok ? (unsigned)(((row0 + r) * stride_el + coff + c * 8) * 2) : OOB;
+            const unsigned voff = ok ? (unsigned)(((row0 + r) * stride_el + coff + c * 8) * 2) : kBufferOOB;
             __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (lds_void*)(dst + ii * 1024), 16, voff, 0, 0, 0);
         }
     };

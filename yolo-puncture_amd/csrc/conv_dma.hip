@@ -31,8 +31,6 @@ __global__ __launch_bounds__(WGM * WGN * 64) void conv_dma_kernel(const ConvPara
     constexpr int WM = BM / WGM, WN = BN / WGN, FM = WM / 16, FN = WN / 16;
     constexpr int KSUB = BK / 32;
     static_assert((NW == 4 || NW == 8) && A_INSTR % NW == 0 && A_IPW >= 1, "tile/wave layout");
-    constexpr unsigned OOB = 0x80000000u;
-
     extern __shared__ __attribute__((aligned(1024))) unsigned char smem[];   // NS stages + 1 KiB dump slot
 
     const int tid = threadIdx.x, lane = tid & 63;
@@ -78,7 +76,7 @@ __global__ __launch_bounds__(WGM * WGN * 64) void conv_dma_kernel(const ConvPara
         const int s = ii * 64 + lane;
         const int row = s / CPR, pc = s - row * CPR;
         const int c = pc ^ cswz<BK>(row);
-        wconst[j] = (ii < W_INSTR) ? (unsigned)(((n0 + row) * p.Kpad + c * 8) * 2) : OOB;
+        wconst[j] = (ii < W_INSTR) ? (unsigned)(((n0 + row) * p.Kpad + c * 8) * 2) : kBufferOOB;
     }
 
     // ---- scalar k-step state for the NEXT stage to issue -----------------------------------------------------
@@ -88,14 +86,14 @@ __global__ __launch_bounds__(WGM * WGN * 64) void conv_dma_kernel(const ConvPara
         unsigned char* sbase = smem + slot * SB;
 #pragma unroll
         for (int j = 0; j < A_IPW; ++j) {
-            const unsigned voff = ((amask[j] >> is_tap) & 1u) ? (aconst[j] + tapoff) : OOB;
+            const unsigned voff = ((amask[j] >> is_tap) & 1u) ? (aconst[j] + tapoff) : kBufferOOB;
             __builtin_amdgcn_raw_ptr_buffer_load_lds(xrs, (lds_void*)(sbase + (wave * A_IPW + j) * 1024), 16, voff, 0, 0, 0);
         }
 #pragma unroll
         for (int j = 0; j < W_IPW; ++j) {
             const int ii = wave * W_IPW + j;
             unsigned char* dst = (ii < W_INSTR) ? (sbase + BM * RB + ii * 1024) : (smem + NS * SB);
-            const unsigned voff = (wconst[j] == OOB || is_k0 >= p.Kpad) ? OOB : (wconst[j] + (unsigned)is_k0 * 2u);
+            const unsigned voff = (wconst[j] == kBufferOOB || is_k0 >= p.Kpad) ? kBufferOOB : (wconst[j] + (unsigned)is_k0 * 2u);
             __builtin_amdgcn_raw_ptr_buffer_load_lds(wrs, (lds_void*)dst, 16, voff, 0, 0, 0);
         }
         // advance by BK k
@@ -189,8 +187,7 @@ __global__ __launch_bounds__(WGM * WGN * 64) void conv_dma_kernel(const ConvPara
                 const __bf16* rp = (const __bf16*)p.res + (size_t)m * p.res_stride + p.res_coff + co;
                 if (vec_ok) {
                     const uint2 rr = *(const uint2*)rp;
-                    v[0] += __uint_as_float(rr.x << 16); v[1] += __uint_as_float(rr.x & 0xffff0000u);
-                    v[2] += __uint_as_float(rr.y << 16); v[3] += __uint_as_float(rr.y & 0xffff0000u);
+                    add_res_bf16x4(v, rr);
                 } else {
 #pragma unroll
                     for (int r = 0; r < 4; ++r)
@@ -207,8 +204,7 @@ __global__ __launch_bounds__(WGM * WGN * 64) void conv_dma_kernel(const ConvPara
             } else {
                 __bf16* yp = (__bf16*)p.y + opix * p.y_stride + p.y_coff + co;
                 if (vec_ok) {
-                    __attribute__((aligned(8))) __bf16 o[4] = {(__bf16)v[0], (__bf16)v[1], (__bf16)v[2], (__bf16)v[3]};
-                    *(uint2*)yp = *(const uint2*)o;
+                    *(u32x2*)yp = pack_bf16x4(v);
                 } else {
 #pragma unroll
                     for (int r = 0; r < 4; ++r)

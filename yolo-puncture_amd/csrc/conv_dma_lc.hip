@@ -34,7 +34,6 @@ __global__ __launch_bounds__((WGM * WGN + NL) * 64) void conv_dma_lc_kernel(cons
     constexpr int WM = BM / WGM, WN = BN / WGN, FM = WM / 16, FN = WN / 16;
     constexpr int KSUB = BK / 32;
     static_assert(MAXP >= 1 && (NS - 2) * MAXP < 64, "vmcnt immediate");
-    constexpr unsigned OOB = 0x80000000u;
 
     extern __shared__ __attribute__((aligned(1024))) unsigned char smem[];
 
@@ -112,10 +111,10 @@ __global__ __launch_bounds__((WGM * WGN + NL) * 64) void conv_dma_lc_kernel(cons
             for (int j = 0; j < MAXP; ++j) {
                 const int q = lw + j * NL;              // wave-uniform
                 if (q < A_INSTR) {
-                    const unsigned voff = ((pmask[j] >> is_tap) & 1u) ? ((src2 ? pconst2[j] : pconst[j]) + tapoff) : OOB;
+                    const unsigned voff = ((pmask[j] >> is_tap) & 1u) ? ((src2 ? pconst2[j] : pconst[j]) + tapoff) : kBufferOOB;
                     __builtin_amdgcn_raw_ptr_buffer_load_lds(src2 ? xrs2 : xrs, (lds_void*)(sbase + q * 1024), 16, voff, 0, 0, 0);
                 } else if (q < PIECES) {
-                    const unsigned voff = live ? (pconst[j] + (unsigned)(it_kt * BK) * 2u) : OOB;
+                    const unsigned voff = live ? (pconst[j] + (unsigned)(it_kt * BK) * 2u) : kBufferOOB;
                     __builtin_amdgcn_raw_ptr_buffer_load_lds(wrs, (lds_void*)(sbase + BM * RB + (q - A_INSTR) * 1024), 16, voff, 0, 0, 0);
                 }
             }
@@ -209,9 +208,7 @@ __global__ __launch_bounds__((WGM * WGN + NL) * 64) void conv_dma_lc_kernel(cons
 #pragma unroll
                 for (int a = 0; a < FN; ++a) {
                     const int co = n0 + wn * WN + a * 16 + fc * 4;
-                    rres[b][a] = (m < p.M && co < p.Cout)
-                                     ? *(const uint2*)((const __bf16*)p.res + (size_t)m * p.res_stride + p.res_coff + co)
-                                     : make_uint2(0u, 0u);
+                    rres[b][a] = load_res_bf16x4((const __bf16*)p.res + (size_t)m * p.res_stride + p.res_coff + co, m < p.M && co < p.Cout);
                 }
             }
         }
@@ -224,19 +221,10 @@ __global__ __launch_bounds__((WGM * WGN + NL) * 64) void conv_dma_lc_kernel(cons
                 const bool ok = (m < p.M) && (co < p.Cout);
                 float v[4] = {acc[a][b][0], acc[a][b][1], acc[a][b][2], acc[a][b][3]};
                 if (p.act == ACT_SILU) silu4_packed(v);
-                if (HAS_RES) {
-                    const uint2 rr = rres[b][a];
-                    v[0] += __uint_as_float(rr.x << 16); v[1] += __uint_as_float(rr.x & 0xffff0000u);
-                    v[2] += __uint_as_float(rr.y << 16); v[3] += __uint_as_float(rr.y & 0xffff0000u);
-                }
-                if (OUT_F32) {
-                    const unsigned off = ok ? ((unsigned)m * (unsigned)p.y_stride + (unsigned)(p.y_coff + co)) * 4u : OOB;
-                    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(__attribute__((ext_vector_type(4))) unsigned, make_float4(v[0], v[1], v[2], v[3])), yrs, off, 0, 0);
-                } else {
-                    const unsigned off = ok ? ((unsigned)m * (unsigned)p.y_stride + (unsigned)(p.y_coff + co)) * 2u : OOB;
-                    __attribute__((aligned(8))) __bf16 o[4] = {(__bf16)v[0], (__bf16)v[1], (__bf16)v[2], (__bf16)v[3]};
-                    __builtin_amdgcn_raw_buffer_store_b64(*(const __attribute__((ext_vector_type(2))) unsigned*)o, yrs, off, 0, 0);
-                }
+                if (HAS_RES) add_res_bf16x4(v, rres[b][a]);
+                const unsigned elem = (unsigned)m * (unsigned)p.y_stride + (unsigned)(p.y_coff + co);
+                if (OUT_F32) store_f32x4(v, yrs, ok ? elem * 4u : kBufferOOB);
+                else store_bf16x4(v, yrs, ok ? elem * 2u : kBufferOOB);
             }
         }
     }

@@ -36,8 +36,6 @@ __global__ __launch_bounds__(WGM * WGN * 64) void conv_dma_p_kernel(const ConvPa
     static_assert((NW == 4 || NW == 8) && A_INSTR % NW == 0 && A_IPW >= 1, "tile/wave layout");
     static_assert((NS - 2) * LPW + (NS - 1) * S < 64, "vmcnt immediate");
     static_assert(!PIPE || NS >= 4, "the pipelined form gives up one stage of prefetch distance");
-    constexpr unsigned OOB = 0x80000000u;
-
     extern __shared__ __attribute__((aligned(1024))) unsigned char smem[];
 
     const int tid = threadIdx.x, lane = tid & 63;
@@ -125,7 +123,7 @@ __global__ __launch_bounds__(WGM * WGN * 64) void conv_dma_p_kernel(const ConvPa
         const int s = ii * 64 + lane;
         const int row = s / CPR, pc = s - row * CPR;
         const int c = pc ^ cswz<BK>(row);
-        wconst[j] = (ii < W_INSTR) ? (unsigned)(((n0 + row) * p.Kpad + c * 8) * 2) : OOB;
+        wconst[j] = (ii < W_INSTR) ? (unsigned)(((n0 + row) * p.Kpad + c * 8) * 2) : kBufferOOB;
     }
     const int nk = p.Kpad / BK;
     int it_tile = j0, it_kt = 0, it_slot = 0;
@@ -138,7 +136,7 @@ __global__ __launch_bounds__(WGM * WGN * 64) void conv_dma_p_kernel(const ConvPa
         const __amdgpu_buffer_rsrc_t ars = src2 ? xrs2 : xrs;
 #pragma unroll
         for (int j = 0; j < A_IPW; ++j) {
-            const unsigned voff = ((amask[j] >> is_tap) & 1u) ? ((src2 ? aconst2[j] : aconst[j]) + tapoff) : OOB;
+            const unsigned voff = ((amask[j] >> is_tap) & 1u) ? ((src2 ? aconst2[j] : aconst[j]) + tapoff) : kBufferOOB;
             __builtin_amdgcn_raw_ptr_buffer_load_lds(ars, (lds_void*)(sbase + (wave * A_IPW + j) * 1024), 16, voff, 0, 0, 0);
         }
         const bool live = it_tile < mtiles;
@@ -147,7 +145,7 @@ __global__ __launch_bounds__(WGM * WGN * 64) void conv_dma_p_kernel(const ConvPa
         for (int j = 0; j < W_IPW; ++j) {
             const int ii = wave * W_IPW + j;
             unsigned char* dst = (ii < W_INSTR) ? (sbase + BM * RB + ii * 1024) : (smem + NS * SB);
-            const unsigned voff = (wconst[j] == OOB || !live) ? OOB : (wconst[j] + (unsigned)(it_kt * BK) * 2u);
+            const unsigned voff = (wconst[j] == kBufferOOB || !live) ? kBufferOOB : (wconst[j] + (unsigned)(it_kt * BK) * 2u);
             __builtin_amdgcn_raw_ptr_buffer_load_lds(wrs, (lds_void*)dst, 16, voff, 0, 0, 0);
         }
         it_slot = (it_slot + 1 == NS) ? 0 : it_slot + 1;
@@ -229,16 +227,14 @@ __global__ __launch_bounds__(WGM * WGN * 64) void conv_dma_p_kernel(const ConvPa
                 if (p.act == ACT_SILU) silu4_packed(v);
                 if (HAS_RES) {
                     const uint2 rr = rres[b][a];
-                    v[0] += __uint_as_float(rr.x << 16); v[1] += __uint_as_float(rr.x & 0xffff0000u);
-                    v[2] += __uint_as_float(rr.y << 16); v[3] += __uint_as_float(rr.y & 0xffff0000u);
+                    add_res_bf16x4(v, rr);
                 }
                 if (OUT_F32) {
-                    const unsigned off = ok ? ((unsigned)m * (unsigned)p.y_stride + (unsigned)(p.y_coff + co)) * 4u : OOB;
-                    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(__attribute__((ext_vector_type(4))) unsigned, make_float4(v[0], v[1], v[2], v[3])), yrs, off, 0, 0);
+                    const unsigned off = ok ? ((unsigned)m * (unsigned)p.y_stride + (unsigned)(p.y_coff + co)) * 4u : kBufferOOB;
+                    store_f32x4(v, yrs, off);
                 } else {
-                    const unsigned off = ok ? ((unsigned)m * (unsigned)p.y_stride + (unsigned)(p.y_coff + co)) * 2u : OOB;
-                    __attribute__((aligned(8))) __bf16 o[4] = {(__bf16)v[0], (__bf16)v[1], (__bf16)v[2], (__bf16)v[3]};
-                    __builtin_amdgcn_raw_buffer_store_b64(*(const __attribute__((ext_vector_type(2))) unsigned*)o, yrs, off, 0, 0);
+                    const unsigned off = ok ? ((unsigned)m * (unsigned)p.y_stride + (unsigned)(p.y_coff + co)) * 2u : kBufferOOB;
+                    store_bf16x4(v, yrs, off);
                 }
             }
         }

@@ -34,7 +34,6 @@ __global__ __launch_bounds__(NW * 64) void conv_dwpw_kernel(const DwPwParams p, 
     constexpr int NSH = 3;
     constexpr int WM = BM / WGM, WN = BN / WGN, FM = WM / 16, FN = WN / 16;
     constexpr int S = FM * FN;
-    constexpr unsigned OOB = 0x80000000u;
     static_assert(LH + 2 * S < 64, "vmcnt immediate");
 
     extern __shared__ __attribute__((aligned(1024))) unsigned char smem[];
@@ -92,7 +91,7 @@ __global__ __launch_bounds__(NW * 64) void conv_dwpw_kernel(const DwPwParams p, 
             const int s = ii * 64 + lane;
             const int row = s >> 2, c8 = s & 3;
             const int ch = row / 9, tap = row - ch * 9;
-            const unsigned voff = (row < nchunk * 9) ? (unsigned)((tap * p.C + ch * 32 + c8 * 8) * 2) : OOB;
+            const unsigned voff = (row < nchunk * 9) ? (unsigned)((tap * p.C + ch * 32 + c8 * 8) * 2) : kBufferOOB;
             __builtin_amdgcn_raw_ptr_buffer_load_lds(drs, (lds_void*)(Wdw + ii * 1024), 16, voff, 0, 0, 0);
         }
         const int b_instr = (p.C * 4 + 1023) / 1024;
@@ -113,7 +112,7 @@ __global__ __launch_bounds__(NW * 64) void conv_dwpw_kernel(const DwPwParams p, 
             }
             if (wave == 0) {                                           // bias: 512 bytes, bytes past C3 * 4 come back as zeros (descriptor bound)
                 const __amdgpu_buffer_rsrc_t b3rs = __builtin_amdgcn_make_buffer_rsrc((void*)p.b3, 0, (int)(p.C3 * 4), 0x00020000);
-                __builtin_amdgcn_raw_ptr_buffer_load_lds(b3rs, (lds_void*)B3s, 16, (unsigned)(lane * 16) < 512u ? (unsigned)(lane * 16) : OOB, 0, 0, 0);
+                __builtin_amdgcn_raw_ptr_buffer_load_lds(b3rs, (lds_void*)B3s, 16, (unsigned)(lane * 16) < 512u ? (unsigned)(lane * 16) : kBufferOOB, 0, 0, 0);
             }
         }
     }
@@ -135,7 +134,7 @@ __global__ __launch_bounds__(NW * 64) void conv_dwpw_kernel(const DwPwParams p, 
             const int hy = hp / 18, hx = hp - hy * 18;
             const int hi = h0 - 1 + hy, wi = w0 - 1 + hx;
             const bool ok = (tile < num_tiles) && (ii < H_INSTR) && (hp < HP) && ((unsigned)hi < (unsigned)p.H) && ((unsigned)wi < (unsigned)p.W);
-            hconst[j] = ok ? (unsigned)((((b * p.H + hi) * p.W + wi) * p.x_stride + p.x_coff) * 2 + c8 * 16) : OOB;
+            hconst[j] = ok ? (unsigned)((((b * p.H + hi) * p.W + wi) * p.x_stride + p.x_coff) * 2 + c8 * 16) : kBufferOOB;
         }
     };
     int it_tile = j0, it_c = 0, it_slot = 0;
@@ -146,7 +145,7 @@ __global__ __launch_bounds__(NW * 64) void conv_dwpw_kernel(const DwPwParams p, 
 #pragma unroll
         for (int j = 0; j < LH; ++j) {
             const int ii = wave * LH + j;
-            const unsigned voff = (hconst[j] == OOB) ? OOB : hconst[j] + coff;
+            const unsigned voff = (hconst[j] == kBufferOOB) ? kBufferOOB : hconst[j] + coff;
             __builtin_amdgcn_raw_ptr_buffer_load_lds(xrs, (lds_void*)((ii < H_INSTR) ? dst + ii * 1024 : dump), 16, voff, 0, 0, 0);
         }
         it_slot = (it_slot + 1 == NSH) ? 0 : it_slot + 1;
@@ -215,13 +214,10 @@ __global__ __launch_bounds__(NW * 64) void conv_dwpw_kernel(const DwPwParams p, 
             const int px = wave * 16 + fr;
 #pragma unroll
             for (int h = 0; h < 2; ++h) {
-                __attribute__((aligned(8))) __bf16 o[4];
                 float sv[4] = {dacc[h][0], dacc[h][1], dacc[h][2], dacc[h][3]};
                 if (p.act_dw == ACT_SILU) silu4_packed(sv);
-#pragma unroll
-                for (int i = 0; i < 4; ++i) o[i] = (__bf16)sv[i];
                 const int c8 = 2 * h + (fc >> 1);
-                lds_write8(asl + px * 64 + ((c8 ^ cswz64(px)) * 16) + (fc & 1) * 8, *(const uint2*)o);
+                lds_write8(asl + px * 64 + ((c8 ^ cswz64(px)) * 16) + (fc & 1) * 8, pack_bf16x4(sv));
             }
         }
     };
@@ -271,18 +267,17 @@ __global__ __launch_bounds__(NW * 64) void conv_dwpw_kernel(const DwPwParams p, 
                 if (TAIL) {
                     // the activated tile stays on chip: bf16 (the rounding the materialised tensor would have had) into the third stage's
                     // pixel-operand image, chunk = 32 output channels of this stage = 32 k of the next
-                    __attribute__((aligned(8))) __bf16 o[4] = {(__bf16)v[0], (__bf16)v[1], (__bf16)v[2], (__bf16)v[3]};
+                    const u32x2 o = pack_bf16x4(v);
                     const int px = (wm * (WM / 16) + bb) * 16 + fr;
                     const int cch = wn * WN + a * 16 + fc * 4;               // channel inside the BN block
                     const int c8 = (cch >> 3) & 3;
-                    lds_write8(Ts + (size_t)(cch >> 5) * BM * 64 + px * 64 + ((c8 ^ cswz64(px)) * 16) + (fc & 1) * 8, *(const uint2*)o);
+                    lds_write8(Ts + (size_t)(cch >> 5) * BM * 64 + px * 64 + ((c8 ^ cswz64(px)) * 16) + (fc & 1) * 8, o);
                 } else if (OUT_F32) {
-                    const unsigned off = ok ? (m * (unsigned)p.y_stride + (unsigned)(p.y_coff + co)) * 4u : OOB;
-                    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(__attribute__((ext_vector_type(4))) unsigned, make_float4(v[0], v[1], v[2], v[3])), yrs, off, 0, 0);
+                    const unsigned off = ok ? (m * (unsigned)p.y_stride + (unsigned)(p.y_coff + co)) * 4u : kBufferOOB;
+                    store_f32x4(v, yrs, off);
                 } else {
-                    const unsigned off = ok ? (m * (unsigned)p.y_stride + (unsigned)(p.y_coff + co)) * 2u : OOB;
-                    __attribute__((aligned(8))) __bf16 o[4] = {(__bf16)v[0], (__bf16)v[1], (__bf16)v[2], (__bf16)v[3]};
-                    __builtin_amdgcn_raw_buffer_store_b64(*(const __attribute__((ext_vector_type(2))) unsigned*)o, yrs, off, 0, 0);
+                    const unsigned off = ok ? (m * (unsigned)p.y_stride + (unsigned)(p.y_coff + co)) * 2u : kBufferOOB;
+                    store_bf16x4(v, yrs, off);
                 }
             }
         }
@@ -324,14 +319,14 @@ __global__ __launch_bounds__(NW * 64) void conv_dwpw_kernel(const DwPwParams p, 
             const int co = f * 16 + fc * 4;
             const bool ok = pix_ok && f < nf3 && (co < p.C3);
             if (f < nf3 && co < p.C3) mx = fmaxf(mx, fmaxf(fmaxf(a3[f][0], a3[f][1]), fmaxf(a3[f][2], a3[f][3])));
-            const unsigned off = ok ? (m * (unsigned)p.y3_stride + (unsigned)(p.y3_coff + co)) * 4u : OOB;
+            const unsigned off = ok ? (m * (unsigned)p.y3_stride + (unsigned)(p.y3_coff + co)) * 4u : kBufferOOB;
             __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(__attribute__((ext_vector_type(4))) unsigned, make_float4(a3[f][0], a3[f][1], a3[f][2], a3[f][3])), y3rs, off, 0, 0);
         }
         mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
         mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
         {   // sigmoid(max logit) exactly as anchor_max_level_kernel forms it (head.hip): the key the top-k kernel reads
             const float sg = 1.0f / (1.0f + expf(-mx));
-            const unsigned off = (p.keys && pix_ok && fc == 0) ? m * 4u : OOB;
+            const unsigned off = (p.keys && pix_ok && fc == 0) ? m * 4u : kBufferOOB;
             __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(sg), krs, off, 0, 0);
         }
     };

@@ -35,7 +35,6 @@ __global__ __launch_bounds__(NW * 64, 2) void conv_dwpw_stream_kernel(const DwPw
     constexpr int NFW = 8 / NW;                                    // 16-channel output fragments per wave (pointwise stage)
     constexpr int NSLOT = NW == 8 ? 2 : 1;
     constexpr int NST = DS_TH * NFW;                               // stores per wave and tile
-    constexpr unsigned OOB = 0x80000000u;
     extern __shared__ __attribute__((aligned(1024))) unsigned char smem[];
     unsigned char* const Hs = smem;                                // 2 halo slots: pixel hp at hp * 256, channel c at c * 2
     unsigned char* const As = smem + NSLOT * DS_HB;                    // [128 px][256 B], 16-byte chunk q of pixel px at position q ^ (px & 15)
@@ -76,7 +75,7 @@ __global__ __launch_bounds__(NW * 64, 2) void conv_dwpw_stream_kernel(const DwPw
             const int hy = (int)(q >> 8), hx = (int)(q & 255u);
             const int hi = h0 + hy, wi = w0 + hx;
             const bool ok = tile < num_tiles && hp < DS_HP && (unsigned)hi < (unsigned)p.H && (unsigned)wi < (unsigned)p.W;
-            const unsigned voff = ok ? (unsigned)((((b * p.H + hi) * p.W + wi) * p.x_stride + p.x_coff + c * 8) * 2) : OOB;
+            const unsigned voff = ok ? (unsigned)((((b * p.H + hi) * p.W + wi) * p.x_stride + p.x_coff + c * 8) * 2) : kBufferOOB;
             __builtin_amdgcn_raw_ptr_buffer_load_lds(xrs, (lds_void*)(dst + ii * 1024), 16, voff, 0, 0, 0);
         }
     };
@@ -208,7 +207,7 @@ __global__ __launch_bounds__(NW * 64, 2) void conv_dwpw_stream_kernel(const DwPw
                         for (int q = 0; q < 4; ++q) v[h][q] = acc[2 * j + h][f][q];
                         if (p.act_pw == ACT_SILU) silu4_packed(v[h]);
                     }
-                    store_bf16x8(v[0], v[1], yrs, ok ? (unsigned)((((b * p.H + ho) * p.W + wo) * p.y_stride + p.y_coff + co) * 2) : OOB);
+                    store_bf16x8(v[0], v[1], yrs, ok ? (unsigned)((((b * p.H + ho) * p.W + wo) * p.y_stride + p.y_coff + co) * 2) : kBufferOOB);
                 }
             }
             continue;
@@ -223,9 +222,8 @@ __global__ __launch_bounds__(NW * 64, 2) void conv_dwpw_stream_kernel(const DwPw
                 const bool ok = ho < p.H && wo < p.W && co < p.Cout;   // (Cout % 4 == 0: a lane's four channels exist together)
                 float v[4] = {acc[i][f][0], acc[i][f][1], acc[i][f][2], acc[i][f][3]};
                 if (p.act_pw == ACT_SILU) silu4_packed(v);
-                __attribute__((aligned(8))) __bf16 o[4] = {(__bf16)v[0], (__bf16)v[1], (__bf16)v[2], (__bf16)v[3]};
-                const unsigned off = ok ? (unsigned)((((b * p.H + ho) * p.W + wo) * p.y_stride + p.y_coff + co) * 2) : OOB;
-                __builtin_amdgcn_raw_buffer_store_b64(*(const __attribute__((ext_vector_type(2))) unsigned*)o, yrs, off, 0, 0);
+                const unsigned off = ok ? (unsigned)((((b * p.H + ho) * p.W + wo) * p.y_stride + p.y_coff + co) * 2) : kBufferOOB;
+                store_bf16x4(v, yrs, off);
             }
         }
     }

@@ -36,7 +36,6 @@ __global__ __launch_bounds__(WGM * WGN * 64) void conv_halo_kernel(const ConvPar
     constexpr int W_INSTR = W_ROWS * 4 / 64;
     constexpr int LW = (W_INSTR + NW - 1) / NW;
     constexpr int WB = W_INSTR * 1024;                // weight slot bytes
-    constexpr unsigned OOB = 0x80000000u;
     static_assert((W_ROWS * 4) % 64 == 0, "weight slab is whole pieces");
 
     extern __shared__ __attribute__((aligned(1024))) unsigned char smem[];
@@ -71,7 +70,7 @@ __global__ __launch_bounds__(WGM * WGN * 64) void conv_halo_kernel(const ConvPar
         const int hy = hp / 18, hx = hp - hy * 18;
         const int hi = h0 - 1 + hy, wi = w0 - 1 + hx;
         const bool ok = (ii < H_INSTR) && (hp < HP) && ((unsigned)hi < (unsigned)p.H) && ((unsigned)wi < (unsigned)p.W);
-        hconst[j] = ok ? (unsigned)((((b * p.H + hi) * p.W + wi) * p.x_stride + p.x_coff) * 2 + c * 16) : OOB;
+        hconst[j] = ok ? (unsigned)((((b * p.H + hi) * p.W + wi) * p.x_stride + p.x_coff) * 2 + c * 16) : kBufferOOB;
     }
     // weight slab pieces: LDS row rw = ky*BN + n  <-  packed W[n0+n][(ky*3+kx)*Cin + c*32 + cc*8]
     unsigned wconst[LW];
@@ -82,7 +81,7 @@ __global__ __launch_bounds__(WGM * WGN * 64) void conv_halo_kernel(const ConvPar
         const int rw = s >> 2, pc = s & 3;
         const int c = pc ^ cswz64(rw);
         const int ky = rw / BN, n = rw - ky * BN;
-        wconst[j] = (ii < W_INSTR) ? (unsigned)(((n0 + n) * p.Kpad + ky * 3 * p.Cin + c * 8) * 2) : OOB;
+        wconst[j] = (ii < W_INSTR) ? (unsigned)(((n0 + n) * p.Kpad + ky * 3 * p.Cin + c * 8) * 2) : kBufferOOB;
     }
     const int nchunk = p.Cin >> 5;
 
@@ -92,7 +91,7 @@ __global__ __launch_bounds__(WGM * WGN * 64) void conv_halo_kernel(const ConvPar
 #pragma unroll
         for (int j = 0; j < LH; ++j) {
             const int ii = wave * LH + j;
-            const unsigned voff = (hconst[j] == OOB || chunk >= nchunk) ? OOB : hconst[j] + coff;
+            const unsigned voff = (hconst[j] == kBufferOOB || chunk >= nchunk) ? kBufferOOB : hconst[j] + coff;
             __builtin_amdgcn_raw_ptr_buffer_load_lds(xrs, (lds_void*)((ii < H_INSTR) ? dst + ii * 1024 : dump), 16, voff, 0, 0, 0);
         }
     };
@@ -102,7 +101,7 @@ __global__ __launch_bounds__(WGM * WGN * 64) void conv_halo_kernel(const ConvPar
 #pragma unroll
         for (int j = 0; j < LW; ++j) {
             const int ii = wave * LW + j;
-            const unsigned voff = (wconst[j] == OOB || chunk >= nchunk) ? OOB : wconst[j] + koff;
+            const unsigned voff = (wconst[j] == kBufferOOB || chunk >= nchunk) ? kBufferOOB : wconst[j] + koff;
             __builtin_amdgcn_raw_ptr_buffer_load_lds(wrs, (lds_void*)((ii < W_INSTR) ? dst + ii * 1024 : dump), 16, voff, 0, 0, 0);
         }
     };
@@ -196,8 +195,7 @@ __global__ __launch_bounds__(WGM * WGN * 64) void conv_halo_kernel(const ConvPar
                 const __bf16* rp = (const __bf16*)p.res + m * p.res_stride + p.res_coff + co;
                 if (vec_ok) {
                     const uint2 rr = *(const uint2*)rp;
-                    v[0] += __uint_as_float(rr.x << 16); v[1] += __uint_as_float(rr.x & 0xffff0000u);
-                    v[2] += __uint_as_float(rr.y << 16); v[3] += __uint_as_float(rr.y & 0xffff0000u);
+                    add_res_bf16x4(v, rr);
                 } else {
 #pragma unroll
                     for (int i = 0; i < 4; ++i)
@@ -214,8 +212,7 @@ __global__ __launch_bounds__(WGM * WGN * 64) void conv_halo_kernel(const ConvPar
             } else {
                 __bf16* yp = (__bf16*)p.y + m * p.y_stride + p.y_coff + co;
                 if (vec_ok) {
-                    __attribute__((aligned(8))) __bf16 o[4] = {(__bf16)v[0], (__bf16)v[1], (__bf16)v[2], (__bf16)v[3]};
-                    *(uint2*)yp = *(const uint2*)o;
+                    *(u32x2*)yp = pack_bf16x4(v);
                 } else {
 #pragma unroll
                     for (int i = 0; i < 4; ++i)

@@ -23,7 +23,6 @@ constexpr int HF_TH = 8, HF_TW = 32;
 // single-buffer form with two workgroups per CU measured 7 .. 11 % slower (128 vs 120 us for 32 -> 64 at 380^2) and was dropped.
 template <int FN>
 __global__ __launch_bounds__(256) void conv_halo_f32_kernel(const ConvParams p, const int tiles_w, const int tiles_h, const int xinstr) {
-    constexpr unsigned OOB = 0x80000000u;
     constexpr int WROWS = 9 * FN * 16, WINSTR = WROWS / 16;
     extern __shared__ __attribute__((aligned(1024))) unsigned char smem[];
     const int tid = threadIdx.x, lane = tid & 63;
@@ -51,7 +50,7 @@ __global__ __launch_bounds__(256) void conv_halo_f32_kernel(const ConvParams p, 
             const int hy = hp / PW, hx = hp - hy * PW;
             const int hi = y0 - d + hy, wi = x0 - d + hx;
             const bool ok = hy < HF_TH + 2 * d && (unsigned)hi < (unsigned)p.H && (unsigned)wi < (unsigned)p.W;
-            const unsigned voff = ok ? (unsigned)((((size_t)(b * p.H + hi) * p.W + wi) * p.x_stride + p.x_coff + cc * 16 + c * 4) * 4) : OOB;
+            const unsigned voff = ok ? (unsigned)((((size_t)(b * p.H + hi) * p.W + wi) * p.x_stride + p.x_coff + cc * 16 + c * 4) * 4) : kBufferOOB;
             __builtin_amdgcn_raw_ptr_buffer_load_lds(xrs, (lds_void*)(Xs + ii * 1024), 16, voff, 0, 0, 0);
         }
         for (int ii = wave; ii < WINSTR; ii += 4) {                // 16 weight rows (tap, co) x 64 B

@@ -27,7 +27,6 @@ __global__ __launch_bounds__(WGM * WGN * 64) void conv_halo_p_kernel(const ConvP
     constexpr int LH = (H_INSTR + NW - 1) / NW;
     constexpr int HB = H_INSTR * 1024;
     constexpr int S = FM * FN;                        // stores per wave per tile
-    constexpr unsigned OOB = 0x80000000u;
     static_assert(NSH == 3, "wait selection below is written for a 3-slot ring");
     static_assert((NSH - 2) * LH + 2 * S < 64, "vmcnt immediate");
 
@@ -93,7 +92,7 @@ __global__ __launch_bounds__(WGM * WGN * 64) void conv_halo_p_kernel(const ConvP
             const int hy = hp / 18, hx = hp - hy * 18;
             const int hi = h0 - 1 + hy, wi = w0 - 1 + hx;
             const bool ok = (tile < num_tiles) && (ii < H_INSTR) && (hp < HP) && ((unsigned)hi < (unsigned)p.H) && ((unsigned)wi < (unsigned)p.W);
-            hconst[j] = ok ? (unsigned)((((b * p.H + hi) * p.W + wi) * p.x_stride + p.x_coff) * 2 + c8 * 16) : OOB;
+            hconst[j] = ok ? (unsigned)((((b * p.H + hi) * p.W + wi) * p.x_stride + p.x_coff) * 2 + c8 * 16) : kBufferOOB;
         }
     };
     int it_tile = j0, it_c = 0, it_slot = 0;
@@ -104,7 +103,7 @@ __global__ __launch_bounds__(WGM * WGN * 64) void conv_halo_p_kernel(const ConvP
 #pragma unroll
         for (int j = 0; j < LH; ++j) {
             const int ii = wave * LH + j;
-            const unsigned voff = (hconst[j] == OOB) ? OOB : hconst[j] + coff;
+            const unsigned voff = (hconst[j] == kBufferOOB) ? kBufferOOB : hconst[j] + coff;
             __builtin_amdgcn_raw_ptr_buffer_load_lds(xrs, (lds_void*)((ii < H_INSTR) ? dst + ii * 1024 : dump), 16, voff, 0, 0, 0);
         }
         it_slot = (it_slot + 1 == NSH) ? 0 : it_slot + 1;
@@ -189,9 +188,7 @@ __global__ __launch_bounds__(WGM * WGN * 64) void conv_halo_p_kernel(const ConvP
 #pragma unroll
                     for (int a = 0; a < FN; ++a) {
                         const int co = n0 + wn * (FN * 16) + a * 16 + fc * 4;
-                        rres[r][a] = (pix_ok && co < p.Cout)
-                                         ? *(const uint2*)((const __bf16*)p.res + (size_t)m * p.res_stride + p.res_coff + co)
-                                         : make_uint2(0u, 0u);
+                        rres[r][a] = load_res_bf16x4((const __bf16*)p.res + (size_t)m * p.res_stride + p.res_coff + co, pix_ok && co < p.Cout);
                     }
                 }
             }
@@ -203,22 +200,7 @@ __global__ __launch_bounds__(WGM * WGN * 64) void conv_halo_p_kernel(const ConvP
 #pragma unroll
                 for (int a = 0; a < FN; ++a) {
                     const int co = n0 + wn * (FN * 16) + a * 16 + fc * 4;
-                    const bool ok = pix_ok && (co < p.Cout);
-                    float v[4] = {acc[a][r][0], acc[a][r][1], acc[a][r][2], acc[a][r][3]};
-                    if (p.act == ACT_SILU) silu4_packed(v);
-                    if (HAS_RES) {
-                        const uint2 rr = rres[r][a];
-                        v[0] += __uint_as_float(rr.x << 16); v[1] += __uint_as_float(rr.x & 0xffff0000u);
-                        v[2] += __uint_as_float(rr.y << 16); v[3] += __uint_as_float(rr.y & 0xffff0000u);
-                    }
-                    if (OUT_F32) {
-                        const unsigned off = ok ? (m * (unsigned)p.y_stride + (unsigned)(p.y_coff + co)) * 4u : OOB;
-                        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(__attribute__((ext_vector_type(4))) unsigned, make_float4(v[0], v[1], v[2], v[3])), yrs, off, 0, 0);
-                    } else {
-                        const unsigned off = ok ? (m * (unsigned)p.y_stride + (unsigned)(p.y_coff + co)) * 2u : OOB;
-                        __attribute__((aligned(8))) __bf16 o[4] = {(__bf16)v[0], (__bf16)v[1], (__bf16)v[2], (__bf16)v[3]};
-                        __builtin_amdgcn_raw_buffer_store_b64(*(const __attribute__((ext_vector_type(2))) unsigned*)o, yrs, off, 0, 0);
-                    }
+                    conv_out_x4(acc[a][r], p.act == ACT_SILU, HAS_RES, rres[r][a], yrs, pix_ok && (co < p.Cout), m * (unsigned)p.y_stride + (unsigned)(p.y_coff + co), OUT_F32);
                 }
             }
         }

@@ -103,16 +103,11 @@ __global__ __launch_bounds__(256) void conv_ks_kernel(const ConvParams p) {
             if (p.act == ACT_SILU) v[j] = silu_rcp(v[j]);
             else if (p.act == ACT_RELU) v[j] = fmaxf(v[j], 0.f);
         }
-        if (HAS_RES) {
-            const uint2 r = *(const uint2*)((const __bf16*)p.res + (size_t)m * p.res_stride + p.res_coff + co);
-            v[0] += __uint_as_float(r.x << 16); v[1] += __uint_as_float(r.x & 0xffff0000u);
-            v[2] += __uint_as_float(r.y << 16); v[3] += __uint_as_float(r.y & 0xffff0000u);
-        }
+        if (HAS_RES) add_res_bf16x4(v, *(const uint2*)((const __bf16*)p.res + (size_t)m * p.res_stride + p.res_coff + co));
         if (OUT_F32) {
             *(float4*)((float*)p.y + (size_t)m * p.y_stride + p.y_coff + co) = make_float4(v[0], v[1], v[2], v[3]);
         } else {
-            __attribute__((aligned(8))) __bf16 o[4] = {(__bf16)v[0], (__bf16)v[1], (__bf16)v[2], (__bf16)v[3]};
-            *(uint2*)((__bf16*)p.y + (size_t)m * p.y_stride + p.y_coff + co) = *(const uint2*)o;
+            *(u32x2*)((__bf16*)p.y + (size_t)m * p.y_stride + p.y_coff + co) = pack_bf16x4(v);
         }
     }
 }

@@ -25,7 +25,6 @@ __global__ __launch_bounds__(WGM * WGN * 64) void conv_pxd_kernel(const ConvPara
     constexpr int LW = (W_INSTR + NW - 1) / NW;        // pieces per wave
     constexpr int SLOT = W_INSTR * 1024;
     constexpr int PL = PXW * 2;                        // pixel loads per wave and k-step
-    constexpr unsigned OOB = 0x80000000u;
     static_assert(LW + 2 * PL < 64, "vmcnt immediate");
 
     extern __shared__ __attribute__((aligned(1024))) unsigned char smem[];
@@ -53,7 +52,7 @@ __global__ __launch_bounds__(WGM * WGN * 64) void conv_pxd_kernel(const ConvPara
     for (int f = 0; f < PXW; ++f) {
         const int ri = (wm * PXW + f) * 16 + fr;
         const int m = m0 + ri;
-        xoff[f] = OOB; xoff2[f] = OOB;
+        xoff[f] = kBufferOOB; xoff2[f] = kBufferOOB;
         if (ri < BMe && m < p.M) {
             xoff[f] = (unsigned)(m * p.x_stride + p.x_coff) * 2u + (unsigned)fc * 16u;
             if (p.x2_C > 0) {
@@ -72,7 +71,7 @@ __global__ __launch_bounds__(WGM * WGN * 64) void conv_pxd_kernel(const ConvPara
         const int s = ii * 64 + lane;
         const int row = s >> 3, pc = s & 7;
         const int c = pc ^ ((row >> 1) & 7);
-        wconst[j] = (ii < W_INSTR) ? (unsigned)(((n0 + weight_row_channel(row, wide)) * p.Kpad + c * 8) * 2) : OOB;
+        wconst[j] = (ii < W_INSTR) ? (unsigned)(((n0 + weight_row_channel(row, wide)) * p.Kpad + c * 8) * 2) : kBufferOOB;
     }
     auto issue_w = [&](int kt, int slot) {
         unsigned char* dst = smem + slot * SLOT;
@@ -80,7 +79,7 @@ __global__ __launch_bounds__(WGM * WGN * 64) void conv_pxd_kernel(const ConvPara
 #pragma unroll
         for (int j = 0; j < LW; ++j) {
             const int ii = wave * LW + j;
-            const unsigned voff = (live && wconst[j] != OOB) ? wconst[j] + (unsigned)(kt * BK) * 2u : OOB;
+            const unsigned voff = (live && wconst[j] != kBufferOOB) ? wconst[j] + (unsigned)(kt * BK) * 2u : kBufferOOB;
             __builtin_amdgcn_raw_ptr_buffer_load_lds(wrs, (lds_void*)((ii < W_INSTR) ? dst + ii * 1024 : dump), 16, voff, 0, 0, 0);
         }
     };
@@ -109,7 +108,7 @@ __global__ __launch_bounds__(WGM * WGN * 64) void conv_pxd_kernel(const ConvPara
 #pragma unroll
             for (int s = 0; s < 2; ++s) {
                 const unsigned base = src2 ? xoff2[f] : xoff[f];
-                const unsigned voff = (live && base != OOB && k0 + s * 32 < p.Kpad) ? base + (unsigned)(k0 + s * 32) * 2u : OOB;
+                const unsigned voff = (live && base != kBufferOOB && k0 + s * 32 < p.Kpad) ? base + (unsigned)(k0 + s * 32) * 2u : kBufferOOB;
                 asm volatile("buffer_load_dwordx4 %0, %1, %2, 0 offen" : "=v"(dst[f][s]) : "v"(voff), "s"(rs) : "memory");
             }
     };
@@ -207,7 +206,7 @@ __global__ __launch_bounds__(WGM * WGN * 64) void conv_pxd_kernel(const ConvPara
                     add_res_bf16x4(v[0], rr[0]);
                     add_res_bf16x4(v[1], rr[1]);
                 }
-                store_bf16x8(v[0], v[1], yrs, ok ? ((unsigned)m * (unsigned)p.y_stride + (unsigned)(p.y_coff + co)) * 2u : OOB);
+                store_bf16x8(v[0], v[1], yrs, ok ? ((unsigned)m * (unsigned)p.y_stride + (unsigned)(p.y_coff + co)) * 2u : kBufferOOB);
             }
             continue;
         }
@@ -220,16 +219,14 @@ __global__ __launch_bounds__(WGM * WGN * 64) void conv_pxd_kernel(const ConvPara
             if (p.act == ACT_SILU) silu4_packed(v);
             if (HAS_RES && ok) {
                 const uint2 rr = *(const uint2*)((const __bf16*)p.res + (size_t)m * p.res_stride + p.res_coff + co);
-                v[0] += __uint_as_float(rr.x << 16); v[1] += __uint_as_float(rr.x & 0xffff0000u);
-                v[2] += __uint_as_float(rr.y << 16); v[3] += __uint_as_float(rr.y & 0xffff0000u);
+                add_res_bf16x4(v, rr);
             }
             if (OUT_F32) {
-                const unsigned off = ok ? ((unsigned)m * (unsigned)p.y_stride + (unsigned)(p.y_coff + co)) * 4u : OOB;
-                __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(__attribute__((ext_vector_type(4))) unsigned, make_float4(v[0], v[1], v[2], v[3])), yrs, off, 0, 0);
+                const unsigned off = ok ? ((unsigned)m * (unsigned)p.y_stride + (unsigned)(p.y_coff + co)) * 4u : kBufferOOB;
+                store_f32x4(v, yrs, off);
             } else {
-                const unsigned off = ok ? ((unsigned)m * (unsigned)p.y_stride + (unsigned)(p.y_coff + co)) * 2u : OOB;
-                __attribute__((aligned(8))) __bf16 o[4] = {(__bf16)v[0], (__bf16)v[1], (__bf16)v[2], (__bf16)v[3]};
-                __builtin_amdgcn_raw_buffer_store_b64(*(const __attribute__((ext_vector_type(2))) unsigned*)o, yrs, off, 0, 0);
+                const unsigned off = ok ? ((unsigned)m * (unsigned)p.y_stride + (unsigned)(p.y_coff + co)) * 2u : kBufferOOB;
+                store_bf16x4(v, yrs, off);
             }
         }
     }

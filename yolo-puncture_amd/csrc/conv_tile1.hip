@@ -37,7 +37,6 @@ __global__ __launch_bounds__(512) void conv_tile1_kernel(const ConvParams p, con
     constexpr int NW = 8, WGM = NW / WGN, FN = 2;
     constexpr int BN = WGN * FN * 16;
     constexpr int WP = BN * 64 / 1024;                 // weight pieces per k-step
-    constexpr unsigned OOB = 0x80000000u;
     extern __shared__ __attribute__((aligned(1024))) unsigned char smem[];
     const int nchunk = p.Cin >> 5;
     unsigned char* const Xs = smem;                                        // [nchunk][ppc*16 px][32 ch]
@@ -81,7 +80,7 @@ __global__ __launch_bounds__(512) void conv_tile1_kernel(const ConvParams p, con
             const int hy = hp / HC, hx = hp - hy * HC;
             const int hi = r0 - 1 + hy, wi = c0 - 1 + hx;
             const bool ok = hp < npx && (unsigned)hi < (unsigned)p.H && (unsigned)wi < (unsigned)p.W;
-            const unsigned voff = ok ? (unsigned)((((b * p.H + hi) * p.W + wi) * p.x_stride + p.x_coff + ch * 32 + c8 * 8) * 2) : OOB;
+            const unsigned voff = ok ? (unsigned)((((b * p.H + hi) * p.W + wi) * p.x_stride + p.x_coff + ch * 32 + c8 * 8) * 2) : kBufferOOB;
             __builtin_amdgcn_raw_ptr_buffer_load_lds(xrs, (lds_void*)(Xs + (ch * g.ppc + pi) * 1024), 16, voff, 0, 0, 0);
         }
     };
@@ -106,7 +105,7 @@ __global__ __launch_bounds__(512) void conv_tile1_kernel(const ConvParams p, con
         const int ch = stage / 3, ky = stage - ch * 3;
         if (!wlive[j]) return;                                               // (wave-uniform; an out-of-range piece would zero-fill LDS)
         if (CLK && (abl & 1) && stage >= T1_NS - 1) return;
-        const unsigned voff = (stage < nst) ? wbase[j] + (unsigned)((ky * 3 * p.Cin + ch * 32) * 2) : OOB;
+        const unsigned voff = (stage < nst) ? wbase[j] + (unsigned)((ky * 3 * p.Cin + ch * 32) * 2) : kBufferOOB;
         __builtin_amdgcn_raw_ptr_buffer_load_lds(wrs, (lds_void*)(Ws + (stage % T1_NS) * SW + (wave + j * NW) * 1024), 16, voff, 0, 0, 0);
     };
 #pragma unroll
@@ -257,7 +256,7 @@ __global__ __launch_bounds__(512) void conv_tile1_kernel(const ConvParams p, con
                     add_res_bf16x4(v[0], rr[0]);
                     add_res_bf16x4(v[1], rr[1]);
                 }
-                store_bf16x8(v[0], v[1], yrs, ok ? (m * (unsigned)p.y_stride + (unsigned)(p.y_coff + co)) * 2u : OOB);
+                store_bf16x8(v[0], v[1], yrs, ok ? (m * (unsigned)p.y_stride + (unsigned)(p.y_coff + co)) * 2u : kBufferOOB);
             }
             continue;
         }
@@ -274,10 +273,10 @@ __global__ __launch_bounds__(512) void conv_tile1_kernel(const ConvParams p, con
                 v[2] += __uint_as_float(rr.y << 16); v[3] += __uint_as_float(rr.y & 0xffff0000u);
             }
             if (OUT_F32) {
-                const unsigned off = ok ? (m * (unsigned)p.y_stride + (unsigned)(p.y_coff + co)) * 4u : OOB;
+                const unsigned off = ok ? (m * (unsigned)p.y_stride + (unsigned)(p.y_coff + co)) * 4u : kBufferOOB;
                 __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(__attribute__((ext_vector_type(4))) unsigned, make_float4(v[0], v[1], v[2], v[3])), yrs, off, 0, 0);
             } else {
-                const unsigned off = ok ? (m * (unsigned)p.y_stride + (unsigned)(p.y_coff + co)) * 2u : OOB;
+                const unsigned off = ok ? (m * (unsigned)p.y_stride + (unsigned)(p.y_coff + co)) * 2u : kBufferOOB;
                 __attribute__((aligned(8))) __bf16 o[4] = {(__bf16)v[0], (__bf16)v[1], (__bf16)v[2], (__bf16)v[3]};
                 __builtin_amdgcn_raw_buffer_store_b64(*(const __attribute__((ext_vector_type(2))) unsigned*)o, yrs, off, 0, 0);
             }
@@ -304,7 +303,6 @@ template <int FMW, bool HAS_RES, bool OUT_F32>
 __global__ __launch_bounds__(512) void conv_tile1w_kernel(const ConvParams p, const Tile1Geo g) {
     constexpr int BN = 128, FN = 4, FM = FMW;
     static_assert(FMW == T1_FMX, "geometry");
-    constexpr unsigned OOB = 0x80000000u;
     extern __shared__ __attribute__((aligned(1024))) unsigned char smem[];
     const int nchunk = p.Cin >> 5;
     unsigned char* const Xs = smem;                                        // [nchunk][ppc*16 px][32 ch]
@@ -339,7 +337,7 @@ __global__ __launch_bounds__(512) void conv_tile1w_kernel(const ConvParams p, co
                 const int hy = hp / HC, hx = hp - hy * HC;
                 const int hi = r0 - 1 + hy, wi = c0 - 1 + hx;
                 const bool ok = hp < npx && (unsigned)hi < (unsigned)p.H && (unsigned)wi < (unsigned)p.W;
-                const unsigned voff = ok ? (unsigned)((((b * p.H + hi) * p.W + wi) * p.x_stride + p.x_coff + ch * 32 + c8 * 8) * 2) : OOB;
+                const unsigned voff = ok ? (unsigned)((((b * p.H + hi) * p.W + wi) * p.x_stride + p.x_coff + ch * 32 + c8 * 8) * 2) : kBufferOOB;
                 __builtin_amdgcn_raw_ptr_buffer_load_lds(xrs, (lds_void*)(Xs + (ch * g.ppc + pi) * 1024), 16, voff, 0, 0, 0);
             }
         };
@@ -355,7 +353,7 @@ __global__ __launch_bounds__(512) void conv_tile1w_kernel(const ConvParams p, co
             const int ch = stage / 3, ky = stage - ch * 3;
 #pragma unroll
             for (int j = 0; j < 6; ++j) {
-                const unsigned voff = (stage < nst) ? wbase[j] + (unsigned)((ky * 3 * p.Cin + ch * 32) * 2) : OOB;
+                const unsigned voff = (stage < nst) ? wbase[j] + (unsigned)((ky * 3 * p.Cin + ch * 32) * 2) : kBufferOOB;
                 __builtin_amdgcn_raw_ptr_buffer_load_lds(wrs, (lds_void*)(Ws + (stage % T1_NS) * SW + (lw + 4 * j) * 1024), 16, voff, 0, 0, 0);
             }
         };
@@ -474,10 +472,10 @@ __global__ __launch_bounds__(512) void conv_tile1w_kernel(const ConvParams p, co
                 v[2] += __uint_as_float(rr.y << 16); v[3] += __uint_as_float(rr.y & 0xffff0000u);
             }
             if (OUT_F32) {
-                const unsigned off = ok ? (m * (unsigned)p.y_stride + (unsigned)(p.y_coff + co)) * 4u : OOB;
+                const unsigned off = ok ? (m * (unsigned)p.y_stride + (unsigned)(p.y_coff + co)) * 4u : kBufferOOB;
                 __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(__attribute__((ext_vector_type(4))) unsigned, make_float4(v[0], v[1], v[2], v[3])), yrs, off, 0, 0);
             } else {
-                const unsigned off = ok ? (m * (unsigned)p.y_stride + (unsigned)(p.y_coff + co)) * 2u : OOB;
+                const unsigned off = ok ? (m * (unsigned)p.y_stride + (unsigned)(p.y_coff + co)) * 2u : kBufferOOB;
                 __attribute__((aligned(8))) __bf16 o[4] = {(__bf16)v[0], (__bf16)v[1], (__bf16)v[2], (__bf16)v[3]};
                 __builtin_amdgcn_raw_buffer_store_b64(*(const __attribute__((ext_vector_type(2))) unsigned*)o, yrs, off, 0, 0);
             }

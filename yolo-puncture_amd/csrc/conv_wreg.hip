@@ -49,7 +49,6 @@ __global__ __launch_bounds__(WGM * WGN * 64) void conv_wreg_kernel(const ConvPar
     constexpr int S = FM * FN;                        // stores per wave per tile
     constexpr int NSH = 3;
     constexpr int NH = RPF * FM + 2 - (RPF - 1);      // distinct halo fragment rows a wave reads per (chunk, kx): FM+2 (TW 16) / 2FM+1 (TW 8)
-    constexpr unsigned OOB = 0x80000000u;
     static_assert(TW == 16 || TW == 8, "fragment shapes");
     static_assert(NCH * 9 * FN * 4 <= 320, "the weight slab of a wave must fit its registers");
     static_assert((NSH - 2) * LH + 2 * S < 64, "vmcnt immediate");
@@ -124,7 +123,7 @@ __global__ __launch_bounds__(WGM * WGN * 64) void conv_wreg_kernel(const ConvPar
         for (int j = 0; j < LH; ++j) {
             const int hy = hyx[j] >> 16, hx = hyx[j] & 0xffff;
             const bool ok = live && (hyx[j] >= 0) && ((unsigned)(h0 + hy) < (unsigned)p.H) && ((unsigned)(w0 + hx) < (unsigned)p.W);
-            hconst[j] = ok ? base + hrel[j] : OOB;
+            hconst[j] = ok ? base + hrel[j] : kBufferOOB;
         }
     };
     int it_tile = j0, it_c = 0, it_slot = 0;
@@ -135,7 +134,7 @@ __global__ __launch_bounds__(WGM * WGN * 64) void conv_wreg_kernel(const ConvPar
 #pragma unroll
         for (int j = 0; j < LH; ++j) {
             const int ii = wave * LH + j;
-            const unsigned voff = (hconst[j] == OOB) ? OOB : hconst[j] + coff;
+            const unsigned voff = (hconst[j] == kBufferOOB) ? kBufferOOB : hconst[j] + coff;
             __builtin_amdgcn_raw_ptr_buffer_load_lds(xrs, (lds_void*)((ii < H_INSTR) ? dst + ii * 1024 : dump), 16, voff, 0, 0, 0);
         }
         it_slot = (it_slot + 1 == NSH) ? 0 : it_slot + 1;
@@ -286,7 +285,7 @@ __global__ __launch_bounds__(WGM * WGN * 64) void conv_wreg_kernel(const ConvPar
                             if (p.act == ACT_SILU) silu4_packed(v[h]);
                             if (HAS_RES) add_res_bf16x4(v[h], rres[r][a + h]);
                         }
-                        store_bf16x8(v[0], v[1], yrs, (pix_ok && co < p.Cout) ? off0 + (unsigned)r * roff + (unsigned)co * 2u : OOB);
+                        store_bf16x8(v[0], v[1], yrs, (pix_ok && co < p.Cout) ? off0 + (unsigned)r * roff + (unsigned)co * 2u : kBufferOOB);
                     }
                 }
             } else {
@@ -320,15 +319,13 @@ __global__ __launch_bounds__(WGM * WGN * 64) void conv_wreg_kernel(const ConvPar
                         if (p.act == ACT_SILU) silu4_packed(v);
                         if (HAS_RES) {
                             const uint2 rr = rres[r][a];
-                            v[0] += __uint_as_float(rr.x << 16); v[1] += __uint_as_float(rr.x & 0xffff0000u);
-                            v[2] += __uint_as_float(rr.y << 16); v[3] += __uint_as_float(rr.y & 0xffff0000u);
+                            add_res_bf16x4(v, rr);
                         }
-                        const unsigned off = ok ? off0 + (unsigned)r * roff + (unsigned)(a * 16) * es : OOB;
+                        const unsigned off = ok ? off0 + (unsigned)r * roff + (unsigned)(a * 16) * es : kBufferOOB;
                         if (OUT_F32) {
-                            __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(__attribute__((ext_vector_type(4))) unsigned, make_float4(v[0], v[1], v[2], v[3])), yrs, off, 0, 0);
+                            store_f32x4(v, yrs, off);
                         } else {
-                            __attribute__((aligned(8))) __bf16 o[4] = {(__bf16)v[0], (__bf16)v[1], (__bf16)v[2], (__bf16)v[3]};
-                            __builtin_amdgcn_raw_buffer_store_b64(*(const __attribute__((ext_vector_type(2))) unsigned*)o, yrs, off, 0, 0);
+                            store_bf16x4(v, yrs, off);
                         }
                     }
                 }

@@ -46,7 +46,6 @@ __device__ __forceinline__ void conv_wres_body(const ConvParams p, const int NB,
     constexpr int FM = TP / (16 * WGM);                            // pixel fragments per wave
     constexpr int NFW = WR_MAXNF / WGN;                            // channel fragments per wave at most
     static_assert(FM >= 1 && FM * 16 * WGM == TP, "pixel tile");
-    constexpr unsigned OOB = 0x80000000u;
     extern __shared__ __attribute__((aligned(1024))) unsigned char smem[];
     const int K = p.Cin, KA = p.x2_C, KB = K - KA;                 // KA channels from the low-resolution source (0: none), KB from x
     const int RBW = K * 2, RBA = KA * 2, RBB = KB * 2;             // row bytes: weights, segment A, segment B
@@ -91,7 +90,7 @@ __device__ __forceinline__ void conv_wres_body(const ConvParams p, const int NB,
                 const int r = s / cpr, pc = s - r * cpr;
                 const int c = pc ^ (r & mA);
                 const long m = row0 + r;
-                unsigned voff = OOB;
+                unsigned voff = kBufferOOB;
                 if (m < p.M && r < TPe) {
                     const int mi = (int)m;
                     const int b = mi / HoWo, q = mi - b * HoWo;
@@ -109,7 +108,7 @@ __device__ __forceinline__ void conv_wres_body(const ConvParams p, const int NB,
                 const int r = s / cpr, pc = s - r * cpr;
                 const int c = pc ^ (r & mB);
                 const long m = row0 + r;
-                const unsigned voff = (m < p.M && r < TPe) ? (unsigned)((m * p.x_stride + p.x_coff + KA + c * 8) * 2) : OOB;
+                const unsigned voff = (m < p.M && r < TPe) ? (unsigned)((m * p.x_stride + p.x_coff + KA + c * 8) * 2) : kBufferOOB;
                 __builtin_amdgcn_raw_ptr_buffer_load_lds(xrs, (lds_void*)(d2 + ii * 1024), 16, voff, 0, 0, 0);
             }
         }
@@ -231,7 +230,7 @@ __device__ __forceinline__ void conv_wres_body(const ConvParams p, const int NB,
                         add_res_bf16x4(v[0], rr[0]);
                         add_res_bf16x4(v[1], rr[1]);
                     }
-                    store_bf16x8(v[0], v[1], yrs, ok ? (unsigned)((m * p.y_stride + p.y_coff + co) * 2) : OOB);
+                    store_bf16x8(v[0], v[1], yrs, ok ? (unsigned)((m * p.y_stride + p.y_coff + co) * 2) : kBufferOOB);
                 }
                 continue;
             }
@@ -248,7 +247,7 @@ __device__ __forceinline__ void conv_wres_body(const ConvParams p, const int NB,
                     v[2] += __uint_as_float(rr.y << 16); v[3] += __uint_as_float(rr.y & 0xffff0000u);
                 }
                 __attribute__((aligned(8))) __bf16 o[4] = {(__bf16)v[0], (__bf16)v[1], (__bf16)v[2], (__bf16)v[3]};
-                const unsigned off = ok ? (unsigned)((m * p.y_stride + p.y_coff + co) * 2) : OOB;
+                const unsigned off = ok ? (unsigned)((m * p.y_stride + p.y_coff + co) * 2) : kBufferOOB;
                 __builtin_amdgcn_raw_buffer_store_b64(*(const __attribute__((ext_vector_type(2))) unsigned*)o, yrs, off, 0, 0);
             }
         }

@@ -24,7 +24,6 @@ __global__ __launch_bounds__(WS_NW * 64) void conv_wrs_kernel(const ConvParams p
     constexpr int FM = TP / 16;                                    // pixel fragments of a tile: every wave takes all of them
     constexpr int K = NKS * 32;
     constexpr int RBW = K * 2;
-    constexpr unsigned OOB = 0x80000000u;
     extern __shared__ __attribute__((aligned(1024))) unsigned char smem[];
     const int KA = p.x2_C, KB = K - KA;                            // KA channels from the low-resolution source (0: none), KB from x
     const int RBA = KA * 2, RBB = KB * 2;
@@ -54,7 +53,7 @@ __global__ __launch_bounds__(WS_NW * 64) void conv_wrs_kernel(const ConvParams p
                 const int r = s / cpr, pc = s - r * cpr;
                 const int c = pc ^ (r & mA);
                 const long m = row0 + r;
-                unsigned voff = OOB;
+                unsigned voff = kBufferOOB;
                 if (m < p.M) {
                     const int mi = (int)m;
                     const int b = mi / HoWo, q = mi - b * HoWo;
@@ -74,7 +73,7 @@ __global__ __launch_bounds__(WS_NW * 64) void conv_wrs_kernel(const ConvParams p
                 const int r = s / cpr, pc = s - r * cpr;
                 const int c = pc ^ (r & mK);
                 const long m = row0 + r;
-                const unsigned voff = (m < p.M) ? (unsigned)((m * p.x_stride + p.x_coff + c * 8) * 2) : OOB;
+                const unsigned voff = (m < p.M) ? (unsigned)((m * p.x_stride + p.x_coff + c * 8) * 2) : kBufferOOB;
                 __builtin_amdgcn_raw_ptr_buffer_load_lds(xrs, (lds_void*)(dst + ii * 1024), 16, voff, 0, 0, 0);
             }
         } else {
@@ -85,7 +84,7 @@ __global__ __launch_bounds__(WS_NW * 64) void conv_wrs_kernel(const ConvParams p
                 const int r = s / cpr, pc = s - r * cpr;
                 const int c = pc ^ (r & mB);
                 const long m = row0 + r;
-                const unsigned voff = (m < p.M) ? (unsigned)((m * p.x_stride + p.x_coff + KA + c * 8) * 2) : OOB;
+                const unsigned voff = (m < p.M) ? (unsigned)((m * p.x_stride + p.x_coff + KA + c * 8) * 2) : kBufferOOB;
                 __builtin_amdgcn_raw_ptr_buffer_load_lds(xrs, (lds_void*)(d2 + ii * 1024), 16, voff, 0, 0, 0);
             }
         }
@@ -172,11 +171,7 @@ __global__ __launch_bounds__(WS_NW * 64) void conv_wrs_kernel(const ConvParams p
             for (int i = 0; i < NFW; ++i) {
                 const int co = n0 + i * 16 + fc * 4;
                 const bool ok = m < p.M && co < p.Cout;                            // (Cout % 4 == 0: a lane's four channels exist together)
-                float v[4] = {acc[i][f][0], acc[i][f][1], acc[i][f][2], acc[i][f][3]};
-                if (p.act == ACT_SILU) silu4_packed(v);
-                __attribute__((aligned(8))) __bf16 o[4] = {(__bf16)v[0], (__bf16)v[1], (__bf16)v[2], (__bf16)v[3]};
-                const unsigned off = ok ? (unsigned)((m * p.y_stride + p.y_coff + co) * 2) : OOB;
-                __builtin_amdgcn_raw_buffer_store_b64(*(const __attribute__((ext_vector_type(2))) unsigned*)o, yrs, off, 0, 0);
+                conv_out_x4(acc[i][f], p.act == ACT_SILU, false, uint2{}, yrs, ok, (unsigned)(m * p.y_stride + p.y_coff + co), false);
             }
         }
         WS_STAMP(4)

@@ -27,7 +27,6 @@ static inline int dwm_pitch(int W, int KS) {
 
 template <int KS, bool SPLIT>
 __global__ __launch_bounds__(256) void dwconv_mfma_kernel(const DwParams p, const int P, const int x_instr) {
-    constexpr unsigned OOB = 0x80000000u;
     constexpr int W_INSTR = (KS * KS + 15) / 16;
     extern __shared__ __attribute__((aligned(1024))) unsigned char smem[];
     unsigned char* const Xs = smem;                                   // [HP*P px][32 ch] bf16, chunk-swizzled
@@ -51,13 +50,13 @@ __global__ __launch_bounds__(256) void dwconv_mfma_kernel(const DwParams p, cons
         const int hy = hp / P, hx = hp - hy * P;
         const int hi = hy - pad, wi = hx - pad;
         const bool ok = (hy < HP) && ((unsigned)hi < (unsigned)p.H) && ((unsigned)wi < (unsigned)p.W);
-        const unsigned voff = ok ? (unsigned)((((b * p.H + hi) * p.W + wi) * p.x_stride + p.x_coff + c * 32 + c8 * 8) * 2) : OOB;
+        const unsigned voff = ok ? (unsigned)((((b * p.H + hi) * p.W + wi) * p.x_stride + p.x_coff + c * 32 + c8 * 8) * 2) : kBufferOOB;
         __builtin_amdgcn_raw_ptr_buffer_load_lds(xrs, (lds_void*)(Xs + ii * 1024), 16, voff, 0, 0, 0);
     }
     for (int ii = wave; ii < W_INSTR; ii += 4) {
         const int s = ii * 64 + lane;
         const int tap = s >> 2, c8 = s & 3;
-        const unsigned voff = (tap < KS * KS) ? (unsigned)((tap * p.C + c * 32 + c8 * 8) * 2) : OOB;
+        const unsigned voff = (tap < KS * KS) ? (unsigned)((tap * p.C + c * 32 + c8 * 8) * 2) : kBufferOOB;
         __builtin_amdgcn_raw_ptr_buffer_load_lds(wrs, (lds_void*)(Wd + ii * 1024), 16, voff, 0, 0, 0);
     }
 

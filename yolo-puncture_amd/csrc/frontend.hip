@@ -44,7 +44,7 @@ __device__ __forceinline__ void fe_load(const FrontParams& p, const __amdgpu_buf
 #pragma unroll
         for (int k = 0; k < 3; ++k) {
             const int off = base + 4 * k;                          // (signed: no 32-bit wrap inside the address unit)
-            r.d[ky][k] = __builtin_amdgcn_raw_buffer_load_b32(irs, (rok && off >= 0) ? (unsigned)off : 0x80000000u, 0, 0);
+            r.d[ky][k] = __builtin_amdgcn_raw_buffer_load_b32(irs, (rok && off >= 0) ? (unsigned)off : kBufferOOB, 0, 0);
         }
     }
 }
@@ -77,7 +77,6 @@ __device__ __forceinline__ void fe_row(const FeRows& r, int sx, unsigned char* d
 __global__ __launch_bounds__(FE_NW * 64) void frontend_kernel(const FrontParams p, const int tiles_h, const int tiles_w, const int G) {
     constexpr int FM = 2, FN = 2, WGM = 4;
     constexpr int BN = 64;
-    constexpr unsigned OOB = 0x80000000u;
     extern __shared__ __attribute__((aligned(1024))) unsigned char smem[];
     unsigned char* const Hs = smem;                          // halo image of the stem output  [561 px][32 ch]
     unsigned char* const Ib = Hs + FE_HB;                    // im2col rows                    [576 px][32 k]
@@ -321,9 +320,8 @@ __global__ __launch_bounds__(FE_NW * 64) void frontend_kernel(const FrontParams 
                 const int co = wn * (FN * 16) + a * 16 + fc * 4;
                 float v[4] = {acc[a][r][0], acc[a][r][1], acc[a][r][2], acc[a][r][3]};
                 if (p.act2 == ACT_SILU) silu4_packed(v);
-                const unsigned off = pix_ok ? (m * (unsigned)p.y_stride + (unsigned)(p.y_coff + co)) * 2u : OOB;
-                __attribute__((aligned(8))) __bf16 o[4] = {(__bf16)v[0], (__bf16)v[1], (__bf16)v[2], (__bf16)v[3]};
-                __builtin_amdgcn_raw_buffer_store_b64(*(const __attribute__((ext_vector_type(2))) unsigned*)o, yrs, off, 0, 0);
+                const unsigned off = pix_ok ? (m * (unsigned)p.y_stride + (unsigned)(p.y_coff + co)) * 2u : kBufferOOB;
+                store_bf16x4(v, yrs, off);
             }
         }
         FE_STAMP(4)

@@ -39,7 +39,6 @@ template <int CMID>
 __global__ __launch_bounds__(256) void head_pos_kernel(const HeadBranchParams p) {
     constexpr int NCF = CMID / 16, NPG = 4 / NCF, NT = 4 / NPG;        // wave = (channel fragment cf, position group pg); NT 16-position tiles each
     static_assert(NCF * NPG == 4, "4 waves");
-    constexpr unsigned OOB = 0x80000000u;
     constexpr int PSLOT = 9 * 64 * 64;                                // one chunk plane: [9 taps][64 positions][32 ch] bf16
     extern __shared__ __attribute__((aligned(1024))) unsigned char smem[];
     unsigned char* const Ps = smem;                                   // 3 slots: chunk c in slot c % 3, two planes in flight
@@ -84,7 +83,7 @@ __global__ __launch_bounds__(256) void head_pos_kernel(const HeadBranchParams p)
             for (int j = 0; j < 9; ++j) {
                 const int yy = y_d + j / 3 - 1, xx = x_d + j % 3 - 1;
                 const bool ok = live && (unsigned)yy < (unsigned)H && (unsigned)xx < (unsigned)W;
-                const unsigned voff = ok ? (unsigned)((((b_d * H + yy) * W + xx) * xs + xc + c * 32 + dpc * 8) * 2) : OOB;
+                const unsigned voff = ok ? (unsigned)((((b_d * H + yy) * W + xx) * xs + xc + c * 32 + dpc * 8) * 2) : kBufferOOB;
                 __builtin_amdgcn_raw_ptr_buffer_load_lds(xrs, (lds_void*)(Ps + slot * PSLOT + (j * 4 + wave) * 1024), 16, voff, 0, 0, 0);
             }
         };
@@ -152,7 +151,6 @@ template <int CMID, int COUT>
 __global__ __launch_bounds__(256) void head_win_kernel(const HeadBranchParams p) {
     constexpr int NCF = CMID / 16, NKC1 = CMID / 32, NCF2 = COUT / 16;
     static_assert(NCF <= 4 && NCF2 <= 4, "4 waves");
-    constexpr unsigned OOB = 0x80000000u;
     extern __shared__ __attribute__((aligned(1024))) unsigned char smem[];
     unsigned char* const T0 = smem;                                   // [NKC1][9 taps * 16 winners][64 B]
     unsigned char* const T1 = smem + NKC1 * 9 * 1024;                 // [NKC1][16 winners][64 B]
@@ -177,7 +175,7 @@ __global__ __launch_bounds__(256) void head_win_kernel(const HeadBranchParams p)
             const int kc = q / 9, t = q - kc * 9;
             const int yy = y_d + t / 3 - 1, xx = x_d + t % 3 - 1;
             const bool ok = (unsigned)yy < (unsigned)H && (unsigned)xx < (unsigned)W;
-            const unsigned voff = ok ? (unsigned)((base + (size_t)(yy * W + xx) * CMID + kc * 32 + dpc * 8) * 2) : OOB;
+            const unsigned voff = ok ? (unsigned)((base + (size_t)(yy * W + xx) * CMID + kc * 32 + dpc * 8) * 2) : kBufferOOB;
             __builtin_amdgcn_raw_ptr_buffer_load_lds(trs, (lds_void*)(T0 + q * 1024), 16, voff, 0, 0, 0);
         }
     }

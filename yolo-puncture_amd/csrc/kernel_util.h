@@ -10,6 +10,8 @@ typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
 typedef __attribute__((ext_vector_type(4))) float f32x4;
 typedef __attribute__((ext_vector_type(2))) float f32x2;
 typedef __attribute__((ext_vector_type(2))) short short2v;
+typedef __attribute__((ext_vector_type(2))) unsigned u32x2;
+typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
 typedef __attribute__((address_space(3))) void lds_void;
 
 // s_waitcnt vmcnt(N) only (gfx9 encoding: vmcnt[3:0] | expcnt[6:4]=7 | lgkmcnt[11:8]=15 | vmcnt_hi[15:14])
@@ -84,6 +86,8 @@ __host__ __device__ constexpr int paired_channel(int row) { return (row & ~31) |
 __device__ __forceinline__ int weight_row_channel(int row, bool wide) { return wide ? paired_channel(row) : row; }
 // first of the 4 channels that lane group fc holds of fragment a, relative to the first channel of the wave's fragment 0
 __device__ __forceinline__ int acc_channel(int a, int fc, bool wide) { return wide ? (a >> 1) * 32 + fc * 8 + (a & 1) * 4 : a * 16 + fc * 4; }
+// byte offset no buffer holds (every buffer here is below 2 GiB): a load at it returns zeros, a store at it is dropped
+constexpr unsigned kBufferOOB = 0x80000000u;
 // v[0..3] += four bf16 residual values
 __device__ __forceinline__ void add_res_bf16x4(float* v, uint2 rr) {
     v[0] += __uint_as_float(rr.x << 16); v[1] += __uint_as_float(rr.x & 0xffff0000u);
@@ -94,14 +98,46 @@ __device__ __forceinline__ void load_res_bf16x8(const __bf16* src, bool ok, uint
     const uint4 q = ok ? *(const uint4*)src : make_uint4(0u, 0u, 0u, 0u);
     lo = make_uint2(q.x, q.y); hi = make_uint2(q.z, q.w);
 }
+// v[0..3] rounded to bf16: the 8 bytes a store of them writes
+__device__ __forceinline__ u32x2 pack_bf16x4(const float* v) {
+    __attribute__((aligned(8))) __bf16 o[4] = {(__bf16)v[0], (__bf16)v[1], (__bf16)v[2], (__bf16)v[3]};
+    return *(const u32x2*)o;
+}
+// (the stores convert in place and do not go through pack_bf16x4: routed through a uint2 value, conv_wreg<2,4,2,4,2,16> spills four registers more)
 __device__ __forceinline__ void store_bf16x4(const float* v, __amdgpu_buffer_rsrc_t rs, unsigned off) {
     __attribute__((aligned(8))) __bf16 o[4] = {(__bf16)v[0], (__bf16)v[1], (__bf16)v[2], (__bf16)v[3]};
     __builtin_amdgcn_raw_buffer_store_b64(*(const __attribute__((ext_vector_type(2))) unsigned*)o, rs, off, 0, 0);
+}
+__device__ __forceinline__ void store_f32x4(const float* v, __amdgpu_buffer_rsrc_t rs, unsigned off) {
+    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(__attribute__((ext_vector_type(4))) unsigned, make_float4(v[0], v[1], v[2], v[3])), rs, off, 0, 0);
+}
+// both fragments of a pair rounded to bf16: the 16 bytes a store of them writes
+__device__ __forceinline__ u32x4 pack_bf16x8(const float* lo, const float* hi) {
+    __attribute__((aligned(16))) __bf16 o[8] = {(__bf16)lo[0], (__bf16)lo[1], (__bf16)lo[2], (__bf16)lo[3], (__bf16)hi[0], (__bf16)hi[1], (__bf16)hi[2], (__bf16)hi[3]};
+    return *(const u32x4*)o;
 }
 // both fragments of a pair as eight bf16 in one 16-byte store
 __device__ __forceinline__ void store_bf16x8(const float* lo, const float* hi, __amdgpu_buffer_rsrc_t rs, unsigned off) {
     __attribute__((aligned(16))) __bf16 o[8] = {(__bf16)lo[0], (__bf16)lo[1], (__bf16)lo[2], (__bf16)lo[3], (__bf16)hi[0], (__bf16)hi[1], (__bf16)hi[2], (__bf16)hi[3]};
     __builtin_amdgcn_raw_buffer_store_b128(*(const __attribute__((ext_vector_type(4))) unsigned*)o, rs, off, 0, 0);
+}
+__device__ __forceinline__ uint2 load_res_bf16x4(const __bf16* src, bool ok) { return ok ? *(const uint2*)src : make_uint2(0u, 0u); }
+
+// The conv epilogue of one accumulator fragment: SiLU (silu4_packed) when asked, then the residual, then round and store.
+// Leaf pieces - add_res_bf16x4, load_res_bf16x4 / x8, pack_bf16x4 / x8, store_bf16x4 / store_f32x4 / store_bf16x8: a kernel that keeps its own
+// statement order composes these; written that way a kernel compiles to the instructions of its former hand-written loop.
+// Register layer - conv_out_x4: the residual words are already in registers (a kernel that preloads them keeps its own hoisting) and
+// `elem` is the element index the caller computed, scaled here by the output's element size; !ok drops the store (the select sits behind
+// the arithmetic, where the hand-written loops had it: ahead of it the register-tight kernels spill more). A call issues exactly ONE
+// buffer store and nothing else on the vector-memory queue. It also moves the index arithmetic ahead of the SiLU, and register
+// allocation notices (profiles/LAB_NOTES.md, "One conv epilogue"): a kernel takes this layer only where its resources and its time
+// stay the parent's. load_res_bf16x4 has the same catch: its pointer is formed outside the conditional (conv_dma_p keeps a ternary).
+__device__ __forceinline__ void conv_out_x4(f32x4 a, bool silu, bool has_res, uint2 rr, __amdgpu_buffer_rsrc_t rs, bool ok, unsigned elem, bool out_f32) {
+    float v[4] = {a[0], a[1], a[2], a[3]};
+    if (silu) silu4_packed(v);
+    if (has_res) add_res_bf16x4(v, rr);
+    if (out_f32) store_f32x4(v, rs, ok ? elem * 4u : kBufferOOB);
+    else store_bf16x4(v, rs, ok ? elem * 2u : kBufferOOB);
 }
 
 // LDS accesses behind the compiler's back: it cannot tell them from the in-flight LDS-DMA of the next chunk apart and drains vmcnt to 0
@@ -111,6 +147,7 @@ __device__ __forceinline__ void lds_write8(unsigned char* dst, unsigned long lon
     asm volatile("ds_write_b64 %0, %1" ::"v"((unsigned)(size_t)(__attribute__((address_space(3))) unsigned char*)dst), "v"(v) : "memory");
 }
 __device__ __forceinline__ void lds_write8(unsigned char* dst, uint2 v) { lds_write8(dst, *(const unsigned long long*)&v); }
+__device__ __forceinline__ void lds_write8(unsigned char* dst, u32x2 v) { lds_write8(dst, __builtin_bit_cast(unsigned long long, v)); }
 __device__ __forceinline__ unsigned long long lds_read8_async(const unsigned char* src) {
     unsigned long long v;
     asm volatile("ds_read_b64 %0, %1" : "=v"(v) : "v"((unsigned)(size_t)(const __attribute__((address_space(3))) unsigned char*)src) : "memory");

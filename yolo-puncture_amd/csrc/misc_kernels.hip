@@ -320,7 +320,7 @@ __global__ __launch_bounds__(256) void dwconv_row_kernel(const DwParams p) {
         for (int col = 0; col < NCOL; ++col) {
             const int wi = wi0 + col;
             const bool ok = rok && ((unsigned)wi < (unsigned)p.W);
-            const unsigned off = ok ? xbase + (unsigned)((hi * p.W + wi) * p.x_stride) * (unsigned)sizeof(T) : 0x80000000u;
+            const unsigned off = ok ? xbase + (unsigned)((hi * p.W + wi) * p.x_stride) * (unsigned)sizeof(T) : kBufferOOB;
             xv[col].load_buf(xrs, off);
         }
         float wf[KS][8];

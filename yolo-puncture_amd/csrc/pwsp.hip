@@ -42,7 +42,6 @@ __global__ __launch_bounds__(PS_NT) void pwsp_kernel(const PwSpParams p) {
     constexpr int BK = 64, NSLOT = 3;
     constexpr int W_INSTR = NS / 8;                    // 1-KiB weight pieces per k-step ([NS][64] bf16, 8 rows per piece)
     constexpr int SLOT = W_INSTR * 1024;
-    constexpr unsigned OOB = 0x80000000u;
     constexpr int KS = SP == 1 ? 3 : SP == 2 ? 7 : 1, PAD = KS / 2;
     constexpr int PIX = SP == 3 ? NS * 2 : NS * 2 + 8; // bytes per pixel of the LDS image (depthwise: +8 so that 16 pixels spread over the banks)
     constexpr int DW_NP = NS / 2, DW_G = PS_NT / DW_NP; // depthwise stage: channel pairs, thread groups (32 at NS = 64, 64 at NS = 32)
@@ -107,8 +106,8 @@ __global__ __launch_bounds__(PS_NT) void pwsp_kernel(const PwSpParams p) {
         const int row = (wave * 2 + j) * 8 + (lane >> 3);                     // row within the slot = pixel (A) / pixel - 256 (B)
         const int c = (lane & 7) ^ ((row >> 1) & 7);
         p_kc[j] = c * 8;
-        pa_off[j] = (row < HW && row < 256) ? (unsigned)((b * HW + row) * p.x_stride + p.x_coff + c * 8) * 2u : OOB;
-        pb_off[j] = (row + 256 < HW) ? (unsigned)((b * HW + row + 256) * p.x_stride + p.x_coff + c * 8) * 2u : OOB;
+        pa_off[j] = (row < HW && row < 256) ? (unsigned)((b * HW + row) * p.x_stride + p.x_coff + c * 8) * 2u : kBufferOOB;
+        pb_off[j] = (row + 256 < HW) ? (unsigned)((b * HW + row + 256) * p.x_stride + p.x_coff + c * 8) * 2u : kBufferOOB;
     }
     unsigned wconst;
     {
@@ -116,18 +115,18 @@ __global__ __launch_bounds__(PS_NT) void pwsp_kernel(const PwSpParams p) {
         const int row = s_ >> 3, pc = s_ & 7;
         const int c = pc ^ ((row >> 1) & 7);
         w_kc = c * 8;
-        wconst = (wave < W_INSTR) ? (unsigned)(((n0 + weight_row_channel(row, wide)) * p.Kpad1 + c * 8) * 2) : OOB;
+        wconst = (wave < W_INSTR) ? (unsigned)(((n0 + weight_row_channel(row, wide)) * p.Kpad1 + c * 8) * 2) : kBufferOOB;
     }
     auto kbyte = [&](int kt) { return (unsigned)(kt * BK) * 2u; };
     auto issue_A = [&](int kt) {
         const bool live = kt < nk;
         const unsigned kb = kbyte(kt);
         __builtin_amdgcn_raw_ptr_buffer_load_lds(wrs, (lds_void*)((wave < W_INSTR) ? wring + (kt % NSLOT) * SLOT + wave * 1024 : dump), 16,
-                                                 (live && wconst != OOB && kt * BK + w_kc < p.K) ? wconst + kb : OOB, 0, 0, 0);
+                                                 (live && wconst != kBufferOOB && kt * BK + w_kc < p.K) ? wconst + kb : kBufferOOB, 0, 0, 0);
 #pragma unroll
         for (int j = 0; j < 2; ++j)
             __builtin_amdgcn_raw_ptr_buffer_load_lds(xrs, (lds_void*)(pxa + (kt & 1) * PXS + (wave * 2 + j) * 1024), 16,
-                                                     (live && pa_off[j] != OOB && kt * BK + p_kc[j] < p.K && !(p.dbg & 2)) ? pa_off[j] + kb : OOB, 0, 0, 0);
+                                                     (live && pa_off[j] != kBufferOOB && kt * BK + p_kc[j] < p.K && !(p.dbg & 2)) ? pa_off[j] + kb : kBufferOOB, 0, 0, 0);
     };
     auto issue_B = [&](int kt) {
         const bool live = kt < nk;
@@ -135,7 +134,7 @@ __global__ __launch_bounds__(PS_NT) void pwsp_kernel(const PwSpParams p) {
 #pragma unroll
         for (int j = 0; j < 2; ++j)
             __builtin_amdgcn_raw_ptr_buffer_load_lds(xrs, (lds_void*)(pxb + (kt & 1) * PXS + (wave * 2 + j) * 1024), 16,
-                                                     (live && pb_off[j] != OOB && kt * BK + p_kc[j] < p.K && !(p.dbg & 2)) ? pb_off[j] + kb : OOB, 0, 0, 0);
+                                                     (live && pb_off[j] != kBufferOOB && kt * BK + p_kc[j] < p.K && !(p.dbg & 2)) ? pb_off[j] + kb : kBufferOOB, 0, 0, 0);
     };
 
     f32x4 acc[FN][PS_MF];
@@ -218,9 +217,8 @@ __global__ __launch_bounds__(PS_NT) void pwsp_kernel(const PwSpParams p) {
                     add_res_bf16x4(v[0], rr[0]);
                     add_res_bf16x4(v[1], rr[1]);
                 }
-                __attribute__((aligned(16))) __bf16 o[8] = {(__bf16)v[0][0], (__bf16)v[0][1], (__bf16)v[0][2], (__bf16)v[0][3],
-                                                            (__bf16)v[1][0], (__bf16)v[1][1], (__bf16)v[1][2], (__bf16)v[1][3]};
-                if (ok && p.y1) *(uint4*)((__bf16*)p.y1 + (size_t)(b * HW + m) * p.y1_stride + p.y1_coff + n0 + co) = *(const uint4*)o;
+                const u32x4 o = pack_bf16x8(v[0], v[1]);
+                if (ok && p.y1) *(u32x4*)((__bf16*)p.y1 + (size_t)(b * HW + m) * p.y1_stride + p.y1_coff + n0 + co) = o;
             }
             continue;
         }
@@ -232,12 +230,11 @@ __global__ __launch_bounds__(PS_NT) void pwsp_kernel(const PwSpParams p) {
             const int co = a * 16 + fc * 4;
             if (SP == 0 && p.res1 && ok) {
                 const uint2 rr = *(const uint2*)((const __bf16*)p.res1 + (size_t)(b * HW + m) * p.res1_stride + p.res1_coff + n0 + co);
-                v[0] += __uint_as_float(rr.x << 16); v[1] += __uint_as_float(rr.x & 0xffff0000u);
-                v[2] += __uint_as_float(rr.y << 16); v[3] += __uint_as_float(rr.y & 0xffff0000u);
+                add_res_bf16x4(v, rr);
             }
-            __attribute__((aligned(8))) __bf16 o[4] = {(__bf16)v[0], (__bf16)v[1], (__bf16)v[2], (__bf16)v[3]};
-            if (ok && p.y1) *(uint2*)((__bf16*)p.y1 + (size_t)(b * HW + m) * p.y1_stride + p.y1_coff + n0 + co) = *(const uint2*)o;
-            if (SP != 0 && ok && spatial) *(uint2*)(img + (size_t)((py + PAD) * IW + px + PAD) * PIX + co * 2) = *(const uint2*)o;
+            const u32x2 o = pack_bf16x4(v);
+            if (ok && p.y1) *(u32x2*)((__bf16*)p.y1 + (size_t)(b * HW + m) * p.y1_stride + p.y1_coff + n0 + co) = o;
+            if (SP != 0 && ok && spatial) *(u32x2*)(img + (size_t)((py + PAD) * IW + px + PAD) * PIX + co * 2) = o;
         }
     }
     PS_STAMP(3);

@@ -30,7 +30,6 @@ constexpr int SD_WB = 64 * 256;                         // one group's 1x1 weigh
 constexpr int SD_LDS = 2 * SD_XB + 2 * SD_TB + 2 * SD_WB + 5120 + 2048;   // 160768 B
 
 __global__ __launch_bounds__(SD_NW * 64) void scdown_fused_kernel(const ScdParams p, const int tiles_h, const int tiles_w, const int G) {
-    constexpr unsigned OOB = 0x80000000u;
     extern __shared__ __attribute__((aligned(1024))) unsigned char smem[];
     unsigned char* const Xs = smem;                           // 2 x [156 px][128 ch]
     unsigned char* const Ts = Xs + 2 * SD_XB;                 // 2 x [160 px][64 ch]
@@ -66,7 +65,7 @@ __global__ __launch_bounds__(SD_NW * 64) void scdown_fused_kernel(const ScdParam
                 const int py = q / SD_RW, px = q - py * SD_RW;
                 const int iy = 2 * th * SD_TH - 1 + py, ix = 2 * tw * SD_TW - 1 + px;
                 const bool ok = tv && q < SD_RP && (unsigned)iy < (unsigned)p.H && (unsigned)ix < (unsigned)p.W;
-                const unsigned voff = ok ? (unsigned)((((b * p.H + iy) * p.W + ix) * p.x_stride + p.x_coff + c * 8) * 2) : OOB;
+                const unsigned voff = ok ? (unsigned)((((b * p.H + iy) * p.W + ix) * p.x_stride + p.x_coff + c * 8) * 2) : kBufferOOB;
                 __builtin_amdgcn_raw_ptr_buffer_load_lds(xrs, (lds_void*)(dst + ii * 1024), 16, voff, 0, 0, 0);
             }
         }
@@ -125,9 +124,8 @@ __global__ __launch_bounds__(SD_NW * 64) void scdown_fused_kernel(const ScdParam
         if (p.actd == ACT_SILU) silu4_packed(v);
         const int ho = pth * SD_TH + oy, wo = ptw * SD_TW + ox;
         const bool ok = ho < p.Ho && wo < p.Wo;
-        const unsigned off = ok ? ((unsigned)((pb * p.Ho + ho) * p.Wo + wo) * (unsigned)p.y_stride + (unsigned)(p.y_coff + g * 64 + ch)) * 2u : OOB;
-        __attribute__((aligned(8))) __bf16 ob[4] = {(__bf16)v[0], (__bf16)v[1], (__bf16)v[2], (__bf16)v[3]};
-        __builtin_amdgcn_raw_buffer_store_b64(*(const __attribute__((ext_vector_type(2))) unsigned*)ob, yrs, off, 0, 0);
+        const unsigned off = ok ? ((unsigned)((pb * p.Ho + ho) * p.Wo + wo) * (unsigned)p.y_stride + (unsigned)(p.y_coff + g * 64 + ch)) * 2u : kBufferOOB;
+        store_bf16x4(v, yrs, off);
     };
 
     // Skewed by one group: between two barriers a wave runs D of the previous group (VALU) and G of this one (MFMA + SiLU) back to
@@ -152,7 +150,7 @@ __global__ __launch_bounds__(SD_NW * 64) void scdown_fused_kernel(const ScdParam
             const unsigned char* const Wg = Ws + wsel * SD_WB;
             unsigned char* const Tg = Ts + wsel * SD_TB;
             if (pg >= 0) dw_stage(Ts + (wsel ^ 1) * SD_TB, pg, pb, pth, ptw);
-            else { const unsigned zero[2] = {0u, 0u}; __builtin_amdgcn_raw_buffer_store_b64(*(const __attribute__((ext_vector_type(2))) unsigned*)zero, yrs, OOB, 0, 0); }   // (keeps the store count)
+            else { const unsigned zero[2] = {0u, 0u}; __builtin_amdgcn_raw_buffer_store_b64(*(const __attribute__((ext_vector_type(2))) unsigned*)zero, yrs, kBufferOOB, 0, 0); }   // (keeps the store count)
             SD_STAMP(3)
 
             // ---- G: t = act(W1g . x) on the patch ----------------------------------------------------------------------------------

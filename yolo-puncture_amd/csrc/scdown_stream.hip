@@ -33,7 +33,6 @@ __global__ __launch_bounds__(SS_NW * 64, 2) void scdown_stream_kernel(const ScdP
     constexpr int PPW = PIECES / SS_NW;                            // 3 / 6 per wave
     constexpr int CPR = RB / 16;                                   // 16-byte chunks per patch row
     constexpr int NST = SS_T;                                      // stores per wave and tile
-    constexpr unsigned OOB = 0x80000000u;
     extern __shared__ __attribute__((aligned(1024))) unsigned char smem[];
     unsigned char* const Xs = smem;                                // 2 patch slots: row px, chunk q at position q ^ (px & 15)
     unsigned char* const Ts = smem + 2 * XB;                       // t: row px (512 B), chunk q at position q ^ (px & 15) (within its half of 16)
@@ -62,7 +61,7 @@ __global__ __launch_bounds__(SS_NW * 64, 2) void scdown_stream_kernel(const ScdP
             const int ry = px / SS_R, rx = px - ry * SS_R;
             const int hi = h0 + ry, wi = w0 + rx;
             const bool ok = tile < num_tiles && px < SS_RP && (unsigned)hi < (unsigned)p.H && (unsigned)wi < (unsigned)p.W;
-            const unsigned voff = ok ? (unsigned)((((b * p.H + hi) * p.W + wi) * p.x_stride + p.x_coff + c * 8) * 2) : OOB;
+            const unsigned voff = ok ? (unsigned)((((b * p.H + hi) * p.W + wi) * p.x_stride + p.x_coff + c * 8) * 2) : kBufferOOB;
             __builtin_amdgcn_raw_ptr_buffer_load_lds(xrs, (lds_void*)(dst + ii * 1024), 16, voff, 0, 0, 0);
         }
     };
@@ -187,7 +186,7 @@ __global__ __launch_bounds__(SS_NW * 64, 2) void scdown_stream_kernel(const ScdP
                 __attribute__((aligned(4))) __bf16 o[2] = {(__bf16)a[0], (__bf16)a[1]};
                 const int wo = tw * SS_T + x;
                 const bool ok = ho < p.Ho && wo < p.Wo;
-                const unsigned off = ok ? (unsigned)((((b * p.Ho + ho) * p.Wo + wo) * p.y_stride + p.y_coff + 2 * cp) * 2) : OOB;
+                const unsigned off = ok ? (unsigned)((((b * p.Ho + ho) * p.Wo + wo) * p.y_stride + p.y_coff + 2 * cp) * 2) : kBufferOOB;
                 __builtin_amdgcn_raw_buffer_store_b32(*(const unsigned*)o, yrs, off, 0, 0);
 #pragma unroll
                 for (int ky = 0; ky < 3; ++ky) win[ky][0] = win[ky][2];
