@@ -356,6 +356,15 @@ int yp_debug_ablation(int v);
    [0] start, [1] keys loaded, [2] stage-1 lower bound found, [3] stage-1 select done, [4] stage-2 candidates scanned,
    [5] stage-2 select done, [6] decoded; [7] = stage-2 rounds << 32 | candidates that entered the last round's select. */
 int yp_debug_head_clocks(uint64_t* out8);
+/* Test hook: the PSA attention core alone, o = softmax(q.k^T * kd^-0.5).v per image and head, through the launcher an OP_ATTN op takes (the same
+   parameters, scale = 1/sqrt(kd)). qkv_dev: device [B][N][q_stride], head h of a token at channels q_coff + h*(2kd+hd): q(kd) | k(kd) | v(hd);
+   o_dev: device [B][N][o_stride], head h at channels o_coff + h*hd; elements are bf16 (YP_BF16) or float (YP_F32). wgs > 0 replaces the
+   matrix-core form's workgroup target (YOLOP_ATTN_WGS, else 256) for this call: it sets the query tiles a workgroup walks. *kernel_out:
+   1 the matrix-core kernel took the call, 0 the generic one. Returns after the stream has drained. YP_ERR_ARG (nothing launched) on null
+   pointers, non-positive sizes, a slice that does not fit its stride (q_coff + nh*(2kd+hd) > q_stride, o_coff + nh*hd > o_stride), strides
+   or offsets that are not multiples of 4 elements, and shapes no kernel holds (more tokens than the generic kernel's LDS, kd or hd % 4). */
+int yp_debug_attention(const void* qkv_dev, void* o_dev, int dtype, int B, int N, int nh, int kd, int hd, int q_stride, int q_coff, int o_stride,
+                       int o_coff, int wgs, int* kernel_out, void* stream);
 /* Test hook: stage 1 of the top-k head alone (the top k anchors by score descending, anchor index ascending) on caller-made class-max keys,
    through the kernels an engine takes for that anchor count: head_select_kernel<1> up to 12288 anchors, head_chunk_topk_kernel +
    head_select_large_kernel<1> beyond. mk_dev[l]: device uint32 [B][hw[l][0] * hw[l][1]], the bits of the anchors' best sigmoid scores as

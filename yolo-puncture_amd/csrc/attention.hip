@@ -102,16 +102,36 @@ __global__ __launch_bounds__(256) void attention_kernel(const AttnParams p) {
         if (n >= p.N) continue;
         const float* row = S + q * p.N;
         const T* vp = base + 2 * p.kd + dc * 4;
-        float acc[4] = {0.f, 0.f, 0.f, 0.f};
-        for (int m = 0; m < p.N; ++m) {
-            float vv[4];
-            load4<T>(vp + (size_t)m * p.q_stride, vv);
-            const float pr = row[m];
-            acc[0] = fmaf(pr, vv[0], acc[0]);
-            acc[1] = fmaf(pr, vv[1], acc[1]);
-            acc[2] = fmaf(pr, vv[2], acc[2]);
-            acc[3] = fmaf(pr, vv[3], acc[3]);
+        // four partial sums (keys m % 4), added pairwise at the end: one chain of N fp32 additions carries a rounding error that grows
+        // with sqrt(N) (at N = 2368 twice that of a blocked sum), four chains carry half of it and their loads are independent
+        float part[4][4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u)
+#pragma unroll
+            for (int c = 0; c < 4; ++c) part[u][c] = 0.f;
+        int m = 0;
+        for (; m + 4 <= p.N; m += 4) {
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                float vv[4];
+                load4<T>(vp + (size_t)(m + u) * p.q_stride, vv);
+                const float pr = row[m + u];
+#pragma unroll
+                for (int c = 0; c < 4; ++c) part[u][c] = fmaf(pr, vv[c], part[u][c]);
+            }
         }
+#pragma unroll
+        for (int u = 0; u < 3; ++u) {                              // the last N % 4 keys
+            if (m + u >= p.N) break;
+            float vv[4];
+            load4<T>(vp + (size_t)(m + u) * p.q_stride, vv);
+            const float pr = row[m + u];
+#pragma unroll
+            for (int c = 0; c < 4; ++c) part[u][c] = fmaf(pr, vv[c], part[u][c]);
+        }
+        float acc[4];
+#pragma unroll
+        for (int c = 0; c < 4; ++c) acc[c] = (part[0][c] + part[1][c]) + (part[2][c] + part[3][c]);
         store4<T>((T*)p.o + ((size_t)b * p.N + n) * p.o_stride + p.o_coff + h * p.hd + dc * 4, acc);
     }
 }
@@ -288,18 +308,23 @@ static bool attention_takes_mfma(const AttnParams& p, int dtype) {
 static size_t attention_generic_lds(int kd, int N) { return (size_t)(QT * kd + QT * N) * sizeof(float); }
 
 // Whether launch_attention has a kernel for p (the planner asks before anything launches); *max_tokens = the largest N it has one for
-// with p's head sizes: the generic kernel keeps a query tile's QT x N scores in LDS.
+// with p's head sizes: the generic kernel keeps a query tile's QT x N scores in LDS. Both kernels move 4 elements per access (load4 /
+// store4, the 16-B fragments of the matrix-core form), so the strides and channel offsets of both slices are multiples of 4 elements.
 bool attention_fits(const AttnParams& p, int dtype, int* max_tokens) {
     if (max_tokens) *max_tokens = (int)((150 * 1024 / sizeof(float) - (size_t)QT * p.kd) / QT);
+    if ((p.q_stride | p.q_coff | p.o_stride | p.o_coff) & 3) return false;
     if (attention_takes_mfma(p, dtype)) return true;
     return attention_generic_lds(p.kd, p.N) <= 150 * 1024 && !(p.kd & 3) && !(p.hd & 3);
 }
 
-hipError_t launch_attention(const AttnParams& p, int dtype, hipStream_t st) {
+hipError_t launch_attention(const AttnParams& p, int dtype, hipStream_t st, int wgs, int* kernel_out) {
     const size_t qkv_bytes = (size_t)p.B * p.N * p.q_stride * 2;
+    if (!attention_fits(p, dtype, nullptr)) return hipErrorInvalidValue;
     if (attention_takes_mfma(p, dtype)) {
+        if (kernel_out) *kernel_out = 1;
         // query tiles per workgroup: as long as possible (K/V are staged once per workgroup) while the grid still covers the chip
-        static const int target = [] { const int v = env_int("YOLOP_ATTN_WGS", 0); return v > 0 ? v : 256; }();
+        static const int env_target = [] { const int v = env_int("YOLOP_ATTN_WGS", 0); return v > 0 ? v : 256; }();
+        const int target = wgs > 0 ? wgs : env_target;
         const int ntiles = (p.N + 15) / 16, BH = p.B * p.nh;
         int nsplit = std::min(ntiles, std::max(1, (target + BH - 1) / BH));
         const int tpw = (ntiles + nsplit - 1) / nsplit;
@@ -307,8 +332,8 @@ hipError_t launch_attention(const AttnParams& p, int dtype, hipStream_t st) {
         hipLaunchKernelGGL(attention_mfma_kernel, dim3((unsigned)nsplit, (unsigned)BH), dim3(A_MAXW * 64), 0, st, p, tpw, (unsigned)qkv_bytes);
         return hipGetLastError();
     }
+    if (kernel_out) *kernel_out = 0;
     const size_t sh = attention_generic_lds(p.kd, p.N);
-    if (!attention_fits(p, dtype, nullptr)) return hipErrorInvalidValue;
     dim3 grid((p.N + QT - 1) / QT, p.B * p.nh);
     static size_t granted[2] = {0, 0};
     if (dtype == DT_BF16) {

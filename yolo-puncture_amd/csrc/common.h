@@ -362,7 +362,8 @@ bool dwconv_mfma_valid(const DwParams& p, int dtype);
 hipError_t launch_dwconv_mfma(const DwParams& p, hipStream_t st);
 const char* dwconv_mfma_kernel_name(const DwParams& p);
 hipError_t launch_upsample(const UpParams& p, int dtype, hipStream_t st);
-hipError_t launch_attention(const AttnParams& p, int dtype, hipStream_t st);
+// wgs > 0: the matrix-core form's workgroup target for this call (0: YOLOP_ATTN_WGS, else 256); *kernel_out = 1 matrix-core form, 0 generic
+hipError_t launch_attention(const AttnParams& p, int dtype, hipStream_t st, int wgs = 0, int* kernel_out = nullptr);
 bool attention_fits(const AttnParams& p, int dtype, int* max_tokens);      // the predicate of launch_attention, for the planner
 // conv_small.hip: fp32 3x3 for small maps (four waves split K, operands straight from L2)
 bool conv_small_valid(const ConvParams& p, int dtype);

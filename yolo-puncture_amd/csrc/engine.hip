@@ -1138,7 +1138,8 @@ static int make_plan(yp_engine& e, int B, int H, int W) {
         if (o.kind != OP_ATTN) continue;
         const TensorDesc& ti = e.tensors[o.in.t];
         AttnParams q{};
-        q.q_stride = ti.C; q.q_coff = o.in.coff; q.B = B; q.N = (H / ti.sdiv) * (W / ti.sdiv); q.nh = o.nh; q.kd = o.kd; q.hd = o.hd;
+        q.q_stride = ti.C; q.q_coff = o.in.coff; q.o_stride = e.tensors[o.out.t].C; q.o_coff = o.out.coff;
+        q.B = B; q.N = (H / ti.sdiv) * (W / ti.sdiv); q.nh = o.nh; q.kd = o.kd; q.hd = o.hd;
         int max_tokens = 0;
         if (!attention_fits(q, e.dtype, &max_tokens))
             return fail(YP_ERR_ARG, "input %dx%d gives %s %d attention tokens; the attention kernels hold at most %d (a streaming form is not built)", H, W,
@@ -2564,6 +2565,35 @@ int yp_debug_topk_anchors(const uint32_t* const mk_dev[3], int B, const int hw[3
     if (err == hipSuccess) err = hipStreamSynchronize(st);
     (void)hipFree(ws);
     if (err != hipSuccess) return fail(YP_ERR_HIP, "yp_debug_topk_anchors: %s", hipGetErrorString(err));
+    return YP_OK;
+}
+
+int yp_debug_attention(const void* qkv_dev, void* o_dev, int dtype, int B, int N, int nh, int kd, int hd, int q_stride, int q_coff, int o_stride,
+                       int o_coff, int wgs, int* kernel_out, void* stream) {
+    if (!qkv_dev || !o_dev || !kernel_out) return fail(YP_ERR_ARG, "yp_debug_attention: null argument");
+    if (dtype != YP_BF16 && dtype != YP_F32) return fail(YP_ERR_ARG, "yp_debug_attention: dtype = %d (YP_BF16 | YP_F32)", dtype);
+    if (B < 1 || N < 1 || nh < 1 || kd < 1 || hd < 1 || q_stride < 1 || o_stride < 1 || q_coff < 0 || o_coff < 0 || wgs < 0)
+        return fail(YP_ERR_ARG, "yp_debug_attention: non-positive size (B %d, N %d, nh %d, kd %d, hd %d, q_stride %d, q_coff %d, o_stride %d, o_coff %d, wgs %d)",
+                    B, N, nh, kd, hd, q_stride, q_coff, o_stride, o_coff, wgs);
+    if ((int64_t)B * nh > 65535) return fail(YP_ERR_ARG, "yp_debug_attention: B * nh = %lld; the grid holds at most 65535", (long long)B * nh);
+    if ((int64_t)q_coff + (int64_t)nh * (2 * (int64_t)kd + hd) > q_stride)
+        return fail(YP_ERR_ARG, "yp_debug_attention: the qkv slice [%d, %lld) does not fit q_stride = %d", q_coff, (long long)q_coff + (long long)nh * (2 * (long long)kd + hd), q_stride);
+    if ((int64_t)o_coff + (int64_t)nh * hd > o_stride)
+        return fail(YP_ERR_ARG, "yp_debug_attention: the output slice [%d, %lld) does not fit o_stride = %d", o_coff, (long long)o_coff + (long long)nh * hd, o_stride);
+    if ((q_stride | q_coff | o_stride | o_coff) & 3)
+        return fail(YP_ERR_ARG, "yp_debug_attention: strides and channel offsets must be multiples of 4 elements (q_stride %d, q_coff %d, o_stride %d, o_coff %d)",
+                    q_stride, q_coff, o_stride, o_coff);
+    AttnParams p{};
+    p.qkv = qkv_dev; p.q_stride = q_stride; p.q_coff = q_coff; p.o = o_dev; p.o_stride = o_stride; p.o_coff = o_coff;
+    p.B = B; p.N = N; p.nh = nh; p.kd = kd; p.hd = hd; p.scale = 1.0f / std::sqrt((float)kd);
+    int max_tokens = 0;
+    if (!attention_fits(p, dtype, &max_tokens))
+        return fail(YP_ERR_ARG, "yp_debug_attention: no kernel for N = %d, kd = %d, hd = %d: the attention kernels hold at most %d tokens and want kd and hd in multiples of 4",
+                    N, kd, hd, max_tokens);
+    hipStream_t st = (hipStream_t)stream;
+    hipError_t err = launch_attention(p, dtype, st, wgs, kernel_out);
+    if (err == hipSuccess) err = hipStreamSynchronize(st);
+    if (err != hipSuccess) return fail(YP_ERR_HIP, "yp_debug_attention: %s", hipGetErrorString(err));
     return YP_OK;
 }
 
