@@ -279,7 +279,11 @@ int yp_comm_destroy(yp_comm* c);
  *            candidates above `conf` are gathered into a global list first (NMS families; at most the 16384 best-scoring candidates of
  *            an image enter NMS, where ultralytics' max_nms is 30000).
  *   attention tokens (H/32 * W/32, v10 and 11 only): above 400 the PSA block runs a generic kernel that keeps 16 x tokens scores in LDS,
- *            which ends at 2368 tokens for 32-wide keys. v8 has no attention.
+ *            which ends at 2368 tokens for 32-wide keys. v8 has no attention. An engine whose attention form is `stream`
+ *            (yp_set_attention_form) runs bf16 PSA blocks with 32-wide keys and 64-wide heads - every v10 variant except M, every YOLO11
+ *            variant - above 400 tokens on a matrix-core kernel that streams K and V through LDS: no token bound of its own, the anchor
+ *            bound (anchors = 21 x tokens, so 14043 tokens) and the byte bound remain. fp32 engines and v10-M keep the generic kernel
+ *            and its bound under either form.
  *   bytes    every activation stays below 2^31 bytes: yp_max_batch(e, H, W) is the largest B that plans at HxW (callers split to it). */
 #define YP_MAX_ANCHORS 294912   /* 12288 * (12288 / 512): covers 3840x2176 (214200) */
 int yp_max_batch(const yp_engine* e, int H, int W);
@@ -316,6 +320,13 @@ int yp_profile(yp_engine* e, const uint8_t* in_dev, int B, int H, int W, float* 
  * them (defaults 0.25 / 0.7). Rows of yp_forward's det_out are the boxes NMS keeps, best first; may be changed between forwards
  * (the values live in device memory: a captured graph does not go stale). No effect on the v10 family. */
 int yp_set_nms(yp_engine* e, float conf, float iou);
+
+/* Attention form of the PSA block (v10 / 11): 0 auto - the default: the resident matrix-core kernel up to 400 tokens, the generic kernel up to
+ * its LDS bound, refusal beyond -, 1 stream - bf16, key_dim 32, head_dim 64 above 400 tokens run attention_stream_kernel (two passes over K:
+ * row max and sum, then P.V with the normalised bf16 probabilities; same rounding points as the other kernels, no token bound); whatever is
+ * outside that scope runs and is refused as under 0. Any other value: YP_ERR_ARG. Allowed before or after yp_finalize; a change drops the
+ * current plan (the next yp_plan / yp_forward plans again). An engine created while YOLOP_ATTN_FORM=stream is set starts in form 1. */
+int yp_set_attention_form(yp_engine* e, int form);
 
 /* Enable/disable the plan-time autotuner that picks the conv tile configuration per layer (default on). */
 int yp_set_autotune(yp_engine* e, int enable);
@@ -365,6 +376,12 @@ int yp_debug_head_clocks(uint64_t* out8);
    or offsets that are not multiples of 4 elements, and shapes no kernel holds (more tokens than the generic kernel's LDS, kd or hd % 4). */
 int yp_debug_attention(const void* qkv_dev, void* o_dev, int dtype, int B, int N, int nh, int kd, int hd, int q_stride, int q_coff, int o_stride,
                        int o_coff, int wgs, int* kernel_out, void* stream);
+/* yp_debug_attention under an attention form (yp_set_attention_form's values; anything else is refused like the rest, on the host): with
+   form 1 a bf16 call with kd 32, hd 64, q_stride and q_coff in multiples of 8 and more than 400 tokens takes the streaming kernel, *kernel_out
+   = 2, and wgs sets the query groups its workgroups walk; every other call behaves as under form 0, the generic kernel's token bound included.
+   yp_debug_attention is this call with form 0. */
+int yp_debug_attention_form(const void* qkv_dev, void* o_dev, int dtype, int B, int N, int nh, int kd, int hd, int q_stride, int q_coff, int o_stride,
+                            int o_coff, int wgs, int form, int* kernel_out, void* stream);
 /* Test hook: stage 1 of the top-k head alone (the top k anchors by score descending, anchor index ascending) on caller-made class-max keys,
    through the kernels an engine takes for that anchor count: head_select_kernel<1> up to 12288 anchors, head_chunk_topk_kernel +
    head_select_large_kernel<1> beyond. mk_dev[l]: device uint32 [B][hw[l][0] * hw[l][1]], the bits of the anchors' best sigmoid scores as

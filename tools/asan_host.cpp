@@ -78,6 +78,25 @@ int main() {
                 CHECK(yp_plan(e, 1, 3776, 3840) == YP_ERR_ARG && strstr(yp_last_error(), "anchors"));                    // one row past YP_MAX_ANCHORS
                 if (fam != YP_FAMILY_V8) CHECK(yp_plan(e, 1, 2560, 1472) == YP_ERR_ARG && strstr(yp_last_error(), "attention tokens"));
                 else CHECK(yp_plan(e, 1, 2560, 1472) > 0);
+                // the streaming attention form: 3680 tokens plan where the kernel's scope holds (bf16, 32-wide keys), the refusal stays elsewhere
+                CHECK(yp_set_attention_form(e, 2) == YP_ERR_ARG && yp_set_attention_form(nullptr, 1) == YP_ERR_ARG);
+                CHECK(yp_set_attention_form(e, 1) == YP_OK);
+                {
+                    const bool in_scope = fam != YP_FAMILY_V8 && d.dtype == YP_BF16 && !(fam == YP_FAMILY_V10 && d.variant == 'm');
+                    const int rc = yp_plan(e, 1, 2560, 1472);
+                    if (fam == YP_FAMILY_V8 || in_scope) {
+                        CHECK(rc > 0);
+                        bool named = false;
+                        for (int i = 0; i < rc; ++i) {
+                            char kname[256];
+                            CHECK(yp_op_kernel(e, i, kname, sizeof(kname)) == YP_OK);
+                            named |= !strcmp(kname, "attention_stream_kernel");
+                        }
+                        CHECK(named == in_scope);
+                        CHECK(yp_debug_host_selftest(e) > 0);
+                    } else CHECK(rc == YP_ERR_ARG && strstr(yp_last_error(), "attention tokens"));
+                }
+                CHECK(yp_set_attention_form(e, 0) == YP_OK);
                 {
                     const int mb = yp_max_batch(e, 1280, 1280);
                     CHECK(mb >= 1 && yp_max_batch(e, 640, 640) >= mb);

@@ -10,7 +10,12 @@ Per engine and shape: the forward eager and as hipGraph replay (frames resident 
 best and median in ms), and the per-op event timings (Engine.profile, eager, one event pair per launch) of the class-max pass, the head op
 (select or NMS kernels) and the attention op. `ratio_8x1280_vs_32x640` is the replay step of 8x1280x1280 over that of 32x640x640; the
 per-op lines say how much of the excess is the head's and how much the attention's.
-Writes profiles/large_input_latency.json."""
+Writes profiles/large_input_latency.json.
+
+--attention stream: the same engines with the PSA block's streaming kernel (Engine.set_attention_form) beside the default form, per shape
+one after the other in one process (the form is switched on one engine: same weights, same tile configurations), over the shapes above
+400 tokens plus two the default form refuses: 1x1472x2560 (3680 tokens) and 1x2176x3840, a 4K frame at its own size (8160 tokens). Each
+shape holds one record per form ("auto": the timings, or the planner's refusal). Writes profiles/large_input_latency_stream.json."""
 import argparse
 import json
 import os
@@ -23,10 +28,11 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
-from yolo_puncture_amd.engine import Engine  # noqa: E402
+from yolo_puncture_amd.engine import Engine, YolopError  # noqa: E402
 from yolo_puncture_amd.weights import synthetic_state, synthetic_state_family  # noqa: E402
 
 SHAPES = [(32, 640, 640), (8, 1280, 1280), (4, 1088, 1920), (1, 736, 1280)]
+STREAM_SHAPES = [(8, 1280, 1280), (4, 1088, 1920), (1, 736, 1280), (1, 1472, 2560), (1, 2176, 3840)]
 ENGINES = [("v10", "s", False), ("11", "n", True)]
 
 
@@ -62,15 +68,33 @@ def op_lines(ops):
     return out
 
 
+def measure(eng, im, reps):
+    B, H, W = im.shape[:3]
+    rec = {"anchors": sum((H // s) * (W // s) for s in (8, 16, 32)), "tokens": (H // 32) * (W // 32), "max_batch": eng.max_batch(H, W)}
+    eng.set_graph(False)
+    eng.forward(im)                                    # plans, tunes
+    torch.cuda.synchronize()
+    rec["eager"] = timed(lambda: eng.forward(im), reps)
+    eng.set_graph(True)
+    rec["replay"] = timed(lambda: eng.forward(im), reps)
+    eng.set_graph(False)
+    rec["ops"] = op_lines(eng.profile(im, iters=5))
+    return rec
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=30)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "large_input_latency.json"))
+    ap.add_argument("--attention", choices=("auto", "stream"), default="auto", help="stream: both forms per shape, into large_input_latency_stream.json")
+    ap.add_argument("--out", default="")
     ap.add_argument("--shapes", default="", help="comma-separated indices into the shape list (default: all)")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         sys.exit("large_input_latency.py measures on the GPU; none is visible")
-    shapes = [SHAPES[int(i)] for i in a.shapes.split(",")] if a.shapes else SHAPES
+    stream = a.attention == "stream"
+    all_shapes = STREAM_SHAPES if stream else SHAPES
+    shapes = [all_shapes[int(i)] for i in a.shapes.split(",")] if a.shapes else all_shapes
+    a.out = a.out or os.path.join(ROOT, "profiles", "large_input_latency_stream.json" if stream else "large_input_latency.json")
     res = {"device": torch.cuda.get_device_name(0), "dtype": "bf16", "reps": a.reps, "engines": {}}
     for family, variant, seg in ENGINES:
         st = synthetic_state(variant, 80, seg, seed=0, cls_bias=-3.0) if family == "v10" else synthetic_state_family(family, variant, 80, seed=0, cls_bias=-3.0)
@@ -79,15 +103,22 @@ def main():
         for B, H, W in shapes:
             g = torch.Generator().manual_seed(B * H + W)
             im = torch.randint(0, 256, (B, H, W, 3), dtype=torch.uint8, generator=g).cuda()
-            rec = {"anchors": sum((H // s) * (W // s) for s in (8, 16, 32)), "tokens": (H // 32) * (W // 32), "max_batch": eng.max_batch(H, W)}
-            eng.set_graph(False)
-            eng.forward(im)                                    # plans, tunes
-            torch.cuda.synchronize()
-            rec["eager"] = timed(lambda: eng.forward(im), a.reps)
-            eng.set_graph(True)
-            rec["replay"] = timed(lambda: eng.forward(im), a.reps)
-            eng.set_graph(False)
-            rec["ops"] = op_lines(eng.profile(im, iters=5))
+            if stream:
+                rec = {}
+                for form in ("auto", "stream"):
+                    eng.set_attention_form(form)
+                    try:
+                        rec[form] = measure(eng, im, a.reps)
+                    except YolopError as e:                    # the default form above 2368 tokens
+                        rec[form] = {"refused": str(e)}
+                    print(family + variant, f"{B}x{H}x{W}", form, json.dumps(rec[form].get("replay", rec[form])),
+                          json.dumps({k: v for k, v in rec[form].get("ops", {}).items() if k != "kernels"}), flush=True)
+                if "replay" in rec["auto"]:
+                    rec["replay_best_auto_over_stream"] = round(rec["auto"]["replay"]["best_ms"] / rec["stream"]["replay"]["best_ms"], 4)
+                    rec["attention_ms_auto_over_stream"] = round(rec["auto"]["ops"]["attention_ms"] / rec["stream"]["ops"]["attention_ms"], 2)
+                rows[f"{B}x{H}x{W}"] = rec
+                continue
+            rec = measure(eng, im, a.reps)
             rows[f"{B}x{H}x{W}"] = rec
             print(family + variant, f"{B}x{H}x{W}", json.dumps(rec["replay"]), json.dumps({k: v for k, v in rec["ops"].items() if k != "kernels"}), flush=True)
         if "32x640x640" in rows and "8x1280x1280" in rows:

@@ -160,8 +160,6 @@ constexpr int A_NT = 25;            // key tiles of 16 (N <= 400)
 constexpr int A_NPAD = 416;         // 26 tiles = 13 steps of 32 keys
 constexpr int A_MAXW = 8;           // waves per workgroup
 
-__device__ __forceinline__ int vswz(int row) { return ((row >> 1) & 3) << 1; }      // V image: 128-B rows, 32-B pairs swizzled
-
 __global__ __launch_bounds__(A_MAXW * 64) void attention_mfma_kernel(const AttnParams p, const int tiles_per_wg, const unsigned qkv_bytes) {
     __shared__ __attribute__((aligned(1024))) unsigned char lds[A_NPAD * 64 + A_NPAD * 128];
     unsigned char* const Ks = lds;                             // [A_NPAD keys][32] bf16, chunk-swizzled
@@ -307,19 +305,29 @@ static bool attention_takes_mfma(const AttnParams& p, int dtype) {
 }
 static size_t attention_generic_lds(int kd, int N) { return (size_t)(QT * kd + QT * N) * sizeof(float); }
 
-// Whether launch_attention has a kernel for p (the planner asks before anything launches); *max_tokens = the largest N it has one for
-// with p's head sizes: the generic kernel keeps a query tile's QT x N scores in LDS. Both kernels move 4 elements per access (load4 /
-// store4, the 16-B fragments of the matrix-core form), so the strides and channel offsets of both slices are multiples of 4 elements.
-bool attention_fits(const AttnParams& p, int dtype, int* max_tokens) {
+bool attention_takes_stream(const AttnParams& p, int dtype, int form) {
+    return form == ATTN_FORM_STREAM && p.N > ATTN_RESIDENT_TOKENS && attention_stream_scope(p, dtype);
+}
+
+// Whether launch_attention has a kernel for p (the planner asks before anything launches); *max_tokens = the largest N the generic kernel
+// holds with p's head sizes: it keeps a query tile's QT x N scores in LDS (the streaming form, where `form` and the call admit it, has no
+// bound). All kernels move 4 elements per access (load4 / store4, the 16-B fragments of the matrix-core forms), so the strides and
+// channel offsets of both slices are multiples of 4 elements.
+bool attention_fits(const AttnParams& p, int dtype, int* max_tokens, int form) {
     if (max_tokens) *max_tokens = (int)((150 * 1024 / sizeof(float) - (size_t)QT * p.kd) / QT);
+    if (form != ATTN_FORM_AUTO && form != ATTN_FORM_STREAM) return false;
     if ((p.q_stride | p.q_coff | p.o_stride | p.o_coff) & 3) return false;
-    if (attention_takes_mfma(p, dtype)) return true;
+    if (attention_takes_mfma(p, dtype) || attention_takes_stream(p, dtype, form)) return true;
     return attention_generic_lds(p.kd, p.N) <= 150 * 1024 && !(p.kd & 3) && !(p.hd & 3);
 }
 
-hipError_t launch_attention(const AttnParams& p, int dtype, hipStream_t st, int wgs, int* kernel_out) {
+hipError_t launch_attention(const AttnParams& p, int dtype, hipStream_t st, int wgs, int* kernel_out, int form) {
     const size_t qkv_bytes = (size_t)p.B * p.N * p.q_stride * 2;
-    if (!attention_fits(p, dtype, nullptr)) return hipErrorInvalidValue;
+    if (!attention_fits(p, dtype, nullptr, form)) return hipErrorInvalidValue;
+    if (attention_takes_stream(p, dtype, form)) {
+        if (kernel_out) *kernel_out = 2;
+        return launch_attention_stream(p, st, wgs);
+    }
     if (attention_takes_mfma(p, dtype)) {
         if (kernel_out) *kernel_out = 1;
         // query tiles per workgroup: as long as possible (K/V are staged once per workgroup) while the grid still covers the chip

@@ -63,6 +63,7 @@ struct yp_engine {
     bool graph_auto = false;              // yp_set_graph(3): replay or eager per plan, whichever a one-off timing finds faster
     std::map<std::array<int, 3>, bool> auto_replay;
     bool fuse = true;             // dw->pw fusion (YOLOP_NO_FUSE=1 disables, for A/B)
+    int attn_form = ATTN_FORM_AUTO;   // yp_set_attention_form (YOLOP_ATTN_FORM=stream at yp_create): ATTN_FORM_STREAM lets OP_ATTN take attention_stream_kernel
     bool tail = false;            // conv_dwpw TAIL form (YOLOP_TAIL=1 at yp_create enables; see make_plan)
     bool narrow_store = false;    // bf16 conv epilogues keep the 8-byte stores everywhere (YOLOP_NARROW_STORE=1 at yp_create; default: 16-byte paired stores where a launch admits them)
     bool sparse_head = true;      // v10 head: box / coefficient branches on the stage-1 winners only (YOLOP_DENSE_HEAD=1 at yp_create disables)
@@ -1126,6 +1127,15 @@ static int max_batch(const yp_engine& e, int H, int W) {
     return (int)std::min<size_t>(((1ull << 31) - 1) / per, 1u << 20);
 }
 
+// OP_ATTN's launch parameters under the current plan (pointers as they stand: null before the workspace exists)
+static AttnParams attn_params(const yp_engine& e, const Op& o, int B) {
+    const TensorDesc &ti = e.tensors[o.in.t], &to = e.tensors[o.out.t];
+    AttnParams p{};
+    p.qkv = ti.ptr; p.q_stride = ti.C; p.q_coff = o.in.coff; p.o = to.ptr; p.o_stride = to.C; p.o_coff = o.out.coff;
+    p.B = B; p.N = ti.H * ti.W; p.nh = o.nh; p.kd = o.kd; p.hd = o.hd; p.scale = 1.0f / std::sqrt((float)o.kd);
+    return p;
+}
+
 static int make_plan(yp_engine& e, int B, int H, int W) {
     if (B <= 0 || H <= 0 || W <= 0 || (H % 32) || (W % 32)) return fail(YP_ERR_ARG, "input must be [B,H,W,3] with H,W multiples of 32 (got %d,%d,%d)", B, H, W);
     if (e.planned && e.pB == B && e.pH == H && e.pW == W) return YP_OK;
@@ -1141,9 +1151,14 @@ static int make_plan(yp_engine& e, int B, int H, int W) {
         q.q_stride = ti.C; q.q_coff = o.in.coff; q.o_stride = e.tensors[o.out.t].C; q.o_coff = o.out.coff;
         q.B = B; q.N = (H / ti.sdiv) * (W / ti.sdiv); q.nh = o.nh; q.kd = o.kd; q.hd = o.hd;
         int max_tokens = 0;
-        if (!attention_fits(q, e.dtype, &max_tokens))
-            return fail(YP_ERR_ARG, "input %dx%d gives %s %d attention tokens; the attention kernels hold at most %d (a streaming form is not built)", H, W,
-                        o.name.c_str(), q.N, max_tokens);
+        if (!attention_fits(q, e.dtype, &max_tokens, e.attn_form)) {
+            // the streaming kernel's scope ends at 2^31 bytes of qkv: name that bound, not the generic kernel's token bound behind it
+            if (e.attn_form == ATTN_FORM_STREAM && B > max_batch(e, H, W)) break;
+            return fail(YP_ERR_ARG, "input %dx%d gives %s %d attention tokens; the attention kernels hold at most %d (a streaming form is not built)%s", H, W,
+                        o.name.c_str(), q.N, max_tokens,
+                        e.attn_form == ATTN_FORM_AUTO && attention_fits(q, e.dtype, nullptr, ATTN_FORM_STREAM)
+                            ? "; the streaming kernel is opt-in and holds this shape: yp_set_attention_form(e, 1), YOLOP_ATTN_FORM=stream, attention=\"stream\"" : "");
+        }
     }
     {
         const int mb = max_batch(e, H, W);
@@ -1171,6 +1186,7 @@ static int make_plan(yp_engine& e, int B, int H, int W) {
             const TensorDesc& ti = e.tensors[o.in.t];
             const double Nn = (double)ti.H * ti.W;
             o.flops = 2.0 * B * o.nh * Nn * Nn * (o.kd + o.hd);
+            if (attention_takes_stream(attn_params(e, o, B), e.dtype, e.attn_form)) o.flops += 2.0 * B * o.nh * Nn * Nn * o.kd;      // Q.K^T runs in both passes
         } else if (o.kind == OP_HEAD) {
             o.bytes = 0;                       // class-max keys + the winners' class / box rows + the outputs
             for (int l = 0; l < 3; ++l) o.bytes += (o.amax[l].t >= 0) ? view_bytes(e, o.amax[l]) : view_bytes(e, o.cls[l]);
@@ -1221,6 +1237,7 @@ static int make_plan(yp_engine& e, int B, int H, int W) {
         } else if (o.kind == OP_STEM) o.kernel = stem_kernel_name(stem_params(e, o, nullptr), e.dtype);
         else if (o.kind == OP_POOL3 && e.dtype == DT_BF16 && (o.in.C & 31) == 0) o.kernel = "sppf_pool3_bf16_kernel";
         else if (o.kind == OP_HEAD && A > (size_t)HEAD_LDS_ANCHORS) o.kernel = o.nms ? "head_nms_gather_kernel + head_nms_large_kernel" : head_large_kernel_name(0);
+        else if (o.kind == OP_ATTN && attention_takes_stream(attn_params(e, o, B), e.dtype, e.attn_form)) o.kernel = "attention_stream_kernel";
         else o.kernel = (o.kind == OP_HEAD && o.nms) ? "head_nms_kernel" : kn[o.kind];
     }
     // winners-only head (v10 top-k head, bf16): the box / coefficient branches run on the stage-1 winners inside the head op; their dense
@@ -1466,11 +1483,7 @@ static hipError_t run_op(yp_engine& e, const Op& o, const RunArgs& a, hipStream_
             return launch_upsample(p, e.dtype, st);
         }
         case OP_ATTN: {
-            const TensorDesc &ti = T(o.in), &to = T(o.out);
-            AttnParams p{};
-            p.qkv = ti.ptr; p.q_stride = ti.C; p.q_coff = o.in.coff; p.o = to.ptr; p.o_stride = to.C; p.o_coff = o.out.coff;
-            p.B = B; p.N = ti.H * ti.W; p.nh = o.nh; p.kd = o.kd; p.hd = o.hd; p.scale = 1.0f / std::sqrt((float)o.kd);
-            return launch_attention(p, e.dtype, st);
+            return launch_attention(attn_params(e, o, B), e.dtype, st, 0, nullptr, e.attn_form);
         }
         case OP_AMAX: {
             const TensorDesc &ti = T(o.in), &to = T(o.out);
@@ -2023,6 +2036,10 @@ int yp_create(const yp_model_desc* desc, int device, yp_engine** out) {
     e->desc = *desc; e->device = device; e->dtype = desc->dtype;
     e->fuse = !env_on("YOLOP_NO_FUSE");
     e->tail = env_on("YOLOP_TAIL");
+    if (const char* v = std::getenv("YOLOP_ATTN_FORM")) {
+        if (!strcmp(v, "stream")) e->attn_form = ATTN_FORM_STREAM;
+        else if (*v && strcmp(v, "auto")) return fail(YP_ERR_ARG, "YOLOP_ATTN_FORM=%s (auto | stream)", v);
+    }
     e->sparse_head = !env_on("YOLOP_DENSE_HEAD");
     e->narrow_store = env_on("YOLOP_NARROW_STORE");
     int rc = build_graph(*e);
@@ -2252,7 +2269,12 @@ static void remember_tuning(yp_engine& e) {
 static bool recall_tuning(yp_engine& e) {
     auto it = e.tuned.find({e.pB, e.pH, e.pW});
     if (it == e.tuned.end() || it->second.size() != e.ops.size()) return false;
-    for (size_t i = 0; i < e.ops.size(); ++i) { e.ops[i].cfg = it->second[i].cfg; e.ops[i].kernel = it->second[i].kernel; }
+    // (the attention op has no configuration: its kernel is the plan's decision under the engine's attention form, which may have changed
+    // since the shape was remembered - yp_set_attention_form keeps the memo)
+    for (size_t i = 0; i < e.ops.size(); ++i) {
+        e.ops[i].cfg = it->second[i].cfg;
+        if (e.ops[i].kind != OP_ATTN) e.ops[i].kernel = it->second[i].kernel;
+    }
     return true;
 }
 
@@ -2568,13 +2590,14 @@ int yp_debug_topk_anchors(const uint32_t* const mk_dev[3], int B, const int hw[3
     return YP_OK;
 }
 
-int yp_debug_attention(const void* qkv_dev, void* o_dev, int dtype, int B, int N, int nh, int kd, int hd, int q_stride, int q_coff, int o_stride,
-                       int o_coff, int wgs, int* kernel_out, void* stream) {
+int yp_debug_attention_form(const void* qkv_dev, void* o_dev, int dtype, int B, int N, int nh, int kd, int hd, int q_stride, int q_coff, int o_stride,
+                            int o_coff, int wgs, int form, int* kernel_out, void* stream) {
     if (!qkv_dev || !o_dev || !kernel_out) return fail(YP_ERR_ARG, "yp_debug_attention: null argument");
     if (dtype != YP_BF16 && dtype != YP_F32) return fail(YP_ERR_ARG, "yp_debug_attention: dtype = %d (YP_BF16 | YP_F32)", dtype);
     if (B < 1 || N < 1 || nh < 1 || kd < 1 || hd < 1 || q_stride < 1 || o_stride < 1 || q_coff < 0 || o_coff < 0 || wgs < 0)
         return fail(YP_ERR_ARG, "yp_debug_attention: non-positive size (B %d, N %d, nh %d, kd %d, hd %d, q_stride %d, q_coff %d, o_stride %d, o_coff %d, wgs %d)",
                     B, N, nh, kd, hd, q_stride, q_coff, o_stride, o_coff, wgs);
+    if (form != ATTN_FORM_AUTO && form != ATTN_FORM_STREAM) return fail(YP_ERR_ARG, "yp_debug_attention: form = %d (0 auto | 1 stream)", form);
     if ((int64_t)B * nh > 65535) return fail(YP_ERR_ARG, "yp_debug_attention: B * nh = %lld; the grid holds at most 65535", (long long)B * nh);
     if ((int64_t)q_coff + (int64_t)nh * (2 * (int64_t)kd + hd) > q_stride)
         return fail(YP_ERR_ARG, "yp_debug_attention: the qkv slice [%d, %lld) does not fit q_stride = %d", q_coff, (long long)q_coff + (long long)nh * (2 * (long long)kd + hd), q_stride);
@@ -2587,14 +2610,19 @@ int yp_debug_attention(const void* qkv_dev, void* o_dev, int dtype, int B, int N
     p.qkv = qkv_dev; p.q_stride = q_stride; p.q_coff = q_coff; p.o = o_dev; p.o_stride = o_stride; p.o_coff = o_coff;
     p.B = B; p.N = N; p.nh = nh; p.kd = kd; p.hd = hd; p.scale = 1.0f / std::sqrt((float)kd);
     int max_tokens = 0;
-    if (!attention_fits(p, dtype, &max_tokens))
+    if (!attention_fits(p, dtype, &max_tokens, form))
         return fail(YP_ERR_ARG, "yp_debug_attention: no kernel for N = %d, kd = %d, hd = %d: the attention kernels hold at most %d tokens and want kd and hd in multiples of 4",
                     N, kd, hd, max_tokens);
     hipStream_t st = (hipStream_t)stream;
-    hipError_t err = launch_attention(p, dtype, st, wgs, kernel_out);
+    hipError_t err = launch_attention(p, dtype, st, wgs, kernel_out, form);
     if (err == hipSuccess) err = hipStreamSynchronize(st);
     if (err != hipSuccess) return fail(YP_ERR_HIP, "yp_debug_attention: %s", hipGetErrorString(err));
     return YP_OK;
+}
+
+int yp_debug_attention(const void* qkv_dev, void* o_dev, int dtype, int B, int N, int nh, int kd, int hd, int q_stride, int q_coff, int o_stride,
+                       int o_coff, int wgs, int* kernel_out, void* stream) {
+    return yp_debug_attention_form(qkv_dev, o_dev, dtype, B, N, nh, kd, hd, q_stride, q_coff, o_stride, o_coff, wgs, ATTN_FORM_AUTO, kernel_out, stream);
 }
 
 int yp_tuning_source(const yp_engine* e) {
@@ -2772,6 +2800,20 @@ int yp_set_nms(yp_engine* e, float conf, float iou) {
     // (yolo_seg/app.py:91, yolo_seg/yolo_with_deva.py:51) used to pay a device sync + blocking copy per call.
     e->nms_conf = conf; e->nms_iou = iou;
     e->nms_dirty = true;
+    return YP_OK;
+}
+
+int yp_set_attention_form(yp_engine* e, int form) {
+    if (!e) return fail(YP_ERR_ARG, "null engine");
+    if (form != ATTN_FORM_AUTO && form != ATTN_FORM_STREAM) return fail(YP_ERR_ARG, "yp_set_attention_form: form = %d (0 auto | 1 stream)", form);
+    if (form == e->attn_form) return YP_OK;
+    if (e->finalized || e->arena) {      // the plan (and with it the attention op's kernel) changes under nothing in flight
+        HIPCHK(hipSetDevice(e->device));
+        HIPCHK(hipDeviceSynchronize());
+    }
+    e->attn_form = form;
+    e->planned = false;                  // the next yp_plan / yp_forward plans again (allocate_plan drops a captured graph)
+    e->auto_replay.clear();
     return YP_OK;
 }
 

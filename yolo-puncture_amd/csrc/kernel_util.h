@@ -32,6 +32,9 @@ template <int BK> __device__ __forceinline__ int cswz(int row) {
 // costs one add (row offset of the tap, usually a constant) + two bit operations; written on `row`, the compiler spent ~9 VALU instructions per
 // read (PMC on conv_tile1: VALU issue 48 % of the kernel's cycles, matrix pipe busy 30 %).
 __device__ __forceinline__ unsigned swz64(unsigned L) { return L ^ ((L >> 3) & 32u); }
+// The attention kernels' V image ([key][64] bf16, 128-B rows): XOR mask on the 16-B chunk index that moves 32-B pairs, under which the
+// transposing ds_read_b64_tr_b16 of 4 key rows x 16 d per 16-lane group is conflict-free.
+__device__ __forceinline__ int vswz(int row) { return ((row >> 1) & 3) << 1; }
 
 // XCD-aware bijective remap of the linear block id `bid` of an `nwg`-workgroup launch (blocks b, b+8, ... share an XCD / L2): each XCD
 // walks a contiguous run of the remapped ids.

@@ -71,6 +71,10 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     lib.yp_debug_topk_anchors.restype = C.c_int
     lib.yp_debug_attention.argtypes = [vp, vp] + [C.c_int] * 11 + [ip, vp]
     lib.yp_debug_attention.restype = C.c_int
+    lib.yp_debug_attention_form.argtypes = [vp, vp] + [C.c_int] * 12 + [ip, vp]
+    lib.yp_debug_attention_form.restype = C.c_int
+    lib.yp_set_attention_form.argtypes = [vp, C.c_int]
+    lib.yp_set_attention_form.restype = C.c_int
     lib.yp_op_info.argtypes = [vp, C.c_int, C.c_char_p, C.c_int, ip, C.POINTER(C.c_double), C.POINTER(C.c_double)]
     lib.yp_op_output.argtypes = [vp, C.c_int, ip, ip, ip]
     lib.yp_op_kernel.argtypes = [vp, C.c_int, C.c_char_p, C.c_int]
@@ -139,7 +143,7 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
 EXPORTS = ["yp_last_error", "yp_create", "yp_destroy", "yp_weight_count", "yp_weight_info", "yp_set_weight",
            "yp_finalize", "yp_forward", "yp_proto", "yp_masks", "yp_id_mask_resized", "yp_plan", "yp_op_info", "yp_op_output", "yp_op_input", "yp_op_fusion",
            "yp_tensor_count", "yp_tensor_info", "yp_tensor_read", "yp_profile", "yp_set_graph", "yp_run_op",
-           "yp_tensor_write", "yp_op_kernel", "yp_set_autotune", "yp_tuning_export", "yp_tuning_import", "yp_set_nms", "yp_debug_force_conv_cfg", "yp_debug_op_cfg", "yp_debug_op_form", "yp_debug_last_store_form", "yp_debug_max_workgroups", "yp_debug_conv_families", "yp_debug_ablation", "yp_debug_head_clocks", "yp_debug_head_branch_clocks", "yp_debug_head_winners", "yp_debug_contour_clocks", "yp_debug_pwsp_clocks", "yp_debug_host_selftest", "yp_debug_graph_info", "yp_tuning_source", "yp_debug_head_positions", "yp_debug_marker", "yp_max_batch", "yp_debug_topk_anchors", "yp_debug_attention", "yp_letterbox", "yp_letterbox_batch", "yp_masks_frames", "yp_masks_frames_input", "yp_mask_contours",
+           "yp_tensor_write", "yp_op_kernel", "yp_set_autotune", "yp_tuning_export", "yp_tuning_import", "yp_set_nms", "yp_debug_force_conv_cfg", "yp_debug_op_cfg", "yp_debug_op_form", "yp_debug_last_store_form", "yp_debug_max_workgroups", "yp_debug_conv_families", "yp_debug_ablation", "yp_debug_head_clocks", "yp_debug_head_branch_clocks", "yp_debug_head_winners", "yp_debug_contour_clocks", "yp_debug_pwsp_clocks", "yp_debug_host_selftest", "yp_debug_graph_info", "yp_tuning_source", "yp_debug_head_positions", "yp_debug_marker", "yp_max_batch", "yp_debug_topk_anchors", "yp_debug_attention", "yp_debug_attention_form", "yp_set_attention_form", "yp_letterbox", "yp_letterbox_batch", "yp_masks_frames", "yp_masks_frames_input", "yp_mask_contours",
            "yp_mask_contours_scaled", "yp_mask_contours_large_workspace", "yp_mask_contours_large", "yp_comm_unique_id", "yp_comm_create", "yp_allgather", "yp_comm_destroy",
            "yp_u2net_create", "yp_u2net_destroy", "yp_u2net_weight_count", "yp_u2net_weight_info", "yp_u2net_set_weight", "yp_u2net_finalize",
            "yp_u2net_forward", "yp_u2net_forward_crops", "yp_u2net_set_graph", "yp_u2net_tensor_count", "yp_u2net_tensor_info", "yp_u2net_tensor_read",
@@ -149,6 +153,13 @@ EXPORTS = ["yp_last_error", "yp_create", "yp_destroy", "yp_weight_count", "yp_we
 
 
 MAX_ANCHORS = 294912      # YP_MAX_ANCHORS
+ATTENTION_FORMS = {"auto": 0, "stream": 1}      # yp_set_attention_form
+
+
+def _attention_form(form) -> int:
+    if form not in ATTENTION_FORMS:
+        raise ValueError(f"attention form {form!r}: one of {sorted(ATTENTION_FORMS)}")
+    return ATTENTION_FORMS[form]
 
 
 def topk_anchors(mk: List[torch.Tensor], hw, k: int) -> Tuple[torch.Tensor, torch.Tensor]:
@@ -174,12 +185,12 @@ def topk_anchors(mk: List[torch.Tensor], hw, k: int) -> Tuple[torch.Tensor, torc
 
 
 def attention(qkv: torch.Tensor, nh: int, kd: int, hd: int, q_coff: int = 0, out: Optional[torch.Tensor] = None, o_coff: int = 0,
-              wgs: int = 0) -> Tuple[torch.Tensor, int]:
-    """Debug: the PSA attention core alone (yp_debug_attention) through the launcher an engine's attention op takes. qkv: device bf16 or
+              wgs: int = 0, form: str = "auto") -> Tuple[torch.Tensor, int]:
+    """Debug: the PSA attention core alone (yp_debug_attention_form) through the launcher an engine's attention op takes. qkv: device bf16 or
     float32 [B, N, q_stride], head h of a token at channels q_coff + h * (2 kd + hd) as q(kd) | k(kd) | v(hd). out: device [B, N, o_stride]
     of the same dtype (default: a new [B, N, nh * hd]); head h lands at channels o_coff + h * hd, nothing else is written. wgs > 0
-    replaces the matrix-core kernel's workgroup target for this call. Returns (out, kernel): 1 the matrix-core kernel ran, 0 the generic
-    one. Whatever the host check refuses raises YolopError before anything launches."""
+    replaces the matrix-core kernels' workgroup target for this call. form "stream": bf16 calls with kd 32, hd 64 and more than 400 tokens
+    take the streaming kernel. Returns (out, kernel): 2 the streaming kernel ran, 1 the resident matrix-core kernel, 0 the generic one. Whatever the host check refuses raises YolopError before anything launches."""
     lib = load_library()
     if qkv.dim() != 3 or qkv.dtype not in (torch.bfloat16, torch.float32) or not qkv.is_contiguous() or not qkv.is_cuda:
         raise ValueError("qkv must be a contiguous device bf16 / float32 [B, N, q_stride]")
@@ -189,8 +200,8 @@ def attention(qkv: torch.Tensor, nh: int, kd: int, hd: int, q_coff: int = 0, out
     if out.dim() != 3 or out.dtype != qkv.dtype or not out.is_contiguous() or out.device != qkv.device or tuple(out.shape[:2]) != (B, N):
         raise ValueError("out must be a contiguous [B, N, o_stride] of qkv's dtype on its device")
     kernel = C.c_int(-1)
-    rc = lib.yp_debug_attention(C.c_void_p(qkv.data_ptr()), C.c_void_p(out.data_ptr()), YP_BF16 if qkv.dtype == torch.bfloat16 else YP_F32, B, N,
-                                int(nh), int(kd), int(hd), q_stride, int(q_coff), int(out.shape[2]), int(o_coff), int(wgs), C.byref(kernel),
+    rc = lib.yp_debug_attention_form(C.c_void_p(qkv.data_ptr()), C.c_void_p(out.data_ptr()), YP_BF16 if qkv.dtype == torch.bfloat16 else YP_F32, B, N,
+                                int(nh), int(kd), int(hd), q_stride, int(q_coff), int(out.shape[2]), int(o_coff), int(wgs), _attention_form(form), C.byref(kernel),
                                 C.c_void_p(_stream_ptr(qkv.device)))
     if rc < 0:
         raise YolopError(lib.yp_last_error().decode())
@@ -381,7 +392,7 @@ class Engine:
 
     def __init__(self, variant: str = "s", nc: int = 80, seg: bool = False, dtype: str = "bf16",
                  device: int = 0, max_det: int = 300, state: Optional[Dict[str, torch.Tensor]] = None,
-                 finalize: bool = True, family: str = "v10"):
+                 finalize: bool = True, family: str = "v10", attention: Optional[str] = None):
         self.lib = load_library()
         self.variant, self.nc, self.seg, self.max_det = variant, nc, seg, max_det
         self.family = family
@@ -394,6 +405,8 @@ class Engine:
         self._chk(self.lib.yp_create(C.byref(desc), self.device_index, C.byref(self._h)))
         self._keep: List[torch.Tensor] = []
         self.finalized = False
+        if attention is not None:           # (None: what YOLOP_ATTN_FORM said when the engine was created, "auto" without it)
+            self.set_attention_form(attention)
         if state is not None:
             self.load_state(state)
             if finalize:
@@ -440,6 +453,11 @@ class Engine:
     def finalize(self) -> None:
         self._chk(self.lib.yp_finalize(self._h))
         self.finalized = True
+
+    def set_attention_form(self, form: str) -> None:
+        """"auto": the PSA block's resident matrix-core kernel up to 400 tokens, the generic kernel up to 2368, refusal beyond (the default).
+        "stream": bf16 engines with 32-wide keys run attention_stream_kernel above 400 tokens, without a token bound. Drops the current plan."""
+        self._chk(self.lib.yp_set_attention_form(self._h, _attention_form(form)))
 
     def set_autotune(self, enable: bool) -> None:
         self._chk(self.lib.yp_set_autotune(self._h, 1 if enable else 0))
