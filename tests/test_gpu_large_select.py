@@ -1,4 +1,5 @@
-"""Stage 1 of the top-k head alone (yp_debug_topk_anchors), on crafted class-max keys - the logits of a real engine cannot be crafted.
+"""Stage 1 of the top-k head alone (yp_debug_topk_anchors), on crafted class-max keys at anchor counts no input shape has (stage 2 and the
+NMS heads on crafted logits of a real engine: tests/test_gpu_head_crafted.py).
 The entry runs the kernels an engine takes for the anchor count: head_select_kernel<1> up to 12288 anchors (the control case here),
 head_chunk_topk_kernel + head_select_large_kernel<1> beyond. Reference: torch.sort of the same unique 64-bit keys
 score_bits << 32 | (0xFFFFFFFF - anchor) on the host; winners (in rank order) and the stage-1 threshold must match bit for bit, for score

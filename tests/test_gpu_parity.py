@@ -263,8 +263,9 @@ def test_winners_only_head_equals_dense(variant, seg, shape, nc, monkeypatch):
 
 
 def test_topk_adversarial():
-    """Ties and saturation: craft logits through a real engine is not possible, so drive the head kernel with an
-    engine whose class head is constant (all scores equal) -> ordering must be anchor-index then class ascending."""
+    """Ties through a whole forward: an engine whose class head is constant (all scores equal) -> ordering must be anchor-index then
+    class ascending, with fewer anchors than max_det. Crafted logits - tie groups across a cut, saturated scores, two stage-2 rounds -
+    are written over a real engine's head tensors in tests/test_gpu_head_crafted.py."""
     from oracle.yolov10_oracle import Oracle
     st, im = make_case("n", 80, False, 0, (1, 64, 64))
     for l in range(3):

@@ -2024,9 +2024,13 @@ static void install_fatal_handlers() {
     }
 }
 
+static_assert(YP_MAX_DET == HEAD_MAXK, "include/yolop.h promises what the head kernels hold (head_select.h MAXK, head_nms_common.h NMAXK)");
+
 int yp_create(const yp_model_desc* desc, int device, yp_engine** out) {
     if (!desc || !out) return fail(YP_ERR_ARG, "null argument");
-    if (desc->nc <= 0 || desc->max_det <= 0 || desc->max_det > 1024) return fail(YP_ERR_ARG, "bad nc/max_det");
+    if (desc->nc <= 0 || desc->max_det <= 0) return fail(YP_ERR_ARG, "bad nc/max_det");
+    if (desc->max_det > YP_MAX_DET)
+        return fail(YP_ERR_ARG, "max_det = %d: the head kernels rank at most %d rows per image (max_det <= %d)", desc->max_det, YP_MAX_DET, YP_MAX_DET);
     if (desc->task == YP_TASK_SEGMENT && desc->max_det > YP_MAX_MASKS)
         return fail(YP_ERR_ARG, "segmentation engines take max_det <= %d (the mask tail keeps one frame's coefficients in LDS; ultralytics' default is 300)", YP_MAX_MASKS);
     if (desc->dtype != YP_BF16 && desc->dtype != YP_F32) return fail(YP_ERR_ARG, "bad dtype");

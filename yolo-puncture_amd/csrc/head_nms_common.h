@@ -8,6 +8,7 @@ namespace yp {
 constexpr int NT = 1024;
 constexpr int NCAP = 16384;           // sorted-key capacity (power of two >= the 12288-anchor limit of the plan)
 constexpr int NMAXK = 512;
+static_assert(NMAXK == HEAD_MAXK, "one row bound for both heads: include/yolop.h YP_MAX_DET");
 
 struct NmsLocate {
     int A0, A1, A2;
