@@ -284,8 +284,9 @@ int yp_comm_destroy(yp_comm* c);
  *            which ends at 2368 tokens for 32-wide keys. v8 has no attention. An engine whose attention form is `stream`
  *            (yp_set_attention_form) runs bf16 PSA blocks with 32-wide keys and 64-wide heads - every v10 variant except M, every YOLO11
  *            variant - above 400 tokens on a matrix-core kernel that streams K and V through LDS: no token bound of its own, the anchor
- *            bound (anchors = 21 x tokens, so 14043 tokens) and the byte bound remain. fp32 engines and v10-M keep the generic kernel
- *            and its bound under either form.
+ *            bound (anchors = 21 x tokens, so 14043 tokens) and the byte bound remain. v10-M (36-wide keys, 72-wide heads) does the same
+ *            at every token count under the form `stream_wide`, which includes `stream`; under `auto` and `stream` it keeps the generic
+ *            kernel and its bound of 2364 tokens. fp32 engines keep the generic kernel and its bound under every form.
  *   bytes    every activation stays below 2^31 bytes: yp_max_batch(e, H, W) is the largest B that plans at HxW (callers split to it). */
 #define YP_MAX_ANCHORS 294912   /* 12288 * (12288 / 512): covers 3840x2176 (214200) */
 int yp_max_batch(const yp_engine* e, int H, int W);
@@ -326,8 +327,11 @@ int yp_set_nms(yp_engine* e, float conf, float iou);
 /* Attention form of the PSA block (v10 / 11): 0 auto - the default: the resident matrix-core kernel up to 400 tokens, the generic kernel up to
  * its LDS bound, refusal beyond -, 1 stream - bf16, key_dim 32, head_dim 64 above 400 tokens run attention_stream_kernel (two passes over K:
  * row max and sum, then P.V with the normalised bf16 probabilities; same rounding points as the other kernels, no token bound); whatever is
- * outside that scope runs and is refused as under 0. Any other value: YP_ERR_ARG. Allowed before or after yp_finalize; a change drops the
- * current plan (the next yp_plan / yp_forward plans again). An engine created while YOLOP_ATTN_FORM=stream is set starts in form 1. */
+ * outside that scope runs and is refused as under 0 -, 3 stream_wide - form 1, and bf16, key_dim 36, head_dim 72 (YOLOv10-M) run
+ * attention_stream_wide_kernel at every token count (the same two passes and rounding points). The value is a bit set - bit 0 the 32/64
+ * streaming kernel, bit 1 the 36/72 one, itself a streaming kernel: 2 is no form. Any other value: YP_ERR_ARG. Allowed before or after
+ * yp_finalize; a change drops the current plan (the next yp_plan / yp_forward plans again). An engine created while YOLOP_ATTN_FORM=stream
+ * (stream_wide) is set starts in form 1 (3). */
 int yp_set_attention_form(yp_engine* e, int form);
 
 /* Enable/disable the plan-time autotuner that picks the conv tile configuration per layer (default on). */
@@ -381,7 +385,8 @@ int yp_debug_attention(const void* qkv_dev, void* o_dev, int dtype, int B, int N
 /* yp_debug_attention under an attention form (yp_set_attention_form's values; anything else is refused like the rest, on the host): with
    form 1 a bf16 call with kd 32, hd 64, q_stride and q_coff in multiples of 8 and more than 400 tokens takes the streaming kernel, *kernel_out
    = 2, and wgs sets the query groups its workgroups walk; every other call behaves as under form 0, the generic kernel's token bound included.
-   yp_debug_attention is this call with form 0. */
+   Form 3 is form 1, and a bf16 call with kd 36, hd 72, q_stride and q_coff in multiples of 8 takes the wide-head streaming kernel at every
+   token count, *kernel_out = 3. yp_debug_attention is this call with form 0. */
 int yp_debug_attention_form(const void* qkv_dev, void* o_dev, int dtype, int B, int N, int nh, int kd, int hd, int q_stride, int q_coff, int o_stride,
                             int o_coff, int wgs, int form, int* kernel_out, void* stream);
 /* Test hook: stage 1 of the top-k head alone (the top k anchors by score descending, anchor index ascending) on caller-made class-max keys,

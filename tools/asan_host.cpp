@@ -96,6 +96,25 @@ int main() {
                         CHECK(yp_debug_host_selftest(e) > 0);
                     } else CHECK(rc == YP_ERR_ARG && strstr(yp_last_error(), "attention tokens"));
                 }
+                // the wide-head form: form 1's scope, and bf16 v10-M (36-wide keys) on its own kernel
+                CHECK(yp_set_attention_form(e, 3) == YP_OK);
+                {
+                    const bool narrow = fam != YP_FAMILY_V8 && d.dtype == YP_BF16 && !(fam == YP_FAMILY_V10 && d.variant == 'm');
+                    const bool wide = fam == YP_FAMILY_V10 && d.variant == 'm' && d.dtype == YP_BF16;
+                    const int rc = yp_plan(e, 1, 2560, 1472);
+                    if (fam == YP_FAMILY_V8 || narrow || wide) {
+                        CHECK(rc > 0);
+                        bool named = false, named_wide = false;
+                        for (int i = 0; i < rc; ++i) {
+                            char kname[256];
+                            CHECK(yp_op_kernel(e, i, kname, sizeof(kname)) == YP_OK);
+                            named |= !strcmp(kname, "attention_stream_kernel");
+                            named_wide |= !strcmp(kname, "attention_stream_wide_kernel");
+                        }
+                        CHECK(named == narrow && named_wide == wide);
+                        CHECK(yp_debug_host_selftest(e) > 0);
+                    } else CHECK(rc == YP_ERR_ARG && strstr(yp_last_error(), "attention tokens"));
+                }
                 CHECK(yp_set_attention_form(e, 0) == YP_OK);
                 {
                     const int mb = yp_max_batch(e, 1280, 1280);

@@ -7,7 +7,12 @@ Cases (B, N, nh): (8, 1600, 4) v10-S at 8x1280x1280, (4, 2040, 4) v10-S at 4x108
 11n at 8x1280x1280, (1, 3680, 2) 11n at 2560x1472 and (1, 8160, 2) 11n on a 4K frame at its own size. The generic kernel is timed where it
 runs (N <= 2368). TFLOP/s count the algorithm (2 B nh N^2 (kd + hd)), not the streaming kernel's second Q.K^T.
 Writes profiles/attention_stream_latency.json and exits non-zero when the streaming kernel is not faster than the generic one at
-(8, 1600, 4)."""
+(8, 1600, 4).
+
+--heads wide: the same for key_dim 36, head_dim 72 (YOLOv10-M, four heads), the generic kernel against attention_stream_wide_kernel (form
+"stream_wide"), which takes every token count. Cases: (16, 400, 4) M's packaged 16x640x640 workload, (1, 400, 4) one such image (16
+workgroups), (8, 1600, 4), (4, 2040, 4), and (1, 3680, 4), (1, 8160, 4), which the generic kernel refuses (N > 2364). Same gate, at
+(8, 1600, 4). Writes profiles/attention_stream_wide_latency.json."""
 import argparse
 import json
 import os
@@ -20,10 +25,13 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from yolo_puncture_amd.engine import attention  # noqa: E402
 
-CASES = [(8, 1600, 4), (4, 2040, 4), (1, 920, 4), (8, 1600, 2), (1, 3680, 2), (1, 8160, 2)]
 GATE = (8, 1600, 4)
+# --heads: (cases, kd, hd, the generic kernel's last N, the streaming form, its kernel_out, the output file)
+HEADS = {"narrow": ([(8, 1600, 4), (4, 2040, 4), (1, 920, 4), (8, 1600, 2), (1, 3680, 2), (1, 8160, 2)], 32, 64, 2368, "stream", 2,
+                    "attention_stream_latency.json"),
+         "wide": ([(16, 400, 4), (1, 400, 4), (8, 1600, 4), (4, 2040, 4), (1, 3680, 4), (1, 8160, 4)], 36, 72, 2364, "stream_wide", 3,
+                  "attention_stream_wide_latency.json")}
 KD, HD = 32, 64
-GENERIC_MAX_TOKENS = 2368
 
 
 def batch_ms(qkv, out, nh, form, launches):
@@ -40,8 +48,12 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--launches", type=int, default=20)
     ap.add_argument("--rounds", type=int, default=5)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "attention_stream_latency.json"))
+    ap.add_argument("--heads", choices=sorted(HEADS), default="narrow", help="wide: key_dim 36, head_dim 72 under the form stream_wide")
+    ap.add_argument("--out", default="")
     a = ap.parse_args()
+    global KD, HD
+    CASES, KD, HD, GENERIC_MAX_TOKENS, stream_form, stream_kernel, out_name = HEADS[a.heads]
+    a.out = a.out or os.path.join(ROOT, "profiles", out_name)
     if not torch.cuda.is_available():
         sys.exit("attention_latency.py measures on the GPU; none is visible")
     if a.launches < 20:
@@ -51,8 +63,8 @@ def main():
         g = torch.Generator().manual_seed(B * 100003 + N * 7 + nh)
         qkv = torch.randn((B, N, nh * (2 * KD + HD)), generator=g).to(torch.bfloat16).cuda()
         out = torch.empty((B, N, nh * HD), dtype=torch.bfloat16, device="cuda")
-        forms = (["auto"] if N <= GENERIC_MAX_TOKENS else []) + ["stream"]
-        want = {"auto": 0, "stream": 2}
+        forms = (["auto"] if N <= GENERIC_MAX_TOKENS else []) + [stream_form]
+        want = {"auto": 0, stream_form: stream_kernel}
         for f in forms:                                            # warm-up (and: each form takes the kernel this file is about)
             for _ in range(3):
                 assert attention(qkv, nh, KD, HD, out=out, form=f)[1] == want[f]
@@ -62,7 +74,7 @@ def main():
                 ts[f].append(batch_ms(qkv, out, nh, f, a.launches))
         flop = 2.0 * B * nh * N * N * (KD + HD)
         rec = {}
-        for f, name in (("auto", "generic"), ("stream", "stream")):
+        for f, name in (("auto", "generic"), (stream_form, "stream")):
             if f in ts:
                 best = min(ts[f])
                 rec[name] = {"best_ms": round(best, 4), "median_ms": round(statistics.median(ts[f]), 4), "tflops_at_best": round(flop / best * 1e-9, 2)}

@@ -15,7 +15,11 @@ Writes profiles/large_input_latency.json.
 --attention stream: the same engines with the PSA block's streaming kernel (Engine.set_attention_form) beside the default form, per shape
 one after the other in one process (the form is switched on one engine: same weights, same tile configurations), over the shapes above
 400 tokens plus two the default form refuses: 1x1472x2560 (3680 tokens) and 1x2176x3840, a 4K frame at its own size (8160 tokens). Each
-shape holds one record per form ("auto": the timings, or the planner's refusal). Writes profiles/large_input_latency_stream.json."""
+shape holds one record per form ("auto": the timings, or the planner's refusal). Writes profiles/large_input_latency_stream.json.
+
+--attention stream_wide: the same comparison for a YOLOv10-M detect engine (key_dim 36, head_dim 72: attention_stream_wide_kernel at every
+token count) at 16x640x640 (its packaged workload, 400 tokens), 8x1280x1280, 1x1472x2560 and 1x2176x3840; the default form refuses the
+last two (above 2364 tokens). Writes profiles/large_input_latency_stream_wide.json."""
 import argparse
 import json
 import os
@@ -33,7 +37,9 @@ from yolo_puncture_amd.weights import synthetic_state, synthetic_state_family  #
 
 SHAPES = [(32, 640, 640), (8, 1280, 1280), (4, 1088, 1920), (1, 736, 1280)]
 STREAM_SHAPES = [(8, 1280, 1280), (4, 1088, 1920), (1, 736, 1280), (1, 1472, 2560), (1, 2176, 3840)]
+WIDE_SHAPES = [(16, 640, 640), (8, 1280, 1280), (1, 1472, 2560), (1, 2176, 3840)]
 ENGINES = [("v10", "s", False), ("11", "n", True)]
+WIDE_ENGINES = [("v10", "m", False)]
 
 
 def timed(fn, reps, warm=3):
@@ -85,18 +91,20 @@ def measure(eng, im, reps):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=30)
-    ap.add_argument("--attention", choices=("auto", "stream"), default="auto", help="stream: both forms per shape, into large_input_latency_stream.json")
+    ap.add_argument("--attention", choices=("auto", "stream", "stream_wide"), default="auto",
+                    help="stream / stream_wide: both forms per shape, into large_input_latency_stream.json / large_input_latency_stream_wide.json")
     ap.add_argument("--out", default="")
     ap.add_argument("--shapes", default="", help="comma-separated indices into the shape list (default: all)")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         sys.exit("large_input_latency.py measures on the GPU; none is visible")
-    stream = a.attention == "stream"
-    all_shapes = STREAM_SHAPES if stream else SHAPES
+    stream = a.attention != "auto"
+    all_shapes = {"auto": SHAPES, "stream": STREAM_SHAPES, "stream_wide": WIDE_SHAPES}[a.attention]
     shapes = [all_shapes[int(i)] for i in a.shapes.split(",")] if a.shapes else all_shapes
-    a.out = a.out or os.path.join(ROOT, "profiles", "large_input_latency_stream.json" if stream else "large_input_latency.json")
+    a.out = a.out or os.path.join(ROOT, "profiles", {"auto": "large_input_latency.json", "stream": "large_input_latency_stream.json",
+                                                     "stream_wide": "large_input_latency_stream_wide.json"}[a.attention])
     res = {"device": torch.cuda.get_device_name(0), "dtype": "bf16", "reps": a.reps, "engines": {}}
-    for family, variant, seg in ENGINES:
+    for family, variant, seg in (WIDE_ENGINES if a.attention == "stream_wide" else ENGINES):
         st = synthetic_state(variant, 80, seg, seed=0, cls_bias=-3.0) if family == "v10" else synthetic_state_family(family, variant, 80, seed=0, cls_bias=-3.0)
         eng = Engine(variant, 80, seg, "bf16", 0, state=st, family=family)
         rows = {}
@@ -105,7 +113,7 @@ def main():
             im = torch.randint(0, 256, (B, H, W, 3), dtype=torch.uint8, generator=g).cuda()
             if stream:
                 rec = {}
-                for form in ("auto", "stream"):
+                for form in ("auto", a.attention):
                     eng.set_attention_form(form)
                     try:
                         rec[form] = measure(eng, im, a.reps)
@@ -114,8 +122,8 @@ def main():
                     print(family + variant, f"{B}x{H}x{W}", form, json.dumps(rec[form].get("replay", rec[form])),
                           json.dumps({k: v for k, v in rec[form].get("ops", {}).items() if k != "kernels"}), flush=True)
                 if "replay" in rec["auto"]:
-                    rec["replay_best_auto_over_stream"] = round(rec["auto"]["replay"]["best_ms"] / rec["stream"]["replay"]["best_ms"], 4)
-                    rec["attention_ms_auto_over_stream"] = round(rec["auto"]["ops"]["attention_ms"] / rec["stream"]["ops"]["attention_ms"], 2)
+                    rec["replay_best_auto_over_stream"] = round(rec["auto"]["replay"]["best_ms"] / rec[a.attention]["replay"]["best_ms"], 4)
+                    rec["attention_ms_auto_over_stream"] = round(rec["auto"]["ops"]["attention_ms"] / rec[a.attention]["ops"]["attention_ms"], 2)
                 rows[f"{B}x{H}x{W}"] = rec
                 continue
             rec = measure(eng, im, a.reps)

@@ -306,18 +306,21 @@ static bool attention_takes_mfma(const AttnParams& p, int dtype) {
 static size_t attention_generic_lds(int kd, int N) { return (size_t)(QT * kd + QT * N) * sizeof(float); }
 
 bool attention_takes_stream(const AttnParams& p, int dtype, int form) {
-    return form == ATTN_FORM_STREAM && p.N > ATTN_RESIDENT_TOKENS && attention_stream_scope(p, dtype);
+    return attn_form_valid(form) && (form & ATTN_FORM_STREAM) && p.N > ATTN_RESIDENT_TOKENS && attention_stream_scope(p, dtype);
+}
+bool attention_takes_stream_wide(const AttnParams& p, int dtype, int form) {
+    return form == ATTN_FORM_STREAM_WIDE && attention_stream_wide_scope(p, dtype);
 }
 
 // Whether launch_attention has a kernel for p (the planner asks before anything launches); *max_tokens = the largest N the generic kernel
-// holds with p's head sizes: it keeps a query tile's QT x N scores in LDS (the streaming form, where `form` and the call admit it, has no
+// holds with p's head sizes: it keeps a query tile's QT x N scores in LDS (the streaming forms, where `form` and the call admit one, have no
 // bound). All kernels move 4 elements per access (load4 / store4, the 16-B fragments of the matrix-core forms), so the strides and
 // channel offsets of both slices are multiples of 4 elements.
 bool attention_fits(const AttnParams& p, int dtype, int* max_tokens, int form) {
     if (max_tokens) *max_tokens = (int)((150 * 1024 / sizeof(float) - (size_t)QT * p.kd) / QT);
-    if (form != ATTN_FORM_AUTO && form != ATTN_FORM_STREAM) return false;
+    if (!attn_form_valid(form)) return false;
     if ((p.q_stride | p.q_coff | p.o_stride | p.o_coff) & 3) return false;
-    if (attention_takes_mfma(p, dtype) || attention_takes_stream(p, dtype, form)) return true;
+    if (attention_takes_mfma(p, dtype) || attention_takes_stream(p, dtype, form) || attention_takes_stream_wide(p, dtype, form)) return true;
     return attention_generic_lds(p.kd, p.N) <= 150 * 1024 && !(p.kd & 3) && !(p.hd & 3);
 }
 
@@ -327,6 +330,10 @@ hipError_t launch_attention(const AttnParams& p, int dtype, hipStream_t st, int 
     if (attention_takes_stream(p, dtype, form)) {
         if (kernel_out) *kernel_out = 2;
         return launch_attention_stream(p, st, wgs);
+    }
+    if (attention_takes_stream_wide(p, dtype, form)) {
+        if (kernel_out) *kernel_out = 3;
+        return launch_attention_stream_wide(p, st, wgs);
     }
     if (attention_takes_mfma(p, dtype)) {
         if (kernel_out) *kernel_out = 1;

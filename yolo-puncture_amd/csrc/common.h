@@ -365,17 +365,25 @@ hipError_t launch_upsample(const UpParams& p, int dtype, hipStream_t st);
 // wgs > 0: the matrix-core form's workgroup target for this call (0: YOLOP_ATTN_WGS, else 256); *kernel_out = 1 matrix-core form, 0 generic
 // Attention form of an engine (yp_set_attention_form): AUTO = the resident matrix-core kernel up to 400 tokens, the generic kernel beyond;
 // STREAM = calls in attention_stream_scope with more than 400 tokens take attention_stream_kernel (no token bound), the rest is AUTO.
-enum AttnForm { ATTN_FORM_AUTO = 0, ATTN_FORM_STREAM = 1 };
+// STREAM_WIDE = STREAM, and calls in attention_stream_wide_scope (key_dim 36, head_dim 72) take attention_stream_wide_kernel at every
+// token count. The value is a bit set: bit 0 the streaming kernel for 32/64 heads, bit 1 the wide-head one, which is a streaming kernel
+// too: bit 1 alone is no form.
+enum AttnForm { ATTN_FORM_AUTO = 0, ATTN_FORM_STREAM = 1, ATTN_FORM_STREAM_WIDE = 3 };
+inline bool attn_form_valid(int form) { return form == ATTN_FORM_AUTO || form == ATTN_FORM_STREAM || form == ATTN_FORM_STREAM_WIDE; }
 constexpr int ATTN_RESIDENT_TOKENS = 400;
-// kernel_out: 0 generic, 1 resident matrix-core, 2 streaming matrix-core
+// kernel_out: 0 generic, 1 resident matrix-core, 2 streaming matrix-core, 3 streaming matrix-core for 36/72 heads
 hipError_t launch_attention(const AttnParams& p, int dtype, hipStream_t st, int wgs = 0, int* kernel_out = nullptr, int form = ATTN_FORM_AUTO);
 // the predicate of launch_attention, for the planner; *max_tokens = the generic kernel's bound for p's head sizes
 bool attention_fits(const AttnParams& p, int dtype, int* max_tokens, int form = ATTN_FORM_AUTO);
 bool attention_takes_stream(const AttnParams& p, int dtype, int form);     // launch_attention would launch attention_stream_kernel
+bool attention_takes_stream_wide(const AttnParams& p, int dtype, int form);    // ... attention_stream_wide_kernel
 // attention_stream.hip
 bool attention_stream_scope(const AttnParams& p, int dtype);
 void attention_stream_split(int B, int N, int nh, int wgs, int* nsplit_out, int* gpw_out);
 hipError_t launch_attention_stream(const AttnParams& p, hipStream_t st, int wgs);
+// attention_stream_wide.hip
+bool attention_stream_wide_scope(const AttnParams& p, int dtype);
+hipError_t launch_attention_stream_wide(const AttnParams& p, hipStream_t st, int wgs);
 // conv_small.hip: fp32 3x3 for small maps (four waves split K, operands straight from L2)
 bool conv_small_valid(const ConvParams& p, int dtype);
 hipError_t launch_conv_small(const ConvParams& p, int dtype, hipStream_t st);

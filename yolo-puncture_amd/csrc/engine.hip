@@ -63,7 +63,7 @@ struct yp_engine {
     bool graph_auto = false;              // yp_set_graph(3): replay or eager per plan, whichever a one-off timing finds faster
     std::map<std::array<int, 3>, bool> auto_replay;
     bool fuse = true;             // dw->pw fusion (YOLOP_NO_FUSE=1 disables, for A/B)
-    int attn_form = ATTN_FORM_AUTO;   // yp_set_attention_form (YOLOP_ATTN_FORM=stream at yp_create): ATTN_FORM_STREAM lets OP_ATTN take attention_stream_kernel
+    int attn_form = ATTN_FORM_AUTO;   // yp_set_attention_form (YOLOP_ATTN_FORM=stream at yp_create): the stream bit lets OP_ATTN take attention_stream_kernel, ATTN_FORM_STREAM_WIDE attention_stream_wide_kernel too
     bool tail = false;            // conv_dwpw TAIL form (YOLOP_TAIL=1 at yp_create enables; see make_plan)
     bool narrow_store = false;    // bf16 conv epilogues keep the 8-byte stores everywhere (YOLOP_NARROW_STORE=1 at yp_create; default: 16-byte paired stores where a launch admits them)
     bool sparse_head = true;      // v10 head: box / coefficient branches on the stage-1 winners only (YOLOP_DENSE_HEAD=1 at yp_create disables)
@@ -1152,12 +1152,14 @@ static int make_plan(yp_engine& e, int B, int H, int W) {
         q.B = B; q.N = (H / ti.sdiv) * (W / ti.sdiv); q.nh = o.nh; q.kd = o.kd; q.hd = o.hd;
         int max_tokens = 0;
         if (!attention_fits(q, e.dtype, &max_tokens, e.attn_form)) {
-            // the streaming kernel's scope ends at 2^31 bytes of qkv: name that bound, not the generic kernel's token bound behind it
-            if (e.attn_form == ATTN_FORM_STREAM && B > max_batch(e, H, W)) break;
+            // the streaming kernels' scope ends at 2^31 bytes of qkv: name that bound, not the generic kernel's token bound behind it
+            if ((e.attn_form & ATTN_FORM_STREAM) && B > max_batch(e, H, W)) break;
             return fail(YP_ERR_ARG, "input %dx%d gives %s %d attention tokens; the attention kernels hold at most %d (a streaming form is not built)%s", H, W,
                         o.name.c_str(), q.N, max_tokens,
                         e.attn_form == ATTN_FORM_AUTO && attention_fits(q, e.dtype, nullptr, ATTN_FORM_STREAM)
-                            ? "; the streaming kernel is opt-in and holds this shape: yp_set_attention_form(e, 1), YOLOP_ATTN_FORM=stream, attention=\"stream\"" : "");
+                            ? "; the streaming kernel is opt-in and holds this shape: yp_set_attention_form(e, 1), YOLOP_ATTN_FORM=stream, attention=\"stream\""
+                        : e.attn_form != ATTN_FORM_STREAM_WIDE && attention_fits(q, e.dtype, nullptr, ATTN_FORM_STREAM_WIDE)
+                            ? "; the wide-head streaming kernel is opt-in and holds this shape: yp_set_attention_form(e, 3), YOLOP_ATTN_FORM=stream_wide, attention=\"stream_wide\"" : "");
         }
     }
     {
@@ -1186,7 +1188,9 @@ static int make_plan(yp_engine& e, int B, int H, int W) {
             const TensorDesc& ti = e.tensors[o.in.t];
             const double Nn = (double)ti.H * ti.W;
             o.flops = 2.0 * B * o.nh * Nn * Nn * (o.kd + o.hd);
-            if (attention_takes_stream(attn_params(e, o, B), e.dtype, e.attn_form)) o.flops += 2.0 * B * o.nh * Nn * Nn * o.kd;      // Q.K^T runs in both passes
+            const AttnParams ap = attn_params(e, o, B);
+            if (attention_takes_stream(ap, e.dtype, e.attn_form) || attention_takes_stream_wide(ap, e.dtype, e.attn_form))
+                o.flops += 2.0 * B * o.nh * Nn * Nn * o.kd;      // Q.K^T runs in both passes
         } else if (o.kind == OP_HEAD) {
             o.bytes = 0;                       // class-max keys + the winners' class / box rows + the outputs
             for (int l = 0; l < 3; ++l) o.bytes += (o.amax[l].t >= 0) ? view_bytes(e, o.amax[l]) : view_bytes(e, o.cls[l]);
@@ -1238,6 +1242,7 @@ static int make_plan(yp_engine& e, int B, int H, int W) {
         else if (o.kind == OP_POOL3 && e.dtype == DT_BF16 && (o.in.C & 31) == 0) o.kernel = "sppf_pool3_bf16_kernel";
         else if (o.kind == OP_HEAD && A > (size_t)HEAD_LDS_ANCHORS) o.kernel = o.nms ? "head_nms_gather_kernel + head_nms_large_kernel" : head_large_kernel_name(0);
         else if (o.kind == OP_ATTN && attention_takes_stream(attn_params(e, o, B), e.dtype, e.attn_form)) o.kernel = "attention_stream_kernel";
+        else if (o.kind == OP_ATTN && attention_takes_stream_wide(attn_params(e, o, B), e.dtype, e.attn_form)) o.kernel = "attention_stream_wide_kernel";
         else o.kernel = (o.kind == OP_HEAD && o.nms) ? "head_nms_kernel" : kn[o.kind];
     }
     // winners-only head (v10 top-k head, bf16): the box / coefficient branches run on the stage-1 winners inside the head op; their dense
@@ -2042,7 +2047,8 @@ int yp_create(const yp_model_desc* desc, int device, yp_engine** out) {
     e->tail = env_on("YOLOP_TAIL");
     if (const char* v = std::getenv("YOLOP_ATTN_FORM")) {
         if (!strcmp(v, "stream")) e->attn_form = ATTN_FORM_STREAM;
-        else if (*v && strcmp(v, "auto")) return fail(YP_ERR_ARG, "YOLOP_ATTN_FORM=%s (auto | stream)", v);
+        else if (!strcmp(v, "stream_wide")) e->attn_form = ATTN_FORM_STREAM_WIDE;
+        else if (*v && strcmp(v, "auto")) return fail(YP_ERR_ARG, "YOLOP_ATTN_FORM=%s (auto | stream | stream_wide)", v);
     }
     e->sparse_head = !env_on("YOLOP_DENSE_HEAD");
     e->narrow_store = env_on("YOLOP_NARROW_STORE");
@@ -2601,7 +2607,7 @@ int yp_debug_attention_form(const void* qkv_dev, void* o_dev, int dtype, int B, 
     if (B < 1 || N < 1 || nh < 1 || kd < 1 || hd < 1 || q_stride < 1 || o_stride < 1 || q_coff < 0 || o_coff < 0 || wgs < 0)
         return fail(YP_ERR_ARG, "yp_debug_attention: non-positive size (B %d, N %d, nh %d, kd %d, hd %d, q_stride %d, q_coff %d, o_stride %d, o_coff %d, wgs %d)",
                     B, N, nh, kd, hd, q_stride, q_coff, o_stride, o_coff, wgs);
-    if (form != ATTN_FORM_AUTO && form != ATTN_FORM_STREAM) return fail(YP_ERR_ARG, "yp_debug_attention: form = %d (0 auto | 1 stream)", form);
+    if (!attn_form_valid(form)) return fail(YP_ERR_ARG, "yp_debug_attention: form = %d (0 auto | 1 stream | 3 stream_wide)", form);
     if ((int64_t)B * nh > 65535) return fail(YP_ERR_ARG, "yp_debug_attention: B * nh = %lld; the grid holds at most 65535", (long long)B * nh);
     if ((int64_t)q_coff + (int64_t)nh * (2 * (int64_t)kd + hd) > q_stride)
         return fail(YP_ERR_ARG, "yp_debug_attention: the qkv slice [%d, %lld) does not fit q_stride = %d", q_coff, (long long)q_coff + (long long)nh * (2 * (long long)kd + hd), q_stride);
@@ -2809,7 +2815,7 @@ int yp_set_nms(yp_engine* e, float conf, float iou) {
 
 int yp_set_attention_form(yp_engine* e, int form) {
     if (!e) return fail(YP_ERR_ARG, "null engine");
-    if (form != ATTN_FORM_AUTO && form != ATTN_FORM_STREAM) return fail(YP_ERR_ARG, "yp_set_attention_form: form = %d (0 auto | 1 stream)", form);
+    if (!attn_form_valid(form)) return fail(YP_ERR_ARG, "yp_set_attention_form: form = %d (0 auto | 1 stream | 3 stream_wide)", form);
     if (form == e->attn_form) return YP_OK;
     if (e->finalized || e->arena) {      // the plan (and with it the attention op's kernel) changes under nothing in flight
         HIPCHK(hipSetDevice(e->device));

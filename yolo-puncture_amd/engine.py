@@ -153,7 +153,7 @@ EXPORTS = ["yp_last_error", "yp_create", "yp_destroy", "yp_weight_count", "yp_we
 
 
 MAX_ANCHORS = 294912      # YP_MAX_ANCHORS
-ATTENTION_FORMS = {"auto": 0, "stream": 1}      # yp_set_attention_form
+ATTENTION_FORMS = {"auto": 0, "stream": 1, "stream_wide": 3}      # yp_set_attention_form (bit 0: 32/64 streaming kernel, bit 1: 36/72)
 
 
 def _attention_form(form) -> int:
@@ -190,7 +190,8 @@ def attention(qkv: torch.Tensor, nh: int, kd: int, hd: int, q_coff: int = 0, out
     float32 [B, N, q_stride], head h of a token at channels q_coff + h * (2 kd + hd) as q(kd) | k(kd) | v(hd). out: device [B, N, o_stride]
     of the same dtype (default: a new [B, N, nh * hd]); head h lands at channels o_coff + h * hd, nothing else is written. wgs > 0
     replaces the matrix-core kernels' workgroup target for this call. form "stream": bf16 calls with kd 32, hd 64 and more than 400 tokens
-    take the streaming kernel. Returns (out, kernel): 2 the streaming kernel ran, 1 the resident matrix-core kernel, 0 the generic one. Whatever the host check refuses raises YolopError before anything launches."""
+    take the streaming kernel; form "stream_wide": those too, and bf16 calls with kd 36, hd 72 take the wide-head streaming kernel at every token
+    count. Returns (out, kernel): 3 the wide-head streaming kernel ran, 2 the streaming kernel, 1 the resident matrix-core kernel, 0 the generic one. Whatever the host check refuses raises YolopError before anything launches."""
     lib = load_library()
     if qkv.dim() != 3 or qkv.dtype not in (torch.bfloat16, torch.float32) or not qkv.is_contiguous() or not qkv.is_cuda:
         raise ValueError("qkv must be a contiguous device bf16 / float32 [B, N, q_stride]")
@@ -456,7 +457,8 @@ class Engine:
 
     def set_attention_form(self, form: str) -> None:
         """"auto": the PSA block's resident matrix-core kernel up to 400 tokens, the generic kernel up to 2368, refusal beyond (the default).
-        "stream": bf16 engines with 32-wide keys run attention_stream_kernel above 400 tokens, without a token bound. Drops the current plan."""
+        "stream": bf16 engines with 32-wide keys run attention_stream_kernel above 400 tokens, without a token bound. "stream_wide": that, and
+        bf16 engines with 36-wide keys and 72-wide heads (YOLOv10-M) run attention_stream_wide_kernel at every token count. Drops the current plan."""
         self._chk(self.lib.yp_set_attention_form(self._h, _attention_form(form)))
 
     def set_autotune(self, enable: bool) -> None:

@@ -359,7 +359,7 @@ class YOLO:
         self.dtype = dtype
         if attention not in ATTENTION_FORMS:
             raise ValueError(f"attention={attention!r}: one of {sorted(ATTENTION_FORMS)}")
-        self.attention = attention          # "stream": the PSA block's streaming kernel above 400 tokens (Engine.set_attention_form)
+        self.attention = attention          # "stream" / "stream_wide": the PSA block's streaming kernels (Engine.set_attention_form)
         self.family = "v10"
         if self.ckpt_path.startswith("synthetic:"):
             spec = self.ckpt_path.split(":", 1)[1]              # "s", "s-seg" (YOLOv10) ; "v8n-seg", "11x-seg" (the app's families)
