@@ -389,6 +389,18 @@ int yp_debug_attention(const void* qkv_dev, void* o_dev, int dtype, int B, int N
    token count, *kernel_out = 3. yp_debug_attention is this call with form 0. */
 int yp_debug_attention_form(const void* qkv_dev, void* o_dev, int dtype, int B, int N, int nh, int kd, int hd, int q_stride, int q_coff, int o_stride,
                             int o_coff, int wgs, int form, int* kernel_out, void* stream);
+/* Test hook: one 3x3 / stride-2 / pad-1 bf16 convolution alone through the stride-2 halo family (conv_halo_s2.hip), y = act(W * x + bias)
+   [+ res], under configuration id `cfg` of that family (500 ...). x_dev: device bf16 [B][H][W][Cin]; w_dev: device bf16 [Cout][3][3][Cin];
+   bias_dev: device float [Cout]; res_dev: device bf16 [B][H/2][W/2][Cout] or null; y_dev: device [B][H/2][W/2][Cout], float when out_f32,
+   else bf16; silu: 1 = SiLU, 0 = no activation. lds_weights: 1 = the launch keeps its weights in LDS (as under YOLOP_S2_LDS_WEIGHTS=1),
+   0 = the launcher's own pick: the register-weights instance of ids 500 / 501 where Cin is 32 or 64. Returns after the stream has
+   drained. YP_ERR_ARG (nothing launched) on non-positive sizes, an id outside the family and a shape the id's validity predicate
+   refuses. With x_dev, w_dev, bias_dev and y_dev all null the call is host-only: it applies the same checks (res_dev null or not says
+   whether a residual is asked for) and launches nothing. *lds_out (may be null) receives the dynamic LDS bytes of the launch whenever
+   the id belongs to the family, kernel_out (may be null) the kernel symbol of an admitted launch. */
+int yp_debug_conv_s2(const void* x_dev, const void* w_dev, const float* bias_dev, const void* res_dev, void* y_dev, int out_f32, int B, int H,
+                     int W, int Cin, int Cout, int silu, int cfg, int lds_weights, int64_t* lds_out, char* kernel_out, int kernel_cap,
+                     void* stream);
 /* Test hook: stage 1 of the top-k head alone (the top k anchors by score descending, anchor index ascending) on caller-made class-max keys,
    through the kernels an engine takes for that anchor count: head_select_kernel<1> up to 12288 anchors, head_chunk_topk_kernel +
    head_select_large_kernel<1> beyond. mk_dev[l]: device uint32 [B][hw[l][0] * hw[l][1]], the bits of the anchors' best sigmoid scores as

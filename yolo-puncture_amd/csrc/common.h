@@ -351,6 +351,8 @@ extern const ConvFamily conv_dma_family, conv_halo_family, conv_halo_p_family, c
 constexpr int kNumConvFamilies = 12;
 extern const ConvFamily* const kConvFamilies[kNumConvFamilies];
 int conv_halo_s2_pw_cfg(const ConvParams& p);          // configuration for the fused trailing-1x1 form, or -1
+size_t conv_halo_s2_lds_bytes(const ConvParams& p, int c);   // dynamic LDS of the launch of configuration c (id - 500) of conv_halo_s2 for p, 0 = no such c
+int conv_halo_s2_lds_weights(int on);                  // 1 = conv_halo_s2 keeps its weights in LDS everywhere (A/B, tests), 0 = off, < 0 = read; returns the previous value
 hipError_t launch_dwconv(const DwParams& p, int dtype, hipStream_t st);
 std::string dwconv_kernel_name(const DwParams& p, int dtype);    // the kernel launch_dwconv runs for p
 hipError_t launch_stem(const StemParams& p, int dtype, hipStream_t st);

@@ -1,4 +1,5 @@
-// Stride-2 member of the halo family (see conv_halo_p.hip): 3x3, stride 2, pad 1, bf16, persistent, weights resident in LDS.
+// Stride-2 member of the halo family (see conv_halo_p.hip): 3x3, stride 2, pad 1, bf16, persistent, weights resident in LDS or, for
+// Cin = 32 / 64 under ids 500 / 501, in registers.
 //
 // The im2col form of a stride-2 3x3 re-reads every input pixel 2.25 times through the 1-KiB LDS-DMA pieces and streams
 // it a k-step at a time (model.1 / model.3 / model.17: 100 / 80 / 35 us at 3.1 / 2.0 / 1.9 TB/s). Here the input patch of
@@ -11,13 +12,26 @@
 // Rows: input row jr = 2r + ky serves output row r; an even input row feeds (r = jr/2, ky = 0) and (r = jr/2 - 1, ky = 2),
 // an odd one (r = (jr-1)/2, ky = 1), so each fragment read still feeds up to 2*FN MFMAs.
 // vmcnt accounting, persistence, epilogue: identical to conv_halo_p.hip.
+//
+// Register-weights forms (a ninth template argument = the number of 32-channel chunks). With the weights in LDS a wave reads 3 * FN
+// weight fragments and 2 * FM + 1 pixel fragments per kx for 3 * FM * FN MFMAs: two thirds of the LDS read bytes of <1,2,4,2> are
+// weights that are the same for every tile a workgroup walks. These forms stage the workgroup's slab once, a chunk at a time, through
+// the (still unused) halo ring and keep each wave's 9 * chunks * FN fragments in registers (at most 144 VGPRs; one workgroup per CU =
+// two waves per SIMD, as conv_wreg.hip). LDS then holds the ring alone, which admits tiles the weights excluded: 8 rows x 64 channels
+// for Cin = 64, and 4 rows x 128 channels (<2,2,2,4>) - one channel block for a 128-wide layer, so every input tile is fetched by one
+// workgroup instead of two. They are no configuration ids: a launch of id 500 / 501 with Cin = 32 / 64 takes them (halo_s2_form;
+// YOLOP_S2_LDS_WEIGHTS=1 keeps the LDS forms). model.3 of v10-S under id 501: 60 us (LDS) -> 52-54 (<1,2,4,2>, registers) -> 46.5
+// (<2,2,2,4>, what it launches now). The k order of every output element (chunk, kx, ky) is that of the LDS forms: the results are
+// bit-identical (tests/test_gpu_halo_s2_wreg.py).
 #include "common.h"
 
 namespace yp {
 
-template <int FM, int FN, int WGM, int WGN, int NSH, bool HAS_RES, bool OUT_F32, bool PW2>
-__global__ __launch_bounds__(WGM * WGN * 64) void conv_halo_s2_kernel(const ConvParams p, const int tiles_h, const int tiles_w,
-                                                                    const int ntiles, const int G) {
+constexpr int kS2WregMaxVgprs = 144;      // weight registers of a wave in a register-weights form (two waves per SIMD, 256 VGPRs each)
+
+// The kernel body of both forms. NCH = 0: weights resident in LDS, the chunk count is p.Cin / 32; NCH > 0: register weights for NCH chunks.
+template <int FM, int FN, int WGM, int WGN, int NSH, bool HAS_RES, bool OUT_F32, bool PW2, int NCH>
+__device__ __forceinline__ void conv_halo_s2_body(const ConvParams& p, const int tiles_h, const int tiles_w, const int ntiles, const int G) {
     constexpr int NW = WGM * WGN;
     constexpr int TH = WGM * FM, BN = WGN * FN * 16;
     constexpr int HR = 2 * TH + 1;                     // input rows of the patch
@@ -26,19 +40,21 @@ __global__ __launch_bounds__(WGM * WGN * 64) void conv_halo_s2_kernel(const Conv
     constexpr int LH = (H_INSTR + NW - 1) / NW;
     constexpr int HB = H_INSTR * 1024;
     constexpr int S = FM * FN;                        // stores per wave per tile
+    constexpr bool WREG = NCH > 0;                    // (the chunk count is then a constant: the register array is indexed by it)
+    static_assert(!WREG || (!PW2 && 9 * NCH * FN * 4 <= kS2WregMaxVgprs), "register-weights form");
     static_assert(NSH == 3, "wait selection below is written for a 3-slot ring");
     static_assert((NSH - 2) * LH + 2 * S < 64, "vmcnt immediate");
 
     extern __shared__ __attribute__((aligned(1024))) unsigned char smem[];
     unsigned char* const Hs = smem;                   // NSH halo slots
     unsigned char* const dump = smem + NSH * HB;      // 1 KiB landing zone of padding loads
-    unsigned char* const Wres = dump + 1024;          // resident weights: [(chunk*9 + tap)][BN][32] bf16
+    unsigned char* const Wres = dump + 1024;          // resident weights: [(chunk*9 + tap)][BN][32] bf16 (not WREG)
 
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wm = wave % WGM, wn = wave / WGM;
     const int fr = lane & 15, fc = lane >> 4;
-    const int nchunk = p.Cin >> 5;
+    const int nchunk = WREG ? NCH : p.Cin >> 5;
 
     const int bid = xcd_remap(blockIdx.x, gridDim.x);
     const int nt = bid % ntiles, j0 = bid / ntiles;
@@ -60,7 +76,7 @@ __global__ __launch_bounds__(WGM * WGN * 64) void conv_halo_s2_kernel(const Conv
     }
 
     // ---- resident weights: one pass of LDS-DMA pieces, row rg = (chunk*9 + tap)*BN + n -----------------------------
-    {
+    if constexpr (!WREG) {
         const int rows = 9 * nchunk * BN;
         const int ninstr = rows >> 4;
         for (int ii = wave; ii < ninstr; ii += NW) {
@@ -72,6 +88,41 @@ __global__ __launch_bounds__(WGM * WGN * 64) void conv_halo_s2_kernel(const Conv
             const unsigned voff = (unsigned)(((n0 + n) * p.Kpad + tap * p.Cin + ch * 32 + c8 * 8) * 2);
             __builtin_amdgcn_raw_ptr_buffer_load_lds(wrs, (lds_void*)(Wres + ii * 1024), 16, voff, 0, 0, 0);
         }
+    }
+    // ---- register weights: the slab goes through the halo ring a chunk at a time (rows tap*BN + n, the same pieces and swizzle), every
+    //      wave then reads its own 9 * FN fragments (the launcher allots a chunk's bytes where the ring is smaller). Filled once per workgroup, before the first halo piece is issued; known complete
+    //      (lgkmcnt(0)) and passed through empty asm statements, so that no wait for them lands in the tile loop ----
+    bf16x8 wr[WREG ? NCH : 1][9][FN];
+    if constexpr (WREG) {
+        constexpr int W_INSTR = 9 * BN / 16;
+#pragma unroll
+        for (int c = 0; c < NCH; ++c) {
+            for (int ii = wave; ii < W_INSTR; ii += NW) {
+                const int s = ii * 64 + lane;
+                const int rg = s >> 2, pc = s & 3;
+                const int c8 = pc ^ cswz64(rg);
+                const int tap = rg / BN, n = rg - tap * BN;
+                const unsigned voff = (unsigned)(((n0 + n) * p.Kpad + tap * p.Cin + c * 32 + c8 * 8) * 2);
+                __builtin_amdgcn_raw_ptr_buffer_load_lds(wrs, (lds_void*)(Hs + ii * 1024), 16, voff, 0, 0, 0);
+            }
+            wait_vmcnt<0>();
+            __builtin_amdgcn_s_barrier();
+#pragma unroll
+            for (int t = 0; t < 9; ++t)
+#pragma unroll
+                for (int a = 0; a < FN; ++a) {
+                    const int rw = t * BN + wn * (FN * 16) + a * 16 + fr;
+                    wr[c][t][a] = *(const bf16x8*)(Hs + swz64((unsigned)(rw * 64 + fc * 16)));
+                }
+            __builtin_amdgcn_s_waitcnt(0xc07f);               // lgkmcnt(0): the fragments are in registers before the image is overwritten
+            __builtin_amdgcn_s_barrier();                     // (by the next chunk, or by the first halo pieces below)
+        }
+#pragma unroll
+        for (int c = 0; c < NCH; ++c)
+#pragma unroll
+            for (int t = 0; t < 9; ++t)
+#pragma unroll
+                for (int a = 0; a < FN; ++a) asm volatile("" : "+v"(wr[c][t][a]));
     }
 
     // ---- PW2: the trailing 1x1's weights [C2 = BN][BN] (128-B rows, 8-slot swizzle) stay in LDS behind the 3x3 weights ------
@@ -150,7 +201,7 @@ __global__ __launch_bounds__(WGM * WGN * 64) void conv_halo_s2_kernel(const Conv
 #pragma unroll
             for (int r = 0; r < FM; ++r) acc[a][r] = f32x4{bias[a][0], bias[a][1], bias[a][2], bias[a][3]};   // bias rides in the accumulator
 
-        for (int c = 0; c < nchunk; ++c) {
+        auto chunk = [&](const int c) {
             if (!first_iter) {
                 const int k = __builtin_popcount(epmask & ((1u << (NSH - 1)) - 1u));
                 if (k == 0) wait_vmcnt<(NSH - 2) * LH>();
@@ -170,8 +221,12 @@ __global__ __launch_bounds__(WGM * WGN * 64) void conv_halo_s2_kernel(const Conv
                 for (int ky = 0; ky < 3; ++ky)
 #pragma unroll
                     for (int a = 0; a < FN; ++a) {
-                        const int rw = (c * 9 + ky * 3 + kx) * BN + wn * (FN * 16) + a * 16 + fr;
-                        wf[ky][a] = *(const bf16x8*)(Wres + swz64((unsigned)(rw * 64 + fc * 16)));
+                        if constexpr (WREG) {
+                            wf[ky][a] = wr[c][ky * 3 + kx][a];
+                        } else {
+                            const int rw = (c * 9 + ky * 3 + kx) * BN + wn * (FN * 16) + a * 16 + fr;
+                            wf[ky][a] = *(const bf16x8*)(Wres + swz64((unsigned)(rw * 64 + fc * 16)));
+                        }
                     }
                 const int eoff = (kx == 1) ? 17 + fr : fr + (kx >> 1);      // plane O at n, plane E at n / n+1
 #pragma unroll
@@ -197,6 +252,12 @@ __global__ __launch_bounds__(WGM * WGN * 64) void conv_halo_s2_kernel(const Conv
                 }
             }
             rd_slot = (rd_slot + 1 == NSH) ? 0 : rd_slot + 1;
+        };
+        if constexpr (WREG) {
+#pragma unroll
+            for (int c = 0; c < NCH; ++c) chunk(c);
+        } else {
+            for (int c = 0; c < nchunk; ++c) chunk(c);
         }
 
         if (PW2) {
@@ -300,24 +361,67 @@ __global__ __launch_bounds__(WGM * WGN * 64) void conv_halo_s2_kernel(const Conv
     wait_vmcnt<0>();
 }
 
-// ---------------------------------------------------------------------------------------------------------------
-struct HaloS2Cfg { int FM, FN, WGM, WGN; const char* name; };
-static const HaloS2Cfg kS2[] = {
-    {2, 2, 4, 2, "conv_halo_s2_kernel<2,2,4,2,3"},   // 0: 8x16 out px x 64 ch, 8 waves
-    {1, 2, 4, 2, "conv_halo_s2_kernel<1,2,4,2,3"},   // 1: 4x16 out px x 64 ch, 8 waves
-    {2, 2, 4, 1, "conv_halo_s2_kernel<2,2,4,1,3"},   // 2: 8x16 out px x 32 ch, 4 waves
-    {1, 2, 4, 1, "conv_halo_s2_kernel<1,2,4,1,3"},   // 3: 4x16 out px x 32 ch, 4 waves
-    {2, 4, 4, 2, "conv_halo_s2_kernel<2,4,4,2,3"},   // 4: 8x16 out px x 128 ch, 8 waves (Cin = 32)
-};
-constexpr int kNumS2 = (int)(sizeof(kS2) / sizeof(kS2[0]));
-static std::string conv_halo_s2_symbol(const ConvParams& p, int c) {
-    return std::string(kS2[c].name) + (p.C2 > 0 ? ",false,false,true>" : std::string(res_f32_args(p)) + ",false>");
+// Two kernel templates of one name: eight template arguments = weights in LDS (ids 500-504, their symbols as they were), a ninth = the
+// chunk count of a register-weights form.
+template <int FM, int FN, int WGM, int WGN, int NSH, bool HAS_RES, bool OUT_F32, bool PW2>
+__global__ __launch_bounds__(WGM * WGN * 64) void conv_halo_s2_kernel(const ConvParams p, const int tiles_h, const int tiles_w,
+                                                                    const int ntiles, const int G) {
+    conv_halo_s2_body<FM, FN, WGM, WGN, NSH, HAS_RES, OUT_F32, PW2, 0>(p, tiles_h, tiles_w, ntiles, G);
+}
+template <int FM, int FN, int WGM, int WGN, int NSH, bool HAS_RES, bool OUT_F32, bool PW2, int NCH>
+__global__ __launch_bounds__(WGM * WGN * 64) void conv_halo_s2_kernel(const ConvParams p, const int tiles_h, const int tiles_w,
+                                                                    const int ntiles, const int G) {
+    static_assert(NCH > 0, "the ninth argument is a register-weights form's chunk count");
+    conv_halo_s2_body<FM, FN, WGM, WGN, NSH, HAS_RES, OUT_F32, PW2, NCH>(p, tiles_h, tiles_w, ntiles, G);
 }
 
+// ---------------------------------------------------------------------------------------------------------------
+struct HaloS2Cfg { int FM, FN, WGM, WGN; const char* name; bool wreg; };
+// Entries 0-4 are the family's configuration ids (500 + entry). Entries 5-7 are the register-weights instances a launch of id 500 / 501
+// resolves to where they are valid (halo_s2_form): no ids of their own - tuner, tables and the forced id speak of tile requests.
+static const HaloS2Cfg kS2[] = {
+    {2, 2, 4, 2, "conv_halo_s2_kernel<2,2,4,2,3", false},   // 0: 8x16 out px x 64 ch, 8 waves
+    {1, 2, 4, 2, "conv_halo_s2_kernel<1,2,4,2,3", false},   // 1: 4x16 out px x 64 ch, 8 waves
+    {2, 2, 4, 1, "conv_halo_s2_kernel<2,2,4,1,3", false},   // 2: 8x16 out px x 32 ch, 4 waves
+    {1, 2, 4, 1, "conv_halo_s2_kernel<1,2,4,1,3", false},   // 3: 4x16 out px x 32 ch, 4 waves
+    {2, 4, 4, 2, "conv_halo_s2_kernel<2,4,4,2,3", false},   // 4: 8x16 out px x 128 ch, 8 waves (Cin = 32)
+    {1, 2, 4, 2, "conv_halo_s2_kernel<1,2,4,2,3", true},    // 5: 1 with the weights in registers
+    {2, 2, 4, 2, "conv_halo_s2_kernel<2,2,4,2,3", true},    // 6: 0 with the weights in registers (so the 8-row tile fits for Cin = 64 too)
+    {2, 2, 2, 4, "conv_halo_s2_kernel<2,2,2,4,3", true},    // 7: 1 on a layer of more than 96 channels: the same 4x16 pixels, both 64-channel
+                                                            //    blocks in one workgroup, so the input tile is fetched once, not twice
+};
+constexpr int kNumS2 = 5;
+constexpr int kNumS2Forms = (int)(sizeof(kS2) / sizeof(kS2[0]));
+
+// A/B and test switch: 1 = every launch keeps its weights in LDS (YOLOP_S2_LDS_WEIGHTS=1, or yp_debug_conv_s2's argument for one call)
+static std::atomic<int>& s2_lds_weights_ref() {
+    static std::atomic<int> v{env_on("YOLOP_S2_LDS_WEIGHTS") ? 1 : 0};
+    return v;
+}
+int conv_halo_s2_lds_weights(int on) { return on < 0 ? s2_lds_weights_ref().load() : s2_lds_weights_ref().exchange(on ? 1 : 0); }
+
+// The kS2 entry that configuration c launches p with. Register weights: 9 taps x chunks x FN = 2 fragments x 4 VGPRs <= 144 per wave, i.e.
+// Cin = 32 / 64; not with the fused trailing 1x1 (its weights stay in LDS anyway), not for the 4-wave tiles (ids 502 / 503: unmeasured).
+static int halo_s2_form(const ConvParams& p, int c) {
+    if (c > 1 || p.C2 > 0 || s2_lds_weights_ref().load()) return c;
+    if ((p.Cin % 32) != 0 || 9 * (p.Cin / 32) * 2 * 4 > kS2WregMaxVgprs) return c;
+    if (c == 0) return 6;
+    return p.Cout > 96 ? 7 : 5;
+}
+static std::string conv_halo_s2_symbol(const ConvParams& p, int c) {
+    const HaloS2Cfg& k = kS2[halo_s2_form(p, c)];
+    if (k.wreg) return std::string(k.name) + res_f32_args(p) + ",false," + std::to_string(p.Cin / 32) + ">";
+    return std::string(k.name) + (p.C2 > 0 ? ",false,false,true>" : std::string(res_f32_args(p)) + ",false>");
+}
+
+// halo ring + landing zone, then the resident weights (and the fused 1x1's). A register-weights form stages its slab through the ring
+// before the ring is in use, 9 * BN * 64 bytes at a time (a chunk): no weight term, but at least that chunk.
 static size_t halo_s2_lds(const HaloS2Cfg& k, int Cin, bool pw2 = false) {
     const int TH = k.WGM * k.FM, BN = k.WGN * k.FN * 16;
     const int HP = (2 * TH + 1) * 33, H_INSTR = (HP * 4 + 63) / 64;
-    return (size_t)3 * H_INSTR * 1024 + 1024 + (size_t)9 * (Cin / 32) * BN * 64 + (pw2 ? (size_t)BN * 128 : 0);
+    const size_t ring = (size_t)3 * H_INSTR * 1024 + 1024;
+    if (k.wreg) return std::max(ring, (size_t)9 * BN * 64);
+    return ring + (size_t)9 * (Cin / 32) * BN * 64 + (pw2 ? (size_t)BN * 128 : 0);
 }
 
 static bool conv_halo_s2_cfg_valid(const ConvParams& p, int c) {
@@ -327,7 +431,7 @@ static bool conv_halo_s2_cfg_valid(const ConvParams& p, int c) {
     if (p.x_bytes >= (1ull << 31) || p.w_bytes >= (1ull << 31) || p.y_bytes >= (1ull << 31)) return false;
     if ((p.Cout & 3) || (p.y_stride & 3) || (p.y_coff & 3) || (p.res && ((p.res_stride & 3) || (p.res_coff & 3)))) return false;
     if (p.res && p.out_f32) return false;
-    const HaloS2Cfg& k = kS2[c];
+    const HaloS2Cfg& k = kS2[halo_s2_form(p, c)];                // (the instance that would launch: its LDS need decides)
     const int BN = k.WGN * k.FN * 16, TH = k.WGM * k.FM;
     const int cpad = (p.Cout + 31) / 32 * 32;
     if (BN > cpad) return false;
@@ -337,22 +441,38 @@ static bool conv_halo_s2_cfg_valid(const ConvParams& p, int c) {
     return true;
 }
 
-template <int FM, int FN, int WGM, int WGN, bool HAS_RES, bool OUT_F32, bool PW2 = false>
+template <int FM, int FN, int WGM, int WGN, bool HAS_RES, bool OUT_F32, bool PW2 = false, int... WCH>
 static hipError_t launch_halo_s2_var(const ConvParams& p, const HaloS2Cfg& k, hipStream_t st) {
     constexpr int TH = WGM * FM, BN = WGN * FN * 16;
     const size_t sh = halo_s2_lds(k, p.Cin, PW2);
     const int B = p.M / (p.Ho * p.Wo);
     const int tiles_h = (p.Ho + TH - 1) / TH, tiles_w = (p.Wo + 15) / 16, ntiles = (p.Cout + BN - 1) / BN;
     const int num_tiles = B * tiles_h * tiles_w;
-    const int per_cu = (int)std::max<size_t>(1, std::min<size_t>(2, (160 * 1024) / sh));
+    // (a register-weights workgroup takes more than half of a CU's registers: one per CU whatever its LDS need)
+    const int per_cu = sizeof...(WCH) > 0 ? 1 : (int)std::max<size_t>(1, std::min<size_t>(2, (160 * 1024) / sh));
     int G = (256 * per_cu) / ntiles;
     if (G < 1) G = 1;
     if (G > num_tiles) G = num_tiles;
-    auto kern = conv_halo_s2_kernel<FM, FN, WGM, WGN, 3, HAS_RES, OUT_F32, PW2>;
+    auto kern = conv_halo_s2_kernel<FM, FN, WGM, WGN, 3, HAS_RES, OUT_F32, PW2, WCH...>;
     static size_t granted = 0;
     if (hipError_t e = allow_dynamic_lds((const void*)kern, sh, granted)) return e;
     hipLaunchKernelGGL(kern, dim3(G * ntiles), dim3(WGM * WGN * 64), sh, st, p, tiles_h, tiles_w, ntiles, G);
     return hipGetLastError();
+}
+
+// register-weights forms: the chunk count is a template argument (1 or 2 with FN = 2: halo_s2_form's register bound)
+template <int FM, int FN, int WGM, int WGN, int NCH>
+static hipError_t launch_halo_s2_wreg_n(const ConvParams& p, const HaloS2Cfg& k, hipStream_t st) {
+    if (p.out_f32) return launch_halo_s2_var<FM, FN, WGM, WGN, false, true, false, NCH>(p, k, st);
+    if (p.res) return launch_halo_s2_var<FM, FN, WGM, WGN, true, false, false, NCH>(p, k, st);
+    return launch_halo_s2_var<FM, FN, WGM, WGN, false, false, false, NCH>(p, k, st);
+}
+template <int FM, int FN, int WGM, int WGN>
+static hipError_t launch_halo_s2_wreg(const ConvParams& p, const HaloS2Cfg& k, hipStream_t st) {
+    static_assert(FN == 2 && 9 * 2 * FN * 4 <= kS2WregMaxVgprs && 9 * 3 * FN * 4 > kS2WregMaxVgprs, "the chunk counts instantiated below are those halo_s2_form admits");
+    if (p.Cin == 32) return launch_halo_s2_wreg_n<FM, FN, WGM, WGN, 1>(p, k, st);
+    if (p.Cin == 64) return launch_halo_s2_wreg_n<FM, FN, WGM, WGN, 2>(p, k, st);
+    return hipErrorInvalidValue;
 }
 
 template <int FM, int FN, int WGM, int WGN>
@@ -378,19 +498,28 @@ int conv_halo_s2_pw_cfg(const ConvParams& p) {
     return -1;
 }
 
+size_t conv_halo_s2_lds_bytes(const ConvParams& p, int c) { return (c >= 0 && c < kNumS2) ? halo_s2_lds(kS2[halo_s2_form(p, c)], p.Cin) : 0; }
+
 static hipError_t launch_conv_halo_s2(const ConvParams& p, int c, hipStream_t st) {
-    const HaloS2Cfg& k = kS2[c];
+    if (c < 0 || c >= kNumS2) return hipErrorInvalidValue;
+    const int form = halo_s2_form(p, c);
+    const HaloS2Cfg& k = kS2[form];
     if (p.C2 > 0) {
         if (c == 0) return launch_halo_s2_var<2, 2, 4, 2, false, false, true>(p, k, st);
         if (c == 1) return launch_halo_s2_var<1, 2, 4, 2, false, false, true>(p, k, st);
         return hipErrorInvalidValue;
     }
-    switch (c) {
+    static_assert(kNumS2Forms == 8, "one case per entry of kS2");
+    switch (form) {
         case 0: return launch_halo_s2_one<2, 2, 4, 2>(p, k, st);
         case 1: return launch_halo_s2_one<1, 2, 4, 2>(p, k, st);
         case 2: return launch_halo_s2_one<2, 2, 4, 1>(p, k, st);
         case 3: return launch_halo_s2_one<1, 2, 4, 1>(p, k, st);
-        default: return launch_halo_s2_one<2, 4, 4, 2>(p, k, st);
+        case 4: return launch_halo_s2_one<2, 4, 4, 2>(p, k, st);
+        case 5: return launch_halo_s2_wreg<1, 2, 4, 2>(p, k, st);
+        case 6: return launch_halo_s2_wreg<2, 2, 4, 2>(p, k, st);
+        case 7: return launch_halo_s2_wreg<2, 2, 2, 4>(p, k, st);
+        default: return hipErrorInvalidValue;
     }
 }
 

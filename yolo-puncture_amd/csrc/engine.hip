@@ -2635,6 +2635,47 @@ int yp_debug_attention(const void* qkv_dev, void* o_dev, int dtype, int B, int N
     return yp_debug_attention_form(qkv_dev, o_dev, dtype, B, N, nh, kd, hd, q_stride, q_coff, o_stride, o_coff, wgs, ATTN_FORM_AUTO, kernel_out, stream);
 }
 
+int yp_debug_conv_s2(const void* x_dev, const void* w_dev, const float* bias_dev, const void* res_dev, void* y_dev, int out_f32, int B, int H,
+                     int W, int Cin, int Cout, int silu, int cfg, int lds_weights, int64_t* lds_out, char* kernel_out, int kernel_cap, void* stream) {
+    if (lds_out) *lds_out = 0;
+    if (kernel_out && kernel_cap > 0) kernel_out[0] = 0;
+    const bool host_only = !x_dev && !w_dev && !bias_dev && !y_dev;
+    if (!host_only && (!x_dev || !w_dev || !bias_dev || !y_dev)) return fail(YP_ERR_ARG, "yp_debug_conv_s2: null argument");
+    if (B < 1 || H < 2 || W < 2 || Cin < 1 || Cout < 1)
+        return fail(YP_ERR_ARG, "yp_debug_conv_s2: non-positive size (B %d, H %d, W %d, Cin %d, Cout %d)", B, H, W, Cin, Cout);
+    const ConvFamily& f = conv_halo_s2_family;
+    if (cfg < f.base || cfg >= f.base + f.num_cfgs)
+        return fail(YP_ERR_ARG, "yp_debug_conv_s2: cfg = %d is no id of the stride-2 halo family [%d, %d)", cfg, f.base, f.base + f.num_cfgs);
+    const size_t esz = out_f32 ? 4 : 2;
+    ConvParams p{};
+    p.x = x_dev; p.x_stride = Cin; p.x_coff = 0; p.H = H; p.W = W; p.Cin = Cin;
+    p.w = w_dev; p.Kpad = 9 * Cin; p.bias = bias_dev;
+    p.Ho = H / 2; p.Wo = W / 2; p.Cout = Cout;
+    p.y = y_dev; p.y_stride = Cout; p.y_coff = 0;
+    p.res = res_dev; p.res_stride = Cout; p.res_coff = 0;
+    p.M = B * p.Ho * p.Wo;
+    p.ks = 3; p.stride = 2; p.pad = 1; p.up = 1;
+    p.act = silu ? ACT_SILU : ACT_NONE; p.out_f32 = out_f32 ? 1 : 0;
+    p.x_bytes = (size_t)B * H * W * Cin * 2; p.w_bytes = (size_t)Cout * 9 * Cin * 2; p.y_bytes = (size_t)p.M * Cout * esz;
+    p.cfg = -1;
+    const int before = conv_halo_s2_lds_weights(lds_weights ? 1 : 0);      // (for this call; the stream is drained before it is put back)
+    const bool ok = f.valid(p, cfg - f.base);
+    hipError_t err = hipSuccess;
+    if (lds_out) *lds_out = (int64_t)conv_halo_s2_lds_bytes(p, cfg - f.base);
+    if (ok && kernel_out && kernel_cap > 0) std::snprintf(kernel_out, (size_t)kernel_cap, "%s", f.symbol(p, cfg - f.base).c_str());
+    if (ok && !host_only) {
+        hipStream_t st = (hipStream_t)stream;
+        err = f.launch(p, cfg - f.base, st);
+        if (err == hipSuccess) err = hipStreamSynchronize(st);
+    }
+    conv_halo_s2_lds_weights(before);
+    if (!ok)
+        return fail(YP_ERR_ARG, "yp_debug_conv_s2: configuration %d does not admit B %d, H %d, W %d, Cin %d, Cout %d%s%s%s", cfg, B, H, W, Cin, Cout,
+                    res_dev ? ", residual" : "", out_f32 ? ", fp32 output" : "", lds_weights ? ", weights in LDS" : "");
+    if (err != hipSuccess) return fail(YP_ERR_HIP, "yp_debug_conv_s2: %s", hipGetErrorString(err));
+    return YP_OK;
+}
+
 int yp_tuning_source(const yp_engine* e) {
     if (!e) return YP_ERR_ARG;
     return e->tune_source;

@@ -73,6 +73,8 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     lib.yp_debug_attention.restype = C.c_int
     lib.yp_debug_attention_form.argtypes = [vp, vp] + [C.c_int] * 12 + [ip, vp]
     lib.yp_debug_attention_form.restype = C.c_int
+    lib.yp_debug_conv_s2.argtypes = [vp, vp, vp, vp, vp] + [C.c_int] * 9 + [C.POINTER(C.c_int64), C.c_char_p, C.c_int, vp]
+    lib.yp_debug_conv_s2.restype = C.c_int
     lib.yp_set_attention_form.argtypes = [vp, C.c_int]
     lib.yp_set_attention_form.restype = C.c_int
     lib.yp_op_info.argtypes = [vp, C.c_int, C.c_char_p, C.c_int, ip, C.POINTER(C.c_double), C.POINTER(C.c_double)]
@@ -143,7 +145,7 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
 EXPORTS = ["yp_last_error", "yp_create", "yp_destroy", "yp_weight_count", "yp_weight_info", "yp_set_weight",
            "yp_finalize", "yp_forward", "yp_proto", "yp_masks", "yp_id_mask_resized", "yp_plan", "yp_op_info", "yp_op_output", "yp_op_input", "yp_op_fusion",
            "yp_tensor_count", "yp_tensor_info", "yp_tensor_read", "yp_profile", "yp_set_graph", "yp_run_op",
-           "yp_tensor_write", "yp_op_kernel", "yp_set_autotune", "yp_tuning_export", "yp_tuning_import", "yp_set_nms", "yp_debug_force_conv_cfg", "yp_debug_op_cfg", "yp_debug_op_form", "yp_debug_last_store_form", "yp_debug_max_workgroups", "yp_debug_conv_families", "yp_debug_ablation", "yp_debug_head_clocks", "yp_debug_head_branch_clocks", "yp_debug_head_winners", "yp_debug_contour_clocks", "yp_debug_pwsp_clocks", "yp_debug_host_selftest", "yp_debug_graph_info", "yp_tuning_source", "yp_debug_head_positions", "yp_debug_marker", "yp_max_batch", "yp_debug_topk_anchors", "yp_debug_attention", "yp_debug_attention_form", "yp_set_attention_form", "yp_letterbox", "yp_letterbox_batch", "yp_masks_frames", "yp_masks_frames_input", "yp_mask_contours",
+           "yp_tensor_write", "yp_op_kernel", "yp_set_autotune", "yp_tuning_export", "yp_tuning_import", "yp_set_nms", "yp_debug_force_conv_cfg", "yp_debug_op_cfg", "yp_debug_op_form", "yp_debug_last_store_form", "yp_debug_max_workgroups", "yp_debug_conv_families", "yp_debug_ablation", "yp_debug_head_clocks", "yp_debug_head_branch_clocks", "yp_debug_head_winners", "yp_debug_contour_clocks", "yp_debug_pwsp_clocks", "yp_debug_host_selftest", "yp_debug_graph_info", "yp_tuning_source", "yp_debug_head_positions", "yp_debug_marker", "yp_max_batch", "yp_debug_topk_anchors", "yp_debug_attention", "yp_debug_attention_form", "yp_debug_conv_s2", "yp_set_attention_form", "yp_letterbox", "yp_letterbox_batch", "yp_masks_frames", "yp_masks_frames_input", "yp_mask_contours",
            "yp_mask_contours_scaled", "yp_mask_contours_large_workspace", "yp_mask_contours_large", "yp_comm_unique_id", "yp_comm_create", "yp_allgather", "yp_comm_destroy",
            "yp_u2net_create", "yp_u2net_destroy", "yp_u2net_weight_count", "yp_u2net_weight_info", "yp_u2net_set_weight", "yp_u2net_finalize",
            "yp_u2net_forward", "yp_u2net_forward_crops", "yp_u2net_set_graph", "yp_u2net_tensor_count", "yp_u2net_tensor_info", "yp_u2net_tensor_read",
@@ -207,6 +209,44 @@ def attention(qkv: torch.Tensor, nh: int, kd: int, hd: int, q_coff: int = 0, out
     if rc < 0:
         raise YolopError(lib.yp_last_error().decode())
     return out, kernel.value
+
+
+def conv_s2(x: torch.Tensor, w: torch.Tensor, bias: torch.Tensor, cfg: int, res: Optional[torch.Tensor] = None, out_f32: bool = False,
+            silu: bool = True, lds_weights: bool = False) -> torch.Tensor:
+    """Debug: one 3x3 / stride-2 / pad-1 bf16 conv alone (yp_debug_conv_s2) under configuration id `cfg` of the stride-2 halo family.
+    x: device bf16 [B, H, W, Cin]; w: device bf16 [Cout, 3, 3, Cin]; bias: device float32 [Cout]; res: device bf16 [B, H/2, W/2, Cout] or None.
+    lds_weights: keep the weights in LDS where the launcher would take the register-weights instance (ids 500 / 501, Cin 32 / 64).
+    Returns y [B, H/2, W/2, Cout], float32 when out_f32, else bf16. A shape the id does not admit raises YolopError before anything launches."""
+    lib = load_library()
+    if x.dim() != 4 or w.dim() != 4 or x.dtype != torch.bfloat16 or w.dtype != torch.bfloat16 or bias.dtype != torch.float32:
+        raise ValueError("x: bf16 [B, H, W, Cin], w: bf16 [Cout, 3, 3, Cin], bias: float32 [Cout]")
+    B, H, W, Cin = (int(v) for v in x.shape)
+    Cout = int(w.shape[0])
+    if tuple(w.shape) != (Cout, 3, 3, Cin) or tuple(bias.shape) != (Cout,) or not (x.is_cuda and w.is_cuda and bias.is_cuda):
+        raise ValueError("w must be [Cout, 3, 3, Cin] and bias [Cout], all on the device")
+    if not (x.is_contiguous() and w.is_contiguous() and bias.is_contiguous()):
+        raise ValueError("contiguous tensors")
+    if res is not None and (res.dtype != torch.bfloat16 or tuple(res.shape) != (B, H // 2, W // 2, Cout) or not res.is_contiguous() or res.device != x.device):
+        raise ValueError("res must be a contiguous bf16 [B, H/2, W/2, Cout] on x's device")
+    y = torch.zeros((B, H // 2, W // 2, Cout), dtype=torch.float32 if out_f32 else torch.bfloat16, device=x.device)
+    rc = lib.yp_debug_conv_s2(C.c_void_p(x.data_ptr()), C.c_void_p(w.data_ptr()), C.c_void_p(bias.data_ptr()),
+                              C.c_void_p(res.data_ptr()) if res is not None else None, C.c_void_p(y.data_ptr()), int(bool(out_f32)), B, H, W, Cin, Cout,
+                              int(bool(silu)), int(cfg), int(bool(lds_weights)), None, None, 0, C.c_void_p(_stream_ptr(x.device)))
+    if rc < 0:
+        raise YolopError(lib.yp_last_error().decode())
+    return y
+
+
+def conv_s2_admits(cfg: int, B: int, H: int, W: int, Cin: int, Cout: int, res: bool = False, out_f32: bool = False,
+                   lds_weights: bool = False) -> Tuple[bool, int, str]:
+    """Host only (yp_debug_conv_s2 without buffers): does id `cfg` of the stride-2 halo family admit the shape, the dynamic LDS bytes of its
+    launch (0 when the id is not of the family) and the kernel symbol it would launch ("" when refused)."""
+    lib = load_library()
+    lds = C.c_int64(0)
+    name = C.create_string_buffer(160)
+    rc = lib.yp_debug_conv_s2(None, None, None, C.c_void_p(1) if res else None, None, int(bool(out_f32)), int(B), int(H), int(W), int(Cin), int(Cout),
+                              1, int(cfg), int(bool(lds_weights)), C.byref(lds), name, 160, None)
+    return rc >= 0, int(lds.value), name.value.decode()
 
 
 def conv_families() -> List[Tuple[int, int]]:
