@@ -5,6 +5,7 @@ import numpy as np
 import pytest
 import torch
 
+import mask_cases as K
 from helpers import assert_within_noise_floor, make_case, nchw_to_nhwc, rand_image
 from oracle import postprocess_oracle as po
 from oracle.yolov10_oracle import Oracle
@@ -156,6 +157,7 @@ def test_id_mask_resized_bit_level(ckpt):
     eng = Engine("n", 80, True, "fp32", 0, state=st)
     eng.forward(im.cuda())
     torch.cuda.synchronize()
+    proto = eng.proto()
     g = torch.Generator().manual_seed(0)
     for b, (oh, ow), (rh, rw) in ((0, (96, 160), (144, 240)), (1, (200, 333), (90, 160)), (1, (90, 161), (271, 97)), (0, (120, 214), (720, 1280)),
                                   (1, (96, 160), (96, 160))):
@@ -165,6 +167,8 @@ def test_id_mask_resized_bit_level(ckpt):
             if n:
                 boxes[0] = torch.tensor([0., 0., float(ow), float(oh)])
             m, _, _ = eng.masks(b, coeff.cuda(), boxes.cuda(), (oh, ow), retina=True)
+            if n:       # the masks that go into the resize: the per-pixel rule of mask_cases.py against the float64 reference
+                K.check_rule(f"id_mask_resized inputs {(oh, ow)} n={n}", m.cpu(), *K.random_reference(proto[b], coeff, boxes, (oh, ow), True)[:2])
             for min_area in (50, 2000):
                 ids, kept = eng.id_mask_resized(b, coeff.cuda(), boxes.cuda(), (oh, ow), (rh, rw), suppress_small=True, min_area=min_area)
                 wi, winfo = po.auto_segment_oracle(m.cpu().float() if n else None, torch.ones(n), torch.zeros(n), (rh, rw), True, min_area)
@@ -192,17 +196,20 @@ def test_mask_kernels_bit_level(ckpt):
             m, ids, kept = eng.masks(b, coeff.cuda(), boxes.cuda(), (oh, ow), retina=True, want_ids=True, suppress_small=True, min_area=50)
             want = po.process_mask_native(proto[b].permute(2, 0, 1), coeff, boxes, (oh, ow)) if n else torch.zeros(0, oh, ow)
             assert (m.cpu().float() != want).float().mean().item() < 2e-4 if n else m.shape[0] == 0
+            if n:       # and WHICH pixels may differ: only those whose float64 logit lies within the derived allowance of zero (mask_cases.py)
+                K.check_rule(f"mask kernels {(oh, ow)} n={n}", m.cpu(), *K.random_reference(proto[b], coeff, boxes, (oh, ow), True)[:2])
             wi, winfo = po.auto_segment_oracle(m.cpu().float() if n else None, torch.ones(n), torch.zeros(n), (oh, ow), True, 50)
             assert torch.equal(ids.cpu(), wi)
             assert [k for k in kept.cpu().tolist() if k > 0] == [a for a, _, _ in winfo]
     eng.close()
 
 
-@pytest.mark.parametrize("h0,w0", [(720, 1280), (1080, 810), (360, 640), (640, 640), (97, 211), (1333, 777), (33, 1000), (480, 640)])
+@pytest.mark.parametrize("h0,w0", [(720, 1280), (1080, 810), (360, 640), (640, 640), (97, 211), (1333, 777), (33, 1000), (480, 640),
+                                   (1, 300), (300, 1), (2, 2), (8, 8)])
 def test_device_letterbox_bit_exact(h0, w0):
     """yp_letterbox (HIP) against the oracle's restatement of LetterBox = cv2.resize(INTER_LINEAR, 8-bit fixed point) +
     copyMakeBorder(114): integer work, so the bar is bit-exact - down-scaling, up-scaling, identity size, odd sizes,
-    both padding orientations."""
+    both padding orientations, and sources of one or two pixels on an axis (every tap clamps to the same pixel)."""
     from yolo_puncture_amd import hostops
     from yolo_puncture_amd.engine import letterbox_device
     g = torch.Generator().manual_seed(h0 * 10007 + w0)
