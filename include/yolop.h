@@ -38,6 +38,8 @@ extern "C" {
 #define YP_MAX_MASKS 480   /* masks per yp_masks / yp_id_mask_resized call (one frame's coefficients stay in LDS); a YP_TASK_SEGMENT engine
                               therefore takes max_det <= 480 - yp_create refuses more (ultralytics' default, and what every caller of the
                               reference leaves in place, is 300: yolo_seg/app.py:91, yolo_seg/yolo_with_deva.py:51) */
+#define YP_ID_MASKS_FRAMES_BUDGET (1ull << 30)   /* bytes of workspace one yp_id_masks_frames call may ask of the engine before the Python facade
+                                                    splits a chunk's frames over several calls (hostops.group_frames_by_workspace) */
 #define YP_MAX_DET 512     /* rows per image the top-k and NMS head kernels rank in one step (csrc: MAXK, NMAXK, HEAD_MAXK) */
 
 typedef struct yp_engine yp_engine;
@@ -131,6 +133,27 @@ int yp_masks_frames(yp_engine* e, const int32_t* frame_idx_host, int k, const fl
  * Other arguments and checks as yp_masks_frames. */
 int yp_masks_frames_input(yp_engine* e, const int32_t* frame_idx_host, int k, const float* coeff_dev, long coeff_row_stride,
                           const float* boxes_dev, int oh, int ow, uint8_t* masks_out, void* stream);
+
+/* The clip form of `auto_segment` (yolo_seg/yolo_with_deva.py:37-88): ALL masks of k images of the last forward -> one id image per image.
+ * Frame j owns rows row_off[j] .. row_off[j+1] of coeff_dev / boxes_dev (n_j = their number, 0 <= n_j <= YP_MAX_MASKS) and image
+ * frame_idx[j]. Its ids_out[j] and kept_out[row_off[j] .. row_off[j+1]) are byte-equal to
+ *     yp_masks(e, frame_idx[j], coeff_dev + 32 * row_off[j], boxes_dev + 4 * row_off[j], n_j, oh, ow, 1, NULL, ids, kept, ...)   (rh,rw) == (oh,ow)
+ *     yp_id_mask_resized(e, frame_idx[j], the same rows, n_j, oh, ow, rh, rw, ids, kept, ...)                                   otherwise
+ * (float areas closer to min_area than their double sums' rounding excepted, as between two runs of yp_id_mask_resized itself).
+ *    frame_idx_host int32 [k] host, each in [0,B) of the last forward (gaps and repeats allowed); row_off_host int32 [k+1] host, row_off[0] = 0,
+ *                   non-decreasing; both are copied to the device in the call. k >= 1
+ *    coeff_dev      float [n_total,32], boxes_dev float [n_total,4] x1,y1,x2,y2 in (oh,ow) pixels, n_total = row_off[k] (NULL allowed when 0)
+ *    (oh,ow)        the size the masks are made at (retina); (rh,rw) the size of the id images, resized as yp_id_mask_resized when it differs
+ *    ids_out        int64 [k,rh,rw], every byte written - zeros for a frame without rows; kept_out int32 [n_total], every byte written
+ * Limits: k <= 65535, n_total <= 65535, each of oh*ow, oh*rw, rh*rw below 2^31 and n_total times the largest of them below 2^32 (a plane is
+ * indexed with 32 bits, rows and frames with 64), the 16x downscale limit of yp_id_mask_resized. Every argument is checked before anything
+ * is launched; on an error code nothing is written. The workspace is the engine's (grown when needed, as for yp_masks);
+ * yp_id_masks_frames_workspace is its size in bytes for the engine's current plan - host arithmetic, 0 for sizes the call refuses or
+ * before a plan - so that a caller can split frames over calls (YP_ID_MASKS_FRAMES_BUDGET). */
+int yp_id_masks_frames(yp_engine* e, const int32_t* frame_idx_host, const int32_t* row_off_host, int k, const float* coeff_dev,
+                       const float* boxes_dev, int oh, int ow, int rh, int rw, int64_t* ids_out, int32_t* kept_out, int suppress_small,
+                       int min_area, void* stream);
+size_t yp_id_masks_frames_workspace(const yp_engine* e, int n_total, int k, int oh, int ow, int rh, int rw);
 
 /* `results[0].masks.xy[i]` and `get_coord_min_rect_len(...)` on the device (yolo_seg/app.py:101-103, yolo_seg/utils/mask_tools.py:12-22;
  * [U] Masks.xy = masks2segments(strategy): cv2.findContours(RETR_EXTERNAL, CHAIN_APPROX_SIMPLE), then "all" (the 8.3.x line the app's

@@ -261,6 +261,71 @@ int main() {
         CHECK(yp_masks_frames_input(eng, idx, 0, stub_f, 300 * 32, stub_f, 384, 640, stub_u8, nullptr) == YP_ERR_STATE);
         CHECK(yp_destroy(eng) == YP_OK);
     }
+    // the clip form of auto_segment (yp_id_masks_frames, yp_id_masks_frames_workspace): every check runs before the device is touched, the
+    // query is host arithmetic on the engine's plan
+    for (int task = 0; task < 2; ++task) {
+        yp_model_desc d{'n', 80, task, YP_F32, 300, YP_FAMILY_V10};
+        yp_engine* eng = nullptr;
+        CHECK(yp_create(&d, 0, &eng) == YP_OK);
+        static float stub_f[8];                                          // never read or written: every call below is refused first
+        static int64_t stub_ids[2];
+        static int32_t stub_kept[2];
+        const int32_t idx[3] = {0, 3, 3}, off[4] = {0, 2, 2, 5};
+        auto call = [&](yp_engine* e, const int32_t* fi, const int32_t* ro, int k, int oh, int ow, int rh, int rw) {
+            return yp_id_masks_frames(e, fi, ro, k, stub_f, stub_f, oh, ow, rh, rw, stub_ids, stub_kept, 1, 100, nullptr);
+        };
+        CHECK(yp_id_masks_frames_workspace(eng, 5, 3, 96, 160, 96, 160) == 0);                       // no plan yet
+        CHECK(call(eng, idx, off, 3, 96, 160, 96, 160) == YP_ERR_STATE);
+        CHECK(yp_plan(eng, 4, 96, 160) > 0);
+        CHECK(call(nullptr, idx, off, 3, 96, 160, 96, 160) == YP_ERR_ARG);
+        CHECK(call(eng, idx, off, 0, 96, 160, 96, 160) == YP_ERR_ARG && strstr(yp_last_error(), "yp_id_masks_frames"));
+        CHECK(call(eng, nullptr, off, 3, 96, 160, 96, 160) == YP_ERR_ARG);
+        CHECK(call(eng, idx, nullptr, 3, 96, 160, 96, 160) == YP_ERR_ARG);
+        CHECK(yp_id_masks_frames(eng, idx, off, 3, stub_f, stub_f, 96, 160, 96, 160, nullptr, stub_kept, 1, 100, nullptr) == YP_ERR_ARG);
+        CHECK(yp_id_masks_frames(eng, idx, off, 3, nullptr, stub_f, 96, 160, 96, 160, stub_ids, stub_kept, 1, 100, nullptr) == YP_ERR_ARG);
+        CHECK(yp_id_masks_frames(eng, idx, off, 3, stub_f, nullptr, 96, 160, 96, 160, stub_ids, stub_kept, 1, 100, nullptr) == YP_ERR_ARG);
+        CHECK(yp_id_masks_frames(eng, idx, off, 3, stub_f, stub_f, 96, 160, 96, 160, stub_ids, nullptr, 1, 100, nullptr) == YP_ERR_ARG);
+        const int32_t off_start[4] = {1, 2, 2, 5}, off_down[4] = {0, 2, 1, 5}, off_many[4] = {0, 2, 2 + YP_MAX_MASKS + 1, 2 + YP_MAX_MASKS + 1};
+        for (const int32_t* ro : {off_start, off_down, off_many}) CHECK(call(eng, idx, ro, 3, 96, 160, 96, 160) == YP_ERR_ARG);
+        CHECK(call(eng, idx, off, 3, 0, 160, 96, 160) == YP_ERR_ARG);
+        CHECK(call(eng, idx, off, 3, 96, 160, 144, -1) == YP_ERR_ARG);
+        CHECK(call(eng, idx, off, 3, 96, 160, 5, 160) == YP_ERR_ARG && strstr(yp_last_error(), "16x"));
+        CHECK(call(eng, idx, off, 3, 46341, 46341, 46341, 46341) == YP_ERR_ARG && strstr(yp_last_error(), "2^31"));
+        CHECK(call(eng, idx, off, 3, 65536, 4096, 4096, 32768) == YP_ERR_ARG);                       // oh * rw = 2^31
+        {
+            std::vector<int32_t> fi(140, 0), ro(141);
+            for (int j = 0; j <= 140; ++j) ro[j] = YP_MAX_MASKS * j;                                  // 67200 masks in all
+            CHECK(call(eng, fi.data(), ro.data(), 140, 96, 160, 96, 160) == YP_ERR_ARG && strstr(yp_last_error(), "65535"));
+            const int32_t ro4[5] = {0, 300, 600, 900, 1200};
+            CHECK(call(eng, fi.data(), ro4, 4, 2048, 2048, 2048, 2048) == YP_ERR_ARG && strstr(yp_last_error(), "2^32"));
+            std::vector<int32_t> fk(65536, 0), rk(65537, 0);
+            CHECK(call(eng, fk.data(), rk.data(), 65536, 96, 160, 96, 160) == YP_ERR_ARG);
+        }
+        if (task == YP_TASK_SEGMENT) {
+            const int32_t idx_hi[3] = {0, 4, 3}, idx_lo[3] = {0, -1, 3};
+            CHECK(call(eng, idx_hi, off, 3, 96, 160, 96, 160) == YP_ERR_ARG && call(eng, idx_lo, off, 3, 96, 160, 96, 160) == YP_ERR_ARG);
+            // valid arguments, the 16x limit itself and a frame at the mask limit: a plan, but no forward (no device here)
+            const int32_t off_full[4] = {0, YP_MAX_MASKS, YP_MAX_MASKS, YP_MAX_MASKS + 3};
+            CHECK(call(eng, idx, off, 3, 96, 160, 96, 160) == YP_ERR_STATE && call(eng, idx, off, 3, 96, 160, 6, 10) == YP_ERR_STATE);
+            CHECK(call(eng, idx, off_full, 3, 96, 160, 144, 240) == YP_ERR_STATE);
+            const int32_t off_none[4] = {0, 0, 0, 0};
+            CHECK(yp_id_masks_frames(eng, idx, off_none, 3, nullptr, nullptr, 96, 160, 96, 160, stub_ids, nullptr, 1, 100, nullptr) == YP_ERR_STATE);
+            // the query: 256-byte blocks, growing with rows and frames, 0 for what the call refuses
+            size_t prev = 0;
+            for (int n : {0, 1, 17, 480, 5000}) {
+                const size_t a = yp_id_masks_frames_workspace(eng, n, 1, 96, 160, 96, 160), b = yp_id_masks_frames_workspace(eng, n, 64, 96, 160, 144, 240);
+                CHECK(a > prev && b > a && a % 256 == 0 && b % 256 == 0);
+                prev = a;
+            }
+            CHECK(yp_id_masks_frames_workspace(eng, 5, 0, 96, 160, 96, 160) == 0 && yp_id_masks_frames_workspace(eng, 70000, 2, 96, 160, 96, 160) == 0);
+            CHECK(yp_id_masks_frames_workspace(eng, 5, 2, 96, 160, 5, 10) == 0 && yp_id_masks_frames_workspace(eng, 5, 2, 46341, 46341, 46341, 46341) == 0);
+            CHECK(yp_id_masks_frames_workspace(nullptr, 5, 2, 96, 160, 96, 160) == 0);
+        } else {
+            CHECK(call(eng, idx, off, 3, 96, 160, 96, 160) == YP_ERR_STATE);                         // a detect engine has no prototypes
+            CHECK(yp_id_masks_frames_workspace(eng, 5, 2, 96, 160, 96, 160) == 0);
+        }
+        CHECK(yp_destroy(eng) == YP_OK);
+    }
     {
         // yp_mask_contours_scaled: bad arguments fail before anything is launched; n = 0 launches nothing
         static uint8_t m[16];

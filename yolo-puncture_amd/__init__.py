@@ -20,7 +20,7 @@ def __getattr__(name):
     if name in ("load_classify_net", "predict_images", "predict_and_find_start_inserted", "fix_class_prob", "ClassifierEngine"):
         from . import classify
         return getattr(classify, name)
-    if name == "auto_segment":
-        from .deva_adapter import auto_segment
-        return auto_segment
+    if name in ("auto_segment", "auto_segment_clip"):
+        from . import deva_adapter
+        return getattr(deva_adapter, name)
     raise AttributeError(name)

@@ -488,6 +488,18 @@ struct MaskFramesParams {
     size_t proto_stride; long coeff_stride;
 };
 hipError_t launch_masks_frames(const MaskFramesParams& f, float* M, int dtype, hipStream_t st);
+// All masks of many frames -> one id image per frame (yp_id_masks_frames): p describes image 0 and ALL rows (proto of image 0, coeff
+// [n_total,32], boxes [n_total,4], n = n_total, the crop, (oh,ow), (rh,rw) > 0 for the second resize, ids int64 [k,ph,pw], kept int32
+// [n_total] or NULL, suppress_small, min_area; masks and area unused). Frame j: rows row_off[j] .. row_off[j+1] against image fidx[j]
+// (proto + fidx[j] * proto_stride bytes). fidx / row_off are read from the head of the workspace (int32 fidx[k] | row_off[k+1]), where
+// the caller has put them; launch_id_masks_frames sets the two pointers.
+struct IdMaskFramesParams {
+    MaskParams p;
+    const int32_t* fidx; const int32_t* row_off; int k;
+    size_t proto_stride;
+};
+size_t id_masks_frames_workspace_bytes(const MaskParams& p, int k);
+hipError_t launch_id_masks_frames(const IdMaskFramesParams& f, int max_n, void* ws, int dtype, hipStream_t st);
 hipError_t contour_read_clocks(unsigned long long* out12);
 hipError_t launch_contours(const uint8_t* masks, int n, int H, int W, int strategy, int max_pts, int32_t* pts, int32_t* count, int32_t* parts, int parts_cap,
                            double* rect, hipStream_t st);

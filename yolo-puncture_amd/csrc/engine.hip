@@ -3083,4 +3083,77 @@ int yp_id_mask_resized(yp_engine* e, int b, const float* coeff_dev, const float*
     return masks_common(e, b, coeff_dev, boxes_dev, n, oh, ow, 1, rh, rw, nullptr, id_out, kept_out, suppress_small, min_area, stream);
 }
 
+// The sizes of yp_id_masks_frames and its workspace query: every plane (oh*ow, oh*rw, rh*rw) below 2^31 - the kernels index a plane with
+// an int and everything across rows and frames with 64 bits - and at most 2^32 - 1 threads in a launch, which is n_total * plane. -> NULL
+// when they hold, else what is wrong.
+static const char* idmf_size_error(long long n_total, int k, int oh, int ow, int rh, int rw) {
+    if (k < 1) return "k < 1";
+    if (k > 65535) return "more than 65535 frames";
+    if (n_total < 0 || n_total > 65535) return "more than 65535 masks in all";
+    if (oh <= 0 || ow <= 0 || rh <= 0 || rw <= 0) return "sizes must be positive";
+    const long long plane = std::max({(long long)oh * ow, (long long)oh * rw, (long long)rh * rw});
+    if (plane >= (1ll << 31)) return "a plane of 2^31 pixels or more";
+    if (((plane + 255) / 256 * 256) * std::max(n_total, 1ll) >= (1ll << 32)) return "n_total * plane reaches 2^32";
+    if ((rh != oh || rw != ow) && ((double)oh / rh > 16.0 || (double)ow / rw > 16.0)) return "second resize shrinks by more than 16x";
+    return nullptr;
+}
+
+static void idmf_params(const yp_engine* e, int n_total, int oh, int ow, int rh, int rw, MaskParams& p) {
+    const TensorDesc& t = e->tensors[e->proto_t];
+    p.proto = t.ptr; p.Hp = t.H; p.Wp = t.W; p.n = n_total; p.oh = oh; p.ow = ow;
+    retina_crop(t, oh, ow, p);
+    if (rh != oh || rw != ow) { p.rh = rh; p.rw = rw; }
+}
+
+size_t yp_id_masks_frames_workspace(const yp_engine* e, int n_total, int k, int oh, int ow, int rh, int rw) {
+    if (!e || e->proto_t < 0 || !e->planned || idmf_size_error(n_total, k, oh, ow, rh, rw)) return 0;
+    MaskParams p{};
+    idmf_params(e, n_total, oh, ow, rh, rw, p);
+    return id_masks_frames_workspace_bytes(p, k);
+}
+
+int yp_id_masks_frames(yp_engine* e, const int32_t* frame_idx_host, const int32_t* row_off_host, int k, const float* coeff_dev,
+                       const float* boxes_dev, int oh, int ow, int rh, int rw, int64_t* ids_out, int32_t* kept_out, int suppress_small,
+                       int min_area, void* stream) {
+    const char* fn = "yp_id_masks_frames";
+    if (!e) return fail(YP_ERR_ARG, "%s: null engine", fn);
+    if (k < 1) return fail(YP_ERR_ARG, "%s: k = %d, at least one frame is needed", fn, k);
+    if (!frame_idx_host || !row_off_host || !ids_out) return fail(YP_ERR_ARG, "%s: null frame_idx / row_off / ids_out", fn);
+    if (k > 65535) return fail(YP_ERR_ARG, "%s: at most 65535 frames per call", fn);
+    if (row_off_host[0] != 0) return fail(YP_ERR_ARG, "%s: row_off[0] = %d, must be 0", fn, row_off_host[0]);
+    int max_n = 0;
+    for (int j = 0; j < k; ++j) {
+        const long long n_j = (long long)row_off_host[j + 1] - row_off_host[j];
+        if (n_j < 0) return fail(YP_ERR_ARG, "%s: row_off decreases at frame %d", fn, j);
+        if (n_j > YP_MAX_MASKS) return fail(YP_ERR_ARG, "%s: frame %d has %lld masks, at most %d per frame (coefficients are LDS-resident)", fn, j, n_j, YP_MAX_MASKS);
+        max_n = std::max(max_n, (int)n_j);
+    }
+    const int n_total = row_off_host[k];
+    if (const char* why = idmf_size_error(n_total, k, oh, ow, rh, rw))
+        return fail(YP_ERR_ARG, "%s: %s (k=%d, n_total=%d, masks %dx%d, ids %dx%d)", fn, why, k, n_total, oh, ow, rh, rw);
+    if (n_total > 0 && (!coeff_dev || !boxes_dev || !kept_out)) return fail(YP_ERR_ARG, "%s: null coefficient / box / kept buffer", fn);
+    if (e->proto_t < 0) return fail(YP_ERR_STATE, "%s: engine was not created with YP_TASK_SEGMENT", fn);
+    if (!e->planned) return fail(YP_ERR_STATE, "%s: no forward has run yet", fn);
+    for (int j = 0; j < k; ++j)
+        if (frame_idx_host[j] < 0 || frame_idx_host[j] >= e->pB)
+            return fail(YP_ERR_ARG, "%s: frame_idx[%d] = %d outside [0,%d)", fn, j, frame_idx_host[j], e->pB);
+    if (!e->allocated) return fail(YP_ERR_STATE, "%s: no forward has run yet", fn);
+    HIPCHK(hipSetDevice(e->device));
+    const TensorDesc& t = e->tensors[e->proto_t];
+    IdMaskFramesParams f{};
+    MaskParams& p = f.p;
+    idmf_params(e, n_total, oh, ow, rh, rw, p);
+    p.coeff = coeff_dev; p.boxes = boxes_dev; p.ids = ids_out; p.kept = kept_out; p.suppress_small = suppress_small; p.min_area = min_area;
+    f.k = k;
+    f.proto_stride = (size_t)t.H * t.W * t.C * tensor_elem_bytes(*e, t);
+    const int rc = ensure_mask_ws(e, id_masks_frames_workspace_bytes(p, k), stream);
+    if (rc != YP_OK) return rc;
+    // int32 frame_idx[k] | row_off[k+1] at the head of the workspace, from the caller's arrays as yp_masks_frames copies its frame_idx
+    HIPCHK(hipMemcpyAsync(e->mask_ws, frame_idx_host, (size_t)k * sizeof(int32_t), hipMemcpyHostToDevice, (hipStream_t)stream));
+    HIPCHK(hipMemcpyAsync((int32_t*)e->mask_ws + k, row_off_host, ((size_t)k + 1) * sizeof(int32_t), hipMemcpyHostToDevice, (hipStream_t)stream));
+    hipError_t err = launch_id_masks_frames(f, max_n, e->mask_ws, e->dtype, (hipStream_t)stream);
+    if (err != hipSuccess) return fail(YP_ERR_HIP, "%s: mask kernels: %s", fn, hipGetErrorString(err));
+    return YP_OK;
+}
+
 }  // extern "C"

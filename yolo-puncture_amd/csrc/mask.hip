@@ -209,7 +209,18 @@ __global__ __launch_bounds__(256) void aa_h_kernel(const uint8_t* masks, int oh,
     T[(size_t)i * oh * rw + pix] = t;
 }
 
-// vertical pass + threshold + area: v = sum_j w[y][j] * T[i][ymin[y]+j][x] (first term a product, the rest fused multiply-adds)
+// vertical pass: v = sum_j w[y][j] * T[i][ymin[y]+j][x] (first term a product, the rest fused multiply-adds). Shared by aa_v_kernel and
+// mask_idf_aa_v_kernel.
+__device__ __forceinline__ float aa_v_value(const float* T, int i, int x, int y, int oh, int rw, const int* ymin, const int* ysize, const float* W) {
+    const float* col = T + ((size_t)i * oh + ymin[y]) * rw + x;
+    const float* w = W + (size_t)y * AA_KMAX;
+    const int sz = ysize[y];
+    float v = sz > 0 ? __fmul_rn(col[0], w[0]) : 0.f;
+    for (int j = 1; j < sz; ++j) v = fmaf(col[(size_t)j * rw], w[j], v);
+    return v;
+}
+
+// vertical pass + threshold + area
 __global__ __launch_bounds__(256) void aa_v_kernel(const float* T, int oh, int rh, int rw, const int* ymin, const int* ysize, const float* W,
                                                    uint8_t* out, double* area) {
     const int i = blockIdx.y;
@@ -217,11 +228,7 @@ __global__ __launch_bounds__(256) void aa_v_kernel(const float* T, int oh, int r
     float v = 0.f;
     if (pix < rh * rw) {
         const int y = pix / rw, x = pix - y * rw;
-        const float* col = T + ((size_t)i * oh + ymin[y]) * rw + x;
-        const float* w = W + (size_t)y * AA_KMAX;
-        const int sz = ysize[y];
-        v = sz > 0 ? __fmul_rn(col[0], w[0]) : 0.f;
-        for (int j = 1; j < sz; ++j) v = fmaf(col[(size_t)j * rw], w[j], v);
+        v = aa_v_value(T, i, x, y, oh, rw, ymin, ysize, W);
         out[(size_t)i * rh * rw + pix] = v > 0.5f ? 1 : 0;
     }
     // mask.sum() of the resized FLOAT mask (yolo_with_deva.py:75), accumulated in double
@@ -422,6 +429,239 @@ hipError_t launch_masks_frames(const MaskFramesParams& f, float* M, int dtype, h
     const long long lines = ((long long)p.oh * p.ow * f.k + ((uintptr_t)p.masks & 15) + 15) / 16;
     if (p.crop_before) hipLaunchKernelGGL(mask_frames_input_resize_kernel, dim3((unsigned)((lines + 255) / 256)), dim3(256), 0, st, f, M, p.masks);
     else hipLaunchKernelGGL(mask_frames_resize_kernel, dim3((unsigned)((lines + 255) / 256)), dim3(256), 0, st, f, M, p.masks);
+    return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// All masks of many frames -> one id image per frame (yp_id_masks_frames; the clip form of `auto_segment`, yolo_seg/yolo_with_deva.py:
+// 37-88). Frame j owns rows row_off[j] .. row_off[j+1] of the flat coefficient / box lists and uses the prototypes of image fidx[j].
+// Every per-row buffer of the one-frame tail (M, masks, T, the resized masks, both areas, kept) is laid out flat over all n_total rows,
+// and every frame has the same crop and the same sizes, so aa_weights_kernel and the row-indexed horizontal pass (aa_h_kernel) run as
+// they are, with n_total rows on the grid. New here:
+//   the GEMM, which calls the one-frame bodies on a per-frame view (a frame's coefficients in LDS) and clears the frame's area sums, so
+//   nothing is memset;
+//   the resize and the vertical pass: mask_resize_kernel's and aa_v_kernel's value per pixel (mask_value, aa_v_value), but one area
+//   atomic per workgroup and, in the resize, 16 output bytes per lane - with n_total rows at 720p the per-wave atomics of the one-frame
+//   kernels (14 400 on every row's sum) cost 2.4 and 2 ms a chunk;
+//   the ids (a wave per frame, consecutive from 1 in every frame) and the paint (integer decisions, no arithmetic to share).
+// A frame without rows takes no GEMM work and is painted 0.
+// ---------------------------------------------------------------------------------------------------------------
+__device__ __forceinline__ MaskParams idf_frame_view(const IdMaskFramesParams& f, int j, int& r0) {
+    MaskParams q = f.p;
+    r0 = f.row_off[j];
+    q.n = f.row_off[j + 1] - r0;
+    q.proto = (const char*)f.p.proto + (size_t)f.fidx[j] * f.proto_stride;
+    q.coeff = f.p.coeff + (size_t)r0 * 32;
+    return q;
+}
+
+__device__ __forceinline__ void idf_clear_areas(int r0, int n, int32_t* area, double* area_f) {
+    if (blockIdx.x != 0) return;
+    for (int i = threadIdx.x; i < n; i += blockDim.x) {
+        area[r0 + i] = 0;
+        if (area_f) area_f[r0 + i] = 0.0;
+    }
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void mask_idf_gemm_kernel(const IdMaskFramesParams f, float* M, int32_t* area, double* area_f) {
+    extern __shared__ float cs[];
+    int r0;
+    const MaskParams q = idf_frame_view(f, blockIdx.y, r0);
+    idf_clear_areas(r0, q.n, area, area_f);
+    mask_gemm_body<T>(q, M + (size_t)r0 * q.ch * q.cw, cs);
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void mask_idf_gemm_mfma_kernel(const IdMaskFramesParams f, float* M, int32_t* area, double* area_f) {
+    extern __shared__ float cs[];
+    int r0;
+    const MaskParams q = idf_frame_view(f, blockIdx.y, r0);
+    idf_clear_areas(r0, q.n, area, area_f);
+    mask_gemm_mfma_body<T>(q, M + (size_t)r0 * q.ch * q.cw, cs);
+}
+
+// bilinear + crop + `> 0` + integer area of row blockIdx.y: mask_resize_kernel's decision per pixel (retina: pixels outside the box are 0
+// without arithmetic, the rest take mask_value), stored as mask_frames_resize_body stores - lane t owns the aligned 16-byte line t of the
+// row's plane (line 0 starts at or before the plane), one uint4 store for a whole line, byte stores for the partial lines at either end,
+// which the neighbouring rows share. The set pixels are counted per workgroup: one integer atomic each.
+__global__ __launch_bounds__(256) void mask_idf_resize_kernel(const MaskParams p, const float* M, uint8_t* masks, int32_t* area) {
+    const int i = blockIdx.y;
+    const long long plane = (long long)p.oh * p.ow;
+    uint8_t* out = masks + (size_t)i * plane;
+    const long long s = ((long long)blockIdx.x * blockDim.x + threadIdx.x) * 16 - (long long)((uintptr_t)out & 15);
+    int on = 0;
+    if (s < plane) {
+        const float x1 = p.boxes[i * 4 + 0], y1 = p.boxes[i * 4 + 1], x2 = p.boxes[i * 4 + 2], y2 = p.boxes[i * 4 + 3];
+        const float* Mi = M + (size_t)i * p.ch * p.cw;
+        const long long b0 = s < 0 ? 0 : s;
+        int y = (int)(b0 / p.ow), x = (int)(b0 - (long long)y * p.ow);
+        uint32_t w[4] = {0u, 0u, 0u, 0u};
+#pragma unroll
+        for (int q = 0; q < 16; ++q) {
+            const long long b = s + q;
+            if (b < b0 || b >= plane) continue;
+            const bool inside = ((float)x >= x1) && ((float)x < x2) && ((float)y >= y1) && ((float)y < y2);
+            if (inside && mask_value(p, Mi, x, y, x1, y1, x2, y2) > 0.f) {
+                w[q >> 2] |= 1u << (8 * (q & 3));
+                ++on;
+            }
+            if (++x == p.ow) { x = 0; ++y; }
+        }
+        if (s >= 0 && s + 16 <= plane) {
+            *(uint4*)(out + s) = make_uint4(w[0], w[1], w[2], w[3]);
+        } else {
+            for (int q = 0; q < 16; ++q) {
+                const long long b = s + q;
+                if (b >= 0 && b < plane) out[b] = (uint8_t)((w[q >> 2] >> (8 * (q & 3))) & 0xffu);
+            }
+        }
+    }
+    // mask.sum() per row (yolo_with_deva.py:75)
+    __shared__ int wave_on[4];
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) on += __shfl_xor(on, o);
+    if ((threadIdx.x & 63) == 0) wave_on[threadIdx.x >> 6] = on;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const int total = wave_on[0] + wave_on[1] + wave_on[2] + wave_on[3];
+        if (total) atomicAdd(&area[i], total);
+    }
+}
+
+// aa_v_kernel for many rows: the same value per pixel (aa_v_value), a lane per pixel, but a workgroup walks IDF_V_TILES tiles of 256
+// pixels and adds its float values up in double - per lane, then across the wave and the workgroup - before ONE double atomic.
+constexpr int IDF_V_TILES = 16;
+__global__ __launch_bounds__(256) void mask_idf_aa_v_kernel(const float* T, int oh, int rh, int rw, const int* ymin, const int* ysize, const float* W,
+                                                            uint8_t* out, double* area) {
+    const int i = blockIdx.y;
+    const int plane = rh * rw;
+    double s = 0.0;
+    for (int t = 0; t < IDF_V_TILES; ++t) {
+        const long long pl = ((long long)blockIdx.x * IDF_V_TILES + t) * 256 + threadIdx.x;
+        if (pl < plane) {
+            const int pix = (int)pl;
+            const int y = pix / rw, x = pix - y * rw;
+            const float v = aa_v_value(T, i, x, y, oh, rw, ymin, ysize, W);
+            out[(size_t)i * plane + pix] = v > 0.5f ? 1 : 0;
+            s += (double)v;
+        }
+    }
+    // mask.sum() of the resized FLOAT mask (yolo_with_deva.py:75), accumulated in double
+    __shared__ double wave_sum[4];
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
+    if ((threadIdx.x & 63) == 0) wave_sum[threadIdx.x >> 6] = s;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const double total = wave_sum[0] + wave_sum[1] + wave_sum[2] + wave_sum[3];
+        if (total != 0.0) atomicAdd(&area[i], total);
+    }
+}
+
+// one wave per frame: the serial count of mask_ids_kernel / mask_ids_f_kernel as a ballot prefix over 64 rows at a time (integers: the same ids)
+__global__ __launch_bounds__(64) void mask_idf_ids_kernel(const IdMaskFramesParams f, const int32_t* area, const double* area_f, int32_t* kept) {
+    const int j = blockIdx.x, lane = threadIdx.x;
+    const int r0 = f.row_off[j], n = f.row_off[j + 1] - r0;
+    int cur = 1;
+    for (int base = 0; base < n; base += 64) {
+        const int i = base + lane;
+        bool keep = false;
+        if (i < n) keep = !(f.p.suppress_small && (area_f ? (float)area_f[r0 + i] < (float)f.p.min_area : area[r0 + i] < f.p.min_area));
+        const unsigned long long bal = __ballot(keep);
+        if (i < n) kept[r0 + i] = keep ? cur + __popcll(bal & ((1ull << lane) - 1ull)) : 0;
+        cur += __popcll(bal);
+    }
+}
+
+// mask_paint_kernel per frame. masks: uint8 [n_total,ph,pw]; ids: int64 [k,ph,pw], every pixel of every frame written
+__global__ __launch_bounds__(256) void mask_idf_paint_kernel(const IdMaskFramesParams f, int ph, int pw, const uint8_t* masks, const int32_t* kept, int64_t* ids) {
+    const int j = blockIdx.y;
+    const int pix = blockIdx.x * blockDim.x + threadIdx.x;
+    if (pix >= ph * pw) return;
+    const int r0 = f.row_off[j], n = f.row_off[j + 1] - r0;
+    const size_t plane = (size_t)ph * pw;
+    int64_t id = 0;
+    for (int i = n - 1; i >= 0; --i) {   // the last painter wins
+        if (kept[r0 + i] > 0 && masks[(size_t)(r0 + i) * plane + pix]) { id = kept[r0 + i]; break; }
+    }
+    ids[(size_t)j * plane + pix] = id;
+}
+
+// workspace of launch_id_masks_frames, every block 256-byte aligned:
+//   int32 fidx[k] row_off[k+1] | int32 area[n] | int32 kept[n] | float M[n*ch*cw] | u8 masks[n*oh*ow]
+//   (+ second resize: double area_f[n] | int xmin/xsize[rw] ymin/ysize[rh] | float Wx/Wy | float T[n*oh*rw] | u8 masks2[n*rh*rw]),  n = n_total
+struct IdfLayout { size_t meta, area, kept, M, masks, area_f, tabs, W, T, masks2, total; };
+static IdfLayout idf_layout(const MaskParams& p, int k) {
+    IdfLayout L{};
+    size_t o = 0;
+    auto take = [&](size_t bytes) { const size_t at = o; o += align256(bytes); return at; };
+    const size_t n = (size_t)p.n;
+    L.meta = take((2 * (size_t)k + 1) * 4);
+    L.area = take(n * 4);
+    L.kept = take(n * 4);
+    L.M = take(n * p.ch * p.cw * 4);
+    L.masks = take(n * p.oh * p.ow);
+    if (p.rh > 0) {
+        L.area_f = take(n * 8);
+        L.tabs = take(2 * (size_t)(p.rw + p.rh) * 4);
+        L.W = take((size_t)(p.rw + p.rh) * AA_KMAX * 4);
+        L.T = take(n * p.oh * p.rw * 4);
+        L.masks2 = take(n * p.rh * p.rw);
+    }
+    L.total = o;
+    return L;
+}
+
+size_t id_masks_frames_workspace_bytes(const MaskParams& p, int k) { return idf_layout(p, k).total; }
+
+// f.p.n = n_total; the first block of `ws` already holds fidx[k] | row_off[k+1]; max_n = the largest frame. 4 launches, 8 with the second resize.
+hipError_t launch_id_masks_frames(const IdMaskFramesParams& f0, int max_n, void* ws, int dtype, hipStream_t st) {
+    IdMaskFramesParams f = f0;
+    const MaskParams& p = f.p;
+    const bool second = p.rh > 0;
+    const int ph = second ? p.rh : p.oh, pw = second ? p.rw : p.ow;
+    if ((size_t)((max_n + 15) & ~15) * 32 * sizeof(float) > 60 * 1024) return hipErrorInvalidValue;
+    if (second && ((float)p.oh / (float)p.rh > 16.f || (float)p.ow / (float)p.rw > 16.f)) return hipErrorInvalidValue;   // (AA_KMAX taps)
+    const IdfLayout L = idf_layout(p, f.k);
+    char* b = (char*)ws;
+    f.fidx = (const int32_t*)(b + L.meta);
+    f.row_off = f.fidx + f.k;
+    int32_t* area = (int32_t*)(b + L.area);
+    int32_t* kept = p.kept ? p.kept : (int32_t*)(b + L.kept);
+    float* M = (float*)(b + L.M);
+    uint8_t* masks = (uint8_t*)(b + L.masks);
+    double* area_f = second ? (double*)(b + L.area_f) : nullptr;
+    const uint8_t* painted = masks;
+    if (p.n > 0) {
+        const int npix = p.ch * p.cw;
+        static const bool valu_gemm = env_on("YOLOP_MASK_VALU");   // as launch_masks
+        if (valu_gemm) {
+            const size_t sh = (size_t)max_n * 32 * sizeof(float);
+            if (dtype == DT_BF16) hipLaunchKernelGGL(mask_idf_gemm_kernel<__bf16>, dim3((npix + 255) / 256, f.k), dim3(256), sh, st, f, M, area, area_f);
+            else hipLaunchKernelGGL(mask_idf_gemm_kernel<float>, dim3((npix + 255) / 256, f.k), dim3(256), sh, st, f, M, area, area_f);
+        } else {
+            const size_t sh = (size_t)((max_n + 15) & ~15) * 32 * sizeof(float);
+            if (dtype == DT_BF16) hipLaunchKernelGGL(mask_idf_gemm_mfma_kernel<__bf16>, dim3((npix + 63) / 64, f.k), dim3(256), sh, st, f, M, area, area_f);
+            else hipLaunchKernelGGL(mask_idf_gemm_mfma_kernel<float>, dim3((npix + 63) / 64, f.k), dim3(256), sh, st, f, M, area, area_f);
+        }
+        const long long lines = ((long long)p.oh * p.ow + 15 + 15) / 16;            // (a plane may start up to 15 bytes into its first line)
+        hipLaunchKernelGGL(mask_idf_resize_kernel, dim3((unsigned)((lines + 255) / 256), p.n), dim3(256), 0, st, p, M, masks, area);
+        if (second) {
+            int* xmin = (int*)(b + L.tabs); int* xsize = xmin + p.rw; int* ymin = xsize + p.rw; int* ysize = ymin + p.rh;
+            float* Wx = (float*)(b + L.W); float* Wy = Wx + (size_t)p.rw * AA_KMAX;
+            float* T = (float*)(b + L.T);
+            uint8_t* masks2 = (uint8_t*)(b + L.masks2);
+            hipLaunchKernelGGL(aa_weights_kernel, dim3((p.rw + 63) / 64), dim3(64), 0, st, p.ow, p.rw, xmin, xsize, Wx);   // once per call:
+            hipLaunchKernelGGL(aa_weights_kernel, dim3((p.rh + 63) / 64), dim3(64), 0, st, p.oh, p.rh, ymin, ysize, Wy);   // every frame shares them
+            hipLaunchKernelGGL(aa_h_kernel, dim3((p.oh * p.rw + 255) / 256, p.n), dim3(256), 0, st, masks, p.oh, p.ow, p.rw, xmin, xsize, Wx, T);
+            hipLaunchKernelGGL(mask_idf_aa_v_kernel, dim3((p.rh * p.rw + 256 * IDF_V_TILES - 1) / (256 * IDF_V_TILES), p.n), dim3(256), 0, st, T, p.oh, p.rh,
+                               p.rw, ymin, ysize, Wy, masks2, area_f);
+            painted = masks2;
+        }
+    }
+    hipLaunchKernelGGL(mask_idf_ids_kernel, dim3(f.k), dim3(64), 0, st, f, area, area_f, kept);
+    hipLaunchKernelGGL(mask_idf_paint_kernel, dim3((ph * pw + 255) / 256, f.k), dim3(256), 0, st, f, ph, pw, painted, kept, p.ids);
     return hipGetLastError();
 }
 

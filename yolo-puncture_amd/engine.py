@@ -126,6 +126,10 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     lib.yp_masks_frames.restype = C.c_int
     lib.yp_masks_frames_input.argtypes = [vp, vp, C.c_int, vp, C.c_long, vp, C.c_int, C.c_int, vp, vp]
     lib.yp_masks_frames_input.restype = C.c_int
+    lib.yp_id_masks_frames.argtypes = [vp, vp, vp, C.c_int, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int, C.c_int, vp]
+    lib.yp_id_masks_frames.restype = C.c_int
+    lib.yp_id_masks_frames_workspace.argtypes = [vp] + [C.c_int] * 6
+    lib.yp_id_masks_frames_workspace.restype = C.c_size_t
     lib.yp_comm_unique_id.argtypes = [vp]
     lib.yp_comm_create.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.POINTER(vp)]
     lib.yp_allgather.argtypes = [vp, vp, vp, C.c_size_t, vp]
@@ -145,7 +149,7 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
 EXPORTS = ["yp_last_error", "yp_create", "yp_destroy", "yp_weight_count", "yp_weight_info", "yp_set_weight",
            "yp_finalize", "yp_forward", "yp_proto", "yp_masks", "yp_id_mask_resized", "yp_plan", "yp_op_info", "yp_op_output", "yp_op_input", "yp_op_fusion",
            "yp_tensor_count", "yp_tensor_info", "yp_tensor_read", "yp_profile", "yp_set_graph", "yp_run_op",
-           "yp_tensor_write", "yp_op_kernel", "yp_set_autotune", "yp_tuning_export", "yp_tuning_import", "yp_set_nms", "yp_debug_force_conv_cfg", "yp_debug_op_cfg", "yp_debug_op_form", "yp_debug_last_store_form", "yp_debug_max_workgroups", "yp_debug_conv_families", "yp_debug_ablation", "yp_debug_head_clocks", "yp_debug_head_branch_clocks", "yp_debug_head_winners", "yp_debug_contour_clocks", "yp_debug_pwsp_clocks", "yp_debug_host_selftest", "yp_debug_graph_info", "yp_tuning_source", "yp_debug_head_positions", "yp_debug_marker", "yp_max_batch", "yp_debug_topk_anchors", "yp_debug_attention", "yp_debug_attention_form", "yp_debug_conv_s2", "yp_set_attention_form", "yp_letterbox", "yp_letterbox_batch", "yp_masks_frames", "yp_masks_frames_input", "yp_mask_contours",
+           "yp_tensor_write", "yp_op_kernel", "yp_set_autotune", "yp_tuning_export", "yp_tuning_import", "yp_set_nms", "yp_debug_force_conv_cfg", "yp_debug_op_cfg", "yp_debug_op_form", "yp_debug_last_store_form", "yp_debug_max_workgroups", "yp_debug_conv_families", "yp_debug_ablation", "yp_debug_head_clocks", "yp_debug_head_branch_clocks", "yp_debug_head_winners", "yp_debug_contour_clocks", "yp_debug_pwsp_clocks", "yp_debug_host_selftest", "yp_debug_graph_info", "yp_tuning_source", "yp_debug_head_positions", "yp_debug_marker", "yp_max_batch", "yp_debug_topk_anchors", "yp_debug_attention", "yp_debug_attention_form", "yp_debug_conv_s2", "yp_set_attention_form", "yp_letterbox", "yp_letterbox_batch", "yp_masks_frames", "yp_masks_frames_input", "yp_id_masks_frames", "yp_id_masks_frames_workspace", "yp_mask_contours",
            "yp_mask_contours_scaled", "yp_mask_contours_large_workspace", "yp_mask_contours_large", "yp_comm_unique_id", "yp_comm_create", "yp_allgather", "yp_comm_destroy",
            "yp_u2net_create", "yp_u2net_destroy", "yp_u2net_weight_count", "yp_u2net_weight_info", "yp_u2net_set_weight", "yp_u2net_finalize",
            "yp_u2net_forward", "yp_u2net_forward_crops", "yp_u2net_set_graph", "yp_u2net_tensor_count", "yp_u2net_tensor_info", "yp_u2net_tensor_read",
@@ -155,6 +159,8 @@ EXPORTS = ["yp_last_error", "yp_create", "yp_destroy", "yp_weight_count", "yp_we
 
 
 MAX_ANCHORS = 294912      # YP_MAX_ANCHORS
+MAX_MASKS = 480           # YP_MAX_MASKS
+ID_MASKS_FRAMES_BUDGET = 1 << 30      # YP_ID_MASKS_FRAMES_BUDGET: workspace bytes of one yp_id_masks_frames call before the facade splits a chunk
 ATTENTION_FORMS = {"auto": 0, "stream": 1, "stream_wide": 3}      # yp_set_attention_form (bit 0: 32/64 streaming kernel, bit 1: 36/72)
 
 
@@ -616,6 +622,49 @@ class Engine:
         self._chk(self.lib.yp_id_mask_resized(self._h, b, C.c_void_p(coeff.data_ptr()), C.c_void_p(boxes.data_ptr()), n, int(mask_hw[0]),
                                               int(mask_hw[1]), int(out_hw[0]), int(out_hw[1]), C.c_void_p(ids.data_ptr()),
                                               C.c_void_p(kept.data_ptr()), 1 if suppress_small else 0, int(min_area),
+                                              C.c_void_p(_stream_ptr(dev))))
+        self._keep = [coeff, boxes]
+        return ids, kept
+
+    def id_masks_frames_workspace(self, n_total: int, k: int, mask_hw: Tuple[int, int], out_hw: Optional[Tuple[int, int]] = None) -> int:
+        """yp_id_masks_frames_workspace: bytes of engine workspace id_masks_frames needs for `k` frames with `n_total` masks in all at the
+        engine's current plan (host arithmetic). 0: no plan yet, or sizes the call refuses."""
+        oh, ow = int(mask_hw[0]), int(mask_hw[1])
+        rh, rw = (oh, ow) if out_hw is None else (int(out_hw[0]), int(out_hw[1]))
+        return int(self.lib.yp_id_masks_frames_workspace(self._h, int(n_total), int(k), oh, ow, rh, rw))
+
+    def id_masks_frames(self, frame_idx, counts, coeff: torch.Tensor, boxes: torch.Tensor, mask_hw: Tuple[int, int],
+                        out_hw: Optional[Tuple[int, int]] = None, suppress_small: bool = False, min_area: int = 100):
+        """yp_id_masks_frames: the id image of every frame of `frame_idx` (images of the last forward; gaps and repeats allowed) from ALL its
+        masks. Frame j owns the next counts[j] rows of `coeff` float32 cuda [n_total,32] and `boxes` float32 cuda [n_total,4] (pixels of
+        `mask_hw`, the size the masks are made at); `out_hw` is the size of the id images (antialiased second resize when it differs).
+        -> (ids int64 cuda [k,rh,rw], kept int32 cuda [n_total]); frame j's part equals masks(frame_idx[j], its rows, mask_hw, want_ids=True)
+        or id_mask_resized(frame_idx[j], its rows, mask_hw, out_hw) byte for byte."""
+        fidx = np.ascontiguousarray(np.asarray(frame_idx, dtype=np.int64).reshape(-1)).astype(np.int32)
+        cnt = np.asarray(counts, dtype=np.int64).reshape(-1)
+        k = int(fidx.shape[0])
+        if cnt.shape[0] != k:
+            raise ValueError(f"id_masks_frames: {k} frames but {cnt.shape[0]} counts")
+        if k and cnt.min() < 0:
+            raise ValueError("id_masks_frames: negative count")
+        n_total = int(cnt.sum())
+        if n_total >= 2 ** 31:
+            raise ValueError("id_masks_frames: too many rows")
+        row_off = np.zeros(k + 1, dtype=np.int32)
+        row_off[1:] = np.cumsum(cnt)
+        oh, ow = int(mask_hw[0]), int(mask_hw[1])
+        rh, rw = (oh, ow) if out_hw is None else (int(out_hw[0]), int(out_hw[1]))
+        if not (coeff.is_cuda and coeff.dtype == torch.float32 and tuple(coeff.shape) == (n_total, 32)):
+            raise ValueError(f"id_masks_frames: coeff must be a float32 CUDA tensor [{n_total},32]")
+        if not (boxes.is_cuda and boxes.dtype == torch.float32 and tuple(boxes.shape) == (n_total, 4) and boxes.device == coeff.device):
+            raise ValueError(f"id_masks_frames: boxes must be a float32 CUDA tensor [{n_total},4] on {coeff.device}")
+        dev = coeff.device
+        coeff, boxes = coeff.contiguous(), boxes.contiguous()
+        ids = torch.empty((k, max(rh, 0), max(rw, 0)), dtype=torch.int64, device=dev)
+        kept = torch.empty((n_total,), dtype=torch.int32, device=dev)
+        self._chk(self.lib.yp_id_masks_frames(self._h, fidx.ctypes.data_as(C.c_void_p), row_off.ctypes.data_as(C.c_void_p), k,
+                                              C.c_void_p(coeff.data_ptr()), C.c_void_p(boxes.data_ptr()), oh, ow, rh, rw,
+                                              C.c_void_p(ids.data_ptr()), C.c_void_p(kept.data_ptr()), 1 if suppress_small else 0, int(min_area),
                                               C.c_void_p(_stream_ptr(dev))))
         self._keep = [coeff, boxes]
         return ids, kept

@@ -381,3 +381,37 @@ def clip_track(detected: Sequence[bool], xyxy: Sequence, polygons: Sequence, rec
             lens.append(last_rect_len)
         boxes.append(xyxy_box)
     return boxes, coords, lens
+
+
+# ---- `auto_segment` over a clip (YOLO.predict_id_mask_clip) -----------------------------------------------------------------
+def group_frames_by_workspace(counts: Sequence[int], workspace_bytes, budget: int, max_rows: int = 65535):
+    """Calls of Engine.id_masks_frames for a chunk whose frame j has counts[j] masks: frames are taken greedily, in order, into one call
+    while `workspace_bytes(n_total, k)` (the engine's query for k frames with n_total masks in all) stays within `budget` bytes and the
+    call has at most `max_rows` masks. -> [(batched, [frame, ...]), ...] covering every frame once, in order; batched=False is ONE frame
+    whose own workspace exceeds the budget (or that the query declines with 0): it goes through the one-frame call. Frames without
+    masks are grouped like any other (their id image comes out of the same launches)."""
+    groups: List[Tuple[bool, List[int]]] = []
+    cur: List[int] = []
+    rows = 0
+
+    def fits(n_total, k):
+        need = int(workspace_bytes(n_total, k))
+        return 0 < need <= budget and n_total <= max_rows
+
+    for j, n in enumerate(int(c) for c in counts):
+        if n < 0:
+            raise ValueError(f"negative mask count {n} for frame {j}")
+        if cur and fits(rows + n, len(cur) + 1):
+            cur.append(j)
+            rows += n
+            continue
+        if cur:
+            groups.append((True, cur))
+            cur, rows = [], 0
+        if fits(n, 1):
+            cur, rows = [j], n
+        else:
+            groups.append((False, [j]))
+    if cur:
+        groups.append((True, cur))
+    return groups

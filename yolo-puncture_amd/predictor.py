@@ -20,7 +20,7 @@ import numpy as np
 import torch
 
 from . import hostops
-from .engine import ATTENTION_FORMS, LARGE_MAX_DIM, Engine, letterbox_batch_device, letterbox_device, mask_contours_device, mask_contours_large_device
+from .engine import ATTENTION_FORMS, ID_MASKS_FRAMES_BUDGET, LARGE_MAX_DIM, Engine, letterbox_batch_device, letterbox_device, mask_contours_device, mask_contours_large_device
 from .weights import read_ultralytics_pt, synthetic_state
 
 _ENGINE_CACHE: Dict[tuple, Engine] = {}
@@ -321,6 +321,29 @@ class ClipResults(tuple):
     @property
     def lens(self):
         return self[2]
+
+
+def _clip_frames(frames, dev: torch.device, what: str):
+    """The clip argument of YOLO.predict_id_mask_clip, checked as predict_clip checks its own and in its words: a list of BGR uint8 HWC
+    ndarrays of one shape, or a uint8 CUDA tensor [N,H,W,3] on `dev`. -> (on_dev, frames (a list, or the tensor), N, H, W); raises before
+    any engine is built."""
+    on_dev = isinstance(frames, torch.Tensor)
+    if on_dev:
+        if not (frames.is_cuda and frames.dtype == torch.uint8 and frames.dim() == 4 and frames.shape[-1] == 3):
+            raise TypeError(f"{what} expects BGR uint8 HWC ndarrays or a uint8 CUDA tensor [N,H,W,3]")
+        if frames.device != dev:
+            raise ValueError(f"frames are on {frames.device}, the engine on {dev}")
+        N, H, W = (int(v) for v in frames.shape[:3])
+    else:
+        frames = list(frames)
+        N = len(frames)
+        for f in frames:
+            if not (isinstance(f, np.ndarray) and f.dtype == np.uint8 and f.ndim == 3 and f.shape[2] == 3):
+                raise TypeError(f"{what} expects BGR uint8 HWC ndarrays or a uint8 CUDA tensor [N,H,W,3]")
+            if f.shape != frames[0].shape:
+                raise ValueError(f"frames differ in shape: {f.shape} vs {frames[0].shape}")
+        H, W = (int(v) for v in frames[0].shape[:2]) if N else (0, 0)
+    return on_dev, frames, N, H, W
 
 
 class _ModelHandle:
@@ -662,3 +685,109 @@ class YOLO:
             # thresholds at 0.5 (:71-79): one GPU pass (yp_id_mask_resized)
             ids, kept = eng.id_mask_resized(0, cf, boxes, (oh, ow), out_hw, suppress_small=suppress_small, min_area=min_area)
         return ids, kept.cpu(), d[:, 4].clone(), d[:, 5].clone()
+
+    def predict_id_mask_clip(self, images, conf: float = 0.9, out_hw: Optional[Tuple[int, int]] = None, suppress_small: bool = False,
+                             min_area: int = 100, imgsz: int = 640, pre_resize: Optional[Tuple[int, int]] = None, batch_size: int = 32):
+        """predict_id_mask for a whole clip of same-shape frames - the detection frames of a DEVA run, which are known in advance
+        (yolo_seg/yolo_with_deva.py:140,197). -> a list with predict_id_mask's 4-tuple for every frame.
+
+        images: a list of uint8 HWC ndarrays of one shape, or a uint8 CUDA tensor [N,H,W,3] on the engine's device. Chunks and padding are
+        predict_clip's (hostops.clip_plan). Per chunk: one upload (host frames), one letterbox launch per resize (`pre_resize`, then the
+        model input), the forward, ONE copy of the [c,max_det,6] rows, the strict `> conf` test and scale_boxes on the host, one gather of
+        the kept coefficient rows by an index built from that host copy, one upload of all boxes, and the id-mask tail of all frames
+        (Engine.id_masks_frames) - in as many calls as keep each call's workspace within ID_MASKS_FRAMES_BUDGET
+        (hostops.group_frames_by_workspace); a frame that exceeds it alone takes the one-frame call."""
+        if not self.seg:
+            raise ValueError("auto_segment needs a segmentation checkpoint")
+        if int(batch_size) < 1:
+            raise ValueError(f"batch_size must be >= 1 (got {batch_size})")
+        dev = torch.device("cuda", self._dev_index)
+        on_dev, frames, N, H, W = _clip_frames(images, dev, "predict_id_mask_clip")
+        if N == 0:
+            return []
+        if H <= 0 or W <= 0:
+            raise ValueError(f"empty frames ({H}x{W})")
+        pre_geo = None
+        oh, ow = H, W
+        if pre_resize is not None and (int(pre_resize[1]), int(pre_resize[0])) != (H, W):
+            ow, oh = int(pre_resize[0]), int(pre_resize[1])
+            pre_geo = dict(out_h=oh, out_w=ow, new_h=oh, new_w=ow, top=0, left=0)          # cv2.resize(INTER_LINEAR) on the device
+        out_hw = (oh, ow) if out_hw is None else (int(out_hw[0]), int(out_hw[1]))
+        geo = hostops.letterbox_geometry(oh, ow, imgsz)
+        Hl, Wl = geo["out_h"], geo["out_w"]
+        eng = self._engine()
+        B, chunks = hostops.clip_plan(N, min(int(batch_size), eng.max_batch(Hl, Wl)))
+        if self.family != "v10":
+            eng.set_nms(conf, 0.7)
+        mode = os.environ.get("YOLOP_PREDICT_GRAPH", "auto")
+
+        def buffer(name, shape):
+            cache = self.__dict__.setdefault(name, {})
+            key = (self._dev_index,) + shape
+            if key not in cache:
+                cache[key] = torch.empty(shape + (3,), dtype=torch.uint8, device=dev)
+            return cache[key]
+
+        batch = buffer("_batch_cache", (B, Hl, Wl))                     # the buffer predict() uses for this shape: one hipGraph per shape
+        stage = None if on_dev else buffer("_clip_stage", (B, H, W))
+        shrunk = buffer("_clip_pre", (B, oh, ow)) if pre_geo is not None else None
+        if on_dev:
+            frames = frames.contiguous()
+        cache = self.__dict__.setdefault("_out_cache", {})
+        okey = (self._dev_index, B)
+        same = out_hw == (oh, ow)
+        results = []
+        for s0, c in chunks:
+            if on_dev:
+                src = frames[s0:s0 + c]
+            else:
+                for q in range(c):
+                    stage[q].copy_(torch.from_numpy(np.ascontiguousarray(frames[s0 + q])), non_blocking=True)
+                src = stage[:c]
+            if pre_geo is not None:
+                src = letterbox_batch_device(src, pre_geo, out=shrunk[:c])
+            letterbox_batch_device(src, geo, out=batch[:c])
+            if c < B:                                                   # pad rows: the chunk's last frame again (their results are dropped)
+                batch[c:].copy_(batch[c - 1:c].expand(B - c, Hl, Wl, 3))
+            eng.set_graph("auto" if mode == "auto" else int(mode))
+            out = eng.forward(batch, cache.get(okey))
+            cache[okey] = out
+            det_host = out["det"][:c].cpu()                             # ONE copy: every row of the chunk's frames
+            max_det = int(det_host.shape[1])
+            rows, gather, counts = [], [], []
+            for j in range(c):
+                dh = det_host[j]
+                keep = torch.nonzero(dh[:, 4] > conf).flatten()         # strict, as predict_id_mask
+                rows.append(dh[keep])
+                gather.append(keep + j * max_det)
+                counts.append(int(keep.shape[0]))
+            d_all = torch.cat(rows)
+            n_all = int(d_all.shape[0])
+            boxes = hostops.scale_boxes_t((Hl, Wl), d_all[:, :4], (oh, ow)).to(dev, non_blocking=True)
+            coeff = out["coeff"].view(-1, 32).index_select(0, torch.cat(gather).to(dev, non_blocking=True)) if n_all else \
+                torch.empty((0, 32), dtype=torch.float32, device=dev)
+            off = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
+            ids_of, kept_of = [None] * c, [None] * c
+            groups = hostops.group_frames_by_workspace(counts, lambda n, k: eng.id_masks_frames_workspace(n, k, (oh, ow), out_hw),
+                                                       ID_MASKS_FRAMES_BUDGET)
+            for batched, js in groups:
+                r0, r1 = int(off[js[0]]), int(off[js[-1] + 1])
+                if batched:
+                    ids, kept = eng.id_masks_frames(js, [counts[j] for j in js], coeff[r0:r1], boxes[r0:r1], (oh, ow), out_hw,
+                                                    suppress_small=suppress_small, min_area=min_area)
+                    kept = kept.cpu()
+                    for t, j in enumerate(js):
+                        ids_of[j], kept_of[j] = ids[t], kept[int(off[j]) - r0:int(off[j + 1]) - r0].clone()
+                else:                                                   # alone beyond the budget: the one-frame call
+                    j = js[0]
+                    if same:
+                        _, ids, kept = eng.masks(j, coeff[r0:r1], boxes[r0:r1], (oh, ow), retina=True, want_masks=False, want_ids=True,
+                                                 suppress_small=suppress_small, min_area=min_area)
+                    else:
+                        ids, kept = eng.id_mask_resized(j, coeff[r0:r1], boxes[r0:r1], (oh, ow), out_hw, suppress_small=suppress_small,
+                                                        min_area=min_area)
+                    ids_of[j], kept_of[j] = ids, kept.cpu()
+            for j in range(c):
+                d = rows[j]
+                results.append((ids_of[j], kept_of[j], d[:, 4].clone(), d[:, 5].clone()))
+        return results
