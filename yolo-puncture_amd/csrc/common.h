@@ -4,7 +4,9 @@
 #include <stdint.h>
 #include <atomic>
 #include <cstdlib>
+#include <initializer_list>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 namespace yp {
@@ -342,8 +344,47 @@ struct ConvFamily {
     const char* tune_env;                                                 // the tuner's A/B switch, null = always a candidate
     bool opt_in;                                                          // tune_env = 1 adds the family instead of removing it
 };
-// ",HAS_RES,OUT_F32" of the persistent conv kernels, as their launchers pick the instance (out_f32 first)
-inline const char* res_f32_args(const ConvParams& p) { return p.out_f32 ? ",false,true" : p.res ? ",true,false" : ",false,false"; }
+// Tile configurations (host side). A configuration is a type that states its kernel's leading template arguments ONCE: a family's
+// `template <int...> struct X : Cfg<...>` with the tile sizes its valid() reads as constexpr members. A family is the CfgList of its
+// configurations in id order; validity, the reported symbol and the launch all go through with_cfg, so they cannot name different instances.
+template <int... V> struct Cfg {};
+template <class... C> struct CfgList { static constexpr int size = (int)sizeof...(C); };
+// f(C{}) for the c-th configuration of the list; c out of range: hipErrorInvalidValue for a launch, else an empty value (no name, not valid)
+template <class F, class... C> auto with_cfg_of(CfgList<C...>, int c, F& f) {
+    using R = std::common_type_t<decltype(f(C{}))...>;
+    R r{};
+    if constexpr (std::is_same_v<R, hipError_t>) r = hipErrorInvalidValue;
+    int i = 0;
+    ((i++ == c ? (void)(r = f(C{})) : (void)0), ...);
+    return r;
+}
+template <class List, class F> auto with_cfg(int c, F f) { return with_cfg_of(List{}, c, f); }
+// "256,128,4,2,32,4" of a Cfg<256,128,4,2,32,4>, ",true,false" of {true, false}
+template <int... V> std::string cfg_args(Cfg<V...>) {
+    std::string s;
+    ((s += (s.empty() ? "" : ",") + std::to_string(V)), ...);
+    return s;
+}
+inline std::string bool_args(std::initializer_list<bool> bs) {
+    std::string s;
+    for (bool b : bs) s += b ? ",true" : ",false";
+    return s;
+}
+// the symbol kernel<V..., variant arguments>
+template <class K> std::string cfg_symbol(const char* kernel, K k, const std::string& variant = "") { return std::string(kernel) + "<" + cfg_args(k) + variant + ">"; }
+// HAS_RES, OUT_F32 of the persistent conv kernels: out_f32 first (fp32 logits never carry a residual), then res, else neither
+template <class F> auto with_res_f32(const ConvParams& p, F f) {
+    if (p.out_f32) return f(std::false_type{}, std::true_type{});
+    if (p.res) return f(std::true_type{}, std::false_type{});
+    return f(std::false_type{}, std::false_type{});
+}
+inline std::string res_f32_args(const ConvParams& p) { return with_res_f32(p, [](auto res, auto f32) { return bool_args({res, f32}); }); }
+// store side of the kernels whose epilogue has only the 4-channel vector form, through buffer descriptors
+inline bool conv_store_side_ok(const ConvParams& p) {
+    if ((p.Cout & 3) || (p.y_stride & 3) || (p.y_coff & 3) || (p.res && ((p.res_stride & 3) || (p.res_coff & 3)))) return false;
+    if (p.res && p.out_f32) return false;
+    return p.x_bytes < (1ull << 31) && p.w_bytes < (1ull << 31) && p.y_bytes < (1ull << 31);
+}
 // conv_dma (ids 0..) picks its configuration from p.cfg / the forced id itself and ignores c; conv_halo_s2 launches its fused trailing 1x1
 // form when p.C2 > 0 (configuration from conv_halo_s2_pw_cfg)
 extern const ConvFamily conv_dma_family, conv_halo_family, conv_halo_p_family, conv_dma_p_family, conv_dma_lc_family, conv_halo_s2_family,

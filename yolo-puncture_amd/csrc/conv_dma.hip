@@ -219,38 +219,40 @@ __global__ __launch_bounds__(WGM * WGN * 64) void conv_dma_kernel(const ConvPara
 // configurations + launch. p.cfg >= 0 selects one explicitly (the engine's plan-time autotuner times the valid ones
 // per layer and keeps the fastest); p.cfg < 0 uses the static heuristic.
 // ---------------------------------------------------------------------------------------------------------------
-struct DmaCfg { int BM, BN, NW, BK, NS; const char* name; };
-static const DmaCfg kCfgs[] = {
-    {128, 32, 4, 32, 4, "conv_dma_kernel<128,32,4,1,32,4>"},     // 0
-    {128, 64, 4, 32, 4, "conv_dma_kernel<128,64,2,2,32,4>"},     // 1
-    {128, 128, 4, 32, 4, "conv_dma_kernel<128,128,2,2,32,4>"},   // 2
-    {64, 64, 4, 32, 4, "conv_dma_kernel<64,64,2,2,32,4>"},       // 3
-    {256, 64, 8, 32, 4, "conv_dma_kernel<256,64,4,2,32,4>"},     // 4
-    {256, 128, 8, 32, 4, "conv_dma_kernel<256,128,4,2,32,4>"},   // 5
-    {256, 128, 8, 64, 3, "conv_dma_kernel<256,128,4,2,64,3>"},   // 6
-    {128, 128, 4, 64, 3, "conv_dma_kernel<128,128,2,2,64,3>"},   // 7
-    {128, 64, 4, 64, 3, "conv_dma_kernel<128,64,2,2,64,3>"},     // 8
-    {256, 64, 8, 64, 3, "conv_dma_kernel<256,64,4,2,64,3>"},     // 9
-    {128, 256, 8, 32, 4, "conv_dma_kernel<128,256,2,4,32,4>"},   // 10
-    {256, 32, 8, 32, 4, "conv_dma_kernel<256,32,8,1,32,4>"},     // 11
-    {128, 256, 8, 64, 3, "conv_dma_kernel<128,256,2,4,64,3>"},   // 12
-    {64, 128, 4, 64, 3, "conv_dma_kernel<64,128,2,2,64,3>"},     // 13
+template <int BM_, int BN_, int WGM, int WGN, int BK_, int NS> struct Dma : Cfg<BM_, BN_, WGM, WGN, BK_, NS> {
+    static constexpr int BM = BM_, BN = BN_, BK = BK_;
+    static constexpr size_t lds() { return (size_t)NS * (BM + BN) * BK * 2 + 1024; }      // NS stages + the landing zone
 };
-constexpr int kNumCfgs = (int)(sizeof(kCfgs) / sizeof(kCfgs[0]));
-
+using DmaCfgs = CfgList<
+    Dma<128, 32, 4, 1, 32, 4>,     // 0
+    Dma<128, 64, 2, 2, 32, 4>,     // 1
+    Dma<128, 128, 2, 2, 32, 4>,    // 2
+    Dma<64, 64, 2, 2, 32, 4>,      // 3
+    Dma<256, 64, 4, 2, 32, 4>,     // 4
+    Dma<256, 128, 4, 2, 32, 4>,    // 5
+    Dma<256, 128, 4, 2, 64, 3>,    // 6
+    Dma<128, 128, 2, 2, 64, 3>,    // 7
+    Dma<128, 64, 2, 2, 64, 3>,     // 8
+    Dma<256, 64, 4, 2, 64, 3>,     // 9
+    Dma<128, 256, 2, 4, 32, 4>,    // 10
+    Dma<256, 32, 8, 1, 32, 4>,     // 11
+    Dma<128, 256, 2, 4, 64, 3>,    // 12
+    Dma<64, 128, 2, 2, 64, 3>>;    // 13
 
 bool conv_dma_supported(const ConvParams& p) {
     return (p.Cin % 32) == 0 && (p.Kpad % 32) == 0 && p.x_bytes < (1ull << 31) && p.w_bytes < (1ull << 31) && p.ks <= 3;
 }
 
 static bool conv_dma_cfg_valid(const ConvParams& p, int c) {
-    if (c < 0 || c >= kNumCfgs || !conv_dma_supported(p)) return false;
-    const DmaCfg& k = kCfgs[c];
-    if (k.BK == 64 && ((p.Cin % 64) != 0 || (p.Kpad % 64) != 0)) return false;
-    const int cpad = (p.Cout + 31) / 32 * 32;
-    if (k.BN > 32 && k.BN >= 2 * cpad) return false;            // more than half the tile would be padding
-    if (k.BN == 32 && p.Cout > 32) return false;
-    return true;
+    if (!conv_dma_supported(p)) return false;
+    return with_cfg<DmaCfgs>(c, [&](auto k) {
+        using K = decltype(k);
+        if (K::BK == 64 && ((p.Cin % 64) != 0 || (p.Kpad % 64) != 0)) return false;
+        const int cpad = (p.Cout + 31) / 32 * 32;
+        if (K::BN > 32 && K::BN >= 2 * cpad) return false;            // more than half the tile would be padding
+        if (K::BN == 32 && p.Cout > 32) return false;
+        return true;
+    });
 }
 
 static int dma_heuristic(const ConvParams& p) {
@@ -277,12 +279,14 @@ static int dma_choice(const ConvParams& p) {
     return c >= 0 ? c : dma_heuristic(p);
 }
 
-static std::string conv_dma_symbol(const ConvParams& p, int) { return kCfgs[dma_choice(p)].name; }
+static std::string conv_dma_symbol(const ConvParams& p, int) {
+    return with_cfg<DmaCfgs>(dma_choice(p), [](auto k) { return cfg_symbol("conv_dma_kernel", k); });
+}
 
 template <int BM, int BN, int WGM, int WGN, int BK, int NS>
-static hipError_t launch_one(const ConvParams& p, hipStream_t st) {
+static hipError_t launch_one(Dma<BM, BN, WGM, WGN, BK, NS> k, const ConvParams& p, hipStream_t st) {
     const int mtiles = (p.M + BM - 1) / BM, ntiles = (p.Cout + BN - 1) / BN;
-    const size_t sh = (size_t)NS * (BM + BN) * BK * 2 + 1024;
+    const size_t sh = k.lds();
     auto kern = conv_dma_kernel<BM, BN, WGM, WGN, BK, NS>;
     static size_t granted = 0;
     if (hipError_t e = allow_dynamic_lds((const void*)kern, sh, granted)) return e;
@@ -291,26 +295,11 @@ static hipError_t launch_one(const ConvParams& p, hipStream_t st) {
 }
 
 static hipError_t launch_conv_dma(const ConvParams& p, int, hipStream_t st) {
-    switch (dma_choice(p)) {
-        case 0: return launch_one<128, 32, 4, 1, 32, 4>(p, st);
-        case 1: return launch_one<128, 64, 2, 2, 32, 4>(p, st);
-        case 2: return launch_one<128, 128, 2, 2, 32, 4>(p, st);
-        case 3: return launch_one<64, 64, 2, 2, 32, 4>(p, st);
-        case 4: return launch_one<256, 64, 4, 2, 32, 4>(p, st);
-        case 5: return launch_one<256, 128, 4, 2, 32, 4>(p, st);
-        case 6: return launch_one<256, 128, 4, 2, 64, 3>(p, st);
-        case 7: return launch_one<128, 128, 2, 2, 64, 3>(p, st);
-        case 8: return launch_one<128, 64, 2, 2, 64, 3>(p, st);
-        case 9: return launch_one<256, 64, 4, 2, 64, 3>(p, st);
-        case 10: return launch_one<128, 256, 2, 4, 32, 4>(p, st);
-        case 11: return launch_one<256, 32, 8, 1, 32, 4>(p, st);
-        case 12: return launch_one<128, 256, 2, 4, 64, 3>(p, st);
-        default: return launch_one<64, 128, 2, 2, 64, 3>(p, st);
-    }
+    return with_cfg<DmaCfgs>(dma_choice(p), [&](auto k) { return launch_one(k, p, st); });
 }
 
 #if !defined(__HIP_DEVICE_COMPILE__)      // (host data: the device pass must not reference the host functions)
-const ConvFamily conv_dma_family = {0, kNumCfgs, conv_dma_cfg_valid, conv_dma_symbol, launch_conv_dma, false, nullptr, false};
+const ConvFamily conv_dma_family = {0, DmaCfgs::size, conv_dma_cfg_valid, conv_dma_symbol, launch_conv_dma, false, nullptr, false};
 #endif
 
 }  // namespace yp

@@ -233,40 +233,40 @@ __global__ __launch_bounds__((WGM * WGN + NL) * 64) void conv_dma_lc_kernel(cons
 }
 
 // ---------------------------------------------------------------------------------------------------------------
-struct LcCfg { int BM, BN, NC, NL, BK, NS; const char* name; };
-static const LcCfg kL[] = {
-    {128, 128, 8, 8, 64, 4, "conv_dma_lc_kernel<128,128,4,2,8,64,4"},   // 0: 16 waves
-    {128, 128, 4, 8, 32, 4, "conv_dma_lc_kernel<128,128,2,2,8,32,4"},   // 1: 12 waves, 32-deep k-steps (Cin % 64 != 0)
-    {128, 64, 4, 8, 64, 4, "conv_dma_lc_kernel<128,64,2,2,8,64,4"},     // 2: 12 waves
-    {128, 64, 8, 8, 64, 4, "conv_dma_lc_kernel<128,64,4,2,8,64,4"},     // 3
-    {128, 128, 4, 8, 64, 4, "conv_dma_lc_kernel<128,128,2,2,8,64,4"},   // 4: 12 waves, one consumer per SIMD
-    {256, 64, 8, 8, 64, 3, "conv_dma_lc_kernel<256,64,4,2,8,64,3"},     // 5
-    {64, 64, 4, 4, 64, 4, "conv_dma_lc_kernel<64,64,2,2,4,64,4"},       // 6: 8 waves, two workgroups per CU
-    {128, 64, 4, 12, 64, 4, "conv_dma_lc_kernel<128,64,2,2,12,64,4"},   // 7: 16 waves, 24 pieces over 12 loaders
-    {64, 128, 4, 12, 64, 4, "conv_dma_lc_kernel<64,128,2,2,12,64,4"},   // 8
+template <int BM, int BN_, int WGM, int WGN, int NL, int BK_, int NS> struct Lc : Cfg<BM, BN_, WGM, WGN, NL, BK_, NS> {
+    static constexpr int BN = BN_, BK = BK_;
+    static constexpr size_t lds() { return (size_t)NS * (BM + BN) * BK * 2; }      // NS stages
 };
-constexpr int kNumL = (int)(sizeof(kL) / sizeof(kL[0]));
-static std::string conv_dma_lc_symbol(const ConvParams& p, int c) { return std::string(kL[c].name) + res_f32_args(p) + ">"; }
-
-static bool conv_dma_lc_cfg_valid(const ConvParams& p, int c) {
-    if (c < 0 || c >= kNumL) return false;
-    if ((p.Cin % 32) != 0 || (p.Kpad % 32) != 0 || p.ks > 3 || p.up != 1) return false;
-    if (p.x_bytes >= (1ull << 31) || p.w_bytes >= (1ull << 31) || p.y_bytes >= (1ull << 31)) return false;
-    if ((p.Cout & 3) || (p.y_stride & 3) || (p.y_coff & 3) || (p.res && ((p.res_stride & 3) || (p.res_coff & 3)))) return false;
-    if (p.res && p.out_f32) return false;
-    const LcCfg& k = kL[c];
-    if (k.BK == 64 && ((p.Cin % 64) != 0 || (p.Kpad % 64) != 0)) return false;
-    if (p.x2_C > 0 && (p.ks != 1 || (p.x2_C % k.BK) != 0 || p.x2_bytes >= (1ull << 31))) return false;
-    const int cpad = (p.Cout + 31) / 32 * 32;
-    if (k.BN >= 2 * cpad) return false;
-    // the weight rows of the block must exist (packed weights are padded to 128 rows)
-    return true;
+using LcCfgs = CfgList<
+    Lc<128, 128, 4, 2, 8, 64, 4>,    // 0: 16 waves
+    Lc<128, 128, 2, 2, 8, 32, 4>,    // 1: 12 waves, 32-deep k-steps (Cin % 64 != 0)
+    Lc<128, 64, 2, 2, 8, 64, 4>,     // 2: 12 waves
+    Lc<128, 64, 4, 2, 8, 64, 4>,     // 3
+    Lc<128, 128, 2, 2, 8, 64, 4>,    // 4: 12 waves, one consumer per SIMD
+    Lc<256, 64, 4, 2, 8, 64, 3>,     // 5
+    Lc<64, 64, 2, 2, 4, 64, 4>,      // 6: 8 waves, two workgroups per CU
+    Lc<128, 64, 2, 2, 12, 64, 4>,    // 7: 16 waves, 24 pieces over 12 loaders
+    Lc<64, 128, 2, 2, 12, 64, 4>>;   // 8
+static std::string conv_dma_lc_symbol(const ConvParams& p, int c) {
+    return with_cfg<LcCfgs>(c, [&](auto k) { return cfg_symbol("conv_dma_lc_kernel", k, res_f32_args(p)); });
 }
 
-template <int BM, int BN, int WGM, int WGN, int NL, int BK, int NS, bool HAS_RES, bool OUT_F32>
-static hipError_t launch_lc_var(const ConvParams& p, hipStream_t st) {
+static bool conv_dma_lc_cfg_valid(const ConvParams& p, int c) {
+    if ((p.Cin % 32) != 0 || (p.Kpad % 32) != 0 || p.ks > 3 || p.up != 1) return false;
+    if (!conv_store_side_ok(p)) return false;
+    return with_cfg<LcCfgs>(c, [&](auto k) {
+        using K = decltype(k);
+        if (K::BK == 64 && ((p.Cin % 64) != 0 || (p.Kpad % 64) != 0)) return false;
+        if (p.x2_C > 0 && (p.ks != 1 || (p.x2_C % K::BK) != 0 || p.x2_bytes >= (1ull << 31))) return false;
+        const int cpad = (p.Cout + 31) / 32 * 32;
+        return K::BN < 2 * cpad;
+    });
+}
+
+template <bool HAS_RES, bool OUT_F32, int BM, int BN, int WGM, int WGN, int NL, int BK, int NS>
+static hipError_t launch_lc_var(Lc<BM, BN, WGM, WGN, NL, BK, NS> k, const ConvParams& p, hipStream_t st) {
     const int mtiles = (p.M + BM - 1) / BM, ntiles = (p.Cout + BN - 1) / BN;
-    const size_t sh = (size_t)NS * (BM + BN) * BK * 2;
+    const size_t sh = k.lds();
     const int per_cu = (int)std::max<size_t>(1, std::min<size_t>((WGM * WGN + NL) >= 12 ? 1 : 2, (160 * 1024) / sh));
     int G = (256 * per_cu) / ntiles;
     if (G < 1) G = 1;
@@ -296,29 +296,15 @@ static hipError_t launch_lc_var(const ConvParams& p, hipStream_t st) {
     hipLaunchKernelGGL(kern, dim3(G * ntiles), dim3((WGM * WGN + NL) * 64), sh, st, p, mtiles, ntiles, G);
     return hipGetLastError();
 }
-template <int BM, int BN, int WGM, int WGN, int NL, int BK, int NS>
-static hipError_t launch_lc_one(const ConvParams& p, hipStream_t st) {
-    if (p.out_f32) return launch_lc_var<BM, BN, WGM, WGN, NL, BK, NS, false, true>(p, st);
-    if (p.res) return launch_lc_var<BM, BN, WGM, WGN, NL, BK, NS, true, false>(p, st);
-    return launch_lc_var<BM, BN, WGM, WGN, NL, BK, NS, false, false>(p, st);
-}
 
 static hipError_t launch_conv_dma_lc(const ConvParams& p, int c, hipStream_t st) {
-    switch (c) {
-        case 0: return launch_lc_one<128, 128, 4, 2, 8, 64, 4>(p, st);
-        case 1: return launch_lc_one<128, 128, 2, 2, 8, 32, 4>(p, st);
-        case 2: return launch_lc_one<128, 64, 2, 2, 8, 64, 4>(p, st);
-        case 3: return launch_lc_one<128, 64, 4, 2, 8, 64, 4>(p, st);
-        case 4: return launch_lc_one<128, 128, 2, 2, 8, 64, 4>(p, st);
-        case 5: return launch_lc_one<256, 64, 4, 2, 8, 64, 3>(p, st);
-        case 6: return launch_lc_one<64, 64, 2, 2, 4, 64, 4>(p, st);
-        case 7: return launch_lc_one<128, 64, 2, 2, 12, 64, 4>(p, st);
-        default: return launch_lc_one<64, 128, 2, 2, 12, 64, 4>(p, st);
-    }
+    return with_cfg<LcCfgs>(c, [&](auto k) {
+        return with_res_f32(p, [&](auto res, auto f32) { return launch_lc_var<res, f32>(k, p, st); });
+    });
 }
 
 #if !defined(__HIP_DEVICE_COMPILE__)      // (host data: the device pass must not reference the host functions)
-const ConvFamily conv_dma_lc_family = {400, kNumL, conv_dma_lc_cfg_valid, conv_dma_lc_symbol, launch_conv_dma_lc, true, "YOLOP_NO_LC", false};
+const ConvFamily conv_dma_lc_family = {400, LcCfgs::size, conv_dma_lc_cfg_valid, conv_dma_lc_symbol, launch_conv_dma_lc, true, "YOLOP_NO_LC", false};
 #endif
 
 }  // namespace yp

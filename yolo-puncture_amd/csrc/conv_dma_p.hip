@@ -399,147 +399,103 @@ __global__ __launch_bounds__(WGM * WGN * 64) void conv_dma_p_kernel(const ConvPa
 }
 
 // ---------------------------------------------------------------------------------------------------------------
-struct DmaPCfg { int BM, BN, NW, BK, NS; const char* name; int wres; int pipe; int pp; };
-static const DmaPCfg kP[] = {
-    {128, 32, 4, 32, 4, "conv_dma_p_kernel<128,32,4,1,32,4"},     // 0
-    {128, 64, 4, 32, 4, "conv_dma_p_kernel<128,64,2,2,32,4"},     // 1
-    {128, 128, 4, 32, 4, "conv_dma_p_kernel<128,128,2,2,32,4"},   // 2
-    {64, 64, 4, 32, 4, "conv_dma_p_kernel<64,64,2,2,32,4"},       // 3
-    {256, 64, 8, 32, 4, "conv_dma_p_kernel<256,64,4,2,32,4"},     // 4
-    {256, 128, 8, 32, 4, "conv_dma_p_kernel<256,128,4,2,32,4"},   // 5
-    {128, 128, 4, 64, 3, "conv_dma_p_kernel<128,128,2,2,64,3"},   // 6
-    {128, 64, 4, 64, 3, "conv_dma_p_kernel<128,64,2,2,64,3"},     // 7
-    {128, 256, 8, 32, 4, "conv_dma_p_kernel<128,256,2,4,32,4"},   // 8
-    {64, 128, 4, 64, 3, "conv_dma_p_kernel<64,128,2,2,64,3"},     // 9
-    {64, 64, 4, 64, 4, "conv_dma_p_kernel<64,64,2,2,64,4"},       // 10
-    {128, 64, 8, 64, 4, "conv_dma_p_kernel<128,64,4,2,64,4"},     // 11
-    // weight-resident forms (ids 12..): the [BN][K] weight block stays in LDS, only the pixel tile streams
-    {128, 64, 4, 32, 4, "conv_dma_p_kernel<128,64,2,2,32,4", 1},   // 12
-    {128, 64, 4, 64, 4, "conv_dma_p_kernel<128,64,2,2,64,4", 1},   // 13
-    {64, 64, 4, 32, 4, "conv_dma_p_kernel<64,64,2,2,32,4", 1},     // 14
-    {64, 64, 4, 64, 4, "conv_dma_p_kernel<64,64,2,2,64,4", 1},     // 15
-    {128, 128, 4, 64, 3, "conv_dma_p_kernel<128,128,2,2,64,3", 1}, // 16
-    {128, 128, 8, 64, 4, "conv_dma_p_kernel<128,128,4,2,64,4", 1}, // 17
-    {128, 32, 4, 32, 4, "conv_dma_p_kernel<128,32,4,1,32,4", 1},   // 18
-    {256, 64, 8, 64, 3, "conv_dma_p_kernel<256,64,4,2,64,3", 1},   // 19
-    {128, 256, 8, 64, 3, "conv_dma_p_kernel<128,256,2,4,64,3", 1}, // 20
-    // software-pipelined fragment forms (ids 21..)
-    {256, 128, 8, 32, 4, "conv_dma_p_kernel<256,128,4,2,32,4", 0, 1},     // 21
-    {256, 64, 8, 32, 4, "conv_dma_p_kernel<256,64,4,2,32,4", 0, 1},       // 22
-    {128, 256, 8, 32, 4, "conv_dma_p_kernel<128,256,2,4,32,4", 0, 1},     // 23
-    {128, 128, 4, 32, 4, "conv_dma_p_kernel<128,128,2,2,32,4", 0, 1},     // 24
-    {128, 64, 4, 32, 4, "conv_dma_p_kernel<128,64,2,2,32,4", 0, 1},       // 25
-    {64, 64, 4, 32, 4, "conv_dma_p_kernel<64,64,2,2,32,4", 0, 1},         // 26
-    {64, 64, 4, 64, 4, "conv_dma_p_kernel<64,64,2,2,64,4", 0, 1},         // 27
-    {128, 64, 8, 64, 4, "conv_dma_p_kernel<128,64,4,2,64,4", 0, 1},       // 28
-    {128, 128, 8, 64, 4, "conv_dma_p_kernel<128,128,4,2,64,4", 1, 1},   // 29
-    {64, 64, 4, 64, 4, "conv_dma_p_kernel<64,64,2,2,64,4", 1, 1},       // 30
-    {128, 64, 4, 64, 4, "conv_dma_p_kernel<128,64,2,2,64,4", 1, 1},     // 31
-    {128, 128, 8, 64, 4, "conv_dma_p_kernel<128,128,4,2,64,4", 0, 1},     // 32
-    // ping-pong forms (ids 33..): the two waves of each SIMD alternate between a load segment and a matrix burst
-    {256, 128, 8, 32, 4, "conv_dma_p_kernel<256,128,4,2,32,4", 0, 0, 1},     // 33
-    {256, 64, 8, 32, 4, "conv_dma_p_kernel<256,64,4,2,32,4", 0, 0, 1},       // 34
-    {128, 256, 8, 32, 4, "conv_dma_p_kernel<128,256,2,4,32,4", 0, 0, 1},     // 35
-    {128, 128, 8, 64, 4, "conv_dma_p_kernel<128,128,4,2,64,4", 0, 0, 1},     // 36
-    {128, 64, 8, 64, 4, "conv_dma_p_kernel<128,64,4,2,64,4", 0, 0, 1},       // 37
-    {128, 128, 8, 64, 4, "conv_dma_p_kernel<128,128,4,2,64,4", 1, 0, 1},   // 38
-    {256, 64, 8, 64, 3, "conv_dma_p_kernel<256,64,4,2,64,3", 1, 0, 1},     // 39
-    {256, 128, 8, 64, 3, "conv_dma_p_kernel<256,128,4,2,64,3", 0, 0, 1},     // 40 (3 x 48 KiB stages)
+enum { P_WRES = 1, P_PIPE = 2, P_PP = 4 };      // the kernel's WRES / PIPE / PP arguments of a configuration
+template <int BM, int BN_, int WGM, int WGN, int BK_, int NS, int FORM = 0> struct DmaP : Cfg<BM, BN_, WGM, WGN, BK_, NS> {
+    static constexpr int BN = BN_, BK = BK_;
+    static constexpr bool wres = FORM & P_WRES, pipe = FORM & P_PIPE, pp = FORM & P_PP;
+    // NS stages + the landing zone; a weight-resident form streams pixels alone and keeps its [BN][Kpad] block behind them
+    static constexpr size_t lds(int Kpad) {
+        return wres ? (size_t)NS * BM * BK * 2 + 1024 + (size_t)BN * Kpad * 2 : (size_t)NS * (BM + BN) * BK * 2 + 1024;
+    }
 };
-constexpr int kNumP = (int)(sizeof(kP) / sizeof(kP[0]));
+using DmaPCfgs = CfgList<
+    DmaP<128, 32, 4, 1, 32, 4>,                     // 0
+    DmaP<128, 64, 2, 2, 32, 4>,                     // 1
+    DmaP<128, 128, 2, 2, 32, 4>,                    // 2
+    DmaP<64, 64, 2, 2, 32, 4>,                      // 3
+    DmaP<256, 64, 4, 2, 32, 4>,                     // 4
+    DmaP<256, 128, 4, 2, 32, 4>,                    // 5
+    DmaP<128, 128, 2, 2, 64, 3>,                    // 6
+    DmaP<128, 64, 2, 2, 64, 3>,                     // 7
+    DmaP<128, 256, 2, 4, 32, 4>,                    // 8
+    DmaP<64, 128, 2, 2, 64, 3>,                     // 9
+    DmaP<64, 64, 2, 2, 64, 4>,                      // 10
+    DmaP<128, 64, 4, 2, 64, 4>,                     // 11
+    // weight-resident forms (ids 12..): the [BN][K] weight block stays in LDS, only the pixel tile streams
+    DmaP<128, 64, 2, 2, 32, 4, P_WRES>,             // 12
+    DmaP<128, 64, 2, 2, 64, 4, P_WRES>,             // 13
+    DmaP<64, 64, 2, 2, 32, 4, P_WRES>,              // 14
+    DmaP<64, 64, 2, 2, 64, 4, P_WRES>,              // 15
+    DmaP<128, 128, 2, 2, 64, 3, P_WRES>,            // 16
+    DmaP<128, 128, 4, 2, 64, 4, P_WRES>,            // 17
+    DmaP<128, 32, 4, 1, 32, 4, P_WRES>,             // 18
+    DmaP<256, 64, 4, 2, 64, 3, P_WRES>,             // 19
+    DmaP<128, 256, 2, 4, 64, 3, P_WRES>,            // 20
+    // software-pipelined fragment forms (ids 21..)
+    DmaP<256, 128, 4, 2, 32, 4, P_PIPE>,            // 21
+    DmaP<256, 64, 4, 2, 32, 4, P_PIPE>,             // 22
+    DmaP<128, 256, 2, 4, 32, 4, P_PIPE>,            // 23
+    DmaP<128, 128, 2, 2, 32, 4, P_PIPE>,            // 24
+    DmaP<128, 64, 2, 2, 32, 4, P_PIPE>,             // 25
+    DmaP<64, 64, 2, 2, 32, 4, P_PIPE>,              // 26
+    DmaP<64, 64, 2, 2, 64, 4, P_PIPE>,              // 27
+    DmaP<128, 64, 4, 2, 64, 4, P_PIPE>,             // 28
+    DmaP<128, 128, 4, 2, 64, 4, P_WRES | P_PIPE>,   // 29
+    DmaP<64, 64, 2, 2, 64, 4, P_WRES | P_PIPE>,     // 30
+    DmaP<128, 64, 2, 2, 64, 4, P_WRES | P_PIPE>,    // 31
+    DmaP<128, 128, 4, 2, 64, 4, P_PIPE>,            // 32
+    // ping-pong forms (ids 33..): the two waves of each SIMD alternate between a load segment and a matrix burst
+    DmaP<256, 128, 4, 2, 32, 4, P_PP>,              // 33
+    DmaP<256, 64, 4, 2, 32, 4, P_PP>,               // 34
+    DmaP<128, 256, 2, 4, 32, 4, P_PP>,              // 35
+    DmaP<128, 128, 4, 2, 64, 4, P_PP>,              // 36
+    DmaP<128, 64, 4, 2, 64, 4, P_PP>,               // 37
+    DmaP<128, 128, 4, 2, 64, 4, P_WRES | P_PP>,     // 38
+    DmaP<256, 64, 4, 2, 64, 3, P_WRES | P_PP>,      // 39
+    DmaP<256, 128, 4, 2, 64, 3, P_PP>>;             // 40 (3 x 48 KiB stages)
 
 static bool conv_dma_p_cfg_valid(const ConvParams& p, int c) {
-    if (c < 0 || c >= kNumP) return false;
     if ((p.Cin % 32) != 0 || (p.Kpad % 32) != 0 || p.ks > 3 || p.up != 1) return false;
-    if (p.x_bytes >= (1ull << 31) || p.w_bytes >= (1ull << 31) || p.y_bytes >= (1ull << 31)) return false;
-    if ((p.Cout & 3) || (p.y_stride & 3) || (p.y_coff & 3) || (p.res && ((p.res_stride & 3) || (p.res_coff & 3)))) return false;
-    if (p.res && p.out_f32) return false;
-    const DmaPCfg& k = kP[c];
-    if (k.BK == 64 && ((p.Cin % 64) != 0 || (p.Kpad % 64) != 0)) return false;
-    if (p.x2_C > 0 && (p.ks != 1 || (p.x2_C % k.BK) != 0 || p.x2_bytes >= (1ull << 31))) return false;
-    const int cpad = (p.Cout + 31) / 32 * 32;
-    if (k.BN > 32 && k.BN >= 2 * cpad) return false;
-    if (k.BN == 32 && p.Cout > 32) return false;
-    if (k.wres) {
-        const size_t sh = (size_t)k.NS * k.BM * k.BK * 2 + 1024 + (size_t)k.BN * p.Kpad * 2;
-        if (sh > 160 * 1024) return false;
-    }
-    return true;
+    if (!conv_store_side_ok(p)) return false;
+    return with_cfg<DmaPCfgs>(c, [&](auto k) {
+        using K = decltype(k);
+        if (K::BK == 64 && ((p.Cin % 64) != 0 || (p.Kpad % 64) != 0)) return false;
+        if (p.x2_C > 0 && (p.ks != 1 || (p.x2_C % K::BK) != 0 || p.x2_bytes >= (1ull << 31))) return false;
+        const int cpad = (p.Cout + 31) / 32 * 32;
+        if (K::BN > 32 && K::BN >= 2 * cpad) return false;
+        if (K::BN == 32 && p.Cout > 32) return false;
+        return !K::wres || K::lds(p.Kpad) <= 160 * 1024;
+    });
 }
 static std::string conv_dma_p_symbol(const ConvParams& p, int c) {
-    const DmaPCfg& k = kP[c];
-    return std::string(k.name) + res_f32_args(p) + (k.wres ? ",true" : ",false") + (k.pipe ? ",true" : ",false") + (k.pp ? ",true>" : ",false>");
+    return with_cfg<DmaPCfgs>(c, [&](auto k) {
+        return cfg_symbol("conv_dma_p_kernel", k, res_f32_args(p) + bool_args({k.wres, k.pipe, k.pp}));
+    });
 }
 
-template <int BM, int BN, int WGM, int WGN, int BK, int NS, bool HAS_RES, bool OUT_F32, bool WRES, bool PIPE, bool PP>
-static hipError_t launch_p_var(const ConvParams& p, hipStream_t st) {
+template <bool HAS_RES, bool OUT_F32, int BM, int BN, int WGM, int WGN, int BK, int NS, int FORM>
+static hipError_t launch_p_var(DmaP<BM, BN, WGM, WGN, BK, NS, FORM> k, const ConvParams& p, hipStream_t st) {
     const int mtiles = (p.M + BM - 1) / BM, ntiles = (p.Cout + BN - 1) / BN;
-    const size_t sh = WRES ? ((size_t)NS * BM * BK * 2 + 1024 + (size_t)BN * p.Kpad * 2) : ((size_t)NS * (BM + BN) * BK * 2 + 1024);
+    const size_t sh = k.lds(p.Kpad);
     const int per_cu = (int)std::max<size_t>(1, std::min<size_t>(WGM * WGN == 8 ? 2 : 4, (160 * 1024) / sh));
     int G = (256 * per_cu) / ntiles;
     if (G < 1) G = 1;
     if (G > mtiles) G = mtiles;
-    auto kern = conv_dma_p_kernel<BM, BN, WGM, WGN, BK, NS, HAS_RES, OUT_F32, WRES, PIPE, PP>;
+    auto kern = conv_dma_p_kernel<BM, BN, WGM, WGN, BK, NS, HAS_RES, OUT_F32, k.wres, k.pipe, k.pp>;
     static size_t granted = 0;
     if (hipError_t e = allow_dynamic_lds((const void*)kern, sh, granted)) return e;
     hipLaunchKernelGGL(kern, dim3(G * ntiles), dim3(WGM * WGN * 64), sh, st, p, mtiles, ntiles, G);
     return hipGetLastError();
 }
-template <int BM, int BN, int WGM, int WGN, int BK, int NS, bool WRES = false, bool PIPE = false, bool PP = false>
-static hipError_t launch_p_one(const ConvParams& p, hipStream_t st) {
-    if (p.out_f32) return launch_p_var<BM, BN, WGM, WGN, BK, NS, false, true, WRES, PIPE, PP>(p, st);
-    if (p.res) return launch_p_var<BM, BN, WGM, WGN, BK, NS, true, false, WRES, PIPE, PP>(p, st);
-    return launch_p_var<BM, BN, WGM, WGN, BK, NS, false, false, WRES, PIPE, PP>(p, st);
-}
 
 static hipError_t launch_conv_dma_p(const ConvParams& p, int c, hipStream_t st) {
-    switch (c) {
-        case 0: return launch_p_one<128, 32, 4, 1, 32, 4>(p, st);
-        case 1: return launch_p_one<128, 64, 2, 2, 32, 4>(p, st);
-        case 2: return launch_p_one<128, 128, 2, 2, 32, 4>(p, st);
-        case 3: return launch_p_one<64, 64, 2, 2, 32, 4>(p, st);
-        case 4: return launch_p_one<256, 64, 4, 2, 32, 4>(p, st);
-        case 5: return launch_p_one<256, 128, 4, 2, 32, 4>(p, st);
-        case 6: return launch_p_one<128, 128, 2, 2, 64, 3>(p, st);
-        case 7: return launch_p_one<128, 64, 2, 2, 64, 3>(p, st);
-        case 8: return launch_p_one<128, 256, 2, 4, 32, 4>(p, st);
-        case 9: return launch_p_one<64, 128, 2, 2, 64, 3>(p, st);
-        case 10: return launch_p_one<64, 64, 2, 2, 64, 4>(p, st);
-        case 11: return launch_p_one<128, 64, 4, 2, 64, 4>(p, st);
-        case 12: return launch_p_one<128, 64, 2, 2, 32, 4, true>(p, st);
-        case 13: return launch_p_one<128, 64, 2, 2, 64, 4, true>(p, st);
-        case 14: return launch_p_one<64, 64, 2, 2, 32, 4, true>(p, st);
-        case 15: return launch_p_one<64, 64, 2, 2, 64, 4, true>(p, st);
-        case 16: return launch_p_one<128, 128, 2, 2, 64, 3, true>(p, st);
-        case 17: return launch_p_one<128, 128, 4, 2, 64, 4, true>(p, st);
-        case 18: return launch_p_one<128, 32, 4, 1, 32, 4, true>(p, st);
-        case 19: return launch_p_one<256, 64, 4, 2, 64, 3, true>(p, st);
-        case 20: return launch_p_one<128, 256, 2, 4, 64, 3, true>(p, st);
-        case 21: return launch_p_one<256, 128, 4, 2, 32, 4, false, true>(p, st);
-        case 22: return launch_p_one<256, 64, 4, 2, 32, 4, false, true>(p, st);
-        case 23: return launch_p_one<128, 256, 2, 4, 32, 4, false, true>(p, st);
-        case 24: return launch_p_one<128, 128, 2, 2, 32, 4, false, true>(p, st);
-        case 25: return launch_p_one<128, 64, 2, 2, 32, 4, false, true>(p, st);
-        case 26: return launch_p_one<64, 64, 2, 2, 32, 4, false, true>(p, st);
-        case 27: return launch_p_one<64, 64, 2, 2, 64, 4, false, true>(p, st);
-        case 28: return launch_p_one<128, 64, 4, 2, 64, 4, false, true>(p, st);
-        case 29: return launch_p_one<128, 128, 4, 2, 64, 4, true, true>(p, st);
-        case 30: return launch_p_one<64, 64, 2, 2, 64, 4, true, true>(p, st);
-        case 31: return launch_p_one<128, 64, 2, 2, 64, 4, true, true>(p, st);
-        case 32: return launch_p_one<128, 128, 4, 2, 64, 4, false, true>(p, st);
-        case 33: return launch_p_one<256, 128, 4, 2, 32, 4, false, false, true>(p, st);
-        case 34: return launch_p_one<256, 64, 4, 2, 32, 4, false, false, true>(p, st);
-        case 35: return launch_p_one<128, 256, 2, 4, 32, 4, false, false, true>(p, st);
-        case 36: return launch_p_one<128, 128, 4, 2, 64, 4, false, false, true>(p, st);
-        case 37: return launch_p_one<128, 64, 4, 2, 64, 4, false, false, true>(p, st);
-        case 38: return launch_p_one<128, 128, 4, 2, 64, 4, true, false, true>(p, st);
-        case 39: return launch_p_one<256, 64, 4, 2, 64, 3, true, false, true>(p, st);
-        default: return launch_p_one<256, 128, 4, 2, 64, 3, false, false, true>(p, st);
-    }
+    return with_cfg<DmaPCfgs>(c, [&](auto k) {
+        return with_res_f32(p, [&](auto res, auto f32) { return launch_p_var<res, f32>(k, p, st); });
+    });
 }
 
 #if !defined(__HIP_DEVICE_COMPILE__)      // (host data: the device pass must not reference the host functions)
-const ConvFamily conv_dma_p_family = {300, kNumP, conv_dma_p_cfg_valid, conv_dma_p_symbol, launch_conv_dma_p, true, nullptr, false};
+const ConvFamily conv_dma_p_family = {300, DmaPCfgs::size, conv_dma_p_cfg_valid, conv_dma_p_symbol, launch_conv_dma_p, true, nullptr, false};
 #endif
 
 }  // namespace yp

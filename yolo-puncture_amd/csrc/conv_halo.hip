@@ -224,39 +224,38 @@ __global__ __launch_bounds__(WGM * WGN * 64) void conv_halo_kernel(const ConvPar
 }
 
 // ---------------------------------------------------------------------------------------------------------------
-struct HaloCfg { int FM, FN, WGM, WGN; const char* name; };
-static const HaloCfg kHalo[] = {
-    {8, 2, 2, 2, "conv_halo_kernel<8,2,2,2>"},   // 0: 16x16 px x 64 ch, 4 waves
-    {4, 2, 4, 1, "conv_halo_kernel<4,2,4,1>"},   // 1: 16x16 px x 32 ch, 4 waves
-    {4, 2, 2, 2, "conv_halo_kernel<4,2,2,2>"},   // 2:  8x16 px x 64 ch, 4 waves
-    {4, 2, 4, 2, "conv_halo_kernel<4,2,4,2>"},   // 3: 16x16 px x 64 ch, 8 waves
-    {4, 2, 2, 1, "conv_halo_kernel<4,2,2,1>"},   // 4:  8x16 px x 32 ch, 2 waves -> not instantiated (NW must be 4/8)
+template <int FM, int FN, int WGM, int WGN> struct Halo : Cfg<FM, FN, WGM, WGN> {
+    static constexpr int TH = WGM * FM, BN = WGN * FN * 16;
+    // 2 halo slots + 6 weight slots in whole 1-KiB pieces + the landing zone (the kernel's HB, WB)
+    static constexpr size_t lds() { return (size_t)2 * (((TH + 2) * 18 * 4 + 63) / 64) * 1024 + (size_t)6 * (3 * BN * 4 / 64) * 1024 + 1024; }
 };
-constexpr int kNumHalo = 4;
-
+using HaloCfgs = CfgList<
+    Halo<8, 2, 2, 2>,    // 0: 16x16 px x 64 ch, 4 waves
+    Halo<4, 2, 4, 1>,    // 1: 16x16 px x 32 ch, 4 waves
+    Halo<4, 2, 2, 2>,    // 2:  8x16 px x 64 ch, 4 waves
+    Halo<4, 2, 4, 2>>;   // 3: 16x16 px x 64 ch, 8 waves
 
 static bool conv_halo_cfg_valid(const ConvParams& p, int c) {
-    if (c < 0 || c >= kNumHalo) return false;
     if (p.ks != 3 || p.stride != 1 || p.pad != 1 || p.up != 1 || (p.Cin % 32) != 0 || (p.Kpad != 9 * p.Cin)) return false;
     if (p.x_bytes >= (1ull << 31) || p.w_bytes >= (1ull << 31)) return false;
-    const HaloCfg& k = kHalo[c];
-    const int BN = k.WGN * k.FN * 16, TH = k.WGM * k.FM;
-    const int cpad = (p.Cout + 31) / 32 * 32;
-    if (BN > cpad) return false;
-    // reject shapes where the fixed 16-wide tiles waste more than a third of the MFMAs
-    const long covered = (long)((p.Ho + TH - 1) / TH * TH) * ((p.Wo + 15) / 16 * 16);
-    if (covered * 2 > (long)p.Ho * p.Wo * 3) return false;
-    return true;
+    return with_cfg<HaloCfgs>(c, [&](auto k) {
+        using K = decltype(k);
+        const int cpad = (p.Cout + 31) / 32 * 32;
+        if (K::BN > cpad) return false;
+        // reject shapes where the fixed 16-wide tiles waste more than a third of the MFMAs
+        const long covered = (long)((p.Ho + K::TH - 1) / K::TH * K::TH) * ((p.Wo + 15) / 16 * 16);
+        return covered * 2 <= (long)p.Ho * p.Wo * 3;
+    });
 }
 
-static std::string conv_halo_symbol(const ConvParams& p, int c) { return kHalo[c].name; }
+static std::string conv_halo_symbol(const ConvParams& p, int c) {
+    return with_cfg<HaloCfgs>(c, [](auto k) { return cfg_symbol("conv_halo_kernel", k); });
+}
 
 template <int FM, int FN, int WGM, int WGN>
-static hipError_t launch_halo_one(const ConvParams& p, hipStream_t st) {
-    constexpr int NW = WGM * WGN, TH = WGM * FM, BN = WGN * FN * 16;
-    constexpr int HP = (TH + 2) * 18, H_INSTR = (HP * 4 + 63) / 64, W_INSTR = 3 * BN * 4 / 64;
-    (void)NW;
-    const size_t sh = (size_t)2 * H_INSTR * 1024 + (size_t)6 * W_INSTR * 1024 + 1024;
+static hipError_t launch_halo_var(Halo<FM, FN, WGM, WGN> k, const ConvParams& p, hipStream_t st) {
+    constexpr int TH = k.TH, BN = k.BN;
+    const size_t sh = k.lds();
     const int B = p.M / (p.Ho * p.Wo);
     const int tiles_h = (p.Ho + TH - 1) / TH, tiles_w = (p.Wo + 15) / 16, ntiles = (p.Cout + BN - 1) / BN;
     auto kern = conv_halo_kernel<FM, FN, WGM, WGN>;
@@ -267,16 +266,11 @@ static hipError_t launch_halo_one(const ConvParams& p, hipStream_t st) {
 }
 
 static hipError_t launch_conv_halo(const ConvParams& p, int c, hipStream_t st) {
-    switch (c) {
-        case 0: return launch_halo_one<8, 2, 2, 2>(p, st);
-        case 1: return launch_halo_one<4, 2, 4, 1>(p, st);
-        case 2: return launch_halo_one<4, 2, 2, 2>(p, st);
-        default: return launch_halo_one<4, 2, 4, 2>(p, st);
-    }
+    return with_cfg<HaloCfgs>(c, [&](auto k) { return launch_halo_var(k, p, st); });
 }
 
 #if !defined(__HIP_DEVICE_COMPILE__)      // (host data: the device pass must not reference the host functions)
-const ConvFamily conv_halo_family = {100, kNumHalo, conv_halo_cfg_valid, conv_halo_symbol, launch_conv_halo, false, nullptr, false};
+const ConvFamily conv_halo_family = {100, HaloCfgs::size, conv_halo_cfg_valid, conv_halo_symbol, launch_conv_halo, false, nullptr, false};
 #endif
 
 }  // namespace yp

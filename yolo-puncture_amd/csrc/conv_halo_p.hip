@@ -210,49 +210,39 @@ __global__ __launch_bounds__(WGM * WGN * 64) void conv_halo_p_kernel(const ConvP
 }
 
 // ---------------------------------------------------------------------------------------------------------------
-struct HaloPCfg { int FM, FN, WGM, WGN; const char* name; };
-static const HaloPCfg kHaloP[] = {
-    {4, 2, 4, 1, "conv_halo_p_kernel<4,2,4,1,3"},   // 0: 16x16 px x 32 ch, 4 waves
-    {8, 2, 2, 2, "conv_halo_p_kernel<8,2,2,2,3"},   // 1: 16x16 px x 64 ch, 4 waves
-    {4, 2, 4, 2, "conv_halo_p_kernel<4,2,4,2,3"},   // 2: 16x16 px x 64 ch, 8 waves
-    {4, 2, 2, 2, "conv_halo_p_kernel<4,2,2,2,3"},   // 3:  8x16 px x 64 ch, 4 waves
-    {4, 2, 2, 1, "conv_halo_p_kernel<4,2,2,1,3"},   // (2 waves: not instantiated)
-    {2, 2, 4, 1, "conv_halo_p_kernel<2,2,4,1,3"},   // 4:  8x16 px x 32 ch, 4 waves
+template <int FM, int FN, int WGM, int WGN> struct HaloP : Cfg<FM, FN, WGM, WGN, 3> {
+    static constexpr int TH = WGM * FM, BN = WGN * FN * 16;
+    // 3 halo slots in whole 1-KiB pieces, the landing zone, the resident weights
+    static constexpr size_t lds(int Cin) { return (size_t)3 * (((TH + 2) * 18 * 4 + 63) / 64) * 1024 + 1024 + (size_t)9 * (Cin / 32) * BN * 64; }
 };
-constexpr int kNumHaloP = 5;
-static const int kHaloPIdx[kNumHaloP] = {0, 1, 2, 3, 5};
-
-
-static size_t halo_p_lds(const HaloPCfg& k, int Cin) {
-    const int NW = k.WGM * k.WGN, TH = k.WGM * k.FM, BN = k.WGN * k.FN * 16;
-    (void)NW;
-    const int HP = (TH + 2) * 18, H_INSTR = (HP * 4 + 63) / 64;
-    return (size_t)3 * H_INSTR * 1024 + 1024 + (size_t)9 * (Cin / 32) * BN * 64;
-}
+using HaloPCfgs = CfgList<
+    HaloP<4, 2, 4, 1>,    // 0: 16x16 px x 32 ch, 4 waves
+    HaloP<8, 2, 2, 2>,    // 1: 16x16 px x 64 ch, 4 waves
+    HaloP<4, 2, 4, 2>,    // 2: 16x16 px x 64 ch, 8 waves
+    HaloP<4, 2, 2, 2>,    // 3:  8x16 px x 64 ch, 4 waves
+    HaloP<2, 2, 4, 1>>;   // 4:  8x16 px x 32 ch, 4 waves
 
 static bool conv_halo_p_cfg_valid(const ConvParams& p, int c) {
-    if (c < 0 || c >= kNumHaloP) return false;
     if (p.ks != 3 || p.stride != 1 || p.pad != 1 || p.up != 1 || (p.Cin % 32) != 0 || (p.Kpad != 9 * p.Cin)) return false;
-    if (p.x_bytes >= (1ull << 31) || p.w_bytes >= (1ull << 31) || p.y_bytes >= (1ull << 31)) return false;
-    // the exact-count epilogue only has the vector store form
-    if ((p.Cout & 3) || (p.y_stride & 3) || (p.y_coff & 3) || (p.res && ((p.res_stride & 3) || (p.res_coff & 3)))) return false;
-    if (p.res && p.out_f32) return false;
-    const HaloPCfg& k = kHaloP[kHaloPIdx[c]];
-    const int BN = k.WGN * k.FN * 16, TH = k.WGM * k.FM;
-    const int cpad = (p.Cout + 31) / 32 * 32;
-    if (BN > cpad) return false;
-    if (halo_p_lds(k, p.Cin) > 160 * 1024) return false;
-    const long covered = (long)((p.Ho + TH - 1) / TH * TH) * ((p.Wo + 15) / 16 * 16);
-    if (covered * 2 > (long)p.Ho * p.Wo * 3) return false;
-    return true;
+    if (!conv_store_side_ok(p)) return false;            // the exact-count epilogue only has the vector store form
+    return with_cfg<HaloPCfgs>(c, [&](auto k) {
+        using K = decltype(k);
+        const int cpad = (p.Cout + 31) / 32 * 32;
+        if (K::BN > cpad) return false;
+        if (K::lds(p.Cin) > 160 * 1024) return false;
+        const long covered = (long)((p.Ho + K::TH - 1) / K::TH * K::TH) * ((p.Wo + 15) / 16 * 16);
+        return covered * 2 <= (long)p.Ho * p.Wo * 3;
+    });
 }
 
-static std::string conv_halo_p_symbol(const ConvParams& p, int c) { return std::string(kHaloP[kHaloPIdx[c]].name) + res_f32_args(p) + ">"; }
+static std::string conv_halo_p_symbol(const ConvParams& p, int c) {
+    return with_cfg<HaloPCfgs>(c, [&](auto k) { return cfg_symbol("conv_halo_p_kernel", k, res_f32_args(p)); });
+}
 
-template <int FM, int FN, int WGM, int WGN, bool HAS_RES, bool OUT_F32>
-static hipError_t launch_halo_p_var(const ConvParams& p, const HaloPCfg& k, hipStream_t st) {
-    constexpr int TH = WGM * FM, BN = WGN * FN * 16;
-    const size_t sh = halo_p_lds(k, p.Cin);
+template <bool HAS_RES, bool OUT_F32, int FM, int FN, int WGM, int WGN>
+static hipError_t launch_halo_p_var(HaloP<FM, FN, WGM, WGN> k, const ConvParams& p, hipStream_t st) {
+    constexpr int TH = k.TH, BN = k.BN;
+    const size_t sh = k.lds(p.Cin);
     const int B = p.M / (p.Ho * p.Wo);
     const int tiles_h = (p.Ho + TH - 1) / TH, tiles_w = (p.Wo + 15) / 16, ntiles = (p.Cout + BN - 1) / BN;
     const int num_tiles = B * tiles_h * tiles_w;
@@ -267,26 +257,14 @@ static hipError_t launch_halo_p_var(const ConvParams& p, const HaloPCfg& k, hipS
     return hipGetLastError();
 }
 
-template <int FM, int FN, int WGM, int WGN>
-static hipError_t launch_halo_p_one(const ConvParams& p, const HaloPCfg& k, hipStream_t st) {
-    if (p.out_f32) return launch_halo_p_var<FM, FN, WGM, WGN, false, true>(p, k, st);     // (fp32 logits never carry a residual)
-    if (p.res) return launch_halo_p_var<FM, FN, WGM, WGN, true, false>(p, k, st);
-    return launch_halo_p_var<FM, FN, WGM, WGN, false, false>(p, k, st);
-}
-
 static hipError_t launch_conv_halo_p(const ConvParams& p, int c, hipStream_t st) {
-    const HaloPCfg& k = kHaloP[kHaloPIdx[c]];
-    switch (c) {
-        case 0: return launch_halo_p_one<4, 2, 4, 1>(p, k, st);
-        case 1: return launch_halo_p_one<8, 2, 2, 2>(p, k, st);
-        case 2: return launch_halo_p_one<4, 2, 4, 2>(p, k, st);
-        case 3: return launch_halo_p_one<4, 2, 2, 2>(p, k, st);
-        default: return launch_halo_p_one<2, 2, 4, 1>(p, k, st);
-    }
+    return with_cfg<HaloPCfgs>(c, [&](auto k) {
+        return with_res_f32(p, [&](auto res, auto f32) { return launch_halo_p_var<res, f32>(k, p, st); });
+    });
 }
 
 #if !defined(__HIP_DEVICE_COMPILE__)      // (host data: the device pass must not reference the host functions)
-const ConvFamily conv_halo_p_family = {200, kNumHaloP, conv_halo_p_cfg_valid, conv_halo_p_symbol, launch_conv_halo_p, false, nullptr, false};
+const ConvFamily conv_halo_p_family = {200, HaloPCfgs::size, conv_halo_p_cfg_valid, conv_halo_p_symbol, launch_conv_halo_p, false, nullptr, false};
 #endif
 
 }  // namespace yp

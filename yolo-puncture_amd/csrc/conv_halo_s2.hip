@@ -376,22 +376,31 @@ __global__ __launch_bounds__(WGM * WGN * 64) void conv_halo_s2_kernel(const Conv
 }
 
 // ---------------------------------------------------------------------------------------------------------------
-struct HaloS2Cfg { int FM, FN, WGM, WGN; const char* name; bool wreg; };
+enum { S2_PW2 = 1, S2_WREG = 2 };      // a configuration also has its fused trailing-1x1 (PW2) instance / keeps its weights in registers
+template <int FM, int FN, int WGM, int WGN, int FORM = 0> struct S2 : Cfg<FM, FN, WGM, WGN, 3> {
+    static constexpr int TH = WGM * FM, BN = WGN * FN * 16;
+    static constexpr bool pw2 = FORM & S2_PW2, wreg = FORM & S2_WREG;
+    // halo ring + landing zone, then the resident weights (and the fused 1x1's). A register-weights form stages its slab through the ring
+    // before the ring is in use, 9 * BN * 64 bytes at a time (a chunk): no weight term, but at least that chunk.
+    static constexpr size_t lds(int Cin, bool with_pw2 = false) {
+        const size_t ring = (size_t)3 * (((2 * TH + 1) * 33 * 4 + 63) / 64) * 1024 + 1024;
+        if (wreg) return std::max(ring, (size_t)9 * BN * 64);
+        return ring + (size_t)9 * (Cin / 32) * BN * 64 + (with_pw2 ? (size_t)BN * 128 : 0);
+    }
+};
 // Entries 0-4 are the family's configuration ids (500 + entry). Entries 5-7 are the register-weights instances a launch of id 500 / 501
 // resolves to where they are valid (halo_s2_form): no ids of their own - tuner, tables and the forced id speak of tile requests.
-static const HaloS2Cfg kS2[] = {
-    {2, 2, 4, 2, "conv_halo_s2_kernel<2,2,4,2,3", false},   // 0: 8x16 out px x 64 ch, 8 waves
-    {1, 2, 4, 2, "conv_halo_s2_kernel<1,2,4,2,3", false},   // 1: 4x16 out px x 64 ch, 8 waves
-    {2, 2, 4, 1, "conv_halo_s2_kernel<2,2,4,1,3", false},   // 2: 8x16 out px x 32 ch, 4 waves
-    {1, 2, 4, 1, "conv_halo_s2_kernel<1,2,4,1,3", false},   // 3: 4x16 out px x 32 ch, 4 waves
-    {2, 4, 4, 2, "conv_halo_s2_kernel<2,4,4,2,3", false},   // 4: 8x16 out px x 128 ch, 8 waves (Cin = 32)
-    {1, 2, 4, 2, "conv_halo_s2_kernel<1,2,4,2,3", true},    // 5: 1 with the weights in registers
-    {2, 2, 4, 2, "conv_halo_s2_kernel<2,2,4,2,3", true},    // 6: 0 with the weights in registers (so the 8-row tile fits for Cin = 64 too)
-    {2, 2, 2, 4, "conv_halo_s2_kernel<2,2,2,4,3", true},    // 7: 1 on a layer of more than 96 channels: the same 4x16 pixels, both 64-channel
-                                                            //    blocks in one workgroup, so the input tile is fetched once, not twice
-};
+using S2Forms = CfgList<
+    S2<2, 2, 4, 2, S2_PW2>,     // 0: 8x16 out px x 64 ch, 8 waves
+    S2<1, 2, 4, 2, S2_PW2>,     // 1: 4x16 out px x 64 ch, 8 waves
+    S2<2, 2, 4, 1>,             // 2: 8x16 out px x 32 ch, 4 waves
+    S2<1, 2, 4, 1>,             // 3: 4x16 out px x 32 ch, 4 waves
+    S2<2, 4, 4, 2>,             // 4: 8x16 out px x 128 ch, 8 waves (Cin = 32; admitted by no shape)
+    S2<1, 2, 4, 2, S2_WREG>,    // 5: 1 with the weights in registers
+    S2<2, 2, 4, 2, S2_WREG>,    // 6: 0 with the weights in registers (so the 8-row tile fits for Cin = 64 too)
+    S2<2, 2, 2, 4, S2_WREG>>;   // 7: 1 on a layer of more than 96 channels: the same 4x16 pixels, both 64-channel
+                                //    blocks in one workgroup, so the input tile is fetched once, not twice
 constexpr int kNumS2 = 5;
-constexpr int kNumS2Forms = (int)(sizeof(kS2) / sizeof(kS2[0]));
 
 // A/B and test switch: 1 = every launch keeps its weights in LDS (YOLOP_S2_LDS_WEIGHTS=1, or yp_debug_conv_s2's argument for one call)
 static std::atomic<int>& s2_lds_weights_ref() {
@@ -400,51 +409,42 @@ static std::atomic<int>& s2_lds_weights_ref() {
 }
 int conv_halo_s2_lds_weights(int on) { return on < 0 ? s2_lds_weights_ref().load() : s2_lds_weights_ref().exchange(on ? 1 : 0); }
 
-// The kS2 entry that configuration c launches p with. Register weights: 9 taps x chunks x FN = 2 fragments x 4 VGPRs <= 144 per wave, i.e.
-// Cin = 32 / 64; not with the fused trailing 1x1 (its weights stay in LDS anyway), not for the 4-wave tiles (ids 502 / 503: unmeasured).
+// The S2Forms entry that configuration c launches p with, -1 = no such c. Register weights: 9 taps x chunks x FN = 2 fragments x 4 VGPRs <= 144
+// per wave, i.e. Cin = 32 / 64; not with the fused trailing 1x1 (its weights stay in LDS anyway), not for the 4-wave tiles (ids 502 / 503: unmeasured).
 static int halo_s2_form(const ConvParams& p, int c) {
+    if (c < 0 || c >= kNumS2) return -1;
     if (c > 1 || p.C2 > 0 || s2_lds_weights_ref().load()) return c;
     if ((p.Cin % 32) != 0 || 9 * (p.Cin / 32) * 2 * 4 > kS2WregMaxVgprs) return c;
     if (c == 0) return 6;
     return p.Cout > 96 ? 7 : 5;
 }
 static std::string conv_halo_s2_symbol(const ConvParams& p, int c) {
-    const HaloS2Cfg& k = kS2[halo_s2_form(p, c)];
-    if (k.wreg) return std::string(k.name) + res_f32_args(p) + ",false," + std::to_string(p.Cin / 32) + ">";
-    return std::string(k.name) + (p.C2 > 0 ? ",false,false,true>" : std::string(res_f32_args(p)) + ",false>");
-}
-
-// halo ring + landing zone, then the resident weights (and the fused 1x1's). A register-weights form stages its slab through the ring
-// before the ring is in use, 9 * BN * 64 bytes at a time (a chunk): no weight term, but at least that chunk.
-static size_t halo_s2_lds(const HaloS2Cfg& k, int Cin, bool pw2 = false) {
-    const int TH = k.WGM * k.FM, BN = k.WGN * k.FN * 16;
-    const int HP = (2 * TH + 1) * 33, H_INSTR = (HP * 4 + 63) / 64;
-    const size_t ring = (size_t)3 * H_INSTR * 1024 + 1024;
-    if (k.wreg) return std::max(ring, (size_t)9 * BN * 64);
-    return ring + (size_t)9 * (Cin / 32) * BN * 64 + (pw2 ? (size_t)BN * 128 : 0);
+    return with_cfg<S2Forms>(halo_s2_form(p, c), [&](auto k) {
+        if (k.wreg) return cfg_symbol("conv_halo_s2_kernel", k, res_f32_args(p) + bool_args({false}) + "," + std::to_string(p.Cin / 32));
+        return cfg_symbol("conv_halo_s2_kernel", k, p.C2 > 0 ? bool_args({false, false, true}) : res_f32_args(p) + bool_args({false}));
+    });
 }
 
 static bool conv_halo_s2_cfg_valid(const ConvParams& p, int c) {
-    if (c < 0 || c >= kNumS2) return false;
     if (p.ks != 3 || p.stride != 2 || p.pad != 1 || p.up != 1 || (p.Cin % 32) != 0 || (p.Kpad != 9 * p.Cin)) return false;
     if ((p.H & 1) || (p.W & 1) || p.Ho * 2 != p.H || p.Wo * 2 != p.W) return false;
-    if (p.x_bytes >= (1ull << 31) || p.w_bytes >= (1ull << 31) || p.y_bytes >= (1ull << 31)) return false;
-    if ((p.Cout & 3) || (p.y_stride & 3) || (p.y_coff & 3) || (p.res && ((p.res_stride & 3) || (p.res_coff & 3)))) return false;
-    if (p.res && p.out_f32) return false;
-    const HaloS2Cfg& k = kS2[halo_s2_form(p, c)];                // (the instance that would launch: its LDS need decides)
-    const int BN = k.WGN * k.FN * 16, TH = k.WGM * k.FM;
-    const int cpad = (p.Cout + 31) / 32 * 32;
-    if (BN > cpad) return false;
-    if (halo_s2_lds(k, p.Cin) > 160 * 1024) return false;
-    const long covered = (long)((p.Ho + TH - 1) / TH * TH) * ((p.Wo + 15) / 16 * 16);
-    if (covered * 2 > (long)p.Ho * p.Wo * 3) return false;
-    return true;
+    if (!conv_store_side_ok(p)) return false;
+    return with_cfg<S2Forms>(halo_s2_form(p, c), [&](auto k) {                // (the instance that would launch: its LDS need decides)
+        using K = decltype(k);
+        const int cpad = (p.Cout + 31) / 32 * 32;
+        if (K::BN > cpad) return false;
+        if (K::lds(p.Cin) > 160 * 1024) return false;
+        const long covered = (long)((p.Ho + K::TH - 1) / K::TH * K::TH) * ((p.Wo + 15) / 16 * 16);
+        return covered * 2 <= (long)p.Ho * p.Wo * 3;
+    });
 }
 
-template <int FM, int FN, int WGM, int WGN, bool HAS_RES, bool OUT_F32, bool PW2 = false, int... WCH>
-static hipError_t launch_halo_s2_var(const ConvParams& p, const HaloS2Cfg& k, hipStream_t st) {
-    constexpr int TH = WGM * FM, BN = WGN * FN * 16;
-    const size_t sh = halo_s2_lds(k, p.Cin, PW2);
+// WCH: the chunk count of a register-weights form (the kernel's ninth argument), none for the weights in LDS
+template <bool HAS_RES, bool OUT_F32, bool PW2, int... WCH, int FM, int FN, int WGM, int WGN, int FORM>
+static hipError_t launch_halo_s2_var(S2<FM, FN, WGM, WGN, FORM> k, const ConvParams& p, hipStream_t st) {
+    static_assert(sizeof...(WCH) == 0 || (FN == 2 && 9 * 2 * FN * 4 <= kS2WregMaxVgprs && 9 * 3 * FN * 4 > kS2WregMaxVgprs), "the chunk counts instantiated are those halo_s2_form admits");
+    constexpr int TH = k.TH, BN = k.BN;
+    const size_t sh = k.lds(p.Cin, PW2);
     const int B = p.M / (p.Ho * p.Wo);
     const int tiles_h = (p.Ho + TH - 1) / TH, tiles_w = (p.Wo + 15) / 16, ntiles = (p.Cout + BN - 1) / BN;
     const int num_tiles = B * tiles_h * tiles_w;
@@ -460,28 +460,6 @@ static hipError_t launch_halo_s2_var(const ConvParams& p, const HaloS2Cfg& k, hi
     return hipGetLastError();
 }
 
-// register-weights forms: the chunk count is a template argument (1 or 2 with FN = 2: halo_s2_form's register bound)
-template <int FM, int FN, int WGM, int WGN, int NCH>
-static hipError_t launch_halo_s2_wreg_n(const ConvParams& p, const HaloS2Cfg& k, hipStream_t st) {
-    if (p.out_f32) return launch_halo_s2_var<FM, FN, WGM, WGN, false, true, false, NCH>(p, k, st);
-    if (p.res) return launch_halo_s2_var<FM, FN, WGM, WGN, true, false, false, NCH>(p, k, st);
-    return launch_halo_s2_var<FM, FN, WGM, WGN, false, false, false, NCH>(p, k, st);
-}
-template <int FM, int FN, int WGM, int WGN>
-static hipError_t launch_halo_s2_wreg(const ConvParams& p, const HaloS2Cfg& k, hipStream_t st) {
-    static_assert(FN == 2 && 9 * 2 * FN * 4 <= kS2WregMaxVgprs && 9 * 3 * FN * 4 > kS2WregMaxVgprs, "the chunk counts instantiated below are those halo_s2_form admits");
-    if (p.Cin == 32) return launch_halo_s2_wreg_n<FM, FN, WGM, WGN, 1>(p, k, st);
-    if (p.Cin == 64) return launch_halo_s2_wreg_n<FM, FN, WGM, WGN, 2>(p, k, st);
-    return hipErrorInvalidValue;
-}
-
-template <int FM, int FN, int WGM, int WGN>
-static hipError_t launch_halo_s2_one(const ConvParams& p, const HaloS2Cfg& k, hipStream_t st) {
-    if (p.out_f32) return launch_halo_s2_var<FM, FN, WGM, WGN, false, true>(p, k, st);
-    if (p.res) return launch_halo_s2_var<FM, FN, WGM, WGN, true, false>(p, k, st);
-    return launch_halo_s2_var<FM, FN, WGM, WGN, false, false>(p, k, st);
-}
-
 // ---- fused trailing 1x1 ------------------------------------------------------------------------------------------------
 // valid when the 3x3 s2 conv and the 1x1 behind it are both 64 wide (model.1 -> model.2.cv1 of v10-S), nothing carries a residual,
 // the intermediate has no other reader (the graph pass checks that), and LDS holds both weight sets beside the halo ring
@@ -492,35 +470,34 @@ int conv_halo_s2_pw_cfg(const ConvParams& p) {
         ConvParams q = p;
         q.Cout = p.C2;                                          // the store-side checks of the plain form apply to the final view
         if (!conv_halo_s2_cfg_valid(q, c)) continue;
-        if (halo_s2_lds(kS2[c], p.Cin, true) > 160 * 1024) continue;
+        if (with_cfg<S2Forms>(c, [&](auto k) { return k.lds(p.Cin, true); }) > 160 * 1024) continue;
         return c;
     }
     return -1;
 }
 
-size_t conv_halo_s2_lds_bytes(const ConvParams& p, int c) { return (c >= 0 && c < kNumS2) ? halo_s2_lds(kS2[halo_s2_form(p, c)], p.Cin) : 0; }
+size_t conv_halo_s2_lds_bytes(const ConvParams& p, int c) {
+    return with_cfg<S2Forms>(halo_s2_form(p, c), [&](auto k) { return k.lds(p.Cin); });
+}
 
 static hipError_t launch_conv_halo_s2(const ConvParams& p, int c, hipStream_t st) {
-    if (c < 0 || c >= kNumS2) return hipErrorInvalidValue;
-    const int form = halo_s2_form(p, c);
-    const HaloS2Cfg& k = kS2[form];
-    if (p.C2 > 0) {
-        if (c == 0) return launch_halo_s2_var<2, 2, 4, 2, false, false, true>(p, k, st);
-        if (c == 1) return launch_halo_s2_var<1, 2, 4, 2, false, false, true>(p, k, st);
-        return hipErrorInvalidValue;
-    }
-    static_assert(kNumS2Forms == 8, "one case per entry of kS2");
-    switch (form) {
-        case 0: return launch_halo_s2_one<2, 2, 4, 2>(p, k, st);
-        case 1: return launch_halo_s2_one<1, 2, 4, 2>(p, k, st);
-        case 2: return launch_halo_s2_one<2, 2, 4, 1>(p, k, st);
-        case 3: return launch_halo_s2_one<1, 2, 4, 1>(p, k, st);
-        case 4: return launch_halo_s2_one<2, 4, 4, 2>(p, k, st);
-        case 5: return launch_halo_s2_wreg<1, 2, 4, 2>(p, k, st);
-        case 6: return launch_halo_s2_wreg<2, 2, 4, 2>(p, k, st);
-        case 7: return launch_halo_s2_wreg<2, 2, 2, 4>(p, k, st);
-        default: return hipErrorInvalidValue;
-    }
+    return with_cfg<S2Forms>(halo_s2_form(p, c), [&](auto k) {
+        using K = decltype(k);
+        if constexpr (K::wreg) {
+            // register-weights forms: the chunk count is a template argument (1 or 2 with FN = 2: halo_s2_form's register bound)
+            return with_res_f32(p, [&](auto res, auto f32) {
+                if (p.Cin == 32) return launch_halo_s2_var<res, f32, false, 1>(k, p, st);
+                if (p.Cin == 64) return launch_halo_s2_var<res, f32, false, 2>(k, p, st);
+                return hipErrorInvalidValue;
+            });
+        } else {
+            if (p.C2 > 0) {
+                if constexpr (K::pw2) return launch_halo_s2_var<false, false, true>(k, p, st);
+                else return hipErrorInvalidValue;
+            }
+            return with_res_f32(p, [&](auto res, auto f32) { return launch_halo_s2_var<res, f32, false>(k, p, st); });
+        }
+    });
 }
 
 #if !defined(__HIP_DEVICE_COMPILE__)      // (host data: the device pass must not reference the host functions)

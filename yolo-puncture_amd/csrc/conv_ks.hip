@@ -112,55 +112,49 @@ __global__ __launch_bounds__(256) void conv_ks_kernel(const ConvParams p) {
     }
 }
 
-struct KsCfg { int FN, PXF; const char* name; };
-static const KsCfg kKs[] = {
-    {4, 1, "conv_ks_kernel<4,1,4"},      // 16 px x 64 couts
-    {4, 2, "conv_ks_kernel<4,2,3"},      // 32 px x 64 couts
-    {8, 1, "conv_ks_kernel<8,1,2"},      // 16 px x 128 couts
-    {2, 2, "conv_ks_kernel<2,2,4"},      // 32 px x 32 couts
-};
-constexpr int kNumKs = (int)(sizeof(kKs) / sizeof(kKs[0]));
-
+template <int FN_, int PXF_, int UB> struct Ks : Cfg<FN_, PXF_, UB> { static constexpr int FN = FN_, PXF = PXF_; };
+using KsCfgs = CfgList<
+    Ks<4, 1, 4>,      // 16 px x 64 couts
+    Ks<4, 2, 3>,      // 32 px x 64 couts
+    Ks<8, 1, 2>,      // 16 px x 128 couts
+    Ks<2, 2, 4>>;     // 32 px x 32 couts
 
 static bool conv_ks_cfg_valid(const ConvParams& p, int c) {
-    if (c < 0 || c >= kNumKs) return false;
-    const KsCfg& k = kKs[c];
     if ((p.ks != 1 && p.ks != 3) || p.up != 1 || p.w2 || p.x2_C > 0 || p.pool_in) return false;
     if ((p.Cin % 32) != 0 || p.pad != p.ks / 2 || (p.dil > 1)) return false;
     if (p.M > 16384) return false;                                                            // a small-problem kernel: one frame, or the deepest level of a few
     if ((p.x_stride & 7) || (p.x_coff & 7) || (p.Kpad & 7)) return false;                     // 16-byte fragment loads
     if ((p.Cout & 3) || (p.y_stride & 3) || (p.y_coff & 3) || (p.res && ((p.res_stride & 3) || (p.res_coff & 3)))) return false;
     if (p.res && p.out_f32) return false;
-    const int BN = k.FN * 16;
-    const int ntiles = (p.Cout + BN - 1) / BN;
-    if ((p.Cout + 127) / 128 * 128 < ntiles * BN) return false;                               // (the packed matrix has rows up to the next multiple of 128)
-    if (BN >= 2 * ((p.Cout + 31) / 32 * 32) && BN > 32) return false;                         // mostly padding
-    return true;
+    return with_cfg<KsCfgs>(c, [&](auto k) {
+        constexpr int BN = decltype(k)::FN * 16;
+        const int ntiles = (p.Cout + BN - 1) / BN;
+        if ((p.Cout + 127) / 128 * 128 < ntiles * BN) return false;                           // (the packed matrix has rows up to the next multiple of 128)
+        if (BN >= 2 * ((p.Cout + 31) / 32 * 32) && BN > 32) return false;                     // mostly padding
+        return true;
+    });
 }
 
-static std::string conv_ks_symbol(const ConvParams& p, int c) { return std::string(kKs[c].name) + res_f32_args(p) + ">"; }
+static std::string conv_ks_symbol(const ConvParams& p, int c) {
+    return with_cfg<KsCfgs>(c, [&](auto k) { return cfg_symbol("conv_ks_kernel", k, res_f32_args(p)); });
+}
 
-template <int FN, int PXF, int UB>
-static hipError_t launch_ks_one(const ConvParams& p, hipStream_t st) {
+template <bool HAS_RES, bool OUT_F32, int FN, int PXF, int UB>
+static hipError_t launch_ks_var(Cfg<FN, PXF, UB>, const ConvParams& p, hipStream_t st) {
     const dim3 grid((unsigned)((p.M + 16 * PXF - 1) / (16 * PXF)), (unsigned)((p.Cout + 16 * FN - 1) / (16 * FN))), blk(256);
-    if (p.out_f32) hipLaunchKernelGGL((conv_ks_kernel<FN, PXF, UB, false, true>), grid, blk, 0, st, p);
-    else if (p.res) hipLaunchKernelGGL((conv_ks_kernel<FN, PXF, UB, true, false>), grid, blk, 0, st, p);
-    else hipLaunchKernelGGL((conv_ks_kernel<FN, PXF, UB, false, false>), grid, blk, 0, st, p);
+    hipLaunchKernelGGL((conv_ks_kernel<FN, PXF, UB, HAS_RES, OUT_F32>), grid, blk, 0, st, p);
     return hipGetLastError();
 }
 
 static hipError_t launch_conv_ks(const ConvParams& p, int c, hipStream_t st) {
     if (!conv_ks_cfg_valid(p, c)) return hipErrorInvalidValue;
-    switch (c) {
-        case 0: return launch_ks_one<4, 1, 4>(p, st);
-        case 1: return launch_ks_one<4, 2, 3>(p, st);
-        case 2: return launch_ks_one<8, 1, 2>(p, st);
-        default: return launch_ks_one<2, 2, 4>(p, st);
-    }
+    return with_cfg<KsCfgs>(c, [&](auto k) {
+        return with_res_f32(p, [&](auto res, auto f32) { return launch_ks_var<res, f32>(k, p, st); });
+    });
 }
 
 #if !defined(__HIP_DEVICE_COMPILE__)      // (host data: the device pass must not reference the host functions)
-const ConvFamily conv_ks_family = {900, kNumKs, conv_ks_cfg_valid, conv_ks_symbol, launch_conv_ks, false, "YOLOP_NO_KS", false};
+const ConvFamily conv_ks_family = {900, KsCfgs::size, conv_ks_cfg_valid, conv_ks_symbol, launch_conv_ks, false, "YOLOP_NO_KS", false};
 #endif
 
 }  // namespace yp

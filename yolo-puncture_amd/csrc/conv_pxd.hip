@@ -233,44 +233,43 @@ __global__ __launch_bounds__(WGM * WGN * 64) void conv_pxd_kernel(const ConvPara
 }
 
 // ---------------------------------------------------------------------------------------------------------------
-struct PxdCfg { int PXW, FN, WGM, WGN; const char* name; };
-static const PxdCfg kPxd[] = {
-    {2, 16, 8, 1, "conv_pxd_kernel<2,16,8,1"},   // 0: 256 px x 256 couts
-    {2, 8, 8, 1, "conv_pxd_kernel<2,8,8,1"},     // 1: 256 px x 128 couts
-    {2, 8, 4, 2, "conv_pxd_kernel<2,8,4,2"},     // 2: 128 px x 256 couts
-    {1, 8, 8, 1, "conv_pxd_kernel<1,8,8,1"},     // 3: 128 px x 128 couts
-    {1, 8, 4, 2, "conv_pxd_kernel<1,8,4,2"},     // 4:  64 px x 256 couts
-    {2, 4, 8, 1, "conv_pxd_kernel<2,4,8,1"},     // 5: 256 px x  64 couts
-    {1, 16, 8, 1, "conv_pxd_kernel<1,16,8,1"},   // 6: 128 px x 256 couts, one pixel fragment per wave
-    {1, 4, 8, 1, "conv_pxd_kernel<1,4,8,1"},     // 7: 128 px x  64 couts
+template <int PXW, int FN, int WGM, int WGN> struct Pxd : Cfg<PXW, FN, WGM, WGN> {
+    static constexpr int BM = WGM * PXW * 16, BN = WGN * FN * 16;
+    static constexpr size_t lds() { return (size_t)3 * (BN * 8 / 64) * 1024 + 1024; }      // 3 weight slots + the landing zone
 };
-constexpr int kNumPxd = (int)(sizeof(kPxd) / sizeof(kPxd[0]));
-
+using PxdCfgs = CfgList<
+    Pxd<2, 16, 8, 1>,    // 0: 256 px x 256 couts
+    Pxd<2, 8, 8, 1>,     // 1: 256 px x 128 couts
+    Pxd<2, 8, 4, 2>,     // 2: 128 px x 256 couts
+    Pxd<1, 8, 8, 1>,     // 3: 128 px x 128 couts
+    Pxd<1, 8, 4, 2>,     // 4:  64 px x 256 couts
+    Pxd<2, 4, 8, 1>,     // 5: 256 px x  64 couts
+    Pxd<1, 16, 8, 1>,    // 6: 128 px x 256 couts, one pixel fragment per wave
+    Pxd<1, 4, 8, 1>>;    // 7: 128 px x  64 couts
 
 static bool conv_pxd_cfg_valid(const ConvParams& p, int c) {
-    if (c < 0 || c >= kNumPxd) return false;
-    const PxdCfg& k = kPxd[c];
     if (p.ks != 1 || p.stride != 1 || p.up != 1 || p.w2 || (p.Cin % 32) != 0 || p.Kpad != p.Cin) return false;
     if ((p.x_stride & 7) || (p.x_coff & 7)) return false;                                  // 16-byte fragment loads
-    if (p.x2_C > 0 && ((p.x2_C % 64) != 0 || (p.x2_stride & 7) || (p.x2_coff & 7))) return false;
-    if (p.x_bytes >= (1ull << 31) || p.w_bytes >= (1ull << 31) || p.y_bytes >= (1ull << 31) || (p.x2_C > 0 && p.x2_bytes >= (1ull << 31))) return false;
-    if ((p.Cout & 3) || (p.y_stride & 3) || (p.y_coff & 3) || (p.res && ((p.res_stride & 3) || (p.res_coff & 3)))) return false;
-    if (p.res && p.out_f32) return false;
-    const int BN = k.WGN * k.FN * 16;
-    const int cpad = (p.Cout + 63) / 64 * 64;
-    if (BN > 64 && BN >= 2 * cpad) return false;                                             // more than half the tile would be padding
-    const int ntiles = (p.Cout + BN - 1) / BN;
-    if ((p.Cout + 127) / 128 * 128 < ntiles * BN) return false;                             // (the packed matrix has rows up to the next multiple of 128)
-    return true;
+    if (p.x2_C > 0 && ((p.x2_C % 64) != 0 || (p.x2_stride & 7) || (p.x2_coff & 7) || p.x2_bytes >= (1ull << 31))) return false;
+    if (!conv_store_side_ok(p)) return false;
+    return with_cfg<PxdCfgs>(c, [&](auto k) {
+        constexpr int BN = decltype(k)::BN;
+        const int cpad = (p.Cout + 63) / 64 * 64;
+        if (BN > 64 && BN >= 2 * cpad) return false;                                         // more than half the tile would be padding
+        const int ntiles = (p.Cout + BN - 1) / BN;
+        return (p.Cout + 127) / 128 * 128 >= ntiles * BN;                                   // (the packed matrix has rows up to the next multiple of 128)
+    });
 }
 
-static std::string conv_pxd_symbol(const ConvParams& p, int c) { return std::string(kPxd[c].name) + res_f32_args(p) + ">"; }
+static std::string conv_pxd_symbol(const ConvParams& p, int c) {
+    return with_cfg<PxdCfgs>(c, [&](auto k) { return cfg_symbol("conv_pxd_kernel", k, res_f32_args(p)); });
+}
 
-template <int PXW, int FN, int WGM, int WGN, bool HAS_RES, bool OUT_F32>
-static hipError_t launch_pxd_var(const ConvParams& p_in, hipStream_t st) {
+template <bool HAS_RES, bool OUT_F32, int PXW, int FN, int WGM, int WGN>
+static hipError_t launch_pxd_var(Pxd<PXW, FN, WGM, WGN> k, const ConvParams& p_in, hipStream_t st) {
     static_assert(FN % 2 == 0, "fragment pairs");
     const ConvParams p = with_store_form(p_in, FN);
-    constexpr int BM = WGM * PXW * 16, BN = WGN * FN * 16;
+    constexpr int BM = k.BM, BN = k.BN;
     const int ntiles = (p.Cout + BN - 1) / BN;
     // whole rounds of 256 workgroups: the rounds the full tiles need, then the tile height that fills exactly those rounds
     int BMe = BM;
@@ -283,7 +282,7 @@ static hipError_t launch_pxd_var(const ConvParams& p_in, hipStream_t st) {
         if (BMe < 16) BMe = 16;
     }
     const int mtiles = (p.M + BMe - 1) / BMe;
-    const size_t sh = (size_t)3 * (BN * 8 / 64) * 1024 + 1024;
+    const size_t sh = k.lds();
     auto kern = conv_pxd_kernel<PXW, FN, WGM, WGN, HAS_RES, OUT_F32>;
     static size_t granted = 0;
     if (hipError_t e = allow_dynamic_lds((const void*)kern, sh, granted)) return e;
@@ -291,28 +290,14 @@ static hipError_t launch_pxd_var(const ConvParams& p_in, hipStream_t st) {
     return hipGetLastError();
 }
 
-template <int PXW, int FN, int WGM, int WGN>
-static hipError_t launch_pxd_one(const ConvParams& p, hipStream_t st) {
-    if (p.out_f32) return launch_pxd_var<PXW, FN, WGM, WGN, false, true>(p, st);
-    if (p.res) return launch_pxd_var<PXW, FN, WGM, WGN, true, false>(p, st);
-    return launch_pxd_var<PXW, FN, WGM, WGN, false, false>(p, st);
-}
-
 static hipError_t launch_conv_pxd(const ConvParams& p, int c, hipStream_t st) {
-    switch (c) {
-        case 0: return launch_pxd_one<2, 16, 8, 1>(p, st);
-        case 1: return launch_pxd_one<2, 8, 8, 1>(p, st);
-        case 2: return launch_pxd_one<2, 8, 4, 2>(p, st);
-        case 3: return launch_pxd_one<1, 8, 8, 1>(p, st);
-        case 4: return launch_pxd_one<1, 8, 4, 2>(p, st);
-        case 5: return launch_pxd_one<2, 4, 8, 1>(p, st);
-        case 6: return launch_pxd_one<1, 16, 8, 1>(p, st);
-        default: return launch_pxd_one<1, 4, 8, 1>(p, st);
-    }
+    return with_cfg<PxdCfgs>(c, [&](auto k) {
+        return with_res_f32(p, [&](auto res, auto f32) { return launch_pxd_var<res, f32>(k, p, st); });
+    });
 }
 
 #if !defined(__HIP_DEVICE_COMPILE__)      // (host data: the device pass must not reference the host functions)
-const ConvFamily conv_pxd_family = {800, kNumPxd, conv_pxd_cfg_valid, conv_pxd_symbol, launch_conv_pxd, true, "YOLOP_NO_PXD", false};
+const ConvFamily conv_pxd_family = {800, PxdCfgs::size, conv_pxd_cfg_valid, conv_pxd_symbol, launch_conv_pxd, true, "YOLOP_NO_PXD", false};
 #endif
 
 }  // namespace yp

@@ -510,30 +510,33 @@ static bool tile1_geometry(const ConvParams& p, int BN, Tile1Geo& g, size_t& lds
     return found;
 }
 
+// Two kernels behind the family's three ids: conv_tile1_kernel tiles the output channels in blocks of BN, conv_tile1w_kernel has one block
+template <int WGN> struct Tile1 : Cfg<WGN> { static constexpr int BN = WGN * 32; static constexpr bool wide = false; };
+template <int FMW> struct Tile1W : Cfg<FMW> { static constexpr int BN = 128; static constexpr bool wide = true; };
+using Tile1Cfgs = CfgList<Tile1<4>, Tile1<2>, Tile1W<T1_FMX>>;
+
 static std::string conv_tile1_symbol(const ConvParams& p, int c) {
-    if (c == 2) return "conv_tile1w_kernel<" + std::to_string(T1_FMX) + res_f32_args(p) + ">";
-    return std::string(c == 0 ? "conv_tile1_kernel<4" : "conv_tile1_kernel<2") + res_f32_args(p) + ",false>";
+    return with_cfg<Tile1Cfgs>(c, [&](auto k) {
+        return k.wide ? cfg_symbol("conv_tile1w_kernel", k, res_f32_args(p)) : cfg_symbol("conv_tile1_kernel", k, res_f32_args(p) + bool_args({false}));
+    });
 }
 
 static bool conv_tile1_cfg_valid(const ConvParams& p, int c) {
-    if (c < 0 || c >= 3) return false;
     if (p.ks != 3 || p.stride != 1 || p.pad != 1 || p.up != 1 || (p.Cin % 32) != 0 || p.Kpad != 9 * p.Cin || p.x2_C > 0) return false;
-    if (p.x_bytes >= (1ull << 31) || p.w_bytes >= (1ull << 31) || p.y_bytes >= (1ull << 31)) return false;
-    if ((p.Cout & 3) || (p.y_stride & 3) || (p.y_coff & 3) || (p.res && ((p.res_stride & 3) || (p.res_coff & 3)))) return false;
-    if (p.res && p.out_f32) return false;
-    const int BN = c == 1 ? 64 : 128;
-    if (BN > (p.Cout + 31) / 32 * 32) return false;
-    if (c == 2 && p.Cout > 128) return false;                // (the wide form has no output-channel tiling)
-    Tile1Geo g;
-    size_t lds;
-    if (!tile1_geometry(p, BN, g, lds)) return false;
-    return true;                                   // (whether one round of tiles pays is the autotuner's call)
+    if (!conv_store_side_ok(p)) return false;
+    return with_cfg<Tile1Cfgs>(c, [&](auto k) {
+        if (k.BN > (p.Cout + 31) / 32 * 32) return false;
+        if (k.wide && p.Cout > 128) return false;            // (the wide form has no output-channel tiling)
+        Tile1Geo g;
+        size_t lds;
+        return tile1_geometry(p, k.BN, g, lds);               // (whether one round of tiles pays is the autotuner's call)
+    });
 }
 
-template <int WGN, bool HAS_RES, bool OUT_F32>
-static hipError_t launch_tile1_var(const ConvParams& p_in, hipStream_t st) {
+template <bool HAS_RES, bool OUT_F32, int WGN>
+static hipError_t launch_tile1_var(Tile1<WGN> k, const ConvParams& p_in, hipStream_t st) {
     const ConvParams p = with_store_form(p_in, 2);
-    constexpr int BN = WGN * 32;
+    constexpr int BN = k.BN;
     Tile1Geo g;
     size_t sh;
     if (!tile1_geometry(p, BN, g, sh)) return hipErrorInvalidValue;
@@ -566,14 +569,14 @@ static hipError_t launch_tile1_var(const ConvParams& p_in, hipStream_t st) {
     return hipGetLastError();
 }
 
-template <bool HAS_RES, bool OUT_F32>
-static hipError_t launch_tile1w_var(const ConvParams& p, hipStream_t st) {
+template <bool HAS_RES, bool OUT_F32, int FMW>
+static hipError_t launch_tile1_var(Tile1W<FMW> k, const ConvParams& p, hipStream_t st) {
     Tile1Geo g;
     size_t sh;
-    if (!tile1_geometry(p, 128, g, sh)) return hipErrorInvalidValue;
+    if (!tile1_geometry(p, k.BN, g, sh)) return hipErrorInvalidValue;
     const int B = p.M / (p.Ho * p.Wo);
     const int tiles = B * g.tiles_h * g.tiles_w;
-    auto kern = conv_tile1w_kernel<T1_FMX, HAS_RES, OUT_F32>;
+    auto kern = conv_tile1w_kernel<FMW, HAS_RES, OUT_F32>;
     static size_t granted = 0;
     if (hipError_t e = allow_dynamic_lds((const void*)kern, sh, granted)) return e;
     hipLaunchKernelGGL(kern, dim3(tiles), dim3(512), sh, st, p, g);
@@ -581,23 +584,13 @@ static hipError_t launch_tile1w_var(const ConvParams& p, hipStream_t st) {
 }
 
 static hipError_t launch_conv_tile1(const ConvParams& p, int c, hipStream_t st) {
-    if (c == 2) {
-        if (p.out_f32) return launch_tile1w_var<false, true>(p, st);
-        if (p.res) return launch_tile1w_var<true, false>(p, st);
-        return launch_tile1w_var<false, false>(p, st);
-    }
-    if (c == 0) {
-        if (p.out_f32) return launch_tile1_var<4, false, true>(p, st);
-        if (p.res) return launch_tile1_var<4, true, false>(p, st);
-        return launch_tile1_var<4, false, false>(p, st);
-    }
-    if (p.out_f32) return launch_tile1_var<2, false, true>(p, st);
-    if (p.res) return launch_tile1_var<2, true, false>(p, st);
-    return launch_tile1_var<2, false, false>(p, st);
+    return with_cfg<Tile1Cfgs>(c, [&](auto k) {
+        return with_res_f32(p, [&](auto res, auto f32) { return launch_tile1_var<res, f32>(k, p, st); });
+    });
 }
 
 #if !defined(__HIP_DEVICE_COMPILE__)      // (host data: the device pass must not reference the host functions)
-const ConvFamily conv_tile1_family = {600, 3, conv_tile1_cfg_valid, conv_tile1_symbol, launch_conv_tile1, false, "YOLOP_NO_T1", false};
+const ConvFamily conv_tile1_family = {600, Tile1Cfgs::size, conv_tile1_cfg_valid, conv_tile1_symbol, launch_conv_tile1, false, "YOLOP_NO_T1", false};
 #endif
 
 }  // namespace yp

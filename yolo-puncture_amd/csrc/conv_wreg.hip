@@ -341,55 +341,49 @@ __global__ __launch_bounds__(WGM * WGN * 64) void conv_wreg_kernel(const ConvPar
 }
 
 // ---------------------------------------------------------------------------------------------------------------
-struct WregCfg { int NCH, FM, FN, WGM, WGN, TW; const char* name; };
-static const WregCfg kWreg[] = {
-    {2, 4, 4, 4, 1, 16, "conv_wreg_kernel<2,4,4,4,1,16"},   // 0: 64 -> <=64, 16x16 px tile
-    {2, 2, 4, 4, 1, 16, "conv_wreg_kernel<2,2,4,4,1,16"},   // 1: 64 -> <=64,  8x16 px tile
-    {4, 8, 2, 1, 4, 16, "conv_wreg_kernel<4,8,2,1,4,16"},   // 2: 128 -> <=128, 8x16 px tile
-    {4, 4, 2, 1, 4, 16, "conv_wreg_kernel<4,4,2,1,4,16"},   // 3: 128 -> <=128, 4x16 px tile
-    {4, 4, 2, 1, 4, 8, "conv_wreg_kernel<4,4,2,1,4,8"},     // 4: 128 -> <=128, 8x8 px tile (40-wide maps)
-    {2, 2, 4, 4, 1, 8, "conv_wreg_kernel<2,2,4,4,1,8"},     // 5: 64 -> <=64, 16x8 px tile
-    {4, 4, 2, 2, 2, 16, "conv_wreg_kernel<4,4,2,2,2,16"},   // 6: 128 -> <=64, 8x16 px tile
-    // two waves per SIMD (256 registers each, 144 of them weights): the partner's MFMAs cover a wave's LDS latency and epilogue
-    {2, 4, 2, 4, 2, 16, "conv_wreg_kernel<2,4,2,4,2,16"},   // 7: 64 -> <=64, 16x16 px tile, 8 waves
-    {2, 2, 2, 4, 2, 16, "conv_wreg_kernel<2,2,2,4,2,16"},   // 8: 64 -> <=64,  8x16 px tile, 8 waves
-    {4, 8, 1, 1, 8, 16, "conv_wreg_kernel<4,8,1,1,8,16"},   // 9: 128 -> <=128, 8x16 px tile, 8 waves
-    {4, 4, 1, 1, 8, 8, "conv_wreg_kernel<4,4,1,1,8,8"},     // 10: 128 -> <=128, 8x8 px tile, 8 waves
-    {4, 8, 1, 1, 8, 8, "conv_wreg_kernel<4,8,1,1,8,8"},     // 11: 128 -> <=128, 16x8 px tile, 8 waves
-    {2, 2, 2, 4, 2, 8, "conv_wreg_kernel<2,2,2,4,2,8"},     // 12: 64 -> <=64, 16x8 px tile, 8 waves
+template <int NCH_, int FM, int FN, int WGM, int WGN, int TW_> struct Wreg : Cfg<NCH_, FM, FN, WGM, WGN, TW_> {
+    static constexpr int NCH = NCH_, TW = TW_, TH = WGM * FM * (16 / TW), BN = WGN * FN * 16;
+    // 3 halo slots in whole 1-KiB pieces, the landing zone, one chunk of the weight slab
+    static constexpr size_t lds() { return (size_t)3 * (((TH + 2) * (TW + 2) * 4 + 63) / 64) * 1024 + 1024 + (size_t)9 * BN * 64; }
 };
-constexpr int kNumWreg = (int)(sizeof(kWreg) / sizeof(kWreg[0]));
-
-
-static size_t wreg_lds(const WregCfg& k) {
-    const int RPF = 16 / k.TW, TH = k.WGM * k.FM * RPF;
-    const int HP = (TH + 2) * (k.TW + 2), H_INSTR = (HP * 4 + 63) / 64;
-    return (size_t)3 * H_INSTR * 1024 + 1024 + (size_t)9 * (k.WGN * k.FN * 16) * 64;
-}
+using WregCfgs = CfgList<
+    Wreg<2, 4, 4, 4, 1, 16>,    // 0: 64 -> <=64, 16x16 px tile
+    Wreg<2, 2, 4, 4, 1, 16>,    // 1: 64 -> <=64,  8x16 px tile
+    Wreg<4, 8, 2, 1, 4, 16>,    // 2: 128 -> <=128, 8x16 px tile
+    Wreg<4, 4, 2, 1, 4, 16>,    // 3: 128 -> <=128, 4x16 px tile
+    Wreg<4, 4, 2, 1, 4, 8>,     // 4: 128 -> <=128, 8x8 px tile (40-wide maps)
+    Wreg<2, 2, 4, 4, 1, 8>,     // 5: 64 -> <=64, 16x8 px tile
+    Wreg<4, 4, 2, 2, 2, 16>,    // 6: 128 -> <=64, 8x16 px tile
+    // two waves per SIMD (256 registers each, 144 of them weights): the partner's MFMAs cover a wave's LDS latency and epilogue
+    Wreg<2, 4, 2, 4, 2, 16>,    // 7: 64 -> <=64, 16x16 px tile, 8 waves
+    Wreg<2, 2, 2, 4, 2, 16>,    // 8: 64 -> <=64,  8x16 px tile, 8 waves
+    Wreg<4, 8, 1, 1, 8, 16>,    // 9: 128 -> <=128, 8x16 px tile, 8 waves
+    Wreg<4, 4, 1, 1, 8, 8>,     // 10: 128 -> <=128, 8x8 px tile, 8 waves
+    Wreg<4, 8, 1, 1, 8, 8>,     // 11: 128 -> <=128, 16x8 px tile, 8 waves
+    Wreg<2, 2, 2, 4, 2, 8>>;    // 12: 64 -> <=64, 16x8 px tile, 8 waves
 
 static bool conv_wreg_cfg_valid(const ConvParams& p, int c) {
-    if (c < 0 || c >= kNumWreg) return false;
-    const WregCfg& k = kWreg[c];
-    if (p.ks != 3 || p.stride != 1 || p.pad != 1 || p.up != 1 || p.Cin != k.NCH * 32 || p.Kpad != 9 * p.Cin || p.x2_C > 0 || p.w2) return false;
-    if (p.x_bytes >= (1ull << 31) || p.w_bytes >= (1ull << 31) || p.y_bytes >= (1ull << 31)) return false;
-    if ((p.Cout & 3) || (p.y_stride & 3) || (p.y_coff & 3) || (p.res && ((p.res_stride & 3) || (p.res_coff & 3)))) return false;
-    if (p.res && p.out_f32) return false;
-    const int BN = k.WGN * k.FN * 16;
-    if (p.Cout > BN || p.Cout * 2 <= BN) return false;                       // one N tile, at least half used
-    if ((size_t)((p.Cout + 127) / 128 * 128) * p.Kpad * 2 > p.w_bytes) return false;
-    const int RPF = 16 / k.TW, TH = k.WGM * k.FM * RPF;
-    const long covered = (long)((p.Ho + TH - 1) / TH * TH) * ((p.Wo + k.TW - 1) / k.TW * k.TW);
-    if (covered * 4 > (long)p.Ho * p.Wo * 5) return false;                  // at most 25 % of the tile area outside the map
-    return true;
+    if (p.ks != 3 || p.stride != 1 || p.pad != 1 || p.up != 1 || p.Kpad != 9 * p.Cin || p.x2_C > 0 || p.w2) return false;
+    if (!conv_store_side_ok(p)) return false;
+    return with_cfg<WregCfgs>(c, [&](auto k) {
+        using K = decltype(k);
+        if (p.Cin != K::NCH * 32) return false;
+        if (p.Cout > K::BN || p.Cout * 2 <= K::BN) return false;                 // one N tile, at least half used
+        if ((size_t)((p.Cout + 127) / 128 * 128) * p.Kpad * 2 > p.w_bytes) return false;
+        const long covered = (long)((p.Ho + K::TH - 1) / K::TH * K::TH) * ((p.Wo + K::TW - 1) / K::TW * K::TW);
+        return covered * 4 <= (long)p.Ho * p.Wo * 5;                            // at most 25 % of the tile area outside the map
+    });
 }
 
-static std::string conv_wreg_symbol(const ConvParams& p, int c) { return std::string(kWreg[c].name) + res_f32_args(p) + ">"; }
+static std::string conv_wreg_symbol(const ConvParams& p, int c) {
+    return with_cfg<WregCfgs>(c, [&](auto k) { return cfg_symbol("conv_wreg_kernel", k, res_f32_args(p)); });
+}
 
-template <int NCH, int FM, int FN, int WGM, int WGN, int TW, bool HAS_RES, bool OUT_F32>
-static hipError_t launch_wreg_var(const ConvParams& p_in, const WregCfg& k, hipStream_t st) {
+template <bool HAS_RES, bool OUT_F32, int NCH, int FM, int FN, int WGM, int WGN, int TW>
+static hipError_t launch_wreg_var(Wreg<NCH, FM, FN, WGM, WGN, TW> k, const ConvParams& p_in, hipStream_t st) {
     const ConvParams p = with_store_form(p_in, wreg_paired<FM, FN, WGM, WGN>() ? FN : 1);
-    constexpr int RPF = 16 / TW, TH = WGM * FM * RPF;
-    const size_t sh = wreg_lds(k);
+    constexpr int TH = k.TH;
+    const size_t sh = k.lds();
     const int B = p.M / (p.Ho * p.Wo);
     const int tiles_h = (p.Ho + TH - 1) / TH, tiles_w = (p.Wo + TW - 1) / TW;
     const int num_tiles = B * tiles_h * tiles_w;
@@ -415,41 +409,21 @@ static hipError_t launch_wreg_var(const ConvParams& p_in, const WregCfg& k, hipS
         for (size_t w = 0; w < n / 5; ++w)
             for (int i = 0; i < 5; ++i) { s5[i] += (double)h[w * 5 + i]; mx[i] = std::max(mx[i], (double)h[w * 5 + i]); }
         fprintf(stderr, "[wreg clocks] %s G=%d tiles=%d  %s stores  per-wave mean cycles: prologue %.0f  wait+barrier %.0f  issue %.0f  compute %.0f  epilogue %.0f   (max %.0f %.0f %.0f %.0f %.0f)\n",
-                k.name, G, num_tiles, p.wide ? "16-byte" : "8-byte", s5[0] / (n / 5), s5[1] / (n / 5), s5[2] / (n / 5), s5[3] / (n / 5), s5[4] / (n / 5), mx[0], mx[1], mx[2], mx[3], mx[4]);
+                ("conv_wreg_kernel<" + cfg_args(k)).c_str(), G, num_tiles, p.wide ? "16-byte" : "8-byte", s5[0] / (n / 5), s5[1] / (n / 5), s5[2] / (n / 5), s5[3] / (n / 5), s5[4] / (n / 5), mx[0], mx[1], mx[2], mx[3], mx[4]);
         return hipGetLastError();
     }
     hipLaunchKernelGGL(kern, dim3(G), dim3(WGM * WGN * 64), sh, st, p, tiles_h, tiles_w, G);
     return hipGetLastError();
 }
 
-template <int NCH, int FM, int FN, int WGM, int WGN, int TW>
-static hipError_t launch_wreg_one(const ConvParams& p, const WregCfg& k, hipStream_t st) {
-    if (p.out_f32) return launch_wreg_var<NCH, FM, FN, WGM, WGN, TW, false, true>(p, k, st);
-    if (p.res) return launch_wreg_var<NCH, FM, FN, WGM, WGN, TW, true, false>(p, k, st);
-    return launch_wreg_var<NCH, FM, FN, WGM, WGN, TW, false, false>(p, k, st);
-}
-
 static hipError_t launch_conv_wreg(const ConvParams& p, int c, hipStream_t st) {
-    const WregCfg& k = kWreg[c];
-    switch (c) {
-        case 0: return launch_wreg_one<2, 4, 4, 4, 1, 16>(p, k, st);
-        case 1: return launch_wreg_one<2, 2, 4, 4, 1, 16>(p, k, st);
-        case 2: return launch_wreg_one<4, 8, 2, 1, 4, 16>(p, k, st);
-        case 3: return launch_wreg_one<4, 4, 2, 1, 4, 16>(p, k, st);
-        case 4: return launch_wreg_one<4, 4, 2, 1, 4, 8>(p, k, st);
-        case 5: return launch_wreg_one<2, 2, 4, 4, 1, 8>(p, k, st);
-        case 6: return launch_wreg_one<4, 4, 2, 2, 2, 16>(p, k, st);
-        case 7: return launch_wreg_one<2, 4, 2, 4, 2, 16>(p, k, st);
-        case 8: return launch_wreg_one<2, 2, 2, 4, 2, 16>(p, k, st);
-        case 9: return launch_wreg_one<4, 8, 1, 1, 8, 16>(p, k, st);
-        case 10: return launch_wreg_one<4, 4, 1, 1, 8, 8>(p, k, st);
-        case 11: return launch_wreg_one<4, 8, 1, 1, 8, 8>(p, k, st);
-        default: return launch_wreg_one<2, 2, 2, 4, 2, 8>(p, k, st);
-    }
+    return with_cfg<WregCfgs>(c, [&](auto k) {
+        return with_res_f32(p, [&](auto res, auto f32) { return launch_wreg_var<res, f32>(k, p, st); });
+    });
 }
 
 #if !defined(__HIP_DEVICE_COMPILE__)      // (host data: the device pass must not reference the host functions)
-const ConvFamily conv_wreg_family = {700, kNumWreg, conv_wreg_cfg_valid, conv_wreg_symbol, launch_conv_wreg, false, "YOLOP_NO_WREG", false};
+const ConvFamily conv_wreg_family = {700, WregCfgs::size, conv_wreg_cfg_valid, conv_wreg_symbol, launch_conv_wreg, false, "YOLOP_NO_WREG", false};
 #endif
 
 }  // namespace yp

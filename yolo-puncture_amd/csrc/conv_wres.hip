@@ -271,49 +271,47 @@ __global__ __launch_bounds__(WR_NW * 64) void conv_wres_clk_kernel(const ConvPar
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------------------
-struct WresCfg { int TP, WGN; const char* name; };
-static const WresCfg kWres[] = {
-    {64, 2, "conv_wres_kernel<64,2"},
-    {128, 2, "conv_wres_kernel<128,2"},
-    {32, 4, "conv_wres_kernel<32,4"},
+template <int TP_, int WGN_> struct Wres : Cfg<TP_, WGN_> {
+    static constexpr int TP = TP_, WGN = WGN_;
+    // channel block of a workgroup: as few blocks as 128 channels each allow, equal sizes, whole fragments (pairs of them for two channel waves)
+    static void blocks(const ConvParams& p, int& NB, int& nblk) {
+        nblk = (p.Cout + 127) / 128;
+        const int q = 16 * WGN;
+        NB = ((p.Cout + nblk - 1) / nblk + q - 1) / q * q;
+    }
+    // the block's resident weights + two pixel tiles
+    static size_t lds(const ConvParams& p) {
+        int NB, nblk;
+        blocks(p, NB, nblk);
+        return (size_t)NB * p.Cin * 2 + (size_t)2 * TP * p.Cin * 2;
+    }
 };
-constexpr int kNumWres = (int)(sizeof(kWres) / sizeof(kWres[0]));
+using WresCfgs = CfgList<Wres<64, 2>, Wres<128, 2>, Wres<32, 4>>;
 
-static std::string conv_wres_symbol(const ConvParams& p, int c) { return std::string(kWres[c].name) + (p.res ? ",true>" : ",false>"); }
-
-// channel block of a workgroup: as few blocks as 128 channels each allow, equal sizes, whole fragments (pairs of them for two channel waves)
-static void wres_blocks(const ConvParams& p, const WresCfg& k, int& NB, int& nblk) {
-    nblk = (p.Cout + 127) / 128;
-    const int q = 16 * k.WGN;
-    NB = ((p.Cout + nblk - 1) / nblk + q - 1) / q * q;
-}
-static size_t wres_lds(const ConvParams& p, const WresCfg& k) {
-    int NB, nblk;
-    wres_blocks(p, k, NB, nblk);
-    return (size_t)NB * p.Cin * 2 + (size_t)2 * k.TP * p.Cin * 2;
+static std::string conv_wres_symbol(const ConvParams& p, int c) {
+    return with_cfg<WresCfgs>(c, [&](auto k) { return cfg_symbol("conv_wres_kernel", k, bool_args({p.res != nullptr})); });
 }
 
 static bool conv_wres_cfg_valid(const ConvParams& p, int c) {
-    if (c < 0 || c >= kNumWres) return false;
-    const WresCfg& k = kWres[c];
     if (p.ks != 1 || p.stride != 1 || p.up != 1 || p.w2 || p.out_f32 || p.pool_in || p.up_bilinear) return false;
     if (p.act != ACT_SILU && p.act != ACT_NONE) return false;
     if (p.Cin < 64 || (p.Cin % 64) != 0 || p.Kpad != p.Cin || p.Cin > 1024) return false;
     if (p.x2_C > 0 && ((p.x2_C % 64) != 0 || p.x2_C >= p.Cin || (p.x2_stride & 7) || (p.x2_coff & 7) || p.x2_bytes >= (1ull << 31))) return false;
     if ((p.x_stride & 7) || (p.x_coff & 7)) return false;
-    if ((p.Cout & 3) || (p.y_stride & 3) || (p.y_coff & 3) || (p.res && ((p.res_stride & 3) || (p.res_coff & 3)))) return false;
-    if (p.x_bytes >= (1ull << 31) || p.w_bytes >= (1ull << 31) || p.y_bytes >= (1ull << 31) || p.M <= 0 || p.Ho <= 0 || p.Wo <= 0) return false;
-    if ((((size_t)k.TP * (p.Cin - p.x2_C) * 2) & 1023) || (((size_t)k.TP * p.x2_C * 2) & 1023)) return false;       // whole 1-KiB pieces per segment
-    return wres_lds(p, k) <= 156 * 1024;
+    if (!conv_store_side_ok(p) || p.M <= 0 || p.Ho <= 0 || p.Wo <= 0) return false;
+    return with_cfg<WresCfgs>(c, [&](auto k) {
+        if ((((size_t)k.TP * (p.Cin - p.x2_C) * 2) & 1023) || (((size_t)k.TP * p.x2_C * 2) & 1023)) return false;       // whole 1-KiB pieces per segment
+        return k.lds(p) <= 156 * 1024;
+    });
 }
 
-template <int TP, int WGN, bool HAS_RES>
-static hipError_t launch_wres_t(const ConvParams& p_in, const WresCfg& k, hipStream_t st) {
+template <bool HAS_RES, int TP, int WGN>
+static hipError_t launch_wres_t(Wres<TP, WGN> k, const ConvParams& p_in, hipStream_t st) {
     int NB, nblk;
-    wres_blocks(p_in, k, NB, nblk);
+    k.blocks(p_in, NB, nblk);
     // paired stores: whole fragment pairs per wave (then NB, and every block's first channel, is a multiple of 32)
     const ConvParams p = with_store_form(p_in, wres_paired<TP, WGN>() ? NB / (16 * WGN) : 1);
-    const size_t sh = wres_lds(p, k);
+    const size_t sh = k.lds(p);
     auto kern = conv_wres_kernel<TP, WGN, HAS_RES>;
     static size_t granted = 0;
     if (hipError_t e = allow_dynamic_lds((const void*)kern, sh, granted)) return e;
@@ -347,7 +345,7 @@ static hipError_t launch_wres_t(const ConvParams& p_in, const WresCfg& k, hipStr
             for (size_t w = 0; w < n / 5; ++w)
                 for (int i = 0; i < 5; ++i) s5[i] += (double)h[w * 5 + i];
             fprintf(stderr, "[wres clocks] %s G=%d tiles=%d  %s stores  per-wave mean cycles: prologue %.0f  wait+barrier %.0f  issue %.0f  k loop %.0f  epilogue %.0f\n",
-                    k.name, G, (p.M + TPe - 1) / TPe, p.wide ? "16-byte" : "8-byte", s5[0] / (n / 5), s5[1] / (n / 5), s5[2] / (n / 5), s5[3] / (n / 5), s5[4] / (n / 5));
+                    ("conv_wres_kernel<" + cfg_args(k)).c_str(), G, (p.M + TPe - 1) / TPe, p.wide ? "16-byte" : "8-byte", s5[0] / (n / 5), s5[1] / (n / 5), s5[2] / (n / 5), s5[3] / (n / 5), s5[4] / (n / 5));
             return hipGetLastError();
         }
     }
@@ -357,17 +355,11 @@ static hipError_t launch_wres_t(const ConvParams& p_in, const WresCfg& k, hipStr
 
 static hipError_t launch_conv_wres(const ConvParams& p, int c, hipStream_t st) {
     if (!conv_wres_cfg_valid(p, c)) return hipErrorInvalidValue;
-    const WresCfg& k = kWres[c];
-    const bool r = p.res != nullptr;
-    switch (c) {
-        case 0: return r ? launch_wres_t<64, 2, true>(p, k, st) : launch_wres_t<64, 2, false>(p, k, st);
-        case 1: return r ? launch_wres_t<128, 2, true>(p, k, st) : launch_wres_t<128, 2, false>(p, k, st);
-        default: return r ? launch_wres_t<32, 4, true>(p, k, st) : launch_wres_t<32, 4, false>(p, k, st);
-    }
+    return with_cfg<WresCfgs>(c, [&](auto k) { return p.res ? launch_wres_t<true>(k, p, st) : launch_wres_t<false>(k, p, st); });
 }
 
 #if !defined(__HIP_DEVICE_COMPILE__)      // (host data: the device pass must not reference the host functions)
-const ConvFamily conv_wres_family = {1100, kNumWres, conv_wres_cfg_valid, conv_wres_symbol, launch_conv_wres, true, "YOLOP_NO_WRES", false};
+const ConvFamily conv_wres_family = {1100, WresCfgs::size, conv_wres_cfg_valid, conv_wres_symbol, launch_conv_wres, true, "YOLOP_NO_WRES", false};
 #endif
 
 }  // namespace yp

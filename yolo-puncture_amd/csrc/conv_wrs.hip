@@ -183,48 +183,57 @@ __global__ __launch_bounds__(WS_NW * 64) void conv_wrs_kernel(const ConvParams p
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------------------
-struct WrsCfg { int TP; };
-static const WrsCfg kWrs[] = {{64}, {32}};
-constexpr int kNumWrs = (int)(sizeof(kWrs) / sizeof(kWrs[0]));
-
+// A configuration id is a pixel tile; the kernel's first two arguments follow from the layer.
+template <int TP_> struct Wrs : Cfg<TP_> {
+    static constexpr int TP = TP_;
+    static constexpr size_t lds(int Cin) { return (size_t)2 * TP * Cin * 2; }      // two pixel tiles
+};
+using WrsCfgs = CfgList<Wrs<64>, Wrs<32>>;
 // (K / 32, channel fragments per wave) pairs this build instantiates: NKS * NFW * 4 weight registers per lane, 128 at most
-static bool wrs_shape(const ConvParams& p, int& nks, int& nfw) {
-    if ((p.Cin % 64) != 0) return false;
+template <int NKS_, int NFW_> struct WrsShape : Cfg<NKS_, NFW_> { static constexpr int NKS = NKS_, NFW = NFW_; };
+using WrsShapes = CfgList<WrsShape<4, 1>, WrsShape<6, 1>, WrsShape<8, 1>, WrsShape<12, 1>, WrsShape<8, 2>, WrsShape<12, 2>, WrsShape<16, 2>, WrsShape<8, 4>>;
+
+// the layer's entry of WrsShapes, -1 = none
+template <class... S> static int wrs_shape_of(CfgList<S...>, int nks, int nfw) {
+    int i = 0, at = -1;
+    ((at = (S::NKS == nks && S::NFW == nfw) ? i : at, ++i), ...);
+    return at;
+}
+static int wrs_shape(const ConvParams& p, int& nks, int& nfw) {
     nks = p.Cin / 32;
     nfw = (p.Cout + 127) / 128;                                    // 8 waves x 16 channels x nfw >= Cout
     if (nfw == 3) nfw = 4;
-    static const int ok[][2] = {{4, 1}, {6, 1}, {8, 1}, {12, 1}, {8, 2}, {12, 2}, {16, 2}, {8, 4}};
-    for (auto& s : ok)
-        if (s[0] == nks && s[1] == nfw) return true;
-    return false;
+    return (p.Cin % 64) != 0 ? -1 : wrs_shape_of(WrsShapes{}, nks, nfw);
 }
 
 static std::string conv_wrs_symbol(const ConvParams& p, int c) {
-    int nks = 0, nfw = 0;
-    wrs_shape(p, nks, nfw);
-    return "conv_wrs_kernel<" + std::to_string(nks) + "," + std::to_string(nfw) + "," + std::to_string(kWrs[c].TP) + ">";
+    int nks, nfw;
+    const int sh = wrs_shape(p, nks, nfw);
+    return with_cfg<WrsCfgs>(c, [&](auto k) {
+        return with_cfg<WrsShapes>(sh, [&](auto s) { return cfg_symbol("conv_wrs_kernel", s, "," + cfg_args(k)); });
+    });
 }
 
 static bool conv_wrs_cfg_valid(const ConvParams& p, int c) {
-    if (c < 0 || c >= kNumWrs) return false;
-    const WrsCfg& k = kWrs[c];
     int nks, nfw;
     if (p.ks != 1 || p.stride != 1 || p.up != 1 || p.w2 || p.out_f32 || p.pool_in || p.up_bilinear || p.res) return false;
     if (p.act != ACT_SILU && p.act != ACT_NONE) return false;
-    if (p.Kpad != p.Cin || !wrs_shape(p, nks, nfw)) return false;
-    if (nks * nfw * 4 >= 128 && k.TP > 32) return false;          // (128 weight registers + the 64-pixel tile's accumulators and fragments spill)
+    if (p.Kpad != p.Cin || wrs_shape(p, nks, nfw) < 0) return false;
     if (p.Cout <= 64 * nfw) return false;                          // (more than half of the waves' channels would be padding)
     if (p.x2_C > 0 && ((p.x2_C % 64) != 0 || p.x2_C >= p.Cin || (p.x2_stride & 7) || (p.x2_coff & 7) || p.x2_bytes >= (1ull << 31))) return false;
     if ((p.x_stride & 7) || (p.x_coff & 7)) return false;
     if ((p.Cout & 3) || (p.y_stride & 3) || (p.y_coff & 3)) return false;
     if (p.x_bytes >= (1ull << 31) || p.w_bytes >= (1ull << 31) || p.y_bytes >= (1ull << 31) || p.M <= 0 || p.Ho <= 0 || p.Wo <= 0) return false;
-    if ((((size_t)k.TP * (p.Cin - p.x2_C) * 2) & 1023) || (((size_t)k.TP * p.x2_C * 2) & 1023)) return false;       // whole 1-KiB pieces per segment
-    return (size_t)2 * k.TP * p.Cin * 2 <= 156 * 1024;
+    return with_cfg<WrsCfgs>(c, [&](auto k) {
+        if (nks * nfw * 4 >= 128 && k.TP > 32) return false;      // (128 weight registers + the 64-pixel tile's accumulators and fragments spill)
+        if ((((size_t)k.TP * (p.Cin - p.x2_C) * 2) & 1023) || (((size_t)k.TP * p.x2_C * 2) & 1023)) return false;       // whole 1-KiB pieces per segment
+        return k.lds(p.Cin) <= 156 * 1024;
+    });
 }
 
 template <int NKS, int NFW, int TP>
-static hipError_t launch_wrs_t(const ConvParams& p, hipStream_t st) {
-    const size_t sh = (size_t)2 * TP * p.Cin * 2;
+static hipError_t launch_wrs_t(WrsShape<NKS, NFW>, Wrs<TP> k, const ConvParams& p, hipStream_t st) {
+    const size_t sh = k.lds(p.Cin);
     auto kern = conv_wrs_kernel<NKS, NFW, TP>;
     static size_t granted = 0;
     if (hipError_t e = allow_dynamic_lds((const void*)kern, sh, granted)) return e;
@@ -256,32 +265,17 @@ static hipError_t launch_wrs_t(const ConvParams& p, hipStream_t st) {
     return hipGetLastError();
 }
 
-template <int TP>
-static hipError_t launch_wrs_tp(const ConvParams& p, int nks, int nfw, hipStream_t st) {
-    if (nfw == 1) switch (nks) {
-        case 4: return launch_wrs_t<4, 1, TP>(p, st);
-        case 6: return launch_wrs_t<6, 1, TP>(p, st);
-        case 8: return launch_wrs_t<8, 1, TP>(p, st);
-        case 12: return launch_wrs_t<12, 1, TP>(p, st);
-    }
-    if (nfw == 2) switch (nks) {
-        case 8: return launch_wrs_t<8, 2, TP>(p, st);
-        case 12: return launch_wrs_t<12, 2, TP>(p, st);
-        case 16: return launch_wrs_t<16, 2, TP>(p, st);
-    }
-    if (nfw == 4 && nks == 8) return launch_wrs_t<8, 4, TP>(p, st);
-    return hipErrorInvalidValue;
-}
-
 static hipError_t launch_conv_wrs(const ConvParams& p, int c, hipStream_t st) {
     if (!conv_wrs_cfg_valid(p, c)) return hipErrorInvalidValue;
     int nks, nfw;
-    wrs_shape(p, nks, nfw);
-    return kWrs[c].TP == 64 ? launch_wrs_tp<64>(p, nks, nfw, st) : launch_wrs_tp<32>(p, nks, nfw, st);
+    const int sh = wrs_shape(p, nks, nfw);
+    return with_cfg<WrsCfgs>(c, [&](auto k) {
+        return with_cfg<WrsShapes>(sh, [&](auto s) { return launch_wrs_t(s, k, p, st); });
+    });
 }
 
 #if !defined(__HIP_DEVICE_COMPILE__)      // (host data: the device pass must not reference the host functions)
-const ConvFamily conv_wrs_family = {1200, kNumWrs, conv_wrs_cfg_valid, conv_wrs_symbol, launch_conv_wrs, true, "YOLOP_WRS", true};
+const ConvFamily conv_wrs_family = {1200, WrsCfgs::size, conv_wrs_cfg_valid, conv_wrs_symbol, launch_conv_wrs, true, "YOLOP_WRS", true};
 #endif
 
 }  // namespace yp
