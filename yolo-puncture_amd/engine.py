@@ -77,6 +77,10 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     lib.yp_debug_conv_s2.restype = C.c_int
     lib.yp_set_attention_form.argtypes = [vp, C.c_int]
     lib.yp_set_attention_form.restype = C.c_int
+    lib.yp_debug_attention_f32.argtypes = [vp, vp] + [C.c_int] * 11 + [ip, vp]
+    lib.yp_debug_attention_f32.restype = C.c_int
+    lib.yp_set_attention_f32_stream.argtypes = [vp, C.c_int]
+    lib.yp_set_attention_f32_stream.restype = C.c_int
     lib.yp_op_info.argtypes = [vp, C.c_int, C.c_char_p, C.c_int, ip, C.POINTER(C.c_double), C.POINTER(C.c_double)]
     lib.yp_op_output.argtypes = [vp, C.c_int, ip, ip, ip]
     lib.yp_op_kernel.argtypes = [vp, C.c_int, C.c_char_p, C.c_int]
@@ -149,7 +153,7 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
 EXPORTS = ["yp_last_error", "yp_create", "yp_destroy", "yp_weight_count", "yp_weight_info", "yp_set_weight",
            "yp_finalize", "yp_forward", "yp_proto", "yp_masks", "yp_id_mask_resized", "yp_plan", "yp_op_info", "yp_op_output", "yp_op_input", "yp_op_fusion",
            "yp_tensor_count", "yp_tensor_info", "yp_tensor_read", "yp_profile", "yp_set_graph", "yp_run_op",
-           "yp_tensor_write", "yp_op_kernel", "yp_set_autotune", "yp_tuning_export", "yp_tuning_import", "yp_set_nms", "yp_debug_force_conv_cfg", "yp_debug_op_cfg", "yp_debug_op_form", "yp_debug_last_store_form", "yp_debug_max_workgroups", "yp_debug_conv_families", "yp_debug_ablation", "yp_debug_head_clocks", "yp_debug_head_branch_clocks", "yp_debug_head_winners", "yp_debug_contour_clocks", "yp_debug_pwsp_clocks", "yp_debug_host_selftest", "yp_debug_graph_info", "yp_tuning_source", "yp_debug_head_positions", "yp_debug_marker", "yp_max_batch", "yp_debug_topk_anchors", "yp_debug_attention", "yp_debug_attention_form", "yp_debug_conv_s2", "yp_set_attention_form", "yp_letterbox", "yp_letterbox_batch", "yp_masks_frames", "yp_masks_frames_input", "yp_id_masks_frames", "yp_id_masks_frames_workspace", "yp_mask_contours",
+           "yp_tensor_write", "yp_op_kernel", "yp_set_autotune", "yp_tuning_export", "yp_tuning_import", "yp_set_nms", "yp_debug_force_conv_cfg", "yp_debug_op_cfg", "yp_debug_op_form", "yp_debug_last_store_form", "yp_debug_max_workgroups", "yp_debug_conv_families", "yp_debug_ablation", "yp_debug_head_clocks", "yp_debug_head_branch_clocks", "yp_debug_head_winners", "yp_debug_contour_clocks", "yp_debug_pwsp_clocks", "yp_debug_host_selftest", "yp_debug_graph_info", "yp_tuning_source", "yp_debug_head_positions", "yp_debug_marker", "yp_max_batch", "yp_debug_topk_anchors", "yp_debug_attention", "yp_debug_attention_form", "yp_debug_attention_f32", "yp_debug_conv_s2", "yp_set_attention_form", "yp_set_attention_f32_stream", "yp_letterbox", "yp_letterbox_batch", "yp_masks_frames", "yp_masks_frames_input", "yp_id_masks_frames", "yp_id_masks_frames_workspace", "yp_mask_contours",
            "yp_mask_contours_scaled", "yp_mask_contours_large_workspace", "yp_mask_contours_large", "yp_comm_unique_id", "yp_comm_create", "yp_allgather", "yp_comm_destroy",
            "yp_u2net_create", "yp_u2net_destroy", "yp_u2net_weight_count", "yp_u2net_weight_info", "yp_u2net_set_weight", "yp_u2net_finalize",
            "yp_u2net_forward", "yp_u2net_forward_crops", "yp_u2net_set_graph", "yp_u2net_tensor_count", "yp_u2net_tensor_info", "yp_u2net_tensor_read",
@@ -162,6 +166,15 @@ MAX_ANCHORS = 294912      # YP_MAX_ANCHORS
 MAX_MASKS = 480           # YP_MAX_MASKS
 ID_MASKS_FRAMES_BUDGET = 1 << 30      # YP_ID_MASKS_FRAMES_BUDGET: workspace bytes of one yp_id_masks_frames call before the facade splits a chunk
 ATTENTION_FORMS = {"auto": 0, "stream": 1, "stream_wide": 3}      # yp_set_attention_form (bit 0: 32/64 streaming kernel, bit 1: 36/72)
+
+
+ATTENTION_F32 = {"generic": 0, "stream": 1}      # yp_set_attention_f32_stream: a switch of its own beside the form
+
+
+def _attention_f32(value) -> int:
+    if value not in ATTENTION_F32:
+        raise ValueError(f"attention_f32 {value!r}: one of {sorted(ATTENTION_F32)}")
+    return ATTENTION_F32[value]
 
 
 def _attention_form(form) -> int:
@@ -212,6 +225,28 @@ def attention(qkv: torch.Tensor, nh: int, kd: int, hd: int, q_coff: int = 0, out
     rc = lib.yp_debug_attention_form(C.c_void_p(qkv.data_ptr()), C.c_void_p(out.data_ptr()), YP_BF16 if qkv.dtype == torch.bfloat16 else YP_F32, B, N,
                                 int(nh), int(kd), int(hd), q_stride, int(q_coff), int(out.shape[2]), int(o_coff), int(wgs), _attention_form(form), C.byref(kernel),
                                 C.c_void_p(_stream_ptr(qkv.device)))
+    if rc < 0:
+        raise YolopError(lib.yp_last_error().decode())
+    return out, kernel.value
+
+
+def attention_f32(qkv: torch.Tensor, nh: int, kd: int, hd: int, q_coff: int = 0, out: Optional[torch.Tensor] = None, o_coff: int = 0,
+                  wgs: int = 0, f32: str = "generic") -> Tuple[torch.Tensor, int]:
+    """Debug: `attention` on a float32 qkv under the fp32 switch (yp_debug_attention_f32). f32 "stream": calls with kd 32, hd 64 and more
+    than 400 tokens take the fp32 streaming kernel, and wgs sets the query groups its workgroups walk; "generic": what `attention` does.
+    Returns (out, kernel): 4 the fp32 streaming kernel ran, 0 the generic one. Whatever the host check refuses raises YolopError before
+    anything launches."""
+    lib = load_library()
+    if qkv.dim() != 3 or qkv.dtype != torch.float32 or not qkv.is_contiguous() or not qkv.is_cuda:
+        raise ValueError("qkv must be a contiguous device float32 [B, N, q_stride]")
+    B, N, q_stride = (int(v) for v in qkv.shape)
+    if out is None:
+        out = torch.empty((B, N, int(nh) * int(hd)), dtype=qkv.dtype, device=qkv.device)
+    if out.dim() != 3 or out.dtype != qkv.dtype or not out.is_contiguous() or out.device != qkv.device or tuple(out.shape[:2]) != (B, N):
+        raise ValueError("out must be a contiguous float32 [B, N, o_stride] on qkv's device")
+    kernel = C.c_int(-1)
+    rc = lib.yp_debug_attention_f32(C.c_void_p(qkv.data_ptr()), C.c_void_p(out.data_ptr()), B, N, int(nh), int(kd), int(hd), q_stride, int(q_coff),
+                                    int(out.shape[2]), int(o_coff), int(wgs), _attention_f32(f32), C.byref(kernel), C.c_void_p(_stream_ptr(qkv.device)))
     if rc < 0:
         raise YolopError(lib.yp_last_error().decode())
     return out, kernel.value
@@ -439,7 +474,7 @@ class Engine:
 
     def __init__(self, variant: str = "s", nc: int = 80, seg: bool = False, dtype: str = "bf16",
                  device: int = 0, max_det: int = 300, state: Optional[Dict[str, torch.Tensor]] = None,
-                 finalize: bool = True, family: str = "v10", attention: Optional[str] = None):
+                 finalize: bool = True, family: str = "v10", attention: Optional[str] = None, attention_f32: Optional[str] = None):
         self.lib = load_library()
         self.variant, self.nc, self.seg, self.max_det = variant, nc, seg, max_det
         self.family = family
@@ -454,6 +489,8 @@ class Engine:
         self.finalized = False
         if attention is not None:           # (None: what YOLOP_ATTN_FORM said when the engine was created, "auto" without it)
             self.set_attention_form(attention)
+        if attention_f32 is not None:       # (None: what YOLOP_ATTN_F32 said when the engine was created, "generic" without it)
+            self.set_attention_f32(attention_f32)
         if state is not None:
             self.load_state(state)
             if finalize:
@@ -506,6 +543,12 @@ class Engine:
         "stream": bf16 engines with 32-wide keys run attention_stream_kernel above 400 tokens, without a token bound. "stream_wide": that, and
         bf16 engines with 36-wide keys and 72-wide heads (YOLOv10-M) run attention_stream_wide_kernel at every token count. Drops the current plan."""
         self._chk(self.lib.yp_set_attention_form(self._h, _attention_form(form)))
+
+    def set_attention_f32(self, value: str) -> None:
+        """"generic": an fp32 engine's PSA block runs the generic kernel up to 2368 tokens and is refused beyond (the default). "stream": fp32
+        engines with 32-wide keys and 64-wide heads run attention_stream_f32_kernel above 400 tokens, without a token bound; bf16 engines
+        and YOLOv10-M are as before. Independent of set_attention_form. Drops the current plan."""
+        self._chk(self.lib.yp_set_attention_f32_stream(self._h, _attention_f32(value)))
 
     def set_autotune(self, enable: bool) -> None:
         self._chk(self.lib.yp_set_autotune(self._h, 1 if enable else 0))

@@ -20,7 +20,7 @@ import numpy as np
 import torch
 
 from . import hostops
-from .engine import ATTENTION_FORMS, ID_MASKS_FRAMES_BUDGET, LARGE_MAX_DIM, Engine, letterbox_batch_device, letterbox_device, mask_contours_device, mask_contours_large_device
+from .engine import ATTENTION_F32, ATTENTION_FORMS, ID_MASKS_FRAMES_BUDGET, LARGE_MAX_DIM, Engine, letterbox_batch_device, letterbox_device, mask_contours_device, mask_contours_large_device
 from .weights import read_ultralytics_pt, synthetic_state
 
 _ENGINE_CACHE: Dict[tuple, Engine] = {}
@@ -377,12 +377,16 @@ class YOLO:
     (seeded weights, for tests/benchmarks: no checkpoint exists offline)."""
 
     def __init__(self, model: Union[str, os.PathLike] = "yolov10s.pt", task: Optional[str] = None, dtype: str = "bf16",
-                 device: Optional[Union[int, str, torch.device]] = None, nc: int = 80, seed: int = 0, attention: str = "auto"):
+                 device: Optional[Union[int, str, torch.device]] = None, nc: int = 80, seed: int = 0, attention: str = "auto",
+                 attention_f32: Optional[str] = None):
         self.ckpt_path = str(model)
         self.dtype = dtype
         if attention not in ATTENTION_FORMS:
             raise ValueError(f"attention={attention!r}: one of {sorted(ATTENTION_FORMS)}")
         self.attention = attention          # "stream" / "stream_wide": the PSA block's streaming kernels (Engine.set_attention_form)
+        if attention_f32 is not None and attention_f32 not in ATTENTION_F32:
+            raise ValueError(f"attention_f32={attention_f32!r}: one of {sorted(ATTENTION_F32)}")
+        self.attention_f32 = attention_f32  # "stream": fp32 engines' streaming attention kernel past 400 tokens (Engine.set_attention_f32); None: the engine's default
         self.family = "v10"
         if self.ckpt_path.startswith("synthetic:"):
             spec = self.ckpt_path.split(":", 1)[1]              # "s", "s-seg" (YOLOv10) ; "v8n-seg", "11x-seg" (the app's families)
@@ -440,10 +444,11 @@ class YOLO:
             mt = os.path.getmtime(self.ckpt_path)
         except OSError:
             mt = 0.0
-        key = (self.ckpt_path, mt, self.family, self.variant, self.nc, self.seg, self.dtype, self._dev_index, self.attention)
+        key = (self.ckpt_path, mt, self.family, self.variant, self.nc, self.seg, self.dtype, self._dev_index, self.attention, self.attention_f32)
         eng = _ENGINE_CACHE.get(key)
         if eng is None:
-            eng = Engine(self.variant, self.nc, self.seg, self.dtype, self._dev_index, state=self._state, family=self.family, attention=self.attention)
+            eng = Engine(self.variant, self.nc, self.seg, self.dtype, self._dev_index, state=self._state, family=self.family, attention=self.attention,
+                         attention_f32=self.attention_f32)
             _ENGINE_CACHE[key] = eng
         return eng
 
