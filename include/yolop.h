@@ -310,8 +310,9 @@ int yp_comm_destroy(yp_comm* c);
  *            bound (anchors = 21 x tokens, so 14043 tokens) and the byte bound remain. v10-M (36-wide keys, 72-wide heads) does the same
  *            at every token count under the form `stream_wide`, which includes `stream`; under `auto` and `stream` it keeps the generic
  *            kernel and its bound of 2364 tokens. fp32 engines keep the generic kernel and its bound under every form; their
- *            streaming kernel has a switch of its own (yp_set_attention_f32_stream: 32-wide keys and 64-wide heads, above 400 tokens,
- *            no token bound; fp32 v10-M keeps the generic kernel and 2364 tokens).
+ *            streaming kernels have a switch of their own (yp_set_attention_f32_stream: value 1 - 32-wide keys and 64-wide heads, above
+ *            400 tokens, no token bound; fp32 v10-M keeps the generic kernel and 2364 tokens under 0 and 1 and streams above 400 tokens
+ *            under value 3).
  *   bytes    every activation stays below 2^31 bytes: yp_max_batch(e, H, W) is the largest B that plans at HxW (callers split to it). */
 #define YP_MAX_ANCHORS 294912   /* 12288 * (12288 / 512): covers 3840x2176 (214200) */
 int yp_max_batch(const yp_engine* e, int H, int W);
@@ -364,10 +365,14 @@ int yp_set_attention_form(yp_engine* e, int form);
  * tokens: K and V stream through LDS in blocks of 64 keys, both products on the fp32 matrix-core instruction (an exact fp32 FMA chain, so
  * the fp32 contract gains no rounding point), two passes over K (row max and sum, then P.V with the normalised probabilities). No token
  * bound of its own: the anchor bound and the byte bound (qkv below 2^31 bytes, yp_max_batch) remain. Up to 400 tokens, in bf16 engines and
- * for v10-M's 36/72 heads the switch changes nothing: same plan, same refusals. on = 0 (the default) is the engine as it was: the generic
- * kernel up to 2368 tokens, refusal beyond. Any other value, or a null engine: YP_ERR_ARG. Allowed before or after yp_finalize; a change
- * drops the current plan and keeps the per-shape tuning memo. An engine created while YOLOP_ATTN_F32=stream is set starts with the switch
- * on; any other non-empty value of the variable fails yp_create. */
+ * for v10-M's 36/72 heads value 1 changes nothing: same plan, same refusals. on = 3 (stream_wide) is on = 1, and an fp32 engine's PSA
+ * block with key_dim 36 and head_dim 72 (YOLOv10-M) runs attention_stream_wide_f32_kernel above 400 tokens: the same two passes and
+ * instruction, nine k-steps over the 36 key dimensions, five 16-column output tiles whose eight dead columns are fed zeros and never
+ * stored; no token bound of its own either. The value is a bit set like the attention form - bit 0 the 32/64 kernel, bit 1 the 36/72 one:
+ * 2 is no value. on = 0 (the default) is the engine as it was: the generic kernel up to 2368 tokens (2364 for v10-M), refusal beyond; the
+ * refusal of v10-M does not name the switch. Any other value, or a null engine: YP_ERR_ARG. Allowed before or after yp_finalize; a change
+ * drops the current plan and keeps the per-shape tuning memo. An engine created while YOLOP_ATTN_F32=stream (stream_wide) is set starts
+ * with value 1 (3); any other non-empty value of the variable fails yp_create. */
 int yp_set_attention_f32_stream(yp_engine* e, int on);
 
 /* Enable/disable the plan-time autotuner that picks the conv tile configuration per layer (default on). */
@@ -429,7 +434,9 @@ int yp_debug_attention_form(const void* qkv_dev, void* o_dev, int dtype, int B, 
    rest, on the host): with f32_stream = 1 a call with kd 32, hd 64, more than 400 tokens and qkv below 2^31 bytes takes the fp32 streaming
    kernel, *kernel_out = 4, and wgs replaces its workgroup target (YOLOP_ATTN_WGS, else 1024), which sets the runs of 64-query groups its
    workgroups walk; every other call behaves as with 0, which is
-   yp_debug_attention with YP_F32, the generic kernel's token bound included. */
+   yp_debug_attention with YP_F32, the generic kernel's token bound included. f32_stream = 3 is 1, and a call with kd 36, hd 72, more than
+   400 tokens and qkv below 2^31 bytes takes the wide-head fp32 streaming kernel, *kernel_out = 5, under the same workgroup target. 2 is
+   refused. */
 int yp_debug_attention_f32(const void* qkv_dev, void* o_dev, int B, int N, int nh, int kd, int hd, int q_stride, int q_coff, int o_stride, int o_coff,
                            int wgs, int f32_stream, int* kernel_out, void* stream);
 /* Test hook: one 3x3 / stride-2 / pad-1 bf16 convolution alone through the stride-2 halo family (conv_halo_s2.hip), y = act(W * x + bias)

@@ -116,6 +116,34 @@ int main() {
                     } else CHECK(rc == YP_ERR_ARG && strstr(yp_last_error(), "attention tokens"));
                 }
                 CHECK(yp_set_attention_form(e, 0) == YP_OK);
+                // the fp32 switch, a bit set too: under 1 fp32 engines with 32-wide keys plan 3680 tokens on the fp32 streaming kernel, under 3
+                // those plan as under 1 and fp32 v10-M (36-wide keys) on its own kernel; bf16 engines ignore it
+                CHECK(yp_set_attention_f32_stream(e, 2) == YP_ERR_ARG && yp_set_attention_f32_stream(nullptr, 3) == YP_ERR_ARG);
+                for (int on : {1, 3}) {
+                    CHECK(yp_set_attention_f32_stream(e, on) == YP_OK);
+                    const bool m = fam == YP_FAMILY_V10 && d.variant == 'm';
+                    const bool narrow = fam != YP_FAMILY_V8 && d.dtype == YP_F32 && !m;
+                    const bool wide = m && d.dtype == YP_F32 && on == 3;
+                    const int rc = yp_plan(e, 1, 2560, 1472);
+                    if (fam == YP_FAMILY_V8 || narrow || wide) {
+                        CHECK(rc > 0);
+                        bool named = false, named_wide = false;
+                        for (int i = 0; i < rc; ++i) {
+                            char kname[256];
+                            CHECK(yp_op_kernel(e, i, kname, sizeof(kname)) == YP_OK);
+                            named |= !strcmp(kname, "attention_stream_f32_kernel");
+                            named_wide |= !strcmp(kname, "attention_stream_wide_f32_kernel");
+                        }
+                        CHECK(named == narrow && named_wide == wide);
+                        CHECK(yp_debug_host_selftest(e) > 0);
+                    } else CHECK(rc == YP_ERR_ARG && strstr(yp_last_error(), "attention tokens"));
+                    if (m && d.dtype == YP_F32) {                       // 2420 tokens: the first shape the generic kernel refuses for M
+                        const int r2 = yp_plan(e, 1, 1408, 1760);
+                        if (on == 3) CHECK(r2 > 0 && yp_debug_host_selftest(e) > 0);
+                        else CHECK(r2 == YP_ERR_ARG && strstr(yp_last_error(), "at most 2364"));
+                    }
+                }
+                CHECK(yp_set_attention_f32_stream(e, 0) == YP_OK);
                 {
                     const int mb = yp_max_batch(e, 1280, 1280);
                     CHECK(mb >= 1 && yp_max_batch(e, 640, 640) >= mb);

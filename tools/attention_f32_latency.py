@@ -7,7 +7,10 @@ Cases (B, N, nh): (8, 1600, 4) v10-S at 8x1280x1280, (4, 2040, 4) v10-S at 4x108
 at 2560x1472 and (1, 8160, 2) 11n on a 4K frame at its own size. The generic kernel is timed where it runs (N <= 2368). TFLOP/s count the
 algorithm (2 B nh N^2 (kd + hd)), not the streaming kernel's second Q.K^T.
 Writes profiles/attention_stream_f32_latency.json and exits non-zero when the streaming kernel is not faster than the generic one at
-(8, 1600, 4)."""
+(8, 1600, 4).
+--heads wide: the same for YOLOv10-M's heads (key_dim 36, head_dim 72) and attention_stream_wide_f32_kernel (switch value "stream_wide"):
+(8, 1600, 4), (4, 2040, 4), (1, 920, 4), (1, 3680, 4), (1, 8160, 4), the generic kernel where it runs (N <= 2364), the same gate; writes
+profiles/attention_stream_wide_f32_latency.json."""
 import argparse
 import json
 import os
@@ -21,17 +24,16 @@ sys.path.insert(0, ROOT)
 from yolo_puncture_amd.engine import attention_f32  # noqa: E402
 
 GATE = (8, 1600, 4)
-CASES = [(8, 1600, 4), (4, 2040, 4), (1, 920, 4), (1, 3680, 2), (1, 8160, 2)]
-KD, HD = 32, 64
-GENERIC_MAX_TOKENS = 2368
-WANT = {"generic": 0, "stream": 4}
+# per --heads: cases (B, N, nh), key_dim, head_dim, the generic kernel's last N, the switch value, the kernel number it must report, output
+HEADS = {"narrow": ([(8, 1600, 4), (4, 2040, 4), (1, 920, 4), (1, 3680, 2), (1, 8160, 2)], 32, 64, 2368, "stream", 4, "attention_stream_f32_latency.json"),
+         "wide": ([(8, 1600, 4), (4, 2040, 4), (1, 920, 4), (1, 3680, 4), (1, 8160, 4)], 36, 72, 2364, "stream_wide", 5, "attention_stream_wide_f32_latency.json")}
 
 
-def batch_ms(qkv, out, nh, f32, launches, wgs=0):
+def batch_ms(qkv, out, nh, kd, hd, f32, launches, wgs=0):
     a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     a.record()
     for _ in range(launches):
-        attention_f32(qkv, nh, KD, HD, out=out, f32=f32, wgs=wgs)
+        attention_f32(qkv, nh, kd, hd, out=out, f32=f32, wgs=wgs)
     b.record()
     torch.cuda.synchronize()
     return a.elapsed_time(b) / launches
@@ -42,8 +44,13 @@ def main():
     ap.add_argument("--launches", type=int, default=20)
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--wgs", type=int, default=0, help="the streaming kernel's workgroup target for the run (0: the launcher's own)")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "attention_stream_f32_latency.json"))
+    ap.add_argument("--heads", choices=sorted(HEADS), default="narrow", help="narrow: 32/64 heads; wide: YOLOv10-M's 36/72")
+    ap.add_argument("--out", default=None, help="default: profiles/attention_stream_f32_latency.json, attention_stream_wide_f32_latency.json for --heads wide")
     a = ap.parse_args()
+    CASES, KD, HD, GENERIC_MAX_TOKENS, value, number, name = HEADS[a.heads]
+    WANT = {"generic": 0, "stream": number}
+    if a.out is None:
+        a.out = os.path.join(ROOT, "profiles", name)
     if not torch.cuda.is_available():
         sys.exit("attention_f32_latency.py measures on the GPU; none is visible")
     if a.launches < 20:
@@ -57,11 +64,11 @@ def main():
         kinds = (["generic"] if N <= GENERIC_MAX_TOKENS else []) + ["stream"]
         for f in kinds:                                            # warm-up (and: each side takes the kernel this file is about)
             for _ in range(3):
-                assert attention_f32(qkv, nh, KD, HD, out=out, f32=f)[1] == WANT[f]
+                assert attention_f32(qkv, nh, KD, HD, out=out, f32=value if f == "stream" else f)[1] == WANT[f]
         ts = {f: [] for f in kinds}
         for _ in range(a.rounds):                                  # alternating
             for f in kinds:
-                ts[f].append(batch_ms(qkv, out, nh, f, a.launches, a.wgs if f == "stream" else 0))
+                ts[f].append(batch_ms(qkv, out, nh, KD, HD, value if f == "stream" else f, a.launches, a.wgs if f == "stream" else 0))
         flop = 2.0 * B * nh * N * N * (KD + HD)
         rec = {}
         for f in kinds:

@@ -311,30 +311,37 @@ bool attention_takes_stream(const AttnParams& p, int dtype, int form) {
 bool attention_takes_stream_wide(const AttnParams& p, int dtype, int form) {
     return form == ATTN_FORM_STREAM_WIDE && attention_stream_wide_scope(p, dtype);
 }
-bool attention_takes_stream_f32(const AttnParams& p, int dtype, bool f32_stream) {
-    return f32_stream && p.N > ATTN_RESIDENT_TOKENS && attention_stream_f32_scope(p, dtype);
+bool attention_takes_stream_f32(const AttnParams& p, int dtype, int f32_stream) {
+    return attn_f32_valid(f32_stream) && (f32_stream & ATTN_F32_STREAM) && p.N > ATTN_RESIDENT_TOKENS && attention_stream_f32_scope(p, dtype);
+}
+bool attention_takes_stream_wide_f32(const AttnParams& p, int dtype, int f32_stream) {
+    return f32_stream == ATTN_F32_STREAM_WIDE && p.N > ATTN_RESIDENT_TOKENS && attention_stream_wide_f32_scope(p, dtype);
 }
 
 // Whether launch_attention has a kernel for p (the planner asks before anything launches); *max_tokens = the largest N the generic kernel
 // holds with p's head sizes: it keeps a query tile's QT x N scores in LDS (the streaming forms, where `form` and the call admit one, have no
-// bound, and neither has the fp32 streaming kernel where f32_stream admits it). All kernels move 4 elements per access (load4 / store4,
+// bound, and neither have the fp32 streaming kernels where f32_stream admits one). All kernels move 4 elements per access (load4 / store4,
 // the 16-B fragments of the matrix-core forms), so the strides and
 // channel offsets of both slices are multiples of 4 elements.
-bool attention_fits(const AttnParams& p, int dtype, int* max_tokens, int form, bool f32_stream) {
+bool attention_fits(const AttnParams& p, int dtype, int* max_tokens, int form, int f32_stream) {
     if (max_tokens) *max_tokens = (int)((150 * 1024 / sizeof(float) - (size_t)QT * p.kd) / QT);
-    if (!attn_form_valid(form)) return false;
+    if (!attn_form_valid(form) || !attn_f32_valid(f32_stream)) return false;
     if ((p.q_stride | p.q_coff | p.o_stride | p.o_coff) & 3) return false;
     if (attention_takes_mfma(p, dtype) || attention_takes_stream(p, dtype, form) || attention_takes_stream_wide(p, dtype, form)) return true;
-    if (attention_takes_stream_f32(p, dtype, f32_stream)) return true;
+    if (attention_takes_stream_f32(p, dtype, f32_stream) || attention_takes_stream_wide_f32(p, dtype, f32_stream)) return true;
     return attention_generic_lds(p.kd, p.N) <= 150 * 1024 && !(p.kd & 3) && !(p.hd & 3);
 }
 
-hipError_t launch_attention(const AttnParams& p, int dtype, hipStream_t st, int wgs, int* kernel_out, int form, bool f32_stream) {
+hipError_t launch_attention(const AttnParams& p, int dtype, hipStream_t st, int wgs, int* kernel_out, int form, int f32_stream) {
     const size_t qkv_bytes = (size_t)p.B * p.N * p.q_stride * 2;
     if (!attention_fits(p, dtype, nullptr, form, f32_stream)) return hipErrorInvalidValue;
     if (attention_takes_stream_f32(p, dtype, f32_stream)) {
         if (kernel_out) *kernel_out = 4;
         return launch_attention_stream_f32(p, st, wgs);
+    }
+    if (attention_takes_stream_wide_f32(p, dtype, f32_stream)) {
+        if (kernel_out) *kernel_out = 5;
+        return launch_attention_stream_wide_f32(p, st, wgs);
     }
     if (attention_takes_stream(p, dtype, form)) {
         if (kernel_out) *kernel_out = 2;

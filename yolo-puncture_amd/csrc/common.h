@@ -415,12 +415,17 @@ enum AttnForm { ATTN_FORM_AUTO = 0, ATTN_FORM_STREAM = 1, ATTN_FORM_STREAM_WIDE 
 inline bool attn_form_valid(int form) { return form == ATTN_FORM_AUTO || form == ATTN_FORM_STREAM || form == ATTN_FORM_STREAM_WIDE; }
 constexpr int ATTN_RESIDENT_TOKENS = 400;
 // kernel_out: 0 generic, 1 resident matrix-core, 2 streaming matrix-core, 3 streaming matrix-core for 36/72 heads, 4 streaming matrix-core
-// in fp32. f32_stream is an engine's fp32 switch (yp_set_attention_f32_stream), orthogonal to the form: fp32 calls in
-// attention_stream_f32_scope with more than 400 tokens take attention_stream_f32_kernel (no token bound); off, nothing changes.
+// in fp32, 5 streaming matrix-core in fp32 for 36/72 heads. f32_stream is an engine's fp32 switch (yp_set_attention_f32_stream),
+// orthogonal to the form and a bit set like it: bit 0 (ATTN_F32_STREAM) - fp32 calls in attention_stream_f32_scope with more than 400
+// tokens take attention_stream_f32_kernel (no token bound); bit 1 - fp32 calls in attention_stream_wide_f32_scope (key_dim 36, head_dim 72)
+// with more than 400 tokens take attention_stream_wide_f32_kernel. Bit 1 alone is no value: 0, 1 and 3 (ATTN_F32_STREAM_WIDE) are. Off,
+// nothing changes.
+enum AttnF32 { ATTN_F32_GENERIC = 0, ATTN_F32_STREAM = 1, ATTN_F32_STREAM_WIDE = 3 };
+inline bool attn_f32_valid(int v) { return v == ATTN_F32_GENERIC || v == ATTN_F32_STREAM || v == ATTN_F32_STREAM_WIDE; }
 hipError_t launch_attention(const AttnParams& p, int dtype, hipStream_t st, int wgs = 0, int* kernel_out = nullptr, int form = ATTN_FORM_AUTO,
-                            bool f32_stream = false);
+                            int f32_stream = ATTN_F32_GENERIC);
 // the predicate of launch_attention, for the planner; *max_tokens = the generic kernel's bound for p's head sizes
-bool attention_fits(const AttnParams& p, int dtype, int* max_tokens, int form = ATTN_FORM_AUTO, bool f32_stream = false);
+bool attention_fits(const AttnParams& p, int dtype, int* max_tokens, int form = ATTN_FORM_AUTO, int f32_stream = ATTN_F32_GENERIC);
 bool attention_takes_stream(const AttnParams& p, int dtype, int form);     // launch_attention would launch attention_stream_kernel
 bool attention_takes_stream_wide(const AttnParams& p, int dtype, int form);    // ... attention_stream_wide_kernel
 // attention_stream.hip
@@ -431,9 +436,13 @@ hipError_t launch_attention_stream(const AttnParams& p, hipStream_t st, int wgs)
 bool attention_stream_wide_scope(const AttnParams& p, int dtype);
 hipError_t launch_attention_stream_wide(const AttnParams& p, hipStream_t st, int wgs);
 // attention_stream_f32.hip
-bool attention_takes_stream_f32(const AttnParams& p, int dtype, bool f32_stream);    // launch_attention would launch attention_stream_f32_kernel
+bool attention_takes_stream_f32(const AttnParams& p, int dtype, int f32_stream);    // launch_attention would launch attention_stream_f32_kernel
 bool attention_stream_f32_scope(const AttnParams& p, int dtype);
 hipError_t launch_attention_stream_f32(const AttnParams& p, hipStream_t st, int wgs);
+// attention_stream_wide_f32.hip
+bool attention_takes_stream_wide_f32(const AttnParams& p, int dtype, int f32_stream);    // ... attention_stream_wide_f32_kernel
+bool attention_stream_wide_f32_scope(const AttnParams& p, int dtype);
+hipError_t launch_attention_stream_wide_f32(const AttnParams& p, hipStream_t st, int wgs);
 // conv_small.hip: fp32 3x3 for small maps (four waves split K, operands straight from L2)
 bool conv_small_valid(const ConvParams& p, int dtype);
 hipError_t launch_conv_small(const ConvParams& p, int dtype, hipStream_t st);

@@ -64,7 +64,7 @@ struct yp_engine {
     std::map<std::array<int, 3>, bool> auto_replay;
     bool fuse = true;             // dw->pw fusion (YOLOP_NO_FUSE=1 disables, for A/B)
     int attn_form = ATTN_FORM_AUTO;   // yp_set_attention_form (YOLOP_ATTN_FORM=stream at yp_create): the stream bit lets OP_ATTN take attention_stream_kernel, ATTN_FORM_STREAM_WIDE attention_stream_wide_kernel too
-    bool attn_f32_stream = false; // yp_set_attention_f32_stream (YOLOP_ATTN_F32=stream at yp_create): fp32 OP_ATTN with 32/64 heads takes attention_stream_f32_kernel above 400 tokens; orthogonal to attn_form
+    int attn_f32_stream = ATTN_F32_GENERIC; // yp_set_attention_f32_stream (YOLOP_ATTN_F32=stream | stream_wide at yp_create): above 400 tokens fp32 OP_ATTN with 32/64 heads takes attention_stream_f32_kernel (bit 0), with 36/72 heads attention_stream_wide_f32_kernel (bit 1); orthogonal to attn_form
     bool tail = false;            // conv_dwpw TAIL form (YOLOP_TAIL=1 at yp_create enables; see make_plan)
     bool narrow_store = false;    // bf16 conv epilogues keep the 8-byte stores everywhere (YOLOP_NARROW_STORE=1 at yp_create; default: 16-byte paired stores where a launch admits them)
     bool sparse_head = true;      // v10 head: box / coefficient branches on the stage-1 winners only (YOLOP_DENSE_HEAD=1 at yp_create disables)
@@ -1157,7 +1157,7 @@ static int make_plan(yp_engine& e, int B, int H, int W) {
             if (((e.attn_form & ATTN_FORM_STREAM) || e.attn_f32_stream) && B > max_batch(e, H, W)) break;
             return fail(YP_ERR_ARG, "input %dx%d gives %s %d attention tokens; the attention kernels hold at most %d (a streaming form is not built)%s", H, W,
                         o.name.c_str(), q.N, max_tokens,
-                        !e.attn_f32_stream && attention_fits(q, e.dtype, nullptr, e.attn_form, true)
+                        !e.attn_f32_stream && attention_fits(q, e.dtype, nullptr, e.attn_form, ATTN_F32_STREAM)
                             ? "; the fp32 streaming kernel is opt-in and holds this shape: yp_set_attention_f32_stream(e, 1), YOLOP_ATTN_F32=stream, attention_f32=\"stream\""
                         : e.attn_form == ATTN_FORM_AUTO && attention_fits(q, e.dtype, nullptr, ATTN_FORM_STREAM)
                             ? "; the streaming kernel is opt-in and holds this shape: yp_set_attention_form(e, 1), YOLOP_ATTN_FORM=stream, attention=\"stream\""
@@ -1193,7 +1193,7 @@ static int make_plan(yp_engine& e, int B, int H, int W) {
             o.flops = 2.0 * B * o.nh * Nn * Nn * (o.kd + o.hd);
             const AttnParams ap = attn_params(e, o, B);
             if (attention_takes_stream(ap, e.dtype, e.attn_form) || attention_takes_stream_wide(ap, e.dtype, e.attn_form) ||
-                attention_takes_stream_f32(ap, e.dtype, e.attn_f32_stream))
+                attention_takes_stream_f32(ap, e.dtype, e.attn_f32_stream) || attention_takes_stream_wide_f32(ap, e.dtype, e.attn_f32_stream))
                 o.flops += 2.0 * B * o.nh * Nn * Nn * o.kd;      // Q.K^T runs in both passes
         } else if (o.kind == OP_HEAD) {
             o.bytes = 0;                       // class-max keys + the winners' class / box rows + the outputs
@@ -1246,6 +1246,7 @@ static int make_plan(yp_engine& e, int B, int H, int W) {
         else if (o.kind == OP_POOL3 && e.dtype == DT_BF16 && (o.in.C & 31) == 0) o.kernel = "sppf_pool3_bf16_kernel";
         else if (o.kind == OP_HEAD && A > (size_t)HEAD_LDS_ANCHORS) o.kernel = o.nms ? "head_nms_gather_kernel + head_nms_large_kernel" : head_large_kernel_name(0);
         else if (o.kind == OP_ATTN && attention_takes_stream_f32(attn_params(e, o, B), e.dtype, e.attn_f32_stream)) o.kernel = "attention_stream_f32_kernel";
+        else if (o.kind == OP_ATTN && attention_takes_stream_wide_f32(attn_params(e, o, B), e.dtype, e.attn_f32_stream)) o.kernel = "attention_stream_wide_f32_kernel";
         else if (o.kind == OP_ATTN && attention_takes_stream(attn_params(e, o, B), e.dtype, e.attn_form)) o.kernel = "attention_stream_kernel";
         else if (o.kind == OP_ATTN && attention_takes_stream_wide(attn_params(e, o, B), e.dtype, e.attn_form)) o.kernel = "attention_stream_wide_kernel";
         else o.kernel = (o.kind == OP_HEAD && o.nms) ? "head_nms_kernel" : kn[o.kind];
@@ -2056,8 +2057,9 @@ int yp_create(const yp_model_desc* desc, int device, yp_engine** out) {
         else if (*v && strcmp(v, "auto")) return fail(YP_ERR_ARG, "YOLOP_ATTN_FORM=%s (auto | stream | stream_wide)", v);
     }
     if (const char* v = std::getenv("YOLOP_ATTN_F32")) {
-        if (!strcmp(v, "stream")) e->attn_f32_stream = true;
-        else if (*v) return fail(YP_ERR_ARG, "YOLOP_ATTN_F32=%s (stream, or unset)", v);
+        if (!strcmp(v, "stream")) e->attn_f32_stream = ATTN_F32_STREAM;
+        else if (!strcmp(v, "stream_wide")) e->attn_f32_stream = ATTN_F32_STREAM_WIDE;
+        else if (*v) return fail(YP_ERR_ARG, "YOLOP_ATTN_F32=%s (stream | stream_wide, or unset)", v);
     }
     e->sparse_head = !env_on("YOLOP_DENSE_HEAD");
     e->narrow_store = env_on("YOLOP_NARROW_STORE");
@@ -2618,7 +2620,7 @@ static int debug_attention(const void* qkv_dev, void* o_dev, int dtype, int B, i
         return fail(YP_ERR_ARG, "yp_debug_attention: non-positive size (B %d, N %d, nh %d, kd %d, hd %d, q_stride %d, q_coff %d, o_stride %d, o_coff %d, wgs %d)",
                     B, N, nh, kd, hd, q_stride, q_coff, o_stride, o_coff, wgs);
     if (!attn_form_valid(form)) return fail(YP_ERR_ARG, "yp_debug_attention: form = %d (0 auto | 1 stream | 3 stream_wide)", form);
-    if (f32_stream != 0 && f32_stream != 1) return fail(YP_ERR_ARG, "yp_debug_attention: f32_stream = %d (0 | 1)", f32_stream);
+    if (!attn_f32_valid(f32_stream)) return fail(YP_ERR_ARG, "yp_debug_attention: f32_stream = %d (0 generic | 1 stream | 3 stream_wide)", f32_stream);
     if ((int64_t)B * nh > 65535) return fail(YP_ERR_ARG, "yp_debug_attention: B * nh = %lld; the grid holds at most 65535", (long long)B * nh);
     if ((int64_t)q_coff + (int64_t)nh * (2 * (int64_t)kd + hd) > q_stride)
         return fail(YP_ERR_ARG, "yp_debug_attention: the qkv slice [%d, %lld) does not fit q_stride = %d", q_coff, (long long)q_coff + (long long)nh * (2 * (long long)kd + hd), q_stride);
@@ -2631,12 +2633,13 @@ static int debug_attention(const void* qkv_dev, void* o_dev, int dtype, int B, i
     p.qkv = qkv_dev; p.q_stride = q_stride; p.q_coff = q_coff; p.o = o_dev; p.o_stride = o_stride; p.o_coff = o_coff;
     p.B = B; p.N = N; p.nh = nh; p.kd = kd; p.hd = hd; p.scale = 1.0f / std::sqrt((float)kd);
     int max_tokens = 0;
-    if (!attention_fits(p, dtype, &max_tokens, form, f32_stream != 0))
+    if (!attention_fits(p, dtype, &max_tokens, form, f32_stream))
         return fail(YP_ERR_ARG, "yp_debug_attention: no kernel for N = %d, kd = %d, hd = %d: the attention kernels hold at most %d tokens and want kd and hd in multiples of 4%s",
                     N, kd, hd, max_tokens,
-                    f32_stream && dtype == YP_F32 && kd == 32 && hd == 64 ? "; the fp32 streaming kernel takes qkv below 2^31 bytes" : "");
+                    dtype == YP_F32 && (((f32_stream & ATTN_F32_STREAM) && kd == 32 && hd == 64) || (f32_stream == ATTN_F32_STREAM_WIDE && kd == 36 && hd == 72))
+                        ? "; the fp32 streaming kernel takes qkv below 2^31 bytes" : "");
     hipStream_t st = (hipStream_t)stream;
-    hipError_t err = launch_attention(p, dtype, st, wgs, kernel_out, form, f32_stream != 0);
+    hipError_t err = launch_attention(p, dtype, st, wgs, kernel_out, form, f32_stream);
     if (err == hipSuccess) err = hipStreamSynchronize(st);
     if (err != hipSuccess) return fail(YP_ERR_HIP, "yp_debug_attention: %s", hipGetErrorString(err));
     return YP_OK;
@@ -2892,13 +2895,13 @@ int yp_set_attention_form(yp_engine* e, int form) {
 
 int yp_set_attention_f32_stream(yp_engine* e, int on) {
     if (!e) return fail(YP_ERR_ARG, "null engine");
-    if (on != 0 && on != 1) return fail(YP_ERR_ARG, "yp_set_attention_f32_stream: on = %d (0 generic | 1 stream)", on);
-    if ((on != 0) == e->attn_f32_stream) return YP_OK;
+    if (!attn_f32_valid(on)) return fail(YP_ERR_ARG, "yp_set_attention_f32_stream: on = %d (0 generic | 1 stream | 3 stream_wide)", on);
+    if (on == e->attn_f32_stream) return YP_OK;
     if (e->finalized || e->arena) {      // as yp_set_attention_form: the plan changes under nothing in flight
         HIPCHK(hipSetDevice(e->device));
         HIPCHK(hipDeviceSynchronize());
     }
-    e->attn_f32_stream = on != 0;
+    e->attn_f32_stream = on;
     e->planned = false;                  // (the per-shape tuning memo stays: the attention op's kernel is the plan's decision)
     e->auto_replay.clear();
     return YP_OK;

@@ -169,12 +169,15 @@ ATTENTION_FORMS = {"auto": 0, "stream": 1, "stream_wide": 3}      # yp_set_atten
 
 
 ATTENTION_F32 = {"generic": 0, "stream": 1}      # yp_set_attention_f32_stream: a switch of its own beside the form
+ATTENTION_F32_WIDE = {"stream_wide": 3}          # ... read as a bit set: bit 0 the 32/64 fp32 streaming kernel, bit 1 the 36/72 one (2 is no value)
 
 
 def _attention_f32(value) -> int:
-    if value not in ATTENTION_F32:
-        raise ValueError(f"attention_f32 {value!r}: one of {sorted(ATTENTION_F32)}")
-    return ATTENTION_F32[value]
+    if value in ATTENTION_F32:
+        return ATTENTION_F32[value]
+    if value in ATTENTION_F32_WIDE:
+        return ATTENTION_F32_WIDE[value]
+    raise ValueError(f"attention_f32 {value!r}: one of {sorted(ATTENTION_F32) + sorted(ATTENTION_F32_WIDE)}")
 
 
 def _attention_form(form) -> int:
@@ -233,9 +236,10 @@ def attention(qkv: torch.Tensor, nh: int, kd: int, hd: int, q_coff: int = 0, out
 def attention_f32(qkv: torch.Tensor, nh: int, kd: int, hd: int, q_coff: int = 0, out: Optional[torch.Tensor] = None, o_coff: int = 0,
                   wgs: int = 0, f32: str = "generic") -> Tuple[torch.Tensor, int]:
     """Debug: `attention` on a float32 qkv under the fp32 switch (yp_debug_attention_f32). f32 "stream": calls with kd 32, hd 64 and more
-    than 400 tokens take the fp32 streaming kernel, and wgs sets the query groups its workgroups walk; "generic": what `attention` does.
-    Returns (out, kernel): 4 the fp32 streaming kernel ran, 0 the generic one. Whatever the host check refuses raises YolopError before
-    anything launches."""
+    than 400 tokens take the fp32 streaming kernel, and wgs sets the query groups its workgroups walk; "stream_wide": those too, and calls
+    with kd 36, hd 72 and more than 400 tokens take the wide-head fp32 streaming kernel; "generic": what `attention` does.
+    Returns (out, kernel): 5 the wide-head fp32 streaming kernel ran, 4 the fp32 streaming kernel, 0 the generic one. Whatever the host
+    check refuses raises YolopError before anything launches."""
     lib = load_library()
     if qkv.dim() != 3 or qkv.dtype != torch.float32 or not qkv.is_contiguous() or not qkv.is_cuda:
         raise ValueError("qkv must be a contiguous device float32 [B, N, q_stride]")
@@ -547,7 +551,8 @@ class Engine:
     def set_attention_f32(self, value: str) -> None:
         """"generic": an fp32 engine's PSA block runs the generic kernel up to 2368 tokens and is refused beyond (the default). "stream": fp32
         engines with 32-wide keys and 64-wide heads run attention_stream_f32_kernel above 400 tokens, without a token bound; bf16 engines
-        and YOLOv10-M are as before. Independent of set_attention_form. Drops the current plan."""
+        and YOLOv10-M are as before. "stream_wide": that, and fp32 engines with 36-wide keys and 72-wide heads (YOLOv10-M) run
+        attention_stream_wide_f32_kernel above 400 tokens. Independent of set_attention_form. Drops the current plan."""
         self._chk(self.lib.yp_set_attention_f32_stream(self._h, _attention_f32(value)))
 
     def set_autotune(self, enable: bool) -> None:

@@ -20,7 +20,7 @@ import numpy as np
 import torch
 
 from . import hostops
-from .engine import ATTENTION_F32, ATTENTION_FORMS, ID_MASKS_FRAMES_BUDGET, LARGE_MAX_DIM, Engine, letterbox_batch_device, letterbox_device, mask_contours_device, mask_contours_large_device
+from .engine import ATTENTION_F32, ATTENTION_F32_WIDE, ATTENTION_FORMS, ID_MASKS_FRAMES_BUDGET, LARGE_MAX_DIM, Engine, letterbox_batch_device, letterbox_device, mask_contours_device, mask_contours_large_device
 from .weights import read_ultralytics_pt, synthetic_state
 
 _ENGINE_CACHE: Dict[tuple, Engine] = {}
@@ -384,9 +384,9 @@ class YOLO:
         if attention not in ATTENTION_FORMS:
             raise ValueError(f"attention={attention!r}: one of {sorted(ATTENTION_FORMS)}")
         self.attention = attention          # "stream" / "stream_wide": the PSA block's streaming kernels (Engine.set_attention_form)
-        if attention_f32 is not None and attention_f32 not in ATTENTION_F32:
-            raise ValueError(f"attention_f32={attention_f32!r}: one of {sorted(ATTENTION_F32)}")
-        self.attention_f32 = attention_f32  # "stream": fp32 engines' streaming attention kernel past 400 tokens (Engine.set_attention_f32); None: the engine's default
+        if attention_f32 is not None and attention_f32 not in ATTENTION_F32 and attention_f32 not in ATTENTION_F32_WIDE:
+            raise ValueError(f"attention_f32={attention_f32!r}: one of {sorted(ATTENTION_F32) + sorted(ATTENTION_F32_WIDE)}")
+        self.attention_f32 = attention_f32  # "stream" / "stream_wide": fp32 engines' streaming attention kernels past 400 tokens (Engine.set_attention_f32); None: the engine's default
         self.family = "v10"
         if self.ckpt_path.startswith("synthetic:"):
             spec = self.ckpt_path.split(":", 1)[1]              # "s", "s-seg" (YOLOv10) ; "v8n-seg", "11x-seg" (the app's families)
