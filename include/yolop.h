@@ -301,8 +301,8 @@ int yp_comm_destroy(yp_comm* c);
  * with a message that names the quantity and the largest value that fits (YP_ERR_ARG):
  *   anchors  (H/8 * W/8 + H/16 * W/16 + H/32 * W/32) <= YP_MAX_ANCHORS. Up to 12288 anchors the heads select inside one workgroup's LDS;
  *            beyond, chunks of 12288 anchors select in parallel and one workgroup per image merges the chunk winners (v10), or the
- *            candidates above `conf` are gathered into a global list first (NMS families; at most the 16384 best-scoring candidates of
- *            an image enter NMS, where ultralytics' max_nms is 30000).
+ *            candidates above `conf` are gathered into a global list first (NMS families; at most the max_nms best-scoring candidates of
+ *            an image enter NMS: 16384 by default, ultralytics' 30000 through yp_set_nms_options).
  *   attention tokens (H/32 * W/32, v10 and 11 only): above 400 the PSA block runs a generic kernel that keeps 16 x tokens scores in LDS,
  *            which ends at 2368 tokens for 32-wide keys. v8 has no attention. An engine whose attention form is `stream`
  *            (yp_set_attention_form) runs bf16 PSA blocks with 32-wide keys and 64-wide heads - every v10 variant except M, every YOLO11
@@ -349,6 +349,21 @@ int yp_profile(yp_engine* e, const uint8_t* in_dev, int B, int H, int W, float* 
  * them (defaults 0.25 / 0.7). Rows of yp_forward's det_out are the boxes NMS keeps, best first; may be changed between forwards
  * (the values live in device memory: a captured graph does not go stale). No effect on the v10 family. */
 int yp_set_nms(yp_engine* e, float conf, float iou);
+
+/* NMS heads (families v8 / 11): the other three arguments of `.predict` that steer `ops.non_max_suppression` [U] (multi_label=False):
+ *   classes   n_classes class ids in [0, nc): only candidates of these classes take part - filtered before NMS and before the max_nms
+ *             cut, as [U] does. NULL or n_classes == 0: all classes (the default).
+ *   agnostic  != 0: no per-class box offset, a kept box suppresses overlapping boxes of every class (`agnostic_nms=True`). Default 0.
+ *   max_nms   in [1, YP_MAX_ANCHORS]: the max_nms best candidates (score descending, lower anchor first among equal scores) enter NMS.
+ *             Default 16384; ultralytics' own value is 30000 - pass it to get [U]'s rows when more than 16384 anchors pass `conf`
+ *             (possible from 1024x800 on). Above 16384 the NMS kernel works through the sorted list in rounds of 16384 keys: exact
+ *             greedy NMS over the whole list.
+ * May be changed between forwards: the values live in device memory beside conf / iou. Any non-default value moves the head op to option
+ * kernels of its own (yp_op_kernel names them); that step - and the step back - drops a captured graph and costs the next forward one
+ * extra eager pass, a change among non-default values costs nothing. Host only (nothing is launched here).
+ * YP_ERR_ARG: a class id outside [0, nc), n_classes < 0, max_nms out of range, or a v10 engine (its head is a top-k without NMS: filter its
+ * rows on the host). */
+int yp_set_nms_options(yp_engine* e, const int32_t* classes, int n_classes, int agnostic, int max_nms);
 
 /* Attention form of the PSA block (v10 / 11): 0 auto - the default: the resident matrix-core kernel up to 400 tokens, the generic kernel up to
  * its LDS bound, refusal beyond -, 1 stream - bf16, key_dim 32, head_dim 64 above 400 tokens run attention_stream_kernel (two passes over K:

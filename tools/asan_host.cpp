@@ -72,6 +72,23 @@ int main() {
                 // back to the first shape: the per-shape memo path
                 CHECK(yp_plan(e, shapes[0][0], shapes[0][1], shapes[0][2]) > 0);
                 CHECK(yp_debug_host_selftest(e) > 0);
+                // NMS options: the class list becomes mask words on the host; refusals are loud; only v8 / 11 have an NMS to steer
+                {
+                    const int32_t cls[3] = {0, d.nc - 1, d.nc / 2}, outside[2] = {1, d.nc}, negative[1] = {-1};
+                    if (fam == YP_FAMILY_V10) {
+                        CHECK(yp_set_nms_options(e, cls, 3, 1, 30000) == YP_ERR_ARG && strstr(yp_last_error(), "v10"));
+                    } else {
+                        CHECK(yp_set_nms_options(nullptr, cls, 3, 1, 30000) == YP_ERR_ARG);
+                        CHECK(yp_set_nms_options(e, outside, 2, 0, 16384) == YP_ERR_ARG && strstr(yp_last_error(), "class id"));
+                        CHECK(yp_set_nms_options(e, negative, 1, 0, 16384) == YP_ERR_ARG);
+                        CHECK(yp_set_nms_options(e, cls, -1, 0, 16384) == YP_ERR_ARG);
+                        CHECK(yp_set_nms_options(e, nullptr, 0, 0, 0) == YP_ERR_ARG && strstr(yp_last_error(), "max_nms"));
+                        CHECK(yp_set_nms_options(e, nullptr, 0, 0, YP_MAX_ANCHORS + 1) == YP_ERR_ARG);
+                        CHECK(yp_set_nms_options(e, cls, 3, 1, YP_MAX_ANCHORS) == YP_OK);
+                        CHECK(yp_debug_host_selftest(e) > 0);
+                        CHECK(yp_set_nms_options(e, nullptr, 0, 0, 16384) == YP_OK);
+                    }
+                }
                 // beyond 12288 anchors: the heads' large forms plan; what no kernel holds is refused by yp_plan and leaves the plan as it was
                 CHECK(yp_plan(e, 1, 800, 768) > 0);
                 CHECK(yp_debug_host_selftest(e) > 0);

@@ -267,9 +267,16 @@ struct HeadBranchParams {
 };
 bool head_branch_valid(const HeadBranchParams& p);
 hipError_t launch_head_branch(const HeadBranchParams& p, hipStream_t st);
-hipError_t launch_head_nms(const HeadParams& p, hipStream_t st);
+// `options`: the forms that honour the class set, the agnostic flag and max_nms (yp_set_nms_options) - kernels of their own, so the
+// default forms keep their registers and LDS. They read the words behind [conf, iou] in the device block `nms_params`:
+constexpr int NMS_OPT_AGNOSTIC = 2, NMS_OPT_MAX_NMS = 3, NMS_OPT_USE_CLASSES = 4, NMS_OPT_MASK = 5;   // word indices (uint32)
+constexpr int NMS_MASK_WORDS = 32;                                                                    // class bit mask: nc <= 1024
+constexpr int NMS_PARAM_WORDS = NMS_OPT_MASK + NMS_MASK_WORDS;
+constexpr int NMS_DEFAULT_MAX_NMS = 16384;                                                             // head_nms_common.h NCAP
+hipError_t launch_head_nms(const HeadParams& p, hipStream_t st, bool options = false);
+const char* head_nms_kernel_name(int A, bool options);
 size_t head_nms_scratch_bytes(int B, int A);
-hipError_t launch_head_nms_large(const HeadParams& p, hipStream_t st);             // head_large.hip: A > HEAD_LDS_ANCHORS
+hipError_t launch_head_nms_large(const HeadParams& p, hipStream_t st, bool options = false);    // head_large.hip: A > HEAD_LDS_ANCHORS
 
 // Experiment switches (YOLOP_* environment variables). env_on: set and its first character is '1'; env_int: atoi of the value, dflt when
 // unset. A launcher keeps the result in a function-local static, so a switch is read once, at the first use of that function.

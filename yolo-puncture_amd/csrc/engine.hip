@@ -103,7 +103,12 @@ struct yp_engine {
     // NMS heads (families v8 / 11)
     const uint8_t* tune_input = nullptr;  // the caller's frames of the forward that triggered the tuner (producer ops that read them)
     float nms_conf = 0.25f, nms_iou = 0.7f;
-    float* d_nms = nullptr;               // device copy of [conf, iou]
+    float* d_nms = nullptr;               // device block [conf, iou | agnostic, max_nms, use_classes, class mask words] (common.h NMS_OPT_*)
+    // yp_set_nms_options: host copy of the words behind the pair. nms_options: they differ from the defaults, the head op launches its
+    // option kernels (head_nms_kernel_name)
+    unsigned nms_opt[NMS_PARAM_WORDS - 2] = {0u, (unsigned)NMS_DEFAULT_MAX_NMS};
+    bool nms_options = false;
+    bool nms_opt_dirty = false;
     bool nms_dirty = false;               // the host pair is newer than the device copy: the next forward rewrites it on its stream
     void* nms_ws = nullptr; size_t nms_ws_bytes = 0;
     int es() const { return dtype == DT_BF16 ? 2 : 4; }
@@ -1244,12 +1249,13 @@ static int make_plan(yp_engine& e, int B, int H, int W) {
             if (!try_form(o, FORM_SCDOWN)) o.kernel = dwconv_kernel_name(dw_params(e, o), e.dtype);
         } else if (o.kind == OP_STEM) o.kernel = stem_kernel_name(stem_params(e, o, nullptr), e.dtype);
         else if (o.kind == OP_POOL3 && e.dtype == DT_BF16 && (o.in.C & 31) == 0) o.kernel = "sppf_pool3_bf16_kernel";
-        else if (o.kind == OP_HEAD && A > (size_t)HEAD_LDS_ANCHORS) o.kernel = o.nms ? "head_nms_gather_kernel + head_nms_large_kernel" : head_large_kernel_name(0);
+        else if (o.kind == OP_HEAD && o.nms) o.kernel = head_nms_kernel_name((int)A, e.nms_options);
+        else if (o.kind == OP_HEAD && A > (size_t)HEAD_LDS_ANCHORS) o.kernel = head_large_kernel_name(0);
         else if (o.kind == OP_ATTN && attention_takes_stream_f32(attn_params(e, o, B), e.dtype, e.attn_f32_stream)) o.kernel = "attention_stream_f32_kernel";
         else if (o.kind == OP_ATTN && attention_takes_stream_wide_f32(attn_params(e, o, B), e.dtype, e.attn_f32_stream)) o.kernel = "attention_stream_wide_f32_kernel";
         else if (o.kind == OP_ATTN && attention_takes_stream(attn_params(e, o, B), e.dtype, e.attn_form)) o.kernel = "attention_stream_kernel";
         else if (o.kind == OP_ATTN && attention_takes_stream_wide(attn_params(e, o, B), e.dtype, e.attn_form)) o.kernel = "attention_stream_wide_kernel";
-        else o.kernel = (o.kind == OP_HEAD && o.nms) ? "head_nms_kernel" : kn[o.kind];
+        else o.kernel = kn[o.kind];
     }
     // winners-only head (v10 top-k head, bf16): the box / coefficient branches run on the stage-1 winners inside the head op; their dense
     // convolutions stay in the op list (yp_run_op steps them, the fp32 parity mode and YOLOP_DENSE_HEAD=1 run them) but launch nothing here
@@ -1409,9 +1415,11 @@ static int allocate_plan(yp_engine& e) {
             e.nms_ws_bytes = need;
         }
         if (!e.d_nms) {
-            HIPCHK(hipMalloc((void**)&e.d_nms, 2 * sizeof(float)));
+            HIPCHK(hipMalloc((void**)&e.d_nms, NMS_PARAM_WORDS * sizeof(float)));
             const float v[2] = {e.nms_conf, e.nms_iou};
             HIPCHK(hipMemcpy(e.d_nms, v, sizeof(v), hipMemcpyHostToDevice));
+            HIPCHK(hipMemcpy(e.d_nms + 2, e.nms_opt, sizeof(e.nms_opt), hipMemcpyHostToDevice));
+            e.nms_opt_dirty = false;
         }
     }
     if ((size_t)e.pB > e.o_cap) {
@@ -1512,7 +1520,7 @@ static hipError_t run_op(yp_engine& e, const Op& o, const RunArgs& a, hipStream_
             p.B = B; p.nc = e.desc.nc; p.max_det = e.desc.max_det;
             p.det = a.det; p.idx = a.idx; p.coeff = (o.cf[0].t >= 0) ? a.coeff : nullptr; p.scratch = e.head_ws;
             for (int l = 0; l < 3; ++l) p.mk[l] = (o.amax[l].t >= 0) ? (const unsigned*)T(o.amax[l]).ptr : nullptr;
-            if (o.nms) { p.nms_params = e.d_nms; p.nms_ws = (float*)e.nms_ws; return launch_head_nms(p, st); }
+            if (o.nms) { p.nms_params = e.d_nms; p.nms_ws = (float*)e.nms_ws; return launch_head_nms(p, st, e.nms_options); }
             if (o.sparse_box || o.sparse_cf) {
                 // winners-only head: stage 1 -> the branch(es) on the winners -> stage 2 + decode. A branch that stays dense (an unsupported
                 // width) is read from its dense map as before.
@@ -2281,6 +2289,15 @@ int yp_tensor_read(yp_engine* e, int i, float* host_out) {
     return YP_OK;
 }
 
+// the NMS head's kernel is the engine's option state's decision (yp_set_nms_options), not the plan's or the tuning memo's
+static void name_nms_head(yp_engine& e) {
+    if (!e.planned) return;
+    int A = 0;
+    for (int l = 0; l < 3; ++l) A += (e.pH / (8 << l)) * (e.pW / (8 << l));
+    for (Op& o : e.ops)
+        if (o.kind == OP_HEAD && o.nms) o.kernel = head_nms_kernel_name(A, e.nms_options);
+}
+
 static void remember_tuning(yp_engine& e) {
     std::vector<yp_engine::Tuned> v;
     v.reserve(e.ops.size());
@@ -2296,6 +2313,7 @@ static bool recall_tuning(yp_engine& e) {
         e.ops[i].cfg = it->second[i].cfg;
         if (e.ops[i].kind != OP_ATTN) e.ops[i].kernel = it->second[i].kernel;
     }
+    name_nms_head(e);
     return true;
 }
 
@@ -2346,11 +2364,24 @@ static int prepare(yp_engine* e, int B, int H, int W, const uint8_t* in, float* 
 }
 
 __global__ void set_pair_kernel(float* dst, float a, float b) { dst[0] = a; dst[1] = b; }
+struct NmsOptWords { unsigned w[NMS_PARAM_WORDS - 2]; };
+__global__ void set_nms_opt_kernel(unsigned* dst, const NmsOptWords v) {
+    if (threadIdx.x < NMS_PARAM_WORDS - 2) dst[threadIdx.x] = v.w[threadIdx.x];
+}
 static int push_nms_params(yp_engine* e, hipStream_t st) {
-    if (!e->nms_dirty || !e->d_nms) return YP_OK;
-    hipLaunchKernelGGL(set_pair_kernel, dim3(1), dim3(1), 0, st, e->d_nms, e->nms_conf, e->nms_iou);
-    HIPCHK(hipGetLastError());
-    e->nms_dirty = false;
+    if (!e->d_nms) return YP_OK;
+    if (e->nms_dirty) {
+        hipLaunchKernelGGL(set_pair_kernel, dim3(1), dim3(1), 0, st, e->d_nms, e->nms_conf, e->nms_iou);
+        HIPCHK(hipGetLastError());
+        e->nms_dirty = false;
+    }
+    if (e->nms_opt_dirty) {
+        NmsOptWords v;
+        memcpy(v.w, e->nms_opt, sizeof(v.w));
+        hipLaunchKernelGGL(set_nms_opt_kernel, dim3(1), dim3(64), 0, st, (unsigned*)(e->d_nms + 2), v);
+        HIPCHK(hipGetLastError());
+        e->nms_opt_dirty = false;
+    }
     return YP_OK;
 }
 
@@ -2876,6 +2907,52 @@ int yp_set_nms(yp_engine* e, float conf, float iou) {
     // (yolo_seg/app.py:91, yolo_seg/yolo_with_deva.py:51) used to pay a device sync + blocking copy per call.
     e->nms_conf = conf; e->nms_iou = iou;
     e->nms_dirty = true;
+    return YP_OK;
+}
+
+// class ids -> the words behind [conf, iou] of the device block; false on an id outside [0, nc) (*bad names it). Host only.
+static bool nms_option_words(const int32_t* classes, int n_classes, int nc, int agnostic, int max_nms, unsigned* w, int* bad) {
+    for (int i = 0; i < NMS_PARAM_WORDS - 2; ++i) w[i] = 0u;
+    w[NMS_OPT_AGNOSTIC - 2] = agnostic ? 1u : 0u;
+    w[NMS_OPT_MAX_NMS - 2] = (unsigned)max_nms;
+    const bool use = classes && n_classes > 0;
+    w[NMS_OPT_USE_CLASSES - 2] = use ? 1u : 0u;
+    for (int i = 0; use && i < n_classes; ++i) {
+        const int c = classes[i];
+        if (c < 0 || c >= nc || c >= NMS_MASK_WORDS * 32) { if (bad) *bad = c; return false; }
+        w[NMS_OPT_MASK - 2 + (c >> 5)] |= 1u << (c & 31);
+    }
+    return true;
+}
+
+int yp_set_nms_options(yp_engine* e, const int32_t* classes, int n_classes, int agnostic, int max_nms) {
+    if (!e) return fail(YP_ERR_ARG, "null engine");
+    if (e->desc.family == YP_FAMILY_V10) return fail(YP_ERR_ARG, "yp_set_nms_options: the v10 family has no NMS (its head is a top-k): filter the rows on the host");
+    if (n_classes < 0) return fail(YP_ERR_ARG, "yp_set_nms_options: n_classes = %d", n_classes);
+    if (max_nms < 1 || max_nms > YP_MAX_ANCHORS) return fail(YP_ERR_ARG, "yp_set_nms_options: max_nms = %d, must lie in [1, %d]", max_nms, YP_MAX_ANCHORS);
+    if (classes && n_classes > 0 && e->desc.nc > NMS_MASK_WORDS * 32) return fail(YP_ERR_ARG, "yp_set_nms_options: a class set covers at most %d classes, the model has %d", NMS_MASK_WORDS * 32, e->desc.nc);
+    unsigned w[NMS_PARAM_WORDS - 2];
+    int bad = 0;
+    if (!nms_option_words(classes, n_classes, e->desc.nc, agnostic, max_nms, w, &bad)) return fail(YP_ERR_ARG, "yp_set_nms_options: class id %d outside [0, %d)", bad, e->desc.nc);
+    if (memcmp(w, e->nms_opt, sizeof(w)) == 0) return YP_OK;
+    // The words live in device memory like the pair of yp_set_nms and reach it the same way (push_nms_params): a captured graph of the
+    // option kernels reads them through a pointer. Only the step between the default kernels and the option kernels changes what is
+    // launched: the captured executable goes (after the last forward has drained, as in yp_set_graph) and the next forward runs one
+    // eager pass first, because a kernel's first launch may not happen inside a capture (prepare).
+    const bool options = w[NMS_OPT_AGNOSTIC - 2] != 0u || w[NMS_OPT_USE_CLASSES - 2] != 0u || w[NMS_OPT_MAX_NMS - 2] != (unsigned)NMS_DEFAULT_MAX_NMS;
+    if (options != e->nms_options) {
+        if (e->gexec) {
+            HIPCHK(hipSetDevice(e->device));
+            if (e->have_last) HIPCHK(hipEventSynchronize(e->ev_done));
+            drop_graph(*e);
+        }
+        e->nms_options = options;
+        e->warmed = false;
+        e->auto_replay.clear();
+        name_nms_head(*e);
+    }
+    memcpy(e->nms_opt, w, sizeof(w));
+    e->nms_opt_dirty = true;
     return YP_OK;
 }
 

@@ -19,6 +19,7 @@
 #define HEAD_CLK7_ROUND(n) do { } while (0)
 #include "head_select.h"
 #include "head_nms_common.h"
+#include "head_nms_opt.h"
 
 namespace yp {
 
@@ -159,8 +160,65 @@ __global__ __launch_bounds__(NT) void head_nms_large_kernel(const HeadParams p, 
     nms_sort_sweep_rows(p, keys, n, s_dead, s_kept, locate, iou_thr);
 }
 
+// The two kernels under yp_set_nms_options. The gather leaves out the classes outside the set; the NMS kernel walks the max_nms best keys of
+// the list in rounds of NCAP: round r takes the keys of rank [r * NCAP, min((r + 1) * NCAP, max_nms, nall)) - below the threshold the round
+// before ended on, down to the exact radix threshold of its last rank (keys are unique: exactly r1 keys reach the r1-th largest). Still one
+// workgroup per image, no read-back, no data-dependent launch dimension.
+__global__ __launch_bounds__(256) void head_nms_gather_opt_kernel(const HeadParams p, unsigned long long* __restrict__ glist, unsigned* __restrict__ gcount) {
+    const NmsLocate locate{p.hw[0][0] * p.hw[0][1], p.hw[1][0] * p.hw[1][1], p.hw[2][0] * p.hw[2][1]};
+    const int b = blockIdx.y, a = blockIdx.x * 256 + threadIdx.x;
+    const unsigned conf_bits = __float_as_uint(fmaxf(p.nms_params[0], 0.f));
+    const unsigned* opt = (const unsigned*)p.nms_params;
+    unsigned sb = 0u;
+    if (a < p.A) {
+        int l, loc, HWl;
+        locate(a, l, loc, HWl);
+        sb = p.mk[l][(size_t)b * HWl + loc];
+    }
+    // (the class slot of the scratch is written for the anchors above conf only: read it behind that test)
+    const bool have = a < p.A && sb > conf_bits && nms_class_in_set(opt, p.nms_ws[((size_t)b * p.A + a) * 8 + 4]);
+    const unsigned pos = wave_append(have, gcount + b);
+    if (have) glist[(size_t)b * p.A + pos] = ((unsigned long long)sb << 32) | (unsigned long long)(0xFFFFFFFFu - (unsigned)a);
+}
+
+__global__ __launch_bounds__(NT) void head_nms_large_opt_kernel(const HeadParams p, const unsigned long long* __restrict__ glist, const unsigned* __restrict__ gcount) {
+    extern __shared__ __attribute__((aligned(16))) unsigned long long keys[];     // [NCAP]
+    __shared__ SelectShared S;
+    __shared__ unsigned s_n;
+    __shared__ unsigned s_dead[NCAP / 32];
+    __shared__ int s_kept[NMAXK];
+    __shared__ float s_kbox[NMAXK][5];                                            // boxes and classes of the rows kept so far
+    const int b = blockIdx.x, tid = threadIdx.x;
+    const NmsLocate locate{p.hw[0][0] * p.hw[0][1], p.hw[1][0] * p.hw[1][1], p.hw[2][0] * p.hw[2][1]};
+    const float iou_thr = p.nms_params[1];
+    const unsigned* opt = (const unsigned*)p.nms_params;
+    const bool agnostic = opt[NMS_OPT_AGNOSTIC] != 0u;
+    const unsigned long long* list = glist + (size_t)b * p.A;
+    const int nall = (int)min(gcount[b], (unsigned)p.A);
+    const int nuse = min(nall, (int)opt[NMS_OPT_MAX_NMS]);
+    const int kmax = min(p.max_det, NMAXK);
+    int nk = 0;
+    unsigned long long hi = 0ull;                                 // the threshold the previous round ended on: this round's keys lie below it
+    for (int r0 = 0; r0 < nuse && nk < kmax; r0 += NCAP) {
+        const int r1 = min(r0 + NCAP, nuse);
+        const unsigned long long lo = r1 < nall ? radix_kth(list, nall, r1, S, (unsigned)p.A) : 0ull;
+        if (tid == 0) s_n = 0;
+        __syncthreads();
+        for (int i = tid; i < nall; i += NT) {
+            const unsigned long long key = list[i];
+            const bool have = key >= lo && (r0 == 0 || key < hi);
+            const unsigned pos = wave_append(have, &s_n);
+            if (have && pos < (unsigned)NCAP) keys[pos] = key;
+        }
+        __syncthreads();
+        nk = nms_opt_round(p, keys, r1 - r0, r1 - r0, s_dead, s_kept, s_kbox, nk, locate, iou_thr, agnostic);
+        hi = lo;
+    }
+    nms_opt_empty_rows(p, nk);
+}
+
 // (called by launch_head_nms behind head_nms_decode_kernel)
-hipError_t launch_head_nms_large(const HeadParams& p, hipStream_t st) {
+hipError_t launch_head_nms_large(const HeadParams& p, hipStream_t st, bool options) {
     if (p.A <= HEAD_LDS_ANCHORS || p.A > HEAD_MAX_ANCHORS || p.max_det > NMAXK || !p.mk[0] || !p.nms_params || !p.nms_ws) return hipErrorInvalidValue;
     const size_t sh = (size_t)NCAP * 8;
     static size_t granted = 0;
@@ -169,6 +227,13 @@ hipError_t launch_head_nms_large(const HeadParams& p, hipStream_t st) {
     unsigned long long* glist = (unsigned long long*)(p.nms_ws + (size_t)p.B * p.A * 8);
     unsigned* gcount = (unsigned*)(glist + (size_t)p.B * p.A);
     if (hipError_t e = hipMemsetAsync(gcount, 0, (size_t)p.B * sizeof(unsigned), st)) return e;
+    if (options) {
+        static size_t granted_opt = 0;
+        if (hipError_t e = allow_dynamic_lds((const void*)head_nms_large_opt_kernel, sh, granted_opt)) return e;
+        hipLaunchKernelGGL(head_nms_gather_opt_kernel, dim3((unsigned)((p.A + 255) / 256), (unsigned)p.B), dim3(256), 0, st, p, glist, gcount);
+        hipLaunchKernelGGL(head_nms_large_opt_kernel, dim3(p.B), dim3(NT), sh, st, p, (const unsigned long long*)glist, (const unsigned*)gcount);
+        return hipGetLastError();
+    }
     hipLaunchKernelGGL(head_nms_gather_kernel, dim3((unsigned)((p.A + 255) / 256), (unsigned)p.B), dim3(256), 0, st, p, glist, gcount);
     hipLaunchKernelGGL(head_nms_large_kernel, dim3(p.B), dim3(NT), sh, st, p, (const unsigned long long*)glist, (const unsigned*)gcount);
     return hipGetLastError();

@@ -11,6 +11,7 @@
 #include "common.h"
 
 #include "head_nms_common.h"
+#include "head_nms_opt.h"
 
 namespace yp {
 
@@ -99,6 +100,46 @@ __global__ __launch_bounds__(NT) void head_nms_kernel(const HeadParams p) {
     nms_sort_sweep_rows(p, keys, (int)s_n, s_dead, s_kept, locate, iou_thr);
 }
 
+// Kernel B under yp_set_nms_options: candidates of the class set only (the class is in the scratch head_nms_decode_kernel filled), at most
+// max_nms of them behind the sort, agnostic or class-offset sweep. A kernel of its own: head_nms_kernel keeps its registers.
+__global__ __launch_bounds__(NT) void head_nms_opt_kernel(const HeadParams p) {
+    extern __shared__ __attribute__((aligned(16))) unsigned long long keys[];     // [NCAP]
+    __shared__ unsigned s_n;
+    __shared__ unsigned s_dead[NCAP / 32];
+    __shared__ int s_kept[NMAXK];
+    const int b = blockIdx.x, tid = threadIdx.x;
+    const NmsLocate locate{p.hw[0][0] * p.hw[0][1], p.hw[1][0] * p.hw[1][1], p.hw[2][0] * p.hw[2][1]};
+    const float conf = p.nms_params[0], iou_thr = p.nms_params[1];
+    const unsigned* opt = (const unsigned*)p.nms_params;
+    const bool agnostic = opt[NMS_OPT_AGNOSTIC] != 0u;
+    const int max_nms = (int)opt[NMS_OPT_MAX_NMS];
+    const unsigned conf_bits = __float_as_uint(fmaxf(conf, 0.f));
+    if (tid == 0) s_n = 0;
+    __syncthreads();
+    {
+        const float* wsa = p.nms_ws + (size_t)b * p.A * 8;
+        int off = 0;
+        for (int l = 0; l < 3; ++l) {
+            const int HWl = p.hw[l][0] * p.hw[l][1];
+            const unsigned* src = p.mk[l] + (size_t)b * HWl;
+            for (int a = tid; a < HWl; a += NT) {
+                const unsigned sb = src[a];
+                if (sb > conf_bits && nms_class_in_set(opt, wsa[(size_t)(off + a) * 8 + 4]))
+                    keys[atomicAdd(&s_n, 1u)] = ((unsigned long long)sb << 32) | (unsigned long long)(0xFFFFFFFFu - (unsigned)(off + a));
+            }
+            off += HWl;
+        }
+    }
+    __syncthreads();
+    const int n = (int)s_n;
+    const int nk = nms_opt_round(p, keys, n, min(n, max_nms), s_dead, s_kept, nullptr, 0, locate, iou_thr, agnostic);
+    nms_opt_empty_rows(p, nk);
+}
+
+const char* head_nms_kernel_name(int A, bool options) {
+    if (A > HEAD_LDS_ANCHORS) return options ? "head_nms_gather_opt_kernel + head_nms_large_opt_kernel" : "head_nms_gather_kernel + head_nms_large_kernel";
+    return options ? "head_nms_opt_kernel" : "head_nms_kernel";
+}
 
 // beyond HEAD_LDS_ANCHORS anchors (head_large.hip) the per-image candidate key lists [B][A] and their counters [B] follow the boxes
 size_t head_nms_scratch_bytes(int B, int A) {
@@ -106,14 +147,20 @@ size_t head_nms_scratch_bytes(int B, int A) {
     return A <= HEAD_LDS_ANCHORS ? boxes : boxes + (size_t)B * A * sizeof(unsigned long long) + (((size_t)B * sizeof(unsigned) + 255) & ~(size_t)255);
 }
 
-hipError_t launch_head_nms(const HeadParams& p, hipStream_t st) {
+hipError_t launch_head_nms(const HeadParams& p, hipStream_t st, bool options) {
     if (p.A > HEAD_MAX_ANCHORS || p.max_det > NMAXK || !p.mk[0] || !p.nms_params || !p.nms_ws) return hipErrorInvalidValue;
     const size_t sh = (size_t)NCAP * 8;
     static size_t granted = 0;
     if (hipError_t e = allow_dynamic_lds((const void*)head_nms_kernel, sh, granted)) return e;
     const long items = (long)p.B * p.A;
     hipLaunchKernelGGL(head_nms_decode_kernel, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, st, p);
-    if (p.A > HEAD_LDS_ANCHORS) return launch_head_nms_large(p, st);      // (the LDS gather below has no room for them)
+    if (p.A > HEAD_LDS_ANCHORS) return launch_head_nms_large(p, st, options);      // (the LDS gather below has no room for them)
+    if (options) {
+        static size_t granted_opt = 0;
+        if (hipError_t e = allow_dynamic_lds((const void*)head_nms_opt_kernel, sh, granted_opt)) return e;
+        hipLaunchKernelGGL(head_nms_opt_kernel, dim3(p.B), dim3(NT), sh, st, p);
+        return hipGetLastError();
+    }
     hipLaunchKernelGGL(head_nms_kernel, dim3(p.B), dim3(NT), sh, st, p);
     return hipGetLastError();
 }

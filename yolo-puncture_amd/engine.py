@@ -98,6 +98,8 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     lib.yp_set_autotune.argtypes = [vp, C.c_int]
     lib.yp_set_nms.argtypes = [vp, C.c_float, C.c_float]
     lib.yp_set_nms.restype = C.c_int
+    lib.yp_set_nms_options.argtypes = [vp, C.POINTER(C.c_int32), C.c_int, C.c_int, C.c_int]
+    lib.yp_set_nms_options.restype = C.c_int
     lib.yp_debug_host_selftest.argtypes = [vp]
     lib.yp_debug_host_selftest.restype = C.c_int
     lib.yp_tuning_source.argtypes = [vp]
@@ -153,7 +155,7 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
 EXPORTS = ["yp_last_error", "yp_create", "yp_destroy", "yp_weight_count", "yp_weight_info", "yp_set_weight",
            "yp_finalize", "yp_forward", "yp_proto", "yp_masks", "yp_id_mask_resized", "yp_plan", "yp_op_info", "yp_op_output", "yp_op_input", "yp_op_fusion",
            "yp_tensor_count", "yp_tensor_info", "yp_tensor_read", "yp_profile", "yp_set_graph", "yp_run_op",
-           "yp_tensor_write", "yp_op_kernel", "yp_set_autotune", "yp_tuning_export", "yp_tuning_import", "yp_set_nms", "yp_debug_force_conv_cfg", "yp_debug_op_cfg", "yp_debug_op_form", "yp_debug_last_store_form", "yp_debug_max_workgroups", "yp_debug_conv_families", "yp_debug_ablation", "yp_debug_head_clocks", "yp_debug_head_branch_clocks", "yp_debug_head_winners", "yp_debug_contour_clocks", "yp_debug_pwsp_clocks", "yp_debug_host_selftest", "yp_debug_graph_info", "yp_tuning_source", "yp_debug_head_positions", "yp_debug_marker", "yp_max_batch", "yp_debug_topk_anchors", "yp_debug_attention", "yp_debug_attention_form", "yp_debug_attention_f32", "yp_debug_conv_s2", "yp_set_attention_form", "yp_set_attention_f32_stream", "yp_letterbox", "yp_letterbox_batch", "yp_masks_frames", "yp_masks_frames_input", "yp_id_masks_frames", "yp_id_masks_frames_workspace", "yp_mask_contours",
+           "yp_tensor_write", "yp_op_kernel", "yp_set_autotune", "yp_tuning_export", "yp_tuning_import", "yp_set_nms", "yp_set_nms_options", "yp_debug_force_conv_cfg", "yp_debug_op_cfg", "yp_debug_op_form", "yp_debug_last_store_form", "yp_debug_max_workgroups", "yp_debug_conv_families", "yp_debug_ablation", "yp_debug_head_clocks", "yp_debug_head_branch_clocks", "yp_debug_head_winners", "yp_debug_contour_clocks", "yp_debug_pwsp_clocks", "yp_debug_host_selftest", "yp_debug_graph_info", "yp_tuning_source", "yp_debug_head_positions", "yp_debug_marker", "yp_max_batch", "yp_debug_topk_anchors", "yp_debug_attention", "yp_debug_attention_form", "yp_debug_attention_f32", "yp_debug_conv_s2", "yp_set_attention_form", "yp_set_attention_f32_stream", "yp_letterbox", "yp_letterbox_batch", "yp_masks_frames", "yp_masks_frames_input", "yp_id_masks_frames", "yp_id_masks_frames_workspace", "yp_mask_contours",
            "yp_mask_contours_scaled", "yp_mask_contours_large_workspace", "yp_mask_contours_large", "yp_comm_unique_id", "yp_comm_create", "yp_allgather", "yp_comm_destroy",
            "yp_u2net_create", "yp_u2net_destroy", "yp_u2net_weight_count", "yp_u2net_weight_info", "yp_u2net_set_weight", "yp_u2net_finalize",
            "yp_u2net_forward", "yp_u2net_forward_crops", "yp_u2net_set_graph", "yp_u2net_tensor_count", "yp_u2net_tensor_info", "yp_u2net_tensor_read",
@@ -575,6 +577,19 @@ class Engine:
     def set_nms(self, conf: float = 0.25, iou: float = 0.7) -> None:
         """families v8 / 11: thresholds of the NMS inside the forward (`.predict(conf=, iou=)`)."""
         self._chk(self.lib.yp_set_nms(self._h, float(conf), float(iou)))
+
+    def set_nms_options(self, classes=None, agnostic: bool = False, max_nms: int = 16384) -> None:
+        """families v8 / 11: `.predict(classes=, agnostic_nms=, max_nms=)` of the NMS inside the forward. `classes`: None (all), an int or
+        a sequence of class ids; they are filtered before NMS and before the max_nms cut. `max_nms=30000` is ultralytics' value (the
+        default keeps this engine's 16384). A v10 engine refuses (it has no NMS)."""
+        if classes is None:
+            ids = []
+        elif isinstance(classes, (int, np.integer)):
+            ids = [int(classes)]
+        else:
+            ids = [int(c) for c in classes]
+        buf = (C.c_int32 * len(ids))(*ids) if ids else None
+        self._chk(self.lib.yp_set_nms_options(self._h, buf, len(ids), int(bool(agnostic)), int(max_nms)))
 
     def set_graph(self, enable) -> None:
         """False / 0: eager launches; True / 1: hipGraph replay with head lanes; 2: replay without lanes; "auto" / 3: per input shape

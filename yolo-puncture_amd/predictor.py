@@ -453,19 +453,49 @@ class YOLO:
         return eng
 
     # -- predict ---------------------------------------------------------------------------------------------------
+    def _class_ids(self, classes) -> Optional[List[int]]:
+        """predict(classes=): None, an int or a sequence of ints -> None or a list of class ids, checked against the model's classes"""
+        if classes is None:
+            return None
+        seq = [classes] if isinstance(classes, (int, np.integer)) else list(classes)
+        nc = self.nc
+        ids = []
+        for c in seq:
+            if isinstance(c, bool) or not isinstance(c, (int, np.integer)):
+                raise TypeError(f"classes must be an int or a sequence of ints (got {c!r})")
+            if not 0 <= int(c) < nc:
+                raise ValueError(f"classes: {int(c)} is not a class of this model (it has {nc}: 0..{nc - 1})")
+            ids.append(int(c))
+        return ids or None                                            # (ultralytics treats an empty list as no filter)
+
+    @staticmethod
+    def _max_nms(max_nms) -> int:
+        if max_nms is None:
+            return 16384
+        if isinstance(max_nms, bool) or not isinstance(max_nms, (int, np.integer)) or int(max_nms) < 1:
+            raise ValueError(f"max_nms must be a positive int (got {max_nms!r}); ultralytics' value is 30000")
+        return int(max_nms)
+
     def __call__(self, source=None, **kw):
         return self.predict(source, **kw)
 
     def predict(self, source=None, conf: float = 0.25, retina_masks: bool = False, device=None, imgsz: int = 640,
-                max_det: int = 300, stream: bool = False, verbose: bool = False, iou: float = 0.7, **ignored) -> List[Results]:
+                max_det: int = 300, stream: bool = False, verbose: bool = False, iou: float = 0.7, classes=None,
+                agnostic_nms: bool = False, max_nms: Optional[int] = None, **ignored) -> List[Results]:
+        """classes / agnostic_nms / max_nms: ultralytics' arguments of the same names. v8 / 11: they steer the NMS inside the forward
+        (Engine.set_nms_options; max_nms None keeps this engine's 16384, 30000 is ultralytics' value). v10 has no NMS: `classes` filters
+        the rows that pass `conf` on the host, before masks are made (ultralytics' end-to-end branch); the other two have no effect."""
         if source is None:
             raise ValueError("predict() needs a source (ndarray BGR HWC uint8, PIL.Image, path or a list of them)")
+        class_ids = self._class_ids(classes)
         if device is not None:
             self._set_device(device)
         imgs, paths = hostops.load_sources(source)                    # list of BGR uint8 HWC (ndarray => taken as BGR)
         eng = self._engine()
         if self.family != "v10":
             eng.set_nms(conf, iou)                                    # v8 / 11: conf filter + NMS run inside the forward
+            eng.set_nms_options(class_ids, agnostic_nms, self._max_nms(max_nms))
+        wanted = torch.tensor(class_ids, dtype=torch.float32) if (self.family == "v10" and class_ids is not None) else None
         dev = torch.device("cuda", self._dev_index)
         results: List[Results] = []
         # frames that letterbox to the same shape run as one batch
@@ -510,6 +540,8 @@ class YOLO:
                 oh, ow = imgs[i].shape[:2]
                 dh = det_host[bi]
                 keep = dh[:, 4] > conf                                  # strict, A.6 step 2
+                if wanted is not None:                                  # v10: the class set acts on the rows above conf
+                    keep &= torch.isin(dh[:, 5], wanted)
                 n = int(keep.sum())
                 prefix = bool(keep[:n].all())
                 d = (dh[:n] if prefix else dh[keep])[:max_det].clone()
@@ -530,7 +562,7 @@ class YOLO:
         return results
 
     def predict_clip(self, frames, conf: float = 0.25, iou: float = 0.7, imgsz: int = 640, batch_size: int = 32, device=None,
-                     retina_masks: bool = True) -> ClipResults:
+                     retina_masks: bool = True, classes=None, agnostic_nms: bool = False, max_nms: Optional[int] = None) -> ClipResults:
         """The app's first video loop (yolo_seg/app.py:85-113: predict(frame, conf, retina_masks=True) -> best row -> masks.xy[best] ->
         get_coord_min_rect_len, with the carry-forward of the last box and length) for a whole clip of same-shape frames.
         retina_masks=False: the same loop as the speed-evaluation script runs it (dev_tools/auto_speed_calc.py:56-84: predict(frame, conf)
@@ -545,6 +577,10 @@ class YOLO:
         4K masks, many blobs - goes through the large path in one further call, host trace where that declines too). -> ClipResults: `boxes, coords, lens = model.predict_clip(frames)`."""
         if not self.seg:
             raise ValueError("predict_clip needs a segmentation checkpoint (-seg): the app reads masks.xy of the best row")
+        class_ids = self._class_ids(classes)
+        if self.family == "v10" and class_ids is not None:
+            raise ValueError("predict_clip(classes=) needs a v8 / 11 checkpoint: the v10 head picks each frame's best row on the device, before "
+                             "a class set could act (use predict(classes=) per frame)")
         if int(batch_size) < 1:
             raise ValueError(f"batch_size must be >= 1 (got {batch_size})")
         retina = bool(retina_masks)
@@ -580,6 +616,7 @@ class YOLO:
         B, chunks = hostops.clip_plan(N, min(int(batch_size), eng.max_batch(Hl, Wl)))      # (no chunk larger than the engine plans at this shape)
         if self.family != "v10":
             eng.set_nms(conf, iou)
+            eng.set_nms_options(class_ids, agnostic_nms, self._max_nms(max_nms))
         mode = os.environ.get("YOLOP_PREDICT_GRAPH", "auto")
         bcache = self.__dict__.setdefault("_batch_cache", {})          # the buffer predict() uses for this shape: one hipGraph per shape
         batch = bcache.get((self._dev_index, B, Hl, Wl))
@@ -668,6 +705,7 @@ class YOLO:
         letterbox_device(raw, geo, out=batch[0])
         if self.family != "v10":
             eng.set_nms(conf, 0.7)
+            eng.set_nms_options()                                     # (fixed arguments: whatever a predict(classes=...) left on the engine goes)
         mode = os.environ.get("YOLOP_PREDICT_GRAPH", "auto")             # (explicit: not whatever the last predict() left; one frame resolves to eager)
         eng.set_graph("auto" if mode == "auto" else int(mode))
         out = eng.forward(batch)
@@ -724,6 +762,7 @@ class YOLO:
         B, chunks = hostops.clip_plan(N, min(int(batch_size), eng.max_batch(Hl, Wl)))
         if self.family != "v10":
             eng.set_nms(conf, 0.7)
+            eng.set_nms_options()                                     # (fixed arguments: whatever a predict(classes=...) left on the engine goes)
         mode = os.environ.get("YOLOP_PREDICT_GRAPH", "auto")
 
         def buffer(name, shape):
