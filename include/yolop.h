@@ -207,6 +207,36 @@ int yp_mask_contours_large(const uint8_t* masks_dev, int n, int H, int W, int st
                            int32_t* parts_out, int parts_cap, double* rect_out, int H0, int W0, int flags, void* workspace_dev,
                            size_t workspace_bytes, void* stream);
 
+/* The "all_merged" polygon order on the device: masks2segments of the later 8.3.x releases joins a mask's contours with
+ * merge_multi_segment (hostops.merge_contours is the definition) instead of laying them end to end. Runs on the buffers the three contour
+ * calls above fill with YP_CONTOURS_ALL - same stream, nothing read back in between - and writes the bridged list to a second buffer:
+ * consecutive contours of the list are bridged at their closest pair of points (first minimum of the squared integer distance in row-major
+ * order of the (index in c_{i-1}, index in c_i) table), a middle contour whose entry index is greater than its exit index is reversed with
+ * the indices swapped, every contour is rolled to its entry point and closed by repeating it; the first and the last contour are listed
+ * whole, a middle one from entry to exit on the way out and the rest on the way back, the way-back pieces in reverse contour order. A list
+ * of k > 1 contours with m points has m + 2k - 2 points afterwards; one contour is copied unchanged (not closed).
+ *    pts_dev, count_dev, parts_dev   what a contour call wrote: int32 [n,max_pts,2], [n], [n,parts_cap]; pts_dev 8-byte aligned;
+ *               coordinates below 4096; max_pts <= YP_CONTOURS_MERGE_MAX_PTS; 2 <= parts_cap <= YP_CONTOURS_LARGE_MAX_STARTS + 1
+ *    merged_out int32 [n,out_cap,2], 8-byte aligned, no overlap with the inputs      merged_count_out int32 [n]: points of the bridged list;
+ *               count_dev[i] <= 0 (empty, or declined by the trace) is passed on as it is; -1 = the bridged list has more than out_cap
+ *               points, the parts row does not list every contour (parts_cap too small) or its lengths do not add up to the count: nothing
+ *               of that mask's rows is written, the other masks of the call are not affected (bridge it on the host from pts_dev)
+ *    workspace_dev  as for the large path: at least the query's bytes for (n, parts_cap), 16-byte aligned, the caller's, free to reuse
+ *               once the stream's work is done. The query returns 0 for sizes the call rejects. n <= 65535.
+ * The closest pairs are searched in tiles of YP_CONTOURS_MERGE_TILE points a side; the per-mask scans step through the contours
+ * YP_CONTOURS_MERGE_SCAN_BLOCK at a time. The tiles query is host arithmetic: the number of work tiles the device derives for one mask
+ * whose contours have these lengths (0 for fewer than two contours or a length outside 1 .. YP_CONTOURS_MERGE_MAX_PTS). */
+#define YP_CONTOURS_MERGE_TILE 256
+#define YP_CONTOURS_MERGE_SCAN_BLOCK 1024
+#define YP_CONTOURS_MERGE_MAX_PTS 524288
+size_t yp_mask_contours_merge_workspace(int n, int parts_cap);
+unsigned long long yp_mask_contours_merge_tiles(const int32_t* lengths_host, int n_contours);
+int yp_mask_contours_merge(const int32_t* pts_dev, const int32_t* count_dev, const int32_t* parts_dev, int n, int max_pts, int parts_cap,
+                           int32_t* merged_out, int32_t* merged_count_out, int out_cap, void* workspace_dev, size_t workspace_bytes,
+                           void* stream);
+/* the two sizes above as the loaded library was built with them (tile, scan block) */
+void yp_mask_contours_merge_sizes(int* tile, int* scan_block);
+
 /* LetterBox on the device (the step before the network inside `.predict`; reference call sites yolo_seg/app.py:86-91,
  * [U] ultralytics LetterBox = cv2.resize INTER_LINEAR + cv2.copyMakeBorder(114)). Engine-free, pure function of its
  * arguments; bit-exact with the fixed-point 8-bit bilinear resize the oracle restates.

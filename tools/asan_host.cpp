@@ -391,6 +391,51 @@ int main() {
         CHECK(yp_mask_contours_scaled(m, 0, 384, 640, YP_CONTOURS_ALL, 16, pts, cnt, parts, 4, rect, 720, 1280, nullptr) == YP_OK);
     }
     {
+        // yp_mask_contours_merge: the tile-list sizes, the workspace arithmetic and the refusals are host code; nothing is launched
+        const int T = YP_CONTOURS_MERGE_TILE, G = 4 * YP_CONTOURS_MERGE_TILE;
+        int tile = 0, scan = 0;
+        yp_mask_contours_merge_sizes(&tile, &scan);
+        yp_mask_contours_merge_sizes(nullptr, nullptr);
+        CHECK(tile == T && scan == YP_CONTOURS_MERGE_SCAN_BLOCK);
+        {
+            const int32_t two[2] = {T + 1, G + 1}, big[3] = {6000, 6000, 3000}, bad[3] = {3, 0, 3}, top[2] = {YP_CONTOURS_MERGE_MAX_PTS, YP_CONTOURS_MERGE_MAX_PTS};
+            CHECK(yp_mask_contours_merge_tiles(two, 2) == 4 && yp_mask_contours_merge_tiles(two, 1) == 0 && yp_mask_contours_merge_tiles(nullptr, 2) == 0);
+            CHECK(yp_mask_contours_merge_tiles(big, 3) == (unsigned long long)((6000 + T - 1) / T) * (((6000 + G - 1) / G) + ((3000 + G - 1) / G)));
+            CHECK(yp_mask_contours_merge_tiles(bad, 3) == 0);
+            CHECK(yp_mask_contours_merge_tiles(top, 2) == (unsigned long long)(YP_CONTOURS_MERGE_MAX_PTS / T) * (YP_CONTOURS_MERGE_MAX_PTS / G));
+            std::vector<int32_t> many(YP_CONTOURS_LARGE_MAX_STARTS, 4);
+            CHECK(yp_mask_contours_merge_tiles(many.data(), (int)many.size()) == (unsigned long long)many.size() - 1);
+        }
+        CHECK(yp_mask_contours_merge_workspace(0, 65) == 0 && yp_mask_contours_merge_workspace(-1, 65) == 0 && yp_mask_contours_merge_workspace(65536, 65) == 0);
+        CHECK(yp_mask_contours_merge_workspace(1, 1) == 0 && yp_mask_contours_merge_workspace(1, YP_CONTOURS_LARGE_MAX_STARTS + 2) == 0);
+        const size_t per = yp_mask_contours_merge_workspace(1, 65) - 16;
+        CHECK(per > 0 && per % 16 == 0);
+        for (int n : {1, 2, 7, 480, 65535})
+            CHECK(yp_mask_contours_merge_workspace(n, 65) == (size_t)((2 * (n + 1) + 3) / 4) * 16 + (size_t)n * per);
+        CHECK(yp_mask_contours_merge_workspace(65535, YP_CONTOURS_LARGE_MAX_STARTS + 1) > ((size_t)1 << 36));      // (size_t arithmetic: no 32-bit wrap)
+        static int32_t pts[64], cnt[4], parts[8], out[80], outc[4];
+        alignas(16) static int32_t ws[4096];
+        const size_t need = yp_mask_contours_merge_workspace(2, 4);
+        CHECK(need > 0 && need <= sizeof ws);
+        CHECK(yp_mask_contours_merge(pts, cnt, parts, -1, 16, 4, out, outc, 20, ws, need, nullptr) == YP_ERR_ARG);
+        CHECK(yp_mask_contours_merge(pts, cnt, parts, 65536, 16, 4, out, outc, 20, ws, need, nullptr) == YP_ERR_ARG);
+        CHECK(yp_mask_contours_merge(pts, cnt, parts, 2, 1, 4, out, outc, 20, ws, need, nullptr) == YP_ERR_ARG);
+        CHECK(yp_mask_contours_merge(pts, cnt, parts, 2, YP_CONTOURS_MERGE_MAX_PTS + 1, 4, out, outc, 20, ws, need, nullptr) == YP_ERR_ARG);
+        CHECK(yp_mask_contours_merge(pts, cnt, parts, 2, 16, 1, out, outc, 20, ws, need, nullptr) == YP_ERR_ARG);
+        CHECK(yp_mask_contours_merge(pts, cnt, parts, 2, 16, YP_CONTOURS_LARGE_MAX_STARTS + 2, out, outc, 20, ws, need, nullptr) == YP_ERR_ARG);
+        CHECK(yp_mask_contours_merge(pts, cnt, parts, 2, 16, 4, out, outc, 0, ws, need, nullptr) == YP_ERR_ARG);
+        CHECK(yp_mask_contours_merge(nullptr, cnt, parts, 2, 16, 4, out, outc, 20, ws, need, nullptr) == YP_ERR_ARG);
+        CHECK(yp_mask_contours_merge(pts, nullptr, parts, 2, 16, 4, out, outc, 20, ws, need, nullptr) == YP_ERR_ARG);
+        CHECK(yp_mask_contours_merge(pts, cnt, nullptr, 2, 16, 4, out, outc, 20, ws, need, nullptr) == YP_ERR_ARG);
+        CHECK(yp_mask_contours_merge(pts, cnt, parts, 2, 16, 4, nullptr, outc, 20, ws, need, nullptr) == YP_ERR_ARG);
+        CHECK(yp_mask_contours_merge(pts, cnt, parts, 2, 16, 4, out, nullptr, 20, ws, need, nullptr) == YP_ERR_ARG);
+        CHECK(yp_mask_contours_merge((const int32_t*)((const char*)pts + 4), cnt, parts, 2, 16, 4, out, outc, 20, ws, need, nullptr) == YP_ERR_ARG);
+        CHECK(yp_mask_contours_merge(pts, cnt, parts, 2, 16, 4, out, outc, 20, nullptr, need, nullptr) == YP_ERR_ARG);
+        CHECK(yp_mask_contours_merge(pts, cnt, parts, 2, 16, 4, out, outc, 20, (char*)ws + 8, need, nullptr) == YP_ERR_ARG);
+        CHECK(yp_mask_contours_merge(pts, cnt, parts, 2, 16, 4, out, outc, 20, ws, need - 1, nullptr) == YP_ERR_ARG);
+        CHECK(yp_mask_contours_merge(pts, cnt, parts, 0, 16, 4, out, outc, 20, nullptr, 0, nullptr) == YP_OK);       // nothing to do
+    }
+    {
         static uint8_t src[16], dst[16];                                 // never read: every call below is refused first or launches nothing
         CHECK(yp_letterbox_batch(nullptr, 2, 720, 1280, dst, 384, 640, 360, 640, 12, 0, 114, nullptr) == YP_ERR_ARG);
         CHECK(yp_letterbox_batch(src, 2, 720, 1280, nullptr, 384, 640, 360, 640, 12, 0, 114, nullptr) == YP_ERR_ARG);

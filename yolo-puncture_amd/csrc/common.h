@@ -579,6 +579,17 @@ size_t contours_large_workspace_bytes(int n, int H, int W);            // 0 on b
 hipError_t launch_contours_large(const uint8_t* masks, int n, int H, int W, int strategy, int max_pts, int32_t* pts, int32_t* count, int32_t* parts,
                                  int parts_cap, double* rect, int H0, int W0, int flags, void* workspace, hipStream_t st);
 
+// the "all_merged" bridge (contour_merge.hip) on the buffers the contour calls fill: closest pairs of consecutive contours over a tile list
+// derived on the device, then every piece copied to its place. Point indices below CM_MAX_PTS (19 bits each in the 64-bit key).
+constexpr int CM_TILE = 256;                 // = YP_CONTOURS_MERGE_TILE: a-points per tile (one per lane) and b-points per LDS tile
+constexpr int CM_SCAN = 1024;                // = YP_CONTOURS_MERGE_SCAN_BLOCK: contours per step of the scans
+constexpr int CM_MAX_PTS = 1 << 19;          // = YP_CONTOURS_MERGE_MAX_PTS
+constexpr int CM_MAX_CONTOURS = CL_MAXCAND;  // a parts row lists at most as many lengths as the large path has border starts
+size_t contours_merge_workspace_bytes(int n, int parts_cap);           // 0 on bad sizes
+unsigned long long contours_merge_tiles(const int32_t* lengths, int n);  // host: work tiles of one mask's contour list (0 on a bad length)
+hipError_t launch_contours_merge(const int32_t* pts, const int32_t* count, const int32_t* parts, int n, int max_pts, int parts_cap, int32_t* out,
+                                 int32_t* out_count, int out_cap, void* workspace, hipStream_t st);
+
 // host-side float -> bf16 (round to nearest even), as the device's v_cvt_pk_bf16_f32
 static inline uint16_t f2bf(float f) {
     uint32_t u;

@@ -2558,6 +2558,33 @@ int yp_mask_contours_large(const uint8_t* masks_dev, int n, int H, int W, int st
     return YP_OK;
 }
 
+size_t yp_mask_contours_merge_workspace(int n, int parts_cap) { return contours_merge_workspace_bytes(n, parts_cap); }
+unsigned long long yp_mask_contours_merge_tiles(const int32_t* lengths_host, int n_contours) {
+    return lengths_host && n_contours > 1 ? contours_merge_tiles(lengths_host, n_contours) : 0;
+}
+void yp_mask_contours_merge_sizes(int* tile, int* scan_block) {
+    if (tile) *tile = CM_TILE;
+    if (scan_block) *scan_block = CM_SCAN;
+}
+
+int yp_mask_contours_merge(const int32_t* pts_dev, const int32_t* count_dev, const int32_t* parts_dev, int n, int max_pts, int parts_cap,
+                           int32_t* merged_out, int32_t* merged_count_out, int out_cap, void* workspace_dev, size_t workspace_bytes,
+                           void* stream) {
+    if (n < 0 || n > 65535 || max_pts < 2 || max_pts > YP_CONTOURS_MERGE_MAX_PTS || out_cap < 1)
+        return fail(YP_ERR_ARG, "yp_mask_contours_merge: bad sizes (n <= 65535, 2 <= max_pts <= %d, out_cap >= 1)", YP_CONTOURS_MERGE_MAX_PTS);
+    if (parts_cap < 2 || parts_cap > YP_CONTOURS_LARGE_MAX_STARTS + 1)
+        return fail(YP_ERR_ARG, "yp_mask_contours_merge: parts_cap %d outside 2 .. %d", parts_cap, YP_CONTOURS_LARGE_MAX_STARTS + 1);
+    if (n > 0 && (!pts_dev || !count_dev || !parts_dev || !merged_out || !merged_count_out)) return fail(YP_ERR_ARG, "yp_mask_contours_merge: null buffer");
+    if (((uintptr_t)pts_dev | (uintptr_t)merged_out) & 7) return fail(YP_ERR_ARG, "yp_mask_contours_merge: point buffers must be 8-byte aligned");
+    const size_t need = contours_merge_workspace_bytes(n, parts_cap);
+    if (n > 0 && (!workspace_dev || ((uintptr_t)workspace_dev & 15))) return fail(YP_ERR_ARG, "yp_mask_contours_merge: workspace null or not 16-byte aligned");
+    if (workspace_bytes < need)
+        return fail(YP_ERR_ARG, "yp_mask_contours_merge: workspace of %zu bytes, %zu needed (yp_mask_contours_merge_workspace)", workspace_bytes, need);
+    HIPCHK(launch_contours_merge(pts_dev, count_dev, parts_dev, n, max_pts, parts_cap, merged_out, merged_count_out, out_cap, workspace_dev,
+                                 (hipStream_t)stream));
+    return YP_OK;
+}
+
 int yp_letterbox(const uint8_t* src_dev, int h0, int w0, uint8_t* dst_dev, int out_h, int out_w, int new_h, int new_w, int top, int left,
                  int pad_value, void* stream) {
     if (!src_dev || !dst_dev) return fail(YP_ERR_ARG, "yp_letterbox: null buffer");

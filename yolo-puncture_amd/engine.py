@@ -64,6 +64,14 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     lib.yp_mask_contours_large.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, C.c_int, vp, C.c_int, C.c_int, C.c_int, vp,
                                            C.c_size_t, vp]
     lib.yp_mask_contours_large.restype = C.c_int
+    lib.yp_mask_contours_merge_workspace.argtypes = [C.c_int, C.c_int]
+    lib.yp_mask_contours_merge_workspace.restype = C.c_size_t
+    lib.yp_mask_contours_merge_tiles.argtypes = [C.POINTER(C.c_int32), C.c_int]
+    lib.yp_mask_contours_merge_tiles.restype = C.c_ulonglong
+    lib.yp_mask_contours_merge.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int, vp, C.c_size_t, vp]
+    lib.yp_mask_contours_merge.restype = C.c_int
+    lib.yp_mask_contours_merge_sizes.argtypes = [ip, ip]
+    lib.yp_mask_contours_merge_sizes.restype = None
     lib.yp_plan.argtypes = [vp, C.c_int, C.c_int, C.c_int]
     lib.yp_max_batch.argtypes = [vp, C.c_int, C.c_int]
     lib.yp_max_batch.restype = C.c_int
@@ -156,7 +164,8 @@ EXPORTS = ["yp_last_error", "yp_create", "yp_destroy", "yp_weight_count", "yp_we
            "yp_finalize", "yp_forward", "yp_proto", "yp_masks", "yp_id_mask_resized", "yp_plan", "yp_op_info", "yp_op_output", "yp_op_input", "yp_op_fusion",
            "yp_tensor_count", "yp_tensor_info", "yp_tensor_read", "yp_profile", "yp_set_graph", "yp_run_op",
            "yp_tensor_write", "yp_op_kernel", "yp_set_autotune", "yp_tuning_export", "yp_tuning_import", "yp_set_nms", "yp_set_nms_options", "yp_debug_force_conv_cfg", "yp_debug_op_cfg", "yp_debug_op_form", "yp_debug_last_store_form", "yp_debug_max_workgroups", "yp_debug_conv_families", "yp_debug_ablation", "yp_debug_head_clocks", "yp_debug_head_branch_clocks", "yp_debug_head_winners", "yp_debug_contour_clocks", "yp_debug_pwsp_clocks", "yp_debug_host_selftest", "yp_debug_graph_info", "yp_tuning_source", "yp_debug_head_positions", "yp_debug_marker", "yp_max_batch", "yp_debug_topk_anchors", "yp_debug_attention", "yp_debug_attention_form", "yp_debug_attention_f32", "yp_debug_conv_s2", "yp_set_attention_form", "yp_set_attention_f32_stream", "yp_letterbox", "yp_letterbox_batch", "yp_masks_frames", "yp_masks_frames_input", "yp_id_masks_frames", "yp_id_masks_frames_workspace", "yp_mask_contours",
-           "yp_mask_contours_scaled", "yp_mask_contours_large_workspace", "yp_mask_contours_large", "yp_comm_unique_id", "yp_comm_create", "yp_allgather", "yp_comm_destroy",
+           "yp_mask_contours_scaled", "yp_mask_contours_large_workspace", "yp_mask_contours_large", "yp_mask_contours_merge_workspace",
+           "yp_mask_contours_merge_tiles", "yp_mask_contours_merge", "yp_mask_contours_merge_sizes", "yp_comm_unique_id", "yp_comm_create", "yp_allgather", "yp_comm_destroy",
            "yp_u2net_create", "yp_u2net_destroy", "yp_u2net_weight_count", "yp_u2net_weight_info", "yp_u2net_set_weight", "yp_u2net_finalize",
            "yp_u2net_forward", "yp_u2net_forward_crops", "yp_u2net_set_graph", "yp_u2net_tensor_count", "yp_u2net_tensor_info", "yp_u2net_tensor_read",
            "yp_u2net_op_count", "yp_u2net_op_info",
@@ -358,7 +367,10 @@ def mask_contours_device(masks: torch.Tensor, max_pts: Optional[int] = None, wan
                          orig_hw: Optional[Tuple[int, int]] = None):
     """yp_mask_contours: uint8 cuda [n,H,W] -> (list of int32 [m,2] numpy polygons (None where the device path declined), rect float64 [n,2]
     numpy (long side, short side) or None[, list of per-mask contour lengths when `want_parts`]). `strategy` as ultralytics' masks2segments:
-    "all" (every external contour, concatenated bottom-up) or "largest". The masks stay on the device; counts, contour lengths, rectangles
+    "all" (every external contour, concatenated bottom-up), "largest", or "all_merged" (the "all" list bridged at the closest points as the
+    later 8.3.x releases do, hostops.merge_contours - traced and bridged on the device, yp_mask_contours_merge; with `want_parts` the third
+    value is None per mask, except for a list the device bridge declined: that polygon comes unbridged with its contour lengths). The
+    masks stay on the device; counts, contour lengths, rectangles
     and the heads of the point lists share one allocation so that a single mask (what the reference's loop asks for per frame) costs ONE
     device-to-host copy. `max_pts` also sizes the kernel's per-candidate lists (1024 points each behind the result): the default is
     generous for one mask, 16384 per mask otherwise.
@@ -367,8 +379,8 @@ def mask_contours_device(masks: torch.Tensor, max_pts: Optional[int] = None, wan
     (W0 >= 2048)."""
     if not (masks.is_cuda and masks.dtype == torch.uint8 and masks.dim() == 3):
         raise ValueError("mask_contours_device needs a uint8 CUDA tensor [n,H,W]")
-    if strategy not in CONTOUR_STRATEGIES:
-        raise ValueError(f"strategy must be 'all' or 'largest', got {strategy!r}")
+    if strategy not in CONTOUR_STRATEGIES and strategy != MERGED:
+        raise ValueError(f"strategy must be 'all', 'largest' or 'all_merged', got {strategy!r}")
     if orig_hw is not None and not (int(orig_hw[0]) > 0 and int(orig_hw[1]) > 0):
         raise ValueError(f"orig_hw must be a positive (H0, W0), got {orig_hw!r}")
     masks = masks.contiguous()
@@ -376,6 +388,15 @@ def mask_contours_device(masks: torch.Tensor, max_pts: Optional[int] = None, wan
     if max_pts is None:
         max_pts = 131072 if n <= 2 else 16384
     dev = masks.device
+    if strategy == MERGED:
+        h0, w0 = (int(orig_hw[0]), int(orig_hw[1])) if orig_hw is not None else (0, 0)
+
+        def trace(lib, pts, count, parts, rect):
+            args = (C.c_void_p(masks.data_ptr()), n, H, W, CONTOUR_STRATEGIES["all"], int(max_pts), pts, count, parts, _PARTS_CAP, rect)
+            if orig_hw is None:
+                return lib.yp_mask_contours(*args, C.c_void_p(_stream_ptr(dev)))
+            return lib.yp_mask_contours_scaled(*args, h0, w0, C.c_void_p(_stream_ptr(dev)))
+        return _trace_and_bridge(trace, dev, n, int(max_pts), _PARTS_CAP, want_rect, want_parts)
     # int32 words: [count (n) | pad | parts (n x _PARTS_CAP, padded to even) | rect (n x 2 float64) | points (n x max_pts x 2)]
     o_parts = (n + 1) // 2 * 2
     o_rect = o_parts + (n * _PARTS_CAP + 1) // 2 * 2
@@ -431,6 +452,106 @@ def _read_contours(buf: torch.Tensor, n: int, max_pts: int, parts_cap: int, o_pa
     return polys, rect, parts
 
 
+MERGED = "all_merged"                               # hostops.POLYGON_STRATEGIES' third: the "all" list, bridged on the device (yp_mask_contours_merge)
+MERGE_MAX_PTS = 1 << 19                             # include/yolop.h YP_CONTOURS_MERGE_MAX_PTS
+
+
+def merge_sizes() -> Tuple[int, int]:
+    """(tile, scan block) of yp_mask_contours_merge as the loaded library was built: points a side of a closest-pair tile, contours per
+    step of the per-mask scans."""
+    tile, scan = C.c_int(0), C.c_int(0)
+    load_library().yp_mask_contours_merge_sizes(C.byref(tile), C.byref(scan))
+    return int(tile.value), int(scan.value)
+
+
+def merge_tiles(lengths) -> int:
+    """yp_mask_contours_merge_tiles: work tiles the device derives for one mask whose contours have these lengths (host arithmetic)."""
+    arr = (C.c_int32 * max(1, len(lengths)))(*[int(v) for v in lengths])
+    return int(load_library().yp_mask_contours_merge_tiles(arr, len(lengths)))
+
+
+def _merge_call(lib, dev, pts_ptr: int, count_ptr: int, parts_ptr: int, n: int, max_pts: int, parts_cap: int, out_ptr: int, out_count_ptr: int,
+                out_cap: int) -> int:
+    """yp_mask_contours_merge on the current stream of `dev`, its workspace allocated for the call (stream-ordered: free to go afterwards)."""
+    ws_bytes = int(lib.yp_mask_contours_merge_workspace(n, parts_cap))
+    ws = torch.empty((max(ws_bytes, 16) // 4,), dtype=torch.int32, device=dev)
+    return lib.yp_mask_contours_merge(C.c_void_p(pts_ptr), C.c_void_p(count_ptr), C.c_void_p(parts_ptr), n, max_pts, parts_cap, C.c_void_p(out_ptr),
+                                      C.c_void_p(out_count_ptr), out_cap, C.c_void_p(ws.data_ptr()), ws_bytes, C.c_void_p(_stream_ptr(dev)))
+
+
+def contours_merge_device(pts: torch.Tensor, count: torch.Tensor, parts: torch.Tensor, out_cap: Optional[int] = None,
+                          out: Optional[torch.Tensor] = None, out_count: Optional[torch.Tensor] = None):
+    """yp_mask_contours_merge on device tensors as the contour calls fill them: pts int32 [n,max_pts,2], count int32 [n], parts int32
+    [n,parts_cap] ([0] = contours, then their lengths) -> (merged int32 [n,out_cap,2], merged_count int32 [n]) on the device:
+    hostops.merge_contours of every mask's list; count <= 0 passed on, -1 where the bridge declines (more than `out_cap` points - default:
+    room for every list the inputs can hold -, a parts row that does not list every contour). `out` / `out_count`: tensors to write into
+    (int32, contiguous, [n,out_cap,2] and [n]) instead of fresh ones."""
+    ok = all(t.is_cuda and t.dtype == torch.int32 and t.is_contiguous() for t in (pts, count, parts))
+    if not (ok and pts.dim() == 3 and pts.shape[2] == 2 and count.dim() == 1 and parts.dim() == 2 and pts.shape[0] == count.shape[0] == parts.shape[0]):
+        raise ValueError("contours_merge_device needs contiguous int32 CUDA tensors pts [n,max_pts,2], count [n], parts [n,parts_cap]")
+    n, max_pts, parts_cap = int(pts.shape[0]), int(pts.shape[1]), int(parts.shape[1])
+    if out_cap is None:
+        out_cap = max_pts + 2 * min(parts_cap - 1, max_pts)
+    out_cap = int(out_cap)
+    dev = pts.device
+    if out is None:
+        out = torch.empty((n, out_cap, 2), dtype=torch.int32, device=dev)
+    if out_count is None:
+        out_count = torch.empty((n,), dtype=torch.int32, device=dev)
+    if not all(t.is_cuda and t.dtype == torch.int32 and t.is_contiguous() and t.device == dev for t in (out, out_count)) or \
+            tuple(out.shape) != (n, out_cap, 2) or tuple(out_count.shape) != (n,):
+        raise ValueError(f"contours_merge_device: out must be int32 [{n},{out_cap},2] and out_count int32 [{n}] on {dev}")
+    lib = load_library()
+    with torch.cuda.device(dev):
+        rc = _merge_call(lib, dev, pts.data_ptr(), count.data_ptr(), parts.data_ptr(), n, max_pts, parts_cap, out.data_ptr(), out_count.data_ptr(), out_cap)
+    if rc != 0:
+        raise YolopError(lib.yp_last_error().decode())
+    return out, out_count
+
+
+def _trace_and_bridge(trace, dev, n: int, max_pts: int, parts_cap: int, want_rect: bool, want_parts: bool):
+    """strategy "all_merged" of the two contour calls: `trace(lib, pts, count, parts, rect)` lists every contour ("all") into the tail of
+    the call's one allocation, yp_mask_contours_merge bridges them into its head on the same stream - nothing is read back in between -
+    and the head is read as for the other strategies. -> (polys, rect[, parts]): parts[i] is None where the device bridged (or the trace
+    declined); where only the bridge declined, polys[i] is the unbridged list and parts[i] its contour lengths when `want_parts`
+    (predictor._finish_contour bridges it), else it is bridged here."""
+    from . import hostops
+    if max_pts > MERGE_MAX_PTS:
+        raise ValueError(f"'all_merged' on the device: max_pts <= {MERGE_MAX_PTS}, got {max_pts}")
+    out_cap = max_pts + 2 * (parts_cap - 1)               # two more points per listable contour: every list the trace can write fits bridged
+    # int32 words: [bridged count (n) | traced count (n) | parts | rect | bridged points (n x out_cap x 2) | traced points (n x max_pts x 2)]
+    o_parts = 2 * n
+    o_rect = o_parts + (n * parts_cap + 1) // 2 * 2
+    o_pts = o_rect + 4 * n
+    o_raw = o_pts + n * out_cap * 2
+    buf = torch.empty((o_raw + n * max_pts * 2,), dtype=torch.int32, device=dev)
+    lib = load_library()
+    with torch.cuda.device(dev):
+        base = buf.data_ptr()
+        rc = trace(lib, C.c_void_p(base + 4 * o_raw), C.c_void_p(base + 4 * n), C.c_void_p(base + 4 * o_parts),
+                   C.c_void_p(base + 4 * o_rect if want_rect else None))
+        if rc == 0:
+            rc = _merge_call(lib, dev, base + 4 * o_raw, base + 4 * n, base + 4 * o_parts, n, max_pts, parts_cap, base + 4 * o_pts, base, out_cap)
+    if rc != 0:
+        raise YolopError(lib.yp_last_error().decode())
+    polys, rect = _read_contours(buf[:o_raw], n, out_cap, parts_cap, o_parts, o_rect, o_pts, want_rect, False)
+    polys.max_pts = max_pts
+    parts = [None] * n
+    if any(p is None for p in polys):                   # which of them did the trace list? (a second, small copy: only when something declined)
+        head = buf[n:o_rect].cpu().numpy()
+        for i in range(n):
+            row = head[o_parts - n + i * parts_cap:o_parts - n + (i + 1) * parts_cap]
+            if polys[i] is not None or head[i] <= 0 or not 1 <= row[0] <= parts_cap - 1:
+                continue
+            raw = buf[o_raw + i * max_pts * 2:o_raw + (i * max_pts + int(head[i])) * 2].cpu().numpy().reshape(-1, 2)
+            lens = [int(v) for v in row[1:1 + int(row[0])]]
+            if want_parts:
+                polys[i], parts[i] = raw, lens
+            else:
+                polys[i] = hostops.merge_contours(np.split(raw, np.cumsum(lens)[:-1])).astype(np.int32)
+    return (polys, rect, parts) if want_parts else (polys, rect)
+
+
 LARGE_MAX_DIM = 4096                                # include/yolop.h YP_CONTOURS_LARGE_MAX_DIM
 _LARGE_MAX_BORDERS = 65536                          # ... YP_CONTOURS_LARGE_MAX_STARTS: a mask has at most as many outer borders
 YP_CONTOURS_ONLY_DECLINED = 1
@@ -444,8 +565,8 @@ def mask_contours_large_device(masks: torch.Tensor, max_pts: Optional[int] = Non
     more than `max_pts` points); masks higher or wider than 4096 raise YolopError. The workspace lives for the call only."""
     if not (masks.is_cuda and masks.dtype == torch.uint8 and masks.dim() == 3):
         raise ValueError("mask_contours_large_device needs a uint8 CUDA tensor [n,H,W]")
-    if strategy not in CONTOUR_STRATEGIES:
-        raise ValueError(f"strategy must be 'all' or 'largest', got {strategy!r}")
+    if strategy not in CONTOUR_STRATEGIES and strategy != MERGED:
+        raise ValueError(f"strategy must be 'all', 'largest' or 'all_merged', got {strategy!r}")
     if orig_hw is not None and not (int(orig_hw[0]) > 0 and int(orig_hw[1]) > 0):
         raise ValueError(f"orig_hw must be a positive (H0, W0), got {orig_hw!r}")
     masks = masks.contiguous()
@@ -455,15 +576,22 @@ def mask_contours_large_device(masks: torch.Tensor, max_pts: Optional[int] = Non
     max_pts = int(max_pts)
     dev = masks.device
     # parts rows: every length the mask can have (a contour has at least one point, so at most max_pts of them are ever listed)
-    parts_cap = 1 + min(_LARGE_MAX_BORDERS, max_pts, max(1, H * ((W + 1) // 2))) if want_parts else 2
+    parts_cap = 1 + min(_LARGE_MAX_BORDERS, max_pts, max(1, H * ((W + 1) // 2))) if want_parts or strategy == MERGED else 2
+    lib = load_library()
+    ws_bytes = int(lib.yp_mask_contours_large_workspace(n, H, W))
+    h0, w0 = (int(orig_hw[0]), int(orig_hw[1])) if orig_hw is not None else (0, 0)
+    if strategy == MERGED:
+        ws = torch.empty((max(ws_bytes, 16) // 4,), dtype=torch.int32, device=dev)
+
+        def trace(lib, pts, count, parts, rect):
+            return lib.yp_mask_contours_large(C.c_void_p(masks.data_ptr()), n, H, W, CONTOUR_STRATEGIES["all"], max_pts, pts, count, parts, parts_cap,
+                                              rect, h0, w0, 0, C.c_void_p(ws.data_ptr()), ws_bytes, C.c_void_p(_stream_ptr(dev)))
+        return _trace_and_bridge(trace, dev, n, max_pts, parts_cap, want_rect, want_parts)
     o_parts = (n + 1) // 2 * 2
     o_rect = o_parts + (n * parts_cap + 1) // 2 * 2
     o_pts = o_rect + 4 * n
-    lib = load_library()
-    ws_bytes = int(lib.yp_mask_contours_large_workspace(n, H, W))
     buf = torch.empty((o_pts + n * max_pts * 2,), dtype=torch.int32, device=dev)
     ws = torch.empty((max(ws_bytes, 16) // 4,), dtype=torch.int32, device=dev)
-    h0, w0 = (int(orig_hw[0]), int(orig_hw[1])) if orig_hw is not None else (0, 0)
     with torch.cuda.device(dev):
         base = buf.data_ptr()
         rc = lib.yp_mask_contours_large(C.c_void_p(masks.data_ptr()), n, H, W, CONTOUR_STRATEGIES[strategy], max_pts, C.c_void_p(base + 4 * o_pts),

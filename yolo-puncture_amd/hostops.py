@@ -240,6 +240,25 @@ def external_contours(mask: np.ndarray) -> List[np.ndarray]:
 POLYGON_STRATEGIES = ("all", "largest", "all_merged")
 
 
+_MERGE_BLOCK_CELLS = 1 << 20      # cells of the squared-distance table held at a time (8 MB of int64 per temporary)
+
+
+def _closest_pair(a: np.ndarray, b: np.ndarray) -> Tuple[int, int]:
+    """(index in a, index in b) of the first minimum, in row-major order, of the |a| x |b| table of squared integer distances - the
+    argmin of the whole table, computed over blocks of rows: a later block replaces the best so far only when strictly smaller."""
+    a, b = a.astype(np.int64), b.astype(np.int64)
+    rows = max(1, _MERGE_BLOCK_CELLS // max(1, b.shape[0]))
+    best, at = None, (0, 0)
+    for r0 in range(0, a.shape[0], rows):
+        blk = a[r0:r0 + rows]
+        d = (blk[:, None, 0] - b[None, :, 0]) ** 2 + (blk[:, None, 1] - b[None, :, 1]) ** 2
+        j = int(d.argmin())
+        v = int(d.flat[j])
+        if best is None or v < best:
+            best, at = v, (r0 + j // d.shape[1], j % d.shape[1])
+    return at
+
+
 def merge_contours(contours: List[np.ndarray]) -> np.ndarray:
     """"all" of the LATER 8.3.x releases [U]: `masks2segments` there joins several contours with `merge_multi_segment` (the COCO converter's
     routine) instead of laying them end to end - consecutive contours of the list are bridged at their closest pair of points (first
@@ -254,11 +273,9 @@ def merge_contours(contours: List[np.ndarray]) -> np.ndarray:
         return segs[0]
     near = [[] for _ in range(n)]
     for i in range(1, n):
-        a, b = segs[i - 1].astype(np.int64), segs[i].astype(np.int64)
-        d = ((a[:, None, :] - b[None, :, :]) ** 2).sum(-1)
-        j = int(d.argmin())
-        near[i - 1].append(j // d.shape[1])
-        near[i].append(j % d.shape[1])
+        ia, ib = _closest_pair(segs[i - 1], segs[i])
+        near[i - 1].append(ia)
+        near[i].append(ib)
     out, back = [], []
     for i in range(n):
         idx = near[i]

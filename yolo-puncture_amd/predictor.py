@@ -178,9 +178,9 @@ class Masks:
             one = (self._data[i:i + 1] > 0.5).to(torch.uint8)
         elif u8 is not None and u8.is_cuda:
             one = u8[i:i + 1]
-        if one is not None:                               # "all_merged": the device lists every external contour ("all") with its length;
-            merged = self.strategy == "all_merged"        # bridged on the host
-            polys, rects, all_parts = _device_contours(one, None, "all" if merged else self.strategy, merged)
+        if one is not None:                               # "all_merged": traced AND bridged on the device (yp_mask_contours_merge); parts
+            merged = self.strategy == "all_merged"        # only where that bridge declined: bridged on the host then
+            polys, rects, all_parts = _device_contours(one, None, self.strategy, merged)
             poly, rect, parts = polys[0], rects[0], (all_parts[0] if merged else None)
 
         def host_mask():
@@ -211,7 +211,8 @@ def _device_contours(masks: torch.Tensor, max_pts: Optional[int], strategy: str,
     """The device trace of Masks.xy and predict_clip: the LDS pass (mask_contours_device) over all masks, then whatever it declined - a
     polygon, or with `orig_hw` a rectangle left at (-1, -1) - through the large path (mask_contours_large_device) in ONE further call,
     with the point capacity the first call ran with. Nothing more is launched when nothing was declined. -> (polys, rects, parts or
-    None); what is still None goes to the host trace."""
+    None); what is still None goes to the host trace. Under "all_merged" both calls bridge the contours on the device as well, and
+    parts[t] is None wherever they did: lengths come back only with a list the device bridge declined (_finish_contour bridges it)."""
     got = mask_contours_device(masks, max_pts=max_pts, strategy=strategy, want_parts=want_parts, orig_hw=orig_hw)
     polys, rects = got[0], got[1]
     parts = got[2] if want_parts else None
@@ -632,7 +633,6 @@ class YOLO:
                 stage = scache[(self._dev_index, B, H, W)] = torch.empty((B, H, W, 3), dtype=torch.uint8, device=dev)
         cache = self.__dict__.setdefault("_out_cache", {})
         okey = (self._dev_index, B)
-        dev_strategy = "all" if strategy == "all_merged" else strategy
 
         detected: List[bool] = [False] * N
         confs: List[Optional[float]] = [None] * N
@@ -664,7 +664,7 @@ class YOLO:
             else:                                                       # process_mask from the boxes in letterboxed-input pixels
                 m = eng.masks_frames(sel, out["coeff"], rows[sel, :4].to(dev, non_blocking=True), (Hl, Wl), retina=False)
                 mask_hw, orig_hw = (Hl, Wl), (H, W)
-            dpolys, drects, dparts = _device_contours(m, 131072, dev_strategy, strategy == "all_merged", orig_hw)
+            dpolys, drects, dparts = _device_contours(m, 131072, strategy, strategy == "all_merged", orig_hw)
             bnp = boxes.numpy()
             for t, j in enumerate(sel):
                 i = s0 + j
