@@ -250,6 +250,31 @@ int yp_letterbox(const uint8_t* src_dev, int h0, int w0, uint8_t* dst_dev, int o
 int yp_letterbox_batch(const uint8_t* src_dev, int n, int h0, int w0, uint8_t* dst_dev, int out_h, int out_w, int new_h,
                        int new_w, int top, int left, int pad_value, void* stream);
 
+/* The app's output frame on the device, n frames in one launch (loop #2 of the video path: the crop-mask paste, create_roi_mask and the
+ * two saturating cv2.addWeighted calls, yolo_seg/app.py:179-190, yolo_seg/utils/mask_tools.py:100-129). Engine-free; launches on the
+ * current device. Per byte of frame f, pixel (y,x), channel c:   dst = min(255, src + M + R[c])
+ *    M     masks_dev[crop][y - y_lt][x - x_lt] inside the window x_lt <= x < x_rd, y_lt <= y < y_rd, else 0: the byte as it is, the same
+ *          for the three channels. masks_dev uint8 [B,ch,cw] (row stride cw, the window at the crop's top-left); a full-frame mask
+ *          [n,H,W] is B = n, ch = H, cw = W with the window (0,0,W,H). An empty window (x_rd == x_lt or y_rd == y_lt) adds nothing.
+ *    R[c]  max(band ? col[c] : 0, (cov * col[c] + 127) / 255): rectangle and label drawn into one image, as the reference does.
+ *    band  cv2.rectangle((x1,y1),(x2,y2), thickness 2) stated as: every in-frame pixel at Chebyshev distance <= 1 from the one-pixel
+ *          outline through the two corners; x2 == W and y2 == H clip to the frame (stated, not pinned against cv2: its round caps may
+ *          leave out the four outer corner pixels).
+ *    cov   labels_dev[f][y - ly][x - lx] for 0 <= x - lx < lw, 0 <= y - ly < lh, else 0. labels_dev uint8 [n,LH,LW] coverage bitmaps
+ *          (may be NULL when no frame has a label); (lx,ly) may lie outside the frame, the bitmap is clipped to it.
+ *    params  HOST int32 [n, YP_OVERLAY_PARAMS]: x_lt, y_lt, x_rd, y_rd, x1, y1, x2, y2, lx, ly, lw, lh, crop (lw or lh 0: no label). The
+ *          rows travel to the device as kernel arguments, 64 frames per launch: the call stages nothing, waits for nothing and keeps
+ *          no state, so it is safe from any thread and on any stream.
+ *    col   HOST uint8 [3] (BGR), NULL = (0,0,255).
+ * dst_dev != src_dev (no overlap): every byte of the n frames is read once and written once, 16 bytes per lane wherever the address
+ * allows, whatever the alignment of the base, of W*3 and of H*W*3. dst_dev == src_dev: in place, only the 16-byte groups that meet the
+ * window, the band or the label are loaded and stored. n >= 0, H*W*3 < 2^31; frame offsets are 64-bit.
+ * Checked before anything is launched (YP_ERR_ARG): null pointers, a window outside the frame or larger than ch x cw, x2 < x1 or
+ * y2 < y1, a crop index outside [0,B), a label larger than LH x LW. */
+#define YP_OVERLAY_PARAMS 13
+int yp_overlay_frames(const uint8_t* src_dev, uint8_t* dst_dev, int n, int H, int W, const uint8_t* masks_dev, int B, int ch, int cw,
+                      const int32_t* params, const uint8_t* labels_dev, int LH, int LW, const uint8_t* col, void* stream);
+
 /* -- U^2-Net-P / U^2-Net: the second per-frame network of the reference's video loop, `unet_predict(unet_model,
  *    cropped_frame)` at yolo_seg/app.py:184. Model: yolo_seg/tasks/models/U2Net.py:424-526 (U2NETP) / :318-420 (U2NET); loader and
  *    post-process: yolo_seg/tasks/unet_segment.py:32-73. variant 'p' = U2NETP, 'f' = U2NET. Weights are handed over folded (conv +

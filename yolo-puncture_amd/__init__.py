@@ -20,6 +20,9 @@ def __getattr__(name):
     if name in ("load_classify_net", "predict_images", "predict_and_find_start_inserted", "fix_class_prob", "ClassifierEngine"):
         from . import classify
         return getattr(classify, name)
+    if name in ("overlay_clip", "render_labels", "render_clip"):
+        from . import overlay
+        return getattr(overlay, name)
     if name in ("auto_segment", "auto_segment_clip"):
         from . import deva_adapter
         return getattr(deva_adapter, name)

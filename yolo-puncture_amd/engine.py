@@ -136,6 +136,8 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     lib.yp_letterbox.restype = C.c_int
     lib.yp_letterbox_batch.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp] + [C.c_int] * 7 + [vp]
     lib.yp_letterbox_batch.restype = C.c_int
+    lib.yp_overlay_frames.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int, C.c_int, vp, vp]
+    lib.yp_overlay_frames.restype = C.c_int
     lib.yp_masks_frames.argtypes = [vp, vp, C.c_int, vp, C.c_long, vp, C.c_int, C.c_int, vp, vp]
     lib.yp_masks_frames.restype = C.c_int
     lib.yp_masks_frames_input.argtypes = [vp, vp, C.c_int, vp, C.c_long, vp, C.c_int, C.c_int, vp, vp]
@@ -163,7 +165,7 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
 EXPORTS = ["yp_last_error", "yp_create", "yp_destroy", "yp_weight_count", "yp_weight_info", "yp_set_weight",
            "yp_finalize", "yp_forward", "yp_proto", "yp_masks", "yp_id_mask_resized", "yp_plan", "yp_op_info", "yp_op_output", "yp_op_input", "yp_op_fusion",
            "yp_tensor_count", "yp_tensor_info", "yp_tensor_read", "yp_profile", "yp_set_graph", "yp_run_op",
-           "yp_tensor_write", "yp_op_kernel", "yp_set_autotune", "yp_tuning_export", "yp_tuning_import", "yp_set_nms", "yp_set_nms_options", "yp_debug_force_conv_cfg", "yp_debug_op_cfg", "yp_debug_op_form", "yp_debug_last_store_form", "yp_debug_max_workgroups", "yp_debug_conv_families", "yp_debug_ablation", "yp_debug_head_clocks", "yp_debug_head_branch_clocks", "yp_debug_head_winners", "yp_debug_contour_clocks", "yp_debug_pwsp_clocks", "yp_debug_host_selftest", "yp_debug_graph_info", "yp_tuning_source", "yp_debug_head_positions", "yp_debug_marker", "yp_max_batch", "yp_debug_topk_anchors", "yp_debug_attention", "yp_debug_attention_form", "yp_debug_attention_f32", "yp_debug_conv_s2", "yp_set_attention_form", "yp_set_attention_f32_stream", "yp_letterbox", "yp_letterbox_batch", "yp_masks_frames", "yp_masks_frames_input", "yp_id_masks_frames", "yp_id_masks_frames_workspace", "yp_mask_contours",
+           "yp_tensor_write", "yp_op_kernel", "yp_set_autotune", "yp_tuning_export", "yp_tuning_import", "yp_set_nms", "yp_set_nms_options", "yp_debug_force_conv_cfg", "yp_debug_op_cfg", "yp_debug_op_form", "yp_debug_last_store_form", "yp_debug_max_workgroups", "yp_debug_conv_families", "yp_debug_ablation", "yp_debug_head_clocks", "yp_debug_head_branch_clocks", "yp_debug_head_winners", "yp_debug_contour_clocks", "yp_debug_pwsp_clocks", "yp_debug_host_selftest", "yp_debug_graph_info", "yp_tuning_source", "yp_debug_head_positions", "yp_debug_marker", "yp_max_batch", "yp_debug_topk_anchors", "yp_debug_attention", "yp_debug_attention_form", "yp_debug_attention_f32", "yp_debug_conv_s2", "yp_set_attention_form", "yp_set_attention_f32_stream", "yp_letterbox", "yp_letterbox_batch", "yp_overlay_frames", "yp_masks_frames", "yp_masks_frames_input", "yp_id_masks_frames", "yp_id_masks_frames_workspace", "yp_mask_contours",
            "yp_mask_contours_scaled", "yp_mask_contours_large_workspace", "yp_mask_contours_large", "yp_mask_contours_merge_workspace",
            "yp_mask_contours_merge_tiles", "yp_mask_contours_merge", "yp_mask_contours_merge_sizes", "yp_comm_unique_id", "yp_comm_create", "yp_allgather", "yp_comm_destroy",
            "yp_u2net_create", "yp_u2net_destroy", "yp_u2net_weight_count", "yp_u2net_weight_info", "yp_u2net_set_weight", "yp_u2net_finalize",

@@ -432,3 +432,48 @@ def group_frames_by_workspace(counts: Sequence[int], workspace_bytes, budget: in
     if cur:
         groups.append((True, cur))
     return groups
+
+
+# ---- the app's output frame (loop #2 of the video path: yolo_seg/app.py:179-190, create_roi_mask at utils/mask_tools.py:100-129) ------
+def roi_band(height: int, width: int, x1: int, y1: int, x2: int, y2: int) -> np.ndarray:
+    """The pixel set of `cv2.rectangle(img, (x1, y1), (x2, y2), color, thickness=2)` as this project states it -> bool [height, width]:
+    every in-frame pixel at Chebyshev distance <= 1 from the one-pixel outline through the two corners, i.e. the rectangle
+    [x1-1, x2+1] x [y1-1, y2+1] without the pixels that are at least 2 away from all four sides. x2 == width and y2 == height (the app
+    clamps to them, app.py:142-143) clip to the frame. Stated, not pinned: cv2 is not available to compare against, and its round line
+    caps may leave out the four outer corner pixels (x1-1, y1-1), (x2+1, y1-1), (x1-1, y2+1), (x2+1, y2+1)."""
+    if x2 < x1 or y2 < y1:
+        raise ValueError(f"roi ({x1},{y1},{x2},{y2}) has x2 < x1 or y2 < y1")
+    ys, xs = np.arange(int(height))[:, None], np.arange(int(width))[None, :]
+    outer = (xs >= x1 - 1) & (xs <= x2 + 1) & (ys >= y1 - 1) & (ys <= y2 + 1)
+    inner = (xs >= x1 + 2) & (xs <= x2 - 2) & (ys >= y1 + 2) & (ys <= y2 - 2)
+    return outer & ~inner
+
+
+def overlay_frame(frame: np.ndarray, crop_mask, window, roi, label=None, label_xy=None, col: Sequence[int] = (0, 0, 255)) -> np.ndarray:
+    """One output frame of the app's loop #2, built the way the reference builds it: a zero image with the crop mask pasted at its window
+    (with fix U-1 of INTEGRATION.md: `crop[:y_rd-y_lt, :x_rd-x_lt, None]`, the byte as it is on all three channels), a zero `roi_mask`
+    with the rectangle (roi_band) and the label drawn into it in `col` (BGR), and two saturating adds (`cv2.addWeighted(a, 1, b, 1, 0)`).
+
+    frame uint8 [H,W,3]; crop_mask uint8 [ch,cw] or None; window (x_lt, y_lt, x_rd, y_rd); roi (x1, y1, x2, y2); label a uint8 coverage
+    bitmap [lh,lw] (0 = background, 255 = full colour) or None, its top-left at label_xy = (lx, ly), clipped to the frame. Where label
+    and rectangle meet the larger value stays: a pixel of the label is max(what is there, (cov * col + 127) // 255) per channel."""
+    if frame.ndim != 3 or frame.shape[2] != 3 or frame.dtype != np.uint8:
+        raise TypeError("overlay_frame expects a BGR uint8 HWC frame")
+    H, W = frame.shape[:2]
+    colour = np.asarray(col, dtype=np.uint8).reshape(3)
+    mask = np.zeros(frame.shape, dtype=np.uint8)
+    x_lt, y_lt, x_rd, y_rd = (int(v) for v in window)
+    if crop_mask is not None and x_rd > x_lt and y_rd > y_lt:
+        mask[y_lt:y_rd, x_lt:x_rd] = np.asarray(crop_mask, dtype=np.uint8)[:y_rd - y_lt, :x_rd - x_lt, None]
+    roi_mask = np.zeros(frame.shape, dtype=np.uint8)
+    roi_mask[roi_band(H, W, *(int(v) for v in roi))] = colour
+    if label is not None and label.size:
+        lx, ly = (int(v) for v in label_xy)
+        lh, lw = label.shape
+        xa, ya, xb, yb = max(lx, 0), max(ly, 0), min(lx + lw, W), min(ly + lh, H)
+        if xa < xb and ya < yb:
+            cov = label[ya - ly:yb - ly, xa - lx:xb - lx].astype(np.uint16)[:, :, None]
+            drawn = ((cov * colour.astype(np.uint16) + 127) // 255).astype(np.uint8)
+            roi_mask[ya:yb, xa:xb] = np.maximum(roi_mask[ya:yb, xa:xb], drawn)
+    combined = np.minimum(frame.astype(np.uint16) + mask, 255).astype(np.uint8)
+    return np.minimum(combined.astype(np.uint16) + roi_mask, 255).astype(np.uint8)
